@@ -5,7 +5,7 @@ One step = one frame of the hot path recorded by the C++ FramePipeline (referenc
 depth downscale, SDF frustum+tile culling, diffuse trace, spatial/temporal/spatial denoise, upscale, deferred shade, TAA,
 bloom x11, tonemap) on synthetic inputs that are resident in HBM before the timed region starts.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: ONE frame of N x the 4K pixel count (7680 x 1080*N; N = 4 is the 7680x4320 frame of BASELINE config 5), partitioned into N
 rectangles, one rank per GPU - N row bands (the default: the faster partition in the single-GPU replay of both, profiles/r05_tile_vs_band.txt) or 2 x N/2 SCREEN
@@ -296,6 +296,31 @@ def cpu_baseline(args, cores, device):
                       "median of 3 timed frames (after the one that bakes the BRDF LUT) = %.2f s each, scaled by the pixel ratio" % (w, h, scale * scale, args.grid ** 2, args.sdf_res, args.shadow_res, t)}
 
 
+DUMP_SAMPLE_PIXELS = 1 << 20  # a 4K frame's dump: 16 MB swapchain + 12 MB colour + 8 MB pixel indices, within the 64 MB budget
+
+
+def dump_outputs(out_dir, be, fp, w, h, rect):
+    """--dump-outputs: what the last timed frame delivered to its caller, as float arrays DIR/<name>.npy - the tonemapped swapchain (RGBA8 values),
+    the TAA + bloom output post1 (R11G11B10 decoded to RGB), the exposure light buffer and the luminance histogram. Only the pixels of this rank's
+    rectangle (x0, y0, x1, y1) of the w x h frame are taken; more than DUMP_SAMPLE_PIXELS of them are sampled at a fixed, seeded set of pixels,
+    listed in pixel_index.npy (y * w + x). Inputs and sample depend on the arguments only, so two builds can be compared output for output."""
+    from plainrenderer_amd import pixfmt
+    x0, y0, x1, y1 = rect
+    idx = (np.arange(y0, y1)[:, None] * w + np.arange(x0, x1)[None, :]).reshape(-1)
+    if idx.size > DUMP_SAMPLE_PIXELS:
+        idx = np.sort(np.random.default_rng(12345).choice(idx, DUMP_SAMPLE_PIXELS, replace=False))
+    swapchain = be.downloadImage(fp.image("swapchain"), 0, np.uint8).reshape(w * h, 4)
+    post1 = be.downloadImage(fp.image("post1"), 0, np.uint32)
+    arrays = {"pixel_index": idx.astype(np.float64),
+              "swapchain": swapchain[idx].astype(np.float32),
+              "post1_rgb": pixfmt.unpack_r11g11b10(post1[idx]),
+              "light": be.downloadStorageBuffer(fp.storage_buffer("light"), 20, dtype=np.float32),
+              "histogram": be.downloadStorageBuffer(fp.storage_buffer("histogram"), 512, dtype=np.uint32).astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -327,7 +352,11 @@ def main():
     ap.add_argument("--exact-partition", action="store_true", help="the same as --gi-exchange exact")
     ap.add_argument("--no-strong-scaling", action="store_true", help="N > 1: skip the single-GPU run of the same frame (rank 0) the strong-scaling figure is taken against")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port when --gpus N spawns its own ranks (0: derived from the pid)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed frame computed as DIR/<name>.npy (float32 / float64, "
+                    "at most 64 MB; a fixed, seeded pixel sample of a large frame; N > 1: rank 0's rectangle)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if args.exact_partition:
         args.gi_exchange = "exact"
     # the byte-identical modes get the G-buffer inputs of the WHOLE frame on every rank (whole-image halo: the denoiser weighs samples anywhere in the frame; request lists:
@@ -648,6 +677,8 @@ def main():
     general_count, general_names = be.getGeneralKernelExecutions()
     if general_count and not args.exact:
         raise SystemExit("bench.py: %d execution(s) of the timed frame ran the general (exact-set) kernel instead of a fast-set kernel: %s" % (general_count, general_names))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, be, fp, w, h, tile_rect[0] if band is not None else (0, 0, w, h))
 
     # per-GPU pixels: the rank's rectangle (a band renders w x rows of the frame, a tile columns x rows)
     bh = h if band is None else band[1] - band[0]
