@@ -22,10 +22,48 @@ PLR_DI float lum(vec3 c) { return c.x * 0.21f + c.y * 0.72f + c.z * 0.07f; }
 PLR_DI vec3 tonemapF(vec3 c) { return c * rcpf(1.f + lum(c)); }
 PLR_DI vec3 tonemapReverseF(vec3 c) { return c * rcpf(1.f - lum(c)); }
 
+// The history fetch's texels and 8-bit sub-texel weights are discrete decisions: the position that picks them follows the
+// shader's operation order - no contraction of u * size into the "- 0.5" of linearCoord, IEEE quotients
+PLR_DI void texelCoord(float u, int size, int* i0, float* alpha) {
+#pragma clang fp contract(off)
+    linearCoord(u * (float)size, i0, alpha);
+}
+// 1 / size correctly rounded (the shader's texelSize = 1.f / imageSize): a Newton step on v_rcp_f32
+PLR_DI float texelSize(int size) {
+    const float f = (float)size, r = rcpf(f);
+    return __builtin_fmaf(__builtin_fmaf(-f, r, 1.f), r, r);
+}
+// a / b correctly rounded for the bicubic tap offset w2 / wB (bicubicSampling.inc:163; w2 in [0, 1], wB in [1, 1.125]: no scaling): the reciprocal
+// refined by a Newton step, then the quotient corrected by its exact (FMA) residual (Markstein). With the raw v_rcp_f32 quotient a tap landed on the
+// other 1/256 weight step and put a pixel two codes off (tests/test_parity_ragged.py, 3074 x 1730)
+PLR_DI float quotRn(float a, float b) {
+    const float y0 = rcpf(b);
+    const float y = __builtin_fmaf(__builtin_fmaf(-b, y0, 1.f), y0, y0);
+    const float q = a * y;
+    return __builtin_fmaf(__builtin_fmaf(-b, q, a), y, q);
+}
+// bicubicSampling.inc:152-163 for one axis at the reprojected texel position iUV + 0.5 + motion * resolution (temporalFilter.comp:117-123), in the
+// shader's operation order
+struct CubicAxis { float trunc, f, w0, w3, wB, t; };
+PLR_DI CubicAxis cubicAxis(int p, float motion, float res) {
+#pragma clang fp contract(off)
+    CubicAxis c;
+    const float i = (float)p + 0.5f + motion * res;
+    c.trunc = floorf(i - 0.5f) + 0.5f;
+    const float f = i - c.trunc, f2 = f * f, f3 = f2 * f;
+    c.f = f;
+    c.w0 = -0.5f * f3 + f2 - 0.5f * f;
+    const float w1 = 1.5f * f3 - 2.5f * f2 + 1.f, w2 = -1.5f * f3 + 2.f * f2 + 0.5f * f;
+    c.w3 = 0.5f * f3 - 0.5f * f2;
+    c.wB = w1 + w2;
+    c.t = quotRn(w2, c.wB);
+    return c;
+}
+
 PLR_DI vec3 historyTap(const ImgView& im, float u, float v) {
     int i0, j0; float a, b;
-    linearCoord(u * (float)im.w, &i0, &a);
-    linearCoord(v * (float)im.h, &j0, &b);
+    texelCoord(u, im.w, &i0, &a);
+    texelCoord(v, im.h, &j0, &b);
     const uint32_t* base = (const uint32_t*)im.ptr;
     const int x0 = clampi(i0, im.w), x1 = clampi(i0 + 1, im.w);
     const size_t r0 = (size_t)clampi(j0, im.h) * (size_t)im.w, r1 = (size_t)clampi(j0 + 1, im.h) * (size_t)im.w;
@@ -76,7 +114,7 @@ __global__ __launch_bounds__(256) void temporalFilterFastKernel(ImgView current,
     const int px = xBase + (int)(blockIdx.x * 64u + (threadIdx.x & 63u)); // columns [xBase, coverW) (tile rendering: PassCtx::colSpan)
     const int py = yBase + (int)(blockIdx.y * 4u + (threadIdx.x >> 6));
     if (px >= coverW || py >= coverH) return;
-    const float tsx = 1.f / (float)output.w, tsy = 1.f / (float)output.h;
+    const float tsx = texelSize(output.w), tsy = texelSize(output.h);
     const float u0 = ((float)px + 0.5f) * tsx, v0 = ((float)py + 0.5f) * tsy;
 
     // current 3x3 (texel centres -> plain fetches), tonemapped; n[x+1][y+1]
@@ -128,9 +166,8 @@ __global__ __launch_bounds__(256) void temporalFilterFastKernel(ImgView current,
     vec3 historySample;
     if (TECH == 0) historySample = historyTap(historySrc, rpx, rpy);
     else {
-        const float ix = (float)px + 0.5f + motion.x * (float)g->screenResolution[0], iy = (float)py + 0.5f + motion.y * (float)g->screenResolution[1];
-        const float tx = floorf(ix - 0.5f) + 0.5f, ty = floorf(iy - 0.5f) + 0.5f;
-        const float fx = ix - tx, fy = iy - ty;
+        const CubicAxis cx = cubicAxis(px, motion.x, (float)g->screenResolution[0]), cy = cubicAxis(py, motion.y, (float)g->screenResolution[1]);
+        const float tx = cx.trunc, ty = cy.trunc, fx = cx.f, fy = cy.f;
         if (TECH == 1) {
             const float wx[4] = {catmullRomWeight1D(fx + 1.f), catmullRomWeight1D(fx), catmullRomWeight1D(1.f - fx), catmullRomWeight1D(2.f - fx)};
             const float wy[4] = {catmullRomWeight1D(fy + 1.f), catmullRomWeight1D(fy), catmullRomWeight1D(1.f - fy), catmullRomWeight1D(2.f - fy)};
@@ -139,12 +176,9 @@ __global__ __launch_bounds__(256) void temporalFilterFastKernel(ImgView current,
                 for (int i = 0; i < 4; i++) r = r + historyTap(historySrc, (tx + (float)(i - 1)) * tsx, (ty + (float)(j - 1)) * tsy) * (wx[i] * wy[j]);
             historySample = r;
         } else {
-            const float fx2 = fx * fx, fx3 = fx2 * fx, fy2 = fy * fy, fy3 = fy2 * fy;
-            const float w0x = -0.5f * fx3 + fx2 - 0.5f * fx, w1x = 1.5f * fx3 - 2.5f * fx2 + 1.f, w2x = -1.5f * fx3 + 2.f * fx2 + 0.5f * fx, w3x = 0.5f * fx3 - 0.5f * fx2;
-            const float w0y = -0.5f * fy3 + fy2 - 0.5f * fy, w1y = 1.5f * fy3 - 2.5f * fy2 + 1.f, w2y = -1.5f * fy3 + 2.f * fy2 + 0.5f * fy, w3y = 0.5f * fy3 - 0.5f * fy2;
-            const float wBx = w1x + w2x, wBy = w1y + w2y;
-            const float u0c = (tx - 1.f) * tsx, uT = (tx + w2x * rcpf(wBx)) * tsx, u3 = (tx + 2.f) * tsx;
-            const float v0c = (ty - 1.f) * tsy, vT = (ty + w2y * rcpf(wBy)) * tsy, v3 = (ty + 2.f) * tsy;
+            const float w0x = cx.w0, w3x = cx.w3, wBx = cx.wB, w0y = cy.w0, w3y = cy.w3, wBy = cy.wB;
+            const float u0c = (tx - 1.f) * tsx, uT = (tx + cx.t) * tsx, u3 = (tx + 2.f) * tsx;
+            const float v0c = (ty - 1.f) * tsy, vT = (ty + cy.t) * tsy, v3 = (ty + 2.f) * tsy;
             if (TECH == 2) {
                 historySample = historyTap(historySrc, u0c, v0c) * (w0x * w0y) + historyTap(historySrc, u0c, vT) * (w0x * wBy) + historyTap(historySrc, u0c, v3) * (w0x * w3y) +
                                 historyTap(historySrc, uT, v0c) * (wBx * w0y) + historyTap(historySrc, uT, vT) * (wBx * wBy) + historyTap(historySrc, uT, v3) * (wBx * w3y) +
@@ -305,7 +339,7 @@ __global__ __launch_bounds__(256, PLR_TAA_WAVES) void temporalFilterStripKernel(
     };
 
     const ResolveWeights rw = *rwp;
-    const float tsx = 1.f / (float)output.w, tsy = 1.f / (float)output.h;
+    const float tsx = texelSize(output.w), tsy = texelSize(output.h);
     const float resX = (float)g->screenResolution[0], resY = (float)g->screenResolution[1];
     const bool cameraCut = g->cameraCut != 0u;
     const BufferDesc hist = texelBuffer(historySrc.ptr, 4u);
@@ -475,17 +509,12 @@ __global__ __launch_bounds__(256, PLR_TAA_WAVES) void temporalFilterStripKernel(
             else {
                 // Bicubic1Tap (bicubicSampling.inc:147-181): one bilinear tap at the bicubic-adjusted position plus the current frame's
                 // neighbourhood differences
-                const float ix = (float)px + 0.5f + m.x * resX, iy = (float)py + 0.5f + m.y * resY;
-                const float tx = floorf(ix - 0.5f) + 0.5f, ty = floorf(iy - 0.5f) + 0.5f;
-                const float fx = ix - tx, fy = iy - ty;
-                const float fx2 = fx * fx, fx3 = fx2 * fx, fy2 = fy * fy, fy3 = fy2 * fy;
-                const float w0x = -0.5f * fx3 + fx2 - 0.5f * fx, w1x = 1.5f * fx3 - 2.5f * fx2 + 1.f, w2x = -1.5f * fx3 + 2.f * fx2 + 0.5f * fx, w3x = 0.5f * fx3 - 0.5f * fx2;
-                const float w0y = -0.5f * fy3 + fy2 - 0.5f * fy, w1y = 1.5f * fy3 - 2.5f * fy2 + 1.f, w2y = -1.5f * fy3 + 2.f * fy2 + 0.5f * fy, w3y = 0.5f * fy3 - 0.5f * fy2;
-                const float wBx = w1x + w2x, wBy = w1y + w2y;
-                const float uT = (tx + w2x * rcpf(wBx)) * tsx, vT = (ty + w2y * rcpf(wBy)) * tsy;
+                const CubicAxis cx = cubicAxis(px, m.x, resX), cy = cubicAxis(py, m.y, resY);
+                const float w0x = cx.w0, w3x = cx.w3, wBx = cx.wB, w0y = cy.w0, w3y = cy.w3, wBy = cy.wB;
+                const float uT = (cx.trunc + cx.t) * tsx, vT = (cy.trunc + cy.t) * tsy;
                 int i1, j1; float a1, b1;
-                linearCoord(uT * (float)hw, &i1, &a1);
-                linearCoord(vT * (float)hh, &j1, &b1);
+                texelCoord(uT, hw, &i1, &a1);
+                texelCoord(vT, hh, &j1, &b1);
                 vec3 h;
                 if (i1 == i0 && j1 == j0) {
                     const vec3 tp = tc[0][0] + (tc[0][1] - tc[0][0]) * a1, bt = tc[1][0] + (tc[1][1] - tc[1][0]) * a1;

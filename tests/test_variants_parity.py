@@ -10,10 +10,9 @@ import numpy as np
 import pytest
 
 import parity
+import pass_parity as pp
 import passes
-import test_parity_fullsize as full
 from plainrenderer_amd import pixfmt
-from util import F
 
 W, H = (int(v) for v in os.environ.get("PLR_VARIANT_SIZE", "1920x1088").split("x"))
 TW, TH = W // 2, H // 2
@@ -26,7 +25,7 @@ def report(name, **kv):
 
 @pytest.fixture(scope="module")
 def vs(backend):
-    s = full.build_state(backend, W, H)
+    s = pp.build_state(backend, W, H)
     yield s
     s.fp.destroy()
     backend.setMathMode(False)
@@ -67,16 +66,7 @@ TAA_VARIANTS = [(clip, True, tech, True) for tech in range(5) for clip in (True,
 @pytest.mark.gpu
 @pytest.mark.parametrize("clip,dilate,tech,tonemap", TAA_VARIANTS)
 def test_gpu_every_shipped_taa_variant_meets_the_quantum_bound(backend, vs, clip, dilate, tech, tonemap):
-    c = vs.cap["taa"]
-    args = (c["inp"], c["history"], vs.gb["motion"], vs.gb["depth"], W, H, c["weights"], vs.gp, clip, dilate, tech, tonemap)
-    og, hg = passes.gpu_taa(backend, *args)
-    oo, ho = passes.orc_taa(*args)
-    d = parity.r11g11b10_code_diff(og, oo)
-    report("taa %d/%d/%d/%d" % (clip, dilate, tech, tonemap), max_code_diff=int(d.max()), differing=float((d != 0).any(axis=1).mean()), over_one=float((d > 1).any(axis=1).mean()))
-    assert np.array_equal(og, hg)
-    # the resolve has no discrete decision a kernel could take differently from the oracle: every channel of every pixel within one code
-    # (measured on MI355X: at most 1e-5 of the pixels differ at all, profiles/r03_variants_parity.txt)
-    assert d.max() <= 1
+    pp.check_taa(backend, vs, W, H, TW, TH, clip, dilate, tech, tonemap, name="taa %d/%d/%d/%d" % (clip, dilate, tech, tonemap))
 
 
 @pytest.mark.gpu
@@ -104,27 +94,7 @@ def test_gpu_trace_without_the_strict_cutoff_meets_the_bound(backend, vs):
 @pytest.mark.parametrize("filter_index", [0, 1])
 def test_gpu_spatial_filter_on_a_full_resolution_grid_meets_the_bound(backend, vs, filter_index):
     """the trace at full resolution (SDFTraceSettings::halfResTrace = false) filters on the D32 depth buffer: the unpacked three-gather kernel"""
-    c = vs.cap["spatial%d" % filter_index]
-    yf = np.repeat(np.repeat(np.asarray(c["inp"][0]).reshape(TH, TW, 4), 2, 0), 2, 1)
-    cf = np.repeat(np.repeat(np.asarray(c["inp"][1]).reshape(TH, TW, 2), 2, 0), 2, 1)
-    args = (yf, cf, W, H, vs.gb["depth"], F.Depth32, W, H, vs.gb["normal"], W, H, vs.gp, filter_index)
-    with passes.gpu_signature(backend, 2 * W * H) as sg:
-        yg, cg = passes.gpu_gi_spatial(backend, *args)
-    with passes.orc_signature(2 * W * H) as so:
-        yo, co = passes.orc_gi_spatial(*args)
-    xw = (sg.words ^ so.words).reshape(-1, 2)
-    x = xw[:, 0] | xw[:, 1]
-    flipped = np.zeros(x.size, np.int32)
-    for b in range(32):
-        flipped += ((x >> np.uint32(b)) & np.uint32(1)).astype(np.int32)
-    clean = flipped == 0
-    got = np.concatenate([U(yg).reshape(-1, 4), U(cg).reshape(-1, 2)], axis=1)
-    ref = np.concatenate([U(yo).reshape(-1, 4), U(co).reshape(-1, 2)], axis=1)
-    bad = parity.half_violations(got, ref, floor_frac=2.0 ** -10)
-    report("spatial%d full-res" % filter_index, sample_flip_rate=float(flipped.sum() / (32.0 * x.size)), clean_violations=int((bad & clean).sum()))
-    assert not (bad & clean).any()
-    assert flipped.sum() <= 1e-3 * 32 * x.size
-
+    pp.check_spatial_filter_full_res(backend, vs, W, H, TW, TH, filter_index)
 
 
 class _GlobalBufferTheHostCannotRead(passes.GlobalBinding):
