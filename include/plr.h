@@ -158,6 +158,11 @@ int plr_wait_for_gpu_idle(void);
 int plr_update_shader_code(void);
 /* RenderBackend::resizeImages, RenderBackend.h:47 */
 int plr_resize_images(const plr_image_handle* images, uint32_t count, uint32_t width, uint32_t height);
+/* extensions of resizeImages for a frame that changes size (plrf_set_resolution; no reference counterpart): an image recreated under the same handle with another
+ * description (a depth pyramid whose mip layout changes with the size), and a storage buffer re-allocated at another size. Both wait for the GPU, zero-fill the
+ * new memory like plr_create_image / plr_create_storage_buffer, and free the old. A buffer with a queued plr_set_storage_buffer_data is refused. */
+int plr_recreate_image(plr_image_handle image, const plr_image_desc* desc);
+int plr_resize_storage_buffer(plr_storage_buffer_handle buffer, size_t size);
 /* RenderBackend::newFrame, RenderBackend.h:50: drops recorded executions and transient images */
 int plr_new_frame(void);
 /* RenderBackend::setComputePassExecution, RenderBackend.h:56 */

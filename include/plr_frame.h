@@ -224,6 +224,24 @@ int plrf_set_sdf_scene(void* pipeline, const void* instance_buffer, size_t insta
 int plrf_set_sun_direction(void* pipeline, const float direction[3]);
 int plrf_set_camera_intrinsic(void* pipeline, float fov_degrees, float near_plane, float far_plane);
 int plrf_set_camera_cut(void* pipeline);
+/* ---- live changes (RenderFrontend::setResolution, RenderFrontend.cpp:408-421, and the stale-flag branches of prepareNewFrame, :198-278): both calls only RECORD
+ * the change; it is applied at the start of the next plrf_frame, before the passes are recorded, or by plrf_apply_changes.
+ * plrf_set_resolution: every image and buffer whose size follows the screen (render targets, post-process buffers, TAA history, GI images at trace resolution and
+ * the upscale targets, HiZ pyramid, half-resolution depth, froxel volumes, swapchain, per-tile histogram, culled tiles) is re-created zero-filled, as plrf_create
+ * creates it, and the next frame is a camera cut; a resize to the size the images already have keeps them (only the cut). What survives: the light buffer
+ * (exposure), the frame counters and the TAA jitter position, SDF volumes and scene, sun direction, camera intrinsics but the aspect ratio, BRDF LUT, shadow maps,
+ * sky LUTs, noise textures. Inputs that follow the screen (G-buffer, and the froxel volume when run_volumetrics is 0) are the caller's to upload again.
+ * Width or height 0 = minimized (RenderFrontend.cpp:229): plrf_frame returns PLR_OK, records and launches nothing, counts nothing; the next non-zero size
+ * resumes with a camera cut.
+ * plrf_update_settings: the settings the reference's UI edits (:1882-2011) - taa_*, bloom_*, sdf_half_res_trace, sdf_strict_influence_radius_cutoff,
+ * sdf_trace_influence_radius, diffuse_brdf, direct_multiscatter, indirect_lighting_tech, use_geometry_aa, sdf_debug_*. A diffuse_brdf change re-bakes the BRDF LUT,
+ * a trace-resolution change re-creates the GI images (zero-filled) and cuts, a TAA change updates the pass descriptions only. Any other field that differs from
+ * the pipeline's returns PLR_ERR_UNSUPPORTED, a width / height other than the current resolution PLR_ERR_INVALID_ARGUMENT; the pipeline is then untouched.
+ * Partitioned pipelines (band_row_end or band_col_end non-zero) refuse both calls with PLR_ERR_UNSUPPORTED: the exchange plan and an attached exchange follow
+ * the frame size, and re-partitioning a live frame is out of scope. */
+int plrf_set_resolution(void* pipeline, uint32_t width, uint32_t height);
+int plrf_update_settings(void* pipeline, const plrf_settings* settings);
+int plrf_apply_changes(void* pipeline); /* apply what was recorded now: a caller uploads the new size's inputs after it */
 /* one iteration of the reference's main loop: record the frame, update camera/UBOs, submit (does not wait for the GPU) */
 int plrf_frame(void* pipeline, const plrf_camera* camera, float delta_time, float time);
 /* host copies of what the last plrf_frame submitted (340-byte global UBO image, 9 TAA resolve weights) */

@@ -144,6 +144,12 @@ public:
         for (const auto& i : images) h.push_back(toC(i));
         check(plr_resize_images(h.data(), (uint32_t)h.size(), width, height));
     }
+    // (extensions, plr.h) the same handle with another description; a storage buffer at another size
+    void recreateImage(const ImageHandle image, const ImageDescription& description) {
+        const plr_image_desc d = toC(description);
+        check(plr_recreate_image(toC(image), &d));
+    }
+    void resizeStorageBuffer(const StorageBufferHandle buffer, const size_t size) { check(plr_resize_storage_buffer(buffer.index, size)); }
     void newFrame() { check(plr_new_frame()); }
 
     void setComputePassExecution(const ComputePassExecution& execution) {

@@ -217,7 +217,7 @@ def _load():
 
 EXPORTED_SYMBOLS = [
     "plr_debug_pcf_tap_table", "plr_setup", "plr_shutdown", "plr_recreate_swapchain", "plr_last_error", "plr_wait_for_gpu_idle", "plr_update_shader_code",
-    "plr_resize_images", "plr_new_frame", "plr_set_compute_pass_execution", "plr_prepare_for_drawcall_recording",
+    "plr_resize_images", "plr_recreate_image", "plr_resize_storage_buffer", "plr_new_frame", "plr_set_compute_pass_execution", "plr_prepare_for_drawcall_recording",
     "plr_set_uniform_buffer_data", "plr_set_storage_buffer_data", "plr_set_global_descriptor_set_resources",
     "plr_update_compute_pass_shader_description", "plr_render_frame", "plr_get_image_global_texture_array_index",
     "plr_create_compute_pass", "plr_create_image", "plr_create_uniform_buffer", "plr_create_storage_buffer", "plr_create_sampler",

@@ -812,8 +812,43 @@ int plr_resize_images(const plr_image_handle* images, uint32_t count, uint32_t w
         freeImage(*im);
         int rc = allocImage(*im, d);
         if (rc) return rc;
+        hostWroteImage(*im); // zero-filled, as created: no longer the image a fused launch left unwritten
     }
     g->bindlessDirty = true;
+    return PLR_OK;
+}
+
+int plr_recreate_image(plr_image_handle image, const plr_image_desc* desc) {
+    NEED_INIT_JOINED();
+    if (!desc) return setErr(PLR_ERR_INVALID_ARGUMENT, "plr_recreate_image: desc is null");
+    if (image.type != PLR_IMAGE_DEFAULT) return setErr(PLR_ERR_INVALID_ARGUMENT, "only default images can be recreated");
+    ImageRes* im = resolveImage(image);
+    if (!im) return setErr(PLR_ERR_INVALID_ARGUMENT, "plr_recreate_image: invalid image handle");
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    freeImage(*im);
+    if (int rc = allocImage(*im, *desc)) return rc;
+    hostWroteImage(*im);
+    g->bindlessDirty = true;
+    return PLR_OK;
+}
+
+int plr_resize_storage_buffer(plr_storage_buffer_handle buffer, size_t size) {
+    NEED_INIT_JOINED();
+    if (buffer >= g->sbufs.size() || !g->sbufs[buffer].dev) return setErr(PLR_ERR_INVALID_ARGUMENT, "plr_resize_storage_buffer: invalid storage buffer handle");
+    if (size == 0) return setErr(PLR_ERR_INVALID_ARGUMENT, "plr_resize_storage_buffer: size is 0");
+    BufferRes& b = g->sbufs[buffer];
+    // a queued fill holds the old address (queueFill): it would land in freed memory
+    for (const auto& f : g->fills)
+        if (f.dst == b.dev) return setErr(PLR_ERR_INVALID_ARGUMENT, "plr_resize_storage_buffer: the buffer has a pending plr_set_storage_buffer_data");
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    HIP_TRY(hipFree(b.dev));
+    g->allocated -= b.size;
+    b.dev = nullptr; b.size = 0;
+    HIP_TRY(hipMalloc(&b.dev, (size + 15) & ~(size_t)15));
+    HIP_TRY(hipMemsetAsync(b.dev, 0, (size + 15) & ~(size_t)15, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    b.size = size;
+    g->allocated += size;
     return PLR_OK;
 }
 
@@ -1459,6 +1494,7 @@ static int launchExecution(Execution& x, hipStream_t stream, const GlobalUbo* gl
 // behind the last execution that writes (or the last host callback that may write) anything the early kernels read - and keeps the plan only if at least one
 // compute execution lies between that position and the sequence: something to run beside. launchEarlyPartsAt(i) issues the plans of position i on the early
 // stream before execution i is launched; tryFusedLaunch makes the launch stream wait for the part's event and tells the launcher (PassCtx::earlyPartDone).
+// (the plans are rebuilt from the recorded executions by every launchAll: no address outlives the frame, a resize cannot leave one stale)
 struct EarlyPlan { size_t at = 0, group = 0, count = 0; const FusionEntry* f = nullptr; hipEvent_t done = nullptr; bool launched = false; };
 static thread_local std::vector<EarlyPlan> g_earlyPlans;
 static bool fusionNamesMatch(const FusionEntry& f, size_t i, size_t n) {

@@ -43,31 +43,48 @@ int plrf_default_settings(plrf_settings* o, uint32_t width, uint32_t height) {
     return PLR_OK;
 }
 
+static FramePipelineSettings toPipelineSettings(const plrf_settings* s) {
+    FramePipelineSettings f;
+    f.width = s->width; f.height = s->height; f.shadowMapRes = s->shadow_map_res; f.brdfLutRes = s->brdf_lut_res; f.maxSdfInstances = s->max_sdf_instances;
+    f.froxelDepth = s->froxel_depth;
+    f.taa.enabled = s->taa_enabled; f.taa.useClipping = s->taa_use_clipping; f.taa.useMotionVectorDilation = s->taa_use_motion_vector_dilation;
+    f.taa.historySamplingTech = (HistorySamplingTech)s->taa_history_sampling_tech; f.taa.filterUseTonemapping = s->taa_filter_use_tonemapping;
+    f.bloom.enabled = s->bloom_enabled; f.bloom.strength = s->bloom_strength; f.bloom.radius = s->bloom_radius;
+    f.sdfTrace.halfResTrace = s->sdf_half_res_trace; f.sdfTrace.strictInfluenceRadiusCutoff = s->sdf_strict_influence_radius_cutoff;
+    f.sdfTrace.traceInfluenceRadius = s->sdf_trace_influence_radius;
+    f.shading.diffuseBRDF = (DiffuseBRDF)s->diffuse_brdf; f.shading.directMultiscatter = (DirectSpecularMultiscattering)s->direct_multiscatter;
+    f.shading.indirectLightingTech = (IndirectLightingTech)s->indirect_lighting_tech; f.shading.useGeometryAA = s->use_geometry_aa;
+    f.shading.sunShadowCascadeCount = (int)s->sun_shadow_cascade_count;
+    f.runExposure = s->run_exposure; f.runHiZ = s->run_hiz; f.runGI = s->run_gi; f.runShading = s->run_shading; f.runTAA = s->run_taa;
+    f.runBloom = s->run_bloom; f.runTonemap = s->run_tonemap;
+    f.band.rowBegin = s->band_row_begin; f.band.rowEnd = s->band_row_end; f.band.giHalo = s->band_gi_halo; f.band.giHistoryHalo = s->band_gi_history_halo;
+    f.band.colorHalo = s->band_color_halo; f.band.postHalo = s->band_post_halo;
+    f.band.colBegin = s->band_col_begin; f.band.colEnd = s->band_col_end;
+    f.runLightMatrix = s->run_light_matrix; f.volumetricsMaxDistance = s->volumetrics_max_distance; f.runSkyLuts = s->run_sky_luts; f.runVolumetrics = s->run_volumetrics; f.band.taaHistoryHalo = s->band_taa_history_halo; f.band.overlapExchange = s->band_overlap_exchange != 0; f.band.rowsFirst = s->band_overlap_exchange >= 2;
+    f.sdfDebug.visualisationMode = (SDFVisualisationMode)s->sdf_debug_mode; f.sdfDebug.showCameraTileUsageWithHiZ = s->sdf_debug_tile_usage_with_hiz;
+    f.sdfDebug.useInfluenceRadiusForDebug = s->sdf_debug_use_influence_radius;
+    f.taa.useSeparateSupersampling = s->taa_use_separate_supersampling; f.taa.supersampleUseTonemapping = s->taa_supersample_use_tonemapping;
+    return f;
+}
+
 int plrf_create(const plrf_settings* s, void** out) {
     if (!s || !out) return PLR_ERR_INVALID_ARGUMENT;
-    PLRF_TRY({
-        FramePipelineSettings f;
-        f.width = s->width; f.height = s->height; f.shadowMapRes = s->shadow_map_res; f.brdfLutRes = s->brdf_lut_res; f.maxSdfInstances = s->max_sdf_instances;
-        f.froxelDepth = s->froxel_depth;
-        f.taa.enabled = s->taa_enabled; f.taa.useClipping = s->taa_use_clipping; f.taa.useMotionVectorDilation = s->taa_use_motion_vector_dilation;
-        f.taa.historySamplingTech = (HistorySamplingTech)s->taa_history_sampling_tech; f.taa.filterUseTonemapping = s->taa_filter_use_tonemapping;
-        f.bloom.enabled = s->bloom_enabled; f.bloom.strength = s->bloom_strength; f.bloom.radius = s->bloom_radius;
-        f.sdfTrace.halfResTrace = s->sdf_half_res_trace; f.sdfTrace.strictInfluenceRadiusCutoff = s->sdf_strict_influence_radius_cutoff;
-        f.sdfTrace.traceInfluenceRadius = s->sdf_trace_influence_radius;
-        f.shading.diffuseBRDF = (DiffuseBRDF)s->diffuse_brdf; f.shading.directMultiscatter = (DirectSpecularMultiscattering)s->direct_multiscatter;
-        f.shading.indirectLightingTech = (IndirectLightingTech)s->indirect_lighting_tech; f.shading.useGeometryAA = s->use_geometry_aa;
-        f.shading.sunShadowCascadeCount = (int)s->sun_shadow_cascade_count;
-        f.runExposure = s->run_exposure; f.runHiZ = s->run_hiz; f.runGI = s->run_gi; f.runShading = s->run_shading; f.runTAA = s->run_taa;
-        f.runBloom = s->run_bloom; f.runTonemap = s->run_tonemap;
-        f.band.rowBegin = s->band_row_begin; f.band.rowEnd = s->band_row_end; f.band.giHalo = s->band_gi_halo; f.band.giHistoryHalo = s->band_gi_history_halo;
-        f.band.colorHalo = s->band_color_halo; f.band.postHalo = s->band_post_halo;
-        f.band.colBegin = s->band_col_begin; f.band.colEnd = s->band_col_end;
-        f.runLightMatrix = s->run_light_matrix; f.volumetricsMaxDistance = s->volumetrics_max_distance; f.runSkyLuts = s->run_sky_luts; f.runVolumetrics = s->run_volumetrics; f.band.taaHistoryHalo = s->band_taa_history_halo; f.band.overlapExchange = s->band_overlap_exchange != 0; f.band.rowsFirst = s->band_overlap_exchange >= 2;
-        f.sdfDebug.visualisationMode = (SDFVisualisationMode)s->sdf_debug_mode; f.sdfDebug.showCameraTileUsageWithHiZ = s->sdf_debug_tile_usage_with_hiz;
-        f.sdfDebug.useInfluenceRadiusForDebug = s->sdf_debug_use_influence_radius;
-        f.taa.useSeparateSupersampling = s->taa_use_separate_supersampling; f.taa.supersampleUseTonemapping = s->taa_supersample_use_tonemapping;
-        *out = new FramePipeline(f);
-    })
+    PLRF_TRY(*out = new FramePipeline(toPipelineSettings(s)))
+}
+
+// a refusal keeps its code (PLR_ERR_UNSUPPORTED / PLR_ERR_INVALID_ARGUMENT); anything else that throws is PLRF_TRY's PLR_ERR_INVALID_ARGUMENT
+#define PLRF_TRY_REFUSAL(...) try { __VA_ARGS__; return PLR_OK; } catch (const FramePipelineRefusal& e) { g_ferr = e.what(); return e.code; } catch (const std::exception& e) { return fail(e); }
+int plrf_set_resolution(void* p, uint32_t width, uint32_t height) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL(((FramePipeline*)p)->setResolution(width, height))
+}
+int plrf_update_settings(void* p, const plrf_settings* s) {
+    if (!p || !s) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL(((FramePipeline*)p)->updateSettings(toPipelineSettings(s)))
+}
+int plrf_apply_changes(void* p) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY(((FramePipeline*)p)->applyPendingChanges())
 }
 
 int plrf_destroy(void* p) { delete (FramePipeline*)p; return PLR_OK; }

@@ -183,6 +183,16 @@ void TAA::init(RenderBackend& be, int w, int h, const TAASettings& settings) { /
     for (auto& b : m_taaResolveWeightBuffers) b = be.createUniformBuffer(ub);
     m_taaResolveWeightBuffer = m_taaResolveWeightBuffers[0];
 }
+void TAA::resizeImages(RenderBackend& be, int w, int h) { // TAA.cpp:69-78
+    be.resizeImages({m_historyBuffers[0], m_historyBuffers[1], m_sceneLuminance[0], m_sceneLuminance[1]}, w, h);
+}
+void TAA::updateSettings(RenderBackend& be, const TAASettings& settings) { // TAA.cpp:80-83
+    be.updateComputePassShaderDescription(m_temporalFilterPass, temporalFilterShaderDescription(settings));
+    ShaderDescription sd;
+    sd.srcPathRelative = "temporalSupersampling.comp";
+    sd.specialisationConstants = {spec(0, settings.supersampleUseTonemapping)};
+    be.updateComputePassShaderDescription(m_temporalSupersamplingPass, sd);
+}
 void TAA::computeTemporalFilter(RenderBackend& be, const FrameIndexCounter& fi, ImageHandle colorSrc, const FrameRenderTargets& currentFrame, ImageHandle target,
                                 RowRange rows, uint32_t edgeRows, const std::function<void()>& edgesDone, bool rowsFirst, ColRange cols) const {
     // TAA.cpp:139-166
@@ -362,6 +372,28 @@ static const size_t sdfCameraCullingTileSize = 32; // SDFGI.cpp:10
 static const size_t maxSdfObjectsPerTile = 100;    // SDFGI.cpp:11
 static const size_t sdfInstanceSize = 96;          // sizeof(SDFInstance), SDFGI.h:31-37
 
+// the reference sizes the culled-tile buffer for 1920x1080 only (SDFGI.cpp:145-151); sized here for the tile-index range the shaders
+// produce: stride = ceil(screenW / 32) (full-res, sdfCulling.inc:17-20) times the trace image's tile rows
+static size_t culledTilesBytes(int screenW, int screenH, uint32_t th) {
+    const size_t strideX = (size_t)std::ceil(screenW / float(sdfCameraCullingTileSize));
+    // (the debug visualisation culls at full resolution, SDFGI.cpp:340-350: rows for the full screen height)
+    const size_t rows = (size_t)std::ceil(std::max<uint32_t>(th, (uint32_t)screenH) / float(sdfCameraCullingTileSize));
+    const size_t tileSize = maxSdfObjectsPerTile * sizeof(uint32_t) + sizeof(uint32_t);
+    return strideX * std::max<size_t>(rows, 1) * tileSize;
+}
+static ShaderDescription sdfDebugShaderDescription(const SDFDebugSettings& ds, int sunShadowCascadeIndex) { // createSDFDebugShaderDescription, SDFGI.cpp:13-28
+    ShaderDescription d;
+    d.srcPathRelative = "sdfDebugVisualisation.comp";
+    d.specialisationConstants = {spec(0, ds.visualisationMode), spec(1, sunShadowCascadeIndex)};
+    return d;
+}
+static ShaderDescription sdfDiffuseTraceShaderDescription(const SDFTraceSettings& ts, int sunShadowCascadeIndex) { // createSDFDiffuseTraceShaderDescription, SDFGI.cpp:30-46
+    ShaderDescription d;
+    d.srcPathRelative = "sdfDiffuseTrace.comp";
+    d.specialisationConstants = {spec(0, ts.strictInfluenceRadiusCutoff), spec(1, sunShadowCascadeIndex)};
+    return d;
+}
+
 void SDFGI::init(RenderBackend& be, int screenW, int screenH, const SDFTraceSettings& ts, const SDFDebugSettings& ds, int sunShadowCascadeIndex, uint32_t maxInstances) { // SDFGI.cpp:48-258
     const uint32_t tw = ts.halfResTrace ? screenW / 2 : screenW, th = ts.halfResTrace ? screenH / 2 : screenH;
     for (int i = 0; i < 2; i++) {
@@ -382,30 +414,20 @@ void SDFGI::init(RenderBackend& be, int screenW, int screenH, const SDFTraceSett
     m_cameraFrustumBuffer = be.createUniformBuffer(ub);
     sb.size = maxInstances * 2 * 4 * sizeof(float);
     m_sdfInstanceWorldBBBuffer = be.createStorageBuffer(sb);
-    {
-        // the reference sizes this for 1920x1080 only (SDFGI.cpp:145-151); sized here for the tile-index range the shaders
-        // produce: stride = ceil(screenW / 32) (full-res, sdfCulling.inc:17-20) times the trace image's tile rows
-        const size_t strideX = (size_t)std::ceil(screenW / float(sdfCameraCullingTileSize));
-        // (the debug visualisation culls at full resolution, SDFGI.cpp:340-350: rows for the full screen height)
-        const size_t rows = (size_t)std::ceil(std::max<uint32_t>(th, (uint32_t)screenH) / float(sdfCameraCullingTileSize));
-        const size_t tileSize = maxSdfObjectsPerTile * sizeof(uint32_t) + sizeof(uint32_t);
-        sb.size = strideX * std::max<size_t>(rows, 1) * tileSize;
-        m_sdfCameraCulledTiles = be.createStorageBuffer(sb);
-    }
+    sb.size = culledTilesBytes(screenW, screenH, th);
+    m_sdfCameraCulledTiles = be.createStorageBuffer(sb);
     ub.size = sizeof(float);
     m_sdfTraceInfluenceRangeBuffer = be.createUniformBuffer(ub);
     {
-        ComputePassDescription d; // createSDFDebugShaderDescription, SDFGI.cpp:13-28
+        ComputePassDescription d;
         d.name = "Visualize SDF";
-        d.shaderDescription.srcPathRelative = "sdfDebugVisualisation.comp";
-        d.shaderDescription.specialisationConstants = {spec(0, ds.visualisationMode), spec(1, sunShadowCascadeIndex)};
+        d.shaderDescription = sdfDebugShaderDescription(ds, sunShadowCascadeIndex);
         m_sdfDebugVisualisationPass = be.createComputePass(d);
     }
     {
         ComputePassDescription d;
         d.name = "Indirect diffuse SDF trace";
-        d.shaderDescription.srcPathRelative = "sdfDiffuseTrace.comp";
-        d.shaderDescription.specialisationConstants = {spec(0, ts.strictInfluenceRadiusCutoff), spec(1, sunShadowCascadeIndex)};
+        d.shaderDescription = sdfDiffuseTraceShaderDescription(ts, sunShadowCascadeIndex);
         m_diffuseSDFTracePass = be.createComputePass(d);
     }
     for (int i = 0; i < 2; i++) {
@@ -448,6 +470,20 @@ void SDFGI::init(RenderBackend& be, int screenW, int screenH, const SDFTraceSett
         d.shaderDescription.specialisationConstants = {spec(0, useHiZ)};
         (useHiZ ? m_sdfCameraTileCullingHiZ : m_sdfCameraTileCulling) = be.createComputePass(d);
     }
+}
+
+void SDFGI::resize(RenderBackend& be, int screenW, int screenH, const SDFTraceSettings& ts) { // SDFGI.cpp:237-258
+    const uint32_t tw = ts.halfResTrace ? screenW / 2 : screenW, th = ts.halfResTrace ? screenH / 2 : screenH;
+    be.resizeImages({m_indirectDiffuse_Y_SH[0], m_indirectDiffuse_Y_SH[1], m_indirectDiffuse_CoCg[0], m_indirectDiffuse_CoCg[1], m_indirectDiffuseHistory_Y_SH[0],
+                     m_indirectDiffuseHistory_Y_SH[1], m_indirectDiffuseHistory_CoCg[0], m_indirectDiffuseHistory_CoCg[1]}, tw, th);
+    be.resizeImages({m_indirectLightingFullRes_Y_SH, m_indirectLightingFullRes_CoCg}, screenW, screenH);
+    be.resizeStorageBuffer(m_sdfCameraCulledTiles, culledTilesBytes(screenW, screenH, th));
+    m_giRequestRowWords = (tw + 31u) / 32u;
+    for (int i = 0; i < 2; i++) be.resizeStorageBuffer(m_giRequestBitmap[i], (size_t)m_giRequestRowWords * th * sizeof(uint32_t));
+}
+void SDFGI::updateSettings(RenderBackend& be, const SDFTraceSettings& ts, const SDFDebugSettings& ds, int sunShadowCascadeIndex) { // SDFGI.cpp:371-378
+    be.updateComputePassShaderDescription(m_sdfDebugVisualisationPass, sdfDebugShaderDescription(ds, sunShadowCascadeIndex));
+    be.updateComputePassShaderDescription(m_diffuseSDFTracePass, sdfDiffuseTraceShaderDescription(ts, sunShadowCascadeIndex));
 }
 
 void SDFGI::updateSDFScene(RenderBackend& be, const void* instanceData, size_t instanceBytes, const void* bbData, size_t bbBytes) { // SDFGI.cpp:260-313
@@ -683,7 +719,52 @@ static const uint32_t maxPyramidMipCount = 11; // depthHiZPyramid.comp binds at 
 static bool perTilePyramid(const FramePipelineSettings& s) { return s.band.enabled() || mipCountFromResolution(s.width / 2, s.height / 2, 1) > maxPyramidMipCount; }
 static uint32_t pyramidMipCount(const FramePipelineSettings& s) { return perTilePyramid(s) ? bandPyramidMipCount : mipCountFromResolution(s.width / 2, s.height / 2, 1); }
 
-FramePipeline::FramePipeline(const FramePipelineSettings& s) : settings(s) {
+// createForwardPassShaderDescription, RenderFrontend.cpp:1093-1131, as the deferred compute pass
+static ShaderDescription forwardPassShaderDescription(const ShadingConfig& c) {
+    ShaderDescription d;
+    d.srcPathRelative = "deferredShading.comp";
+    d.specialisationConstants = {spec(0, c.diffuseBRDF), spec(1, c.directMultiscatter), spec(2, c.useGeometryAA), spec(3, c.indirectLightingTech), spec(4, c.sunShadowCascadeCount)};
+    return d;
+}
+static ShaderDescription brdfLutShaderDescription(const ShadingConfig& c) { // createBRDFLutShaderDescription
+    ShaderDescription d;
+    d.srcPathRelative = "brdfLut.comp";
+    d.specialisationConstants = {spec(0, c.diffuseBRDF)};
+    return d;
+}
+// createDepthPyramidShaderDescription, RenderFrontend.cpp:1770-1805; sets m_depthPyramidThreadgroupCount
+ShaderDescription FramePipeline::depthPyramidShaderDescription() {
+    const uint32_t W = settings.width, H = settings.height;
+    ShaderDescription d;
+    d.srcPathRelative = "depthHiZPyramid.comp";
+    const uint32_t pw = W / 2, ph = H / 2;
+    const uint32_t depthMipCount = pyramidMipCount(settings);
+    uint32_t dc[2];
+    singlePassMipChainDispatchCount(pw, ph, depthMipCount, 11, dc);
+    m_depthPyramidThreadgroupCount = dc[0] * dc[1];
+    d.specialisationConstants = {spec(0, depthMipCount), spec(1, W), spec(2, H), spec(3, m_depthPyramidThreadgroupCount)};
+    return d;
+}
+static ImageDescription depthPyramidDescription(const FramePipelineSettings& s) {
+    return perTilePyramid(s)
+        ? desc2D(s.width / 2, s.height / 2, ImageFormat::RG32_sFloat, ImageUsageFlags::Storage | ImageUsageFlags::Sampled, MipCount::Manual, bandPyramidMipCount)
+        : desc2D(s.width / 2, s.height / 2, ImageFormat::RG32_sFloat, ImageUsageFlags::Storage | ImageUsageFlags::Sampled, MipCount::FullChain);
+}
+static uint32_t histogramTileCount(uint32_t W, uint32_t H) { return (uint32_t)std::ceil(W / float(histogramTileSizeX)) * (uint32_t)std::ceil(H / float(histogramTileSizeY)); }
+static ShaderDescription histogramPerTileShaderDescription(uint32_t W, uint32_t H) {
+    ShaderDescription d;
+    d.srcPathRelative = "histogramPerTile.comp";
+    d.specialisationConstants = {spec(0, nHistogramBins), spec(1, histogramMinValue), spec(2, histogramMaxValue), spec(3, (int)histogramTileCount(W, H))};
+    return d;
+}
+static ShaderDescription histogramCombineShaderDescription(uint32_t W, uint32_t H) {
+    ShaderDescription d;
+    d.srcPathRelative = "histogramCombineTiles.comp";
+    d.specialisationConstants = {spec(0, nHistogramBins), spec(1, (int)histogramTileCount(W, H))};
+    return d;
+}
+
+FramePipeline::FramePipeline(const FramePipelineSettings& s) : settings(s), m_requestedSettings(s), m_targetWidth(s.width), m_targetHeight(s.height) {
     const uint32_t W = s.width, H = s.height;
     if (s.band.enabled()) {
         const BandSettings& b = s.band;
@@ -719,7 +800,7 @@ FramePipeline::FramePipeline(const FramePipelineSettings& s) : settings(s) {
     sb.size = sizeof(lightInit); sb.initialData = lightInit;
     m_lightBuffer = m_be.createStorageBuffer(sb);
     sb.initialData = nullptr;
-    const uint32_t tileCount = (uint32_t)std::ceil(W / float(histogramTileSizeX)) * (uint32_t)std::ceil(H / float(histogramTileSizeY));
+    const uint32_t tileCount = histogramTileCount(W, H);
     sb.size = (size_t)tileCount * nHistogramBins * sizeof(uint32_t); // the reference allocates for 1920x1080 only (:1069-1070)
     m_histogramPerTileBuffer = m_be.createStorageBuffer(sb);
     sb.size = sizeof(uint32_t);
@@ -745,9 +826,7 @@ FramePipeline::FramePipeline(const FramePipelineSettings& s) : settings(s) {
     m_worldSpaceNormalImage = m_be.createImage(desc2D(W, H, ImageFormat::RGBA8), nullptr, 0);
     m_albedoImage = m_be.createImage(desc2D(W, H, ImageFormat::RGBA8), nullptr, 0);
     m_specularImage = m_be.createImage(desc2D(W, H, ImageFormat::RGBA8), nullptr, 0);
-    m_minMaxDepthPyramid = perTilePyramid(s)
-        ? m_be.createImage(desc2D(W / 2, H / 2, ImageFormat::RG32_sFloat, ImageUsageFlags::Storage | ImageUsageFlags::Sampled, MipCount::Manual, bandPyramidMipCount), nullptr, 0)
-        : m_be.createImage(desc2D(W / 2, H / 2, ImageFormat::RG32_sFloat, ImageUsageFlags::Storage | ImageUsageFlags::Sampled, MipCount::FullChain), nullptr, 0);
+    m_minMaxDepthPyramid = m_be.createImage(depthPyramidDescription(s), nullptr, 0);
     // band rendering: the depth range of the whole frame (lightMatrix.comp's "lowest mip"), reduced from the band's per-tile pyramids and all-reduced
     m_bandDepthApex = m_be.createImage(desc2D(1, 1, ImageFormat::RG32_sFloat), nullptr, 0);
     m_depthHalfRes = m_be.createImage(desc2D(W / 2, H / 2, ImageFormat::R16_sFloat), nullptr, 0);
@@ -770,18 +849,15 @@ FramePipeline::FramePipeline(const FramePipelineSettings& s) : settings(s) {
     // ---- initRenderpasses (RenderFrontend.cpp:1618-1760)
     {
         ComputePassDescription d;
-        const int nTiles = (int)tileCount;
         d.name = "Histogram per tile";
-        d.shaderDescription.srcPathRelative = "histogramPerTile.comp";
-        d.shaderDescription.specialisationConstants = {spec(0, nHistogramBins), spec(1, histogramMinValue), spec(2, histogramMaxValue), spec(3, nTiles)};
+        d.shaderDescription = histogramPerTileShaderDescription(W, H);
         m_histogramPerTilePass = m_be.createComputePass(d);
         d.name = "Histogram reset";
         d.shaderDescription.srcPathRelative = "histogramReset.comp";
         d.shaderDescription.specialisationConstants = {spec(0, nHistogramBins)};
         m_histogramResetPass = m_be.createComputePass(d);
         d.name = "Histogram combine tiles";
-        d.shaderDescription.srcPathRelative = "histogramCombineTiles.comp";
-        d.shaderDescription.specialisationConstants = {spec(0, nHistogramBins), spec(1, nTiles)};
+        d.shaderDescription = histogramCombineShaderDescription(W, H);
         m_histogramCombinePass = m_be.createComputePass(d);
         d.name = "Pre-expose lights";
         d.shaderDescription.srcPathRelative = "preExposeLights.comp";
@@ -795,30 +871,19 @@ FramePipeline::FramePipeline(const FramePipelineSettings& s) : settings(s) {
         d.shaderDescription.srcPathRelative = "depthDownscale.comp";
         m_depthDownscalePass = m_be.createComputePass(d);
         d.name = "BRDF Lut creation";
-        d.shaderDescription.srcPathRelative = "brdfLut.comp";
-        d.shaderDescription.specialisationConstants = {spec(0, s.shading.diffuseBRDF)};
+        d.shaderDescription = brdfLutShaderDescription(s.shading);
         m_brdfLutPass = m_be.createComputePass(d);
     }
     {
-        // createDepthPyramidShaderDescription, RenderFrontend.cpp:1770-1805
         ComputePassDescription d;
         d.name = "Depth min/max pyramid";
-        d.shaderDescription.srcPathRelative = "depthHiZPyramid.comp";
-        const uint32_t pw = W / 2, ph = H / 2;
-        const uint32_t depthMipCount = pyramidMipCount(s);
-        uint32_t dc[2];
-        singlePassMipChainDispatchCount(pw, ph, depthMipCount, 11, dc);
-        m_depthPyramidThreadgroupCount = dc[0] * dc[1];
-        d.shaderDescription.specialisationConstants = {spec(0, depthMipCount), spec(1, W), spec(2, H), spec(3, m_depthPyramidThreadgroupCount)};
+        d.shaderDescription = depthPyramidShaderDescription();
         m_depthPyramidPass = m_be.createComputePass(d);
     }
     {
-        // createForwardPassShaderDescription, RenderFrontend.cpp:1093-1131, as the deferred compute pass
         ComputePassDescription d;
         d.name = "Forward shading (deferred)";
-        d.shaderDescription.srcPathRelative = "deferredShading.comp";
-        d.shaderDescription.specialisationConstants = {spec(0, s.shading.diffuseBRDF), spec(1, s.shading.directMultiscatter), spec(2, s.shading.useGeometryAA),
-                                                       spec(3, s.shading.indirectLightingTech), spec(4, s.shading.sunShadowCascadeCount)};
+        d.shaderDescription = forwardPassShaderDescription(s.shading);
         m_deferredShadingPass = m_be.createComputePass(d);
     }
     {
@@ -1529,7 +1594,129 @@ void FramePipeline::updateGlobalShaderInfo(float deltaTime, float time) { // Ren
     m_submittedGlobals = g;
 }
 
+// ------------------------------------------------------------------ live changes (RenderFrontend::setResolution, the UI's stale flags)
+static bool sameTaa(const TAASettings& a, const TAASettings& b) {
+    return a.enabled == b.enabled && a.useSeparateSupersampling == b.useSeparateSupersampling && a.useClipping == b.useClipping &&
+           a.useMotionVectorDilation == b.useMotionVectorDilation && a.historySamplingTech == b.historySamplingTech &&
+           a.supersampleUseTonemapping == b.supersampleUseTonemapping && a.filterUseTonemapping == b.filterUseTonemapping && a.useMipBias == b.useMipBias;
+}
+static bool sameShading(const ShadingConfig& a, const ShadingConfig& b) {
+    return a.diffuseBRDF == b.diffuseBRDF && a.directMultiscatter == b.directMultiscatter && a.indirectLightingTech == b.indirectLightingTech &&
+           a.useGeometryAA == b.useGeometryAA && a.sunShadowCascadeCount == b.sunShadowCascadeCount;
+}
+static bool sameDebug(const SDFDebugSettings& a, const SDFDebugSettings& b) {
+    return a.visualisationMode == b.visualisationMode && a.showCameraTileUsageWithHiZ == b.showCameraTileUsageWithHiZ && a.useInfluenceRadiusForDebug == b.useInfluenceRadiusForDebug;
+}
+// the first field updateSettings may not change that differs, or null: everything but the live settings (TAA, bloom, SDF trace / debug, shading config
+// without the cascade count) and the resolution
+static const char* fixedFieldChanged(const FramePipelineSettings& a, const FramePipelineSettings& b) {
+    if (a.shadowMapRes != b.shadowMapRes) return "shadow_map_res";
+    if (a.brdfLutRes != b.brdfLutRes) return "brdf_lut_res";
+    if (a.maxSdfInstances != b.maxSdfInstances) return "max_sdf_instances";
+    if (a.froxelDepth != b.froxelDepth) return "froxel_depth";
+    if (a.shading.sunShadowCascadeCount != b.shading.sunShadowCascadeCount) return "sun_shadow_cascade_count";
+    if (a.sdfTrace.additionalSunShadowMapPadding != b.sdfTrace.additionalSunShadowMapPadding) return "additional sun shadow map padding";
+    if (a.runExposure != b.runExposure || a.runHiZ != b.runHiZ || a.runGI != b.runGI || a.runShading != b.runShading || a.runTAA != b.runTAA || a.runBloom != b.runBloom ||
+        a.runTonemap != b.runTonemap || a.runLightMatrix != b.runLightMatrix || a.runVolumetrics != b.runVolumetrics || a.runSkyLuts != b.runSkyLuts)
+        return "run_*";
+    if (a.volumetricsMaxDistance != b.volumetricsMaxDistance) return "volumetrics_max_distance";
+    const BandSettings &x = a.band, &y = b.band;
+    if (x.rowBegin != y.rowBegin || x.rowEnd != y.rowEnd || x.colBegin != y.colBegin || x.colEnd != y.colEnd || x.giHalo != y.giHalo || x.giRequested != y.giRequested ||
+        x.giHistoryHalo != y.giHistoryHalo || x.colorHalo != y.colorHalo || x.postHalo != y.postHalo || x.taaHistoryHalo != y.taaHistoryHalo ||
+        x.overlapExchange != y.overlapExchange || x.rowsFirst != y.rowsFirst)
+        return "band_*";
+    return nullptr;
+}
+
+void FramePipeline::setResolution(uint32_t width, uint32_t height) { // RenderFrontend.cpp:408-421
+    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setResolution: a band / tile pipeline cannot change size (its exchange plan follows the frame size)");
+    m_targetWidth = width; m_targetHeight = height;
+    m_minimized = width == 0 || height == 0;
+    if (!m_minimized) m_resolutionChanged = true;
+}
+
+void FramePipeline::updateSettings(const FramePipelineSettings& n) {
+    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "updateSettings: a band / tile pipeline cannot change its settings");
+    if (n.width != m_targetWidth || n.height != m_targetHeight)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "updateSettings: width / height differ from the current resolution (resize with setResolution)");
+    if (const char* field = fixedFieldChanged(n, m_requestedSettings))
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, std::string("updateSettings: ") + field + " is fixed for the pipeline's lifetime");
+    m_pendingSettings = n;
+    m_settingsChanged = true;
+}
+
+void FramePipeline::applyPendingChanges() { // RenderFrontend::prepareNewFrame, RenderFrontend.cpp:199-264
+    if (m_resolutionChanged && !m_minimized) { // (a size recorded before a minimize is applied with the next non-zero size)
+        applyResolution(m_targetWidth, m_targetHeight);
+        m_resolutionChanged = false;
+    }
+    if (m_minimized) return; // (:229) what the UI changed stays pending
+    if (m_settingsChanged) {
+        applySettings(m_pendingSettings);
+        m_settingsChanged = false;
+    }
+}
+
+// RenderFrontend.cpp:199-222 with TAA::resizeImages, Volumetrics::resizeTextures (Volumetrics.cpp:123-133) and SDFGI::resize. Every image and buffer the constructor
+// sizes from the screen is re-created as the constructor creates it (zero-filled); what does not follow the screen - the light buffer, the frame counters, the
+// SDF volumes and scene, the BRDF LUT, shadow maps, sky LUTs, noise textures - is left as it is.
+void FramePipeline::applyResolution(uint32_t W, uint32_t H) {
+    // (before the first frame there is no history to cut from: the pipeline then equals one created at the new size, byte for byte)
+    if (m_frameIndex.frameIndex > 0) setCameraCut();
+    if (W == settings.width && H == settings.height) return; // back from minimized at the same size: the images are kept
+    m_be.recreateSwapchain(W, H);
+    settings.width = W; settings.height = H;
+    const BandSettings& rb = m_requestedSettings.band; // the constructor's clamps (they follow the size)
+    settings.band.giHalo = rb.giHalo == 0xfffffffeu ? 0u : std::min(rb.giHalo, std::max(W, H));
+    settings.band.giHistoryHalo = std::min(rb.giHistoryHalo, std::max(W, H));
+    m_cameraIntrinsic.aspectRatio = (float)W / (float)H;
+    m_be.resizeImages({m_frameRenderTargets[0].motionBuffer, m_frameRenderTargets[1].motionBuffer, m_frameRenderTargets[0].colorBuffer, m_frameRenderTargets[0].depthBuffer,
+                       m_frameRenderTargets[1].colorBuffer, m_frameRenderTargets[1].depthBuffer, m_postProcessBuffers[0], m_postProcessBuffers[1], m_worldSpaceNormalImage,
+                       m_albedoImage, m_specularImage},
+                      W, H);
+    m_be.resizeImages({m_depthHalfRes}, W / 2, H / 2);
+    m_be.recreateImage(m_minMaxDepthPyramid, depthPyramidDescription(settings)); // (its mip layout follows the size: full chain or per tile)
+    m_be.updateComputePassShaderDescription(m_depthPyramidPass, depthPyramidShaderDescription());
+    m_taa.resizeImages(m_be, W, H);
+    // the froxel volumes (Volumetrics.cpp:123-133); also when they are inputs (run_volumetrics off): the constructor sizes the integration volume from the screen
+    m_be.resizeImages({m_volumetricIntegrationVolume, m_scatteringTransmittanceVolume, m_volumetricLightingHistory[0], m_volumetricLightingHistory[1], m_volumeMaterialVolume},
+                      (uint32_t)std::ceil(W / 8.f), (uint32_t)std::ceil(H / 8.f));
+    m_sdfGi.resize(m_be, W, H, settings.sdfTrace);
+    m_be.resizeStorageBuffer(m_histogramPerTileBuffer, (size_t)histogramTileCount(W, H) * nHistogramBins * sizeof(uint32_t));
+    m_be.updateComputePassShaderDescription(m_histogramPerTilePass, histogramPerTileShaderDescription(W, H));
+    m_be.updateComputePassShaderDescription(m_histogramCombinePass, histogramCombineShaderDescription(W, H));
+}
+
+// the stale-flag branches of prepareNewFrame (RenderFrontend.cpp:235-264) for what the UI edits (:1882-2011)
+void FramePipeline::applySettings(const FramePipelineSettings& n) {
+    const FramePipelineSettings old = settings;
+    settings.taa = n.taa;
+    settings.bloom = n.bloom; // read by every frame's recording
+    settings.sdfTrace.halfResTrace = n.sdfTrace.halfResTrace;
+    settings.sdfTrace.strictInfluenceRadiusCutoff = n.sdfTrace.strictInfluenceRadiusCutoff;
+    settings.sdfTrace.traceInfluenceRadius = n.sdfTrace.traceInfluenceRadius;
+    settings.sdfDebug = n.sdfDebug;
+    settings.shading = n.shading; // (the cascade count is fixed: updateSettings refused a change)
+    if (!sameShading(old.shading, settings.shading)) // m_isMainPassShaderDescriptionStale
+        m_be.updateComputePassShaderDescription(m_deferredShadingPass, forwardPassShaderDescription(settings.shading));
+    if (old.shading.diffuseBRDF != settings.shading.diffuseBRDF) { // m_isBRDFLutShaderDescriptionStale (:1976): re-baked by the next prepareRenderpasses
+        m_be.updateComputePassShaderDescription(m_brdfLutPass, brdfLutShaderDescription(settings.shading));
+        m_isBRDFLutShaderDescriptionStale = true;
+    }
+    if (!sameTaa(old.taa, settings.taa)) m_taa.updateSettings(m_be, settings.taa); // m_taaSettingsChanged: the pass descriptions only
+    if (!sameDebug(old.sdfDebug, settings.sdfDebug) || old.sdfTrace.strictInfluenceRadiusCutoff != settings.sdfTrace.strictInfluenceRadiusCutoff)
+        m_sdfGi.updateSettings(m_be, settings.sdfTrace, settings.sdfDebug, settings.shading.sunShadowCascadeCount - 1);
+    if (old.sdfTrace.halfResTrace != settings.sdfTrace.halfResTrace) { // m_sdfTraceResolutionChanged (:257-262)
+        m_sdfGi.resize(m_be, settings.width, settings.height, settings.sdfTrace);
+        setCameraCut();
+    }
+}
+
 void FramePipeline::frame(const CameraExtrinsic& camera, float deltaTime, float time) { // Runtime/main.cpp:79-90
+    applyPendingChanges();
+    if (m_minimized) return; // (RenderFrontend.cpp:229, 525, 537, 687) nothing recorded, launched or counted
     m_frameIndex.markNewFrame();
     m_taa.rotateWeightBuffer(); // before the passes are recorded: they bind the buffer this frame's weights are written to
     m_lastDeltaTime = deltaTime; // Timer::getDeltaTimeFloat() of this frame (Volumetrics.cpp:124)

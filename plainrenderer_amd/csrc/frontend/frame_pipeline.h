@@ -8,6 +8,7 @@
 #include <array>
 #include <string>
 #include <functional>
+#include <stdexcept>
 #include <vector>
 
 #include "../../../include/plr_render_backend.hpp"
@@ -155,6 +156,8 @@ public:
     void computeTemporalFilter(RenderBackend& be, const FrameIndexCounter& fi, ImageHandle colorSrc, const FrameRenderTargets& currentFrame, ImageHandle target,
                                RowRange rows = {}, uint32_t edgeRows = 0, const std::function<void()>& edgesDone = nullptr, bool rowsFirst = false, ColRange cols = {}) const;
     ImageHandle historyDst(const FrameIndexCounter& fi) const { return m_historyBuffers[(fi.mod2() + 1) % 2]; }
+    void resizeImages(RenderBackend& be, int imageWidth, int imageHeight);         // TAA::resizeImages (TAA.cpp:69-83)
+    void updateSettings(RenderBackend& be, const TAASettings& settings);            // TAA::updateSettings: the pass descriptions only
     // TAASettings::useSeparateSupersampling (TAA.cpp:85-137): luminance of the current frame, then a 2-frame blend with contrast / depth rejection
     void computeTemporalSuperSampling(RenderBackend& be, const FrameIndexCounter& fi, const FrameRenderTargets& currentFrame, const FrameRenderTargets& lastFrame,
                                       ImageHandle target, RowRange rows = {}) const;
@@ -229,6 +232,11 @@ public:
     void computeIndirectLighting(RenderBackend& be, const FrameIndexCounter& fi, const SDFTraceDependencies& deps, const SDFTraceSettings& s, const GiBand* band = nullptr) const;
     struct IndirectLightingImages { ImageHandle Y_SH, CoCg; };
     IndirectLightingImages getIndirectLightingResults(bool tracedHalfRes) const;
+    // SDFGI::resize (SDFGI.cpp:237-258): the trace-resolution images (full or half, traceSettings.halfResTrace) and the full-resolution upscale targets, plus the
+    // buffers sized from the screen (culled tiles, request bitmaps)
+    void resize(RenderBackend& be, int screenW, int screenH, const SDFTraceSettings& traceSettings);
+    // SDFGI::updateSDFDebugSettings / updateSDFTraceSettings: the pass descriptions
+    void updateSettings(RenderBackend& be, const SDFTraceSettings& traceSettings, const SDFDebugSettings& debugSettings, int sunShadowCascadeIndex);
     ImageHandle m_indirectDiffuse_Y_SH[2], m_indirectDiffuse_CoCg[2], m_indirectDiffuseHistory_Y_SH[2], m_indirectDiffuseHistory_CoCg[2];
     ImageHandle m_indirectLightingFullRes_Y_SH, m_indirectLightingFullRes_CoCg;
     StorageBufferHandle m_sdfInstanceBuffer, m_sdfCameraFrustumCulledInstances, m_sdfInstanceWorldBBBuffer, m_sdfCameraCulledTiles;
@@ -297,9 +305,28 @@ struct FramePipelineSettings {
     float volumetricsMaxDistance = 30.f; // VolumetricsSettings::maxDistance, the last cascade's minimum far plane
 };
 
+// a change FramePipeline::setResolution / updateSettings refuses; code = PLR_ERR_UNSUPPORTED or PLR_ERR_INVALID_ARGUMENT (plr.h)
+struct FramePipelineRefusal : std::runtime_error {
+    int code;
+    FramePipelineRefusal(int c, const std::string& what) : std::runtime_error(what), code(c) {}
+};
+
 class FramePipeline {
 public:
     explicit FramePipeline(const FramePipelineSettings& s);
+    // RenderFrontend::setResolution (RenderFrontend.cpp:408-421): recorded, applied at the start of the next frame() (prepareNewFrame, :199-222). Every image and
+    // buffer whose size follows the screen is re-created zero-filled, as the constructor creates it, and the next frame is a camera cut; a resize to the size the
+    // images already have (back from minimized) keeps them and only cuts. Width or height 0: minimized, frame() renders nothing and advances nothing.
+    // Partitioned pipelines (band / tile) refuse (FramePipelineRefusal, PLR_ERR_UNSUPPORTED): the exchange plan depends on the frame size.
+    void setResolution(uint32_t width, uint32_t height);
+    // the settings the reference's UI edits at run time (RenderFrontend.cpp:1882-2011; plr_frame.h plrf_update_settings lists them), recorded and applied at the
+    // start of the next frame() with the stale-flag branches of prepareNewFrame (:235-264). Any other field that differs from the pipeline's is refused
+    // (PLR_ERR_UNSUPPORTED), width / height that differ from the current resolution too (PLR_ERR_INVALID_ARGUMENT: resizing is setResolution's).
+    void updateSettings(const FramePipelineSettings& s);
+    // applies what setResolution / updateSettings recorded now instead of at the next frame(): a caller that uploads the frame's inputs (G-buffer, froxel
+    // volume) does so into images of the new size
+    void applyPendingChanges();
+    bool minimized() const { return m_minimized; }
     // one iteration of the reference main loop (Runtime/main.cpp:79-90): markNewFrame, prepareNewFrame, update, renderFrame
     void frame(const CameraExtrinsic& camera, float deltaTime, float time);
     // only re-record + submit with the current state (used by benchmarks that replay one frame)
@@ -329,6 +356,9 @@ public:
 
 private:
     void prepareRenderpasses();
+    void applyResolution(uint32_t width, uint32_t height);
+    void applySettings(const FramePipelineSettings& s);
+    ShaderDescription depthPyramidShaderDescription();
     void computeColorBufferHistogram(ImageHandle lastFrameColor);
     void computeExposure();
     void computeDepthPyramid(ImageHandle depthBuffer);
@@ -351,6 +381,10 @@ private:
     static int exchangeTrampoline(void* user, void* stream);
 
     RenderBackend m_be;
+    FramePipelineSettings m_requestedSettings; // as given to the constructor (before its clamps): what updateSettings holds the fixed fields to
+    uint32_t m_targetWidth = 0, m_targetHeight = 0; // the last resolution asked for (setResolution)
+    bool m_resolutionChanged = false, m_minimized = false, m_settingsChanged = false;
+    FramePipelineSettings m_pendingSettings;
     FrameIndexCounter m_frameIndex;
     GlobalShaderInfo m_globalShaderInfo, m_submittedGlobals;
     float m_lastWeights[9] = {};

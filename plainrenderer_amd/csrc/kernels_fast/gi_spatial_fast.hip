@@ -471,7 +471,8 @@ int spatialFilterPackTarget(const PassCtx& c, SpatialPackTarget* out) {
 }
 
 // ---- what of a filter pass's packed copy its producer filled this frame: rectangles (whole rows in band rendering, a tile's rectangle in tile rendering).
-// Host-side bookkeeping, one entry per filter pass = per scratch slot; the backend is one instance per host thread
+// Host-side bookkeeping, one entry per filter pass = per scratch slot; the backend is one instance per host thread. Across a resize: an entry is valid for one frame
+// (frameSerial), one source image address and one packed copy address only, and the rectangles are clipped to the consumer's current image - nothing carries over
 struct PackRect { int x0, y0, x1, y1; };
 struct PackedRects {
     uint64_t frameSerial = 0;

@@ -146,6 +146,7 @@ static int prepare(const PassCtx& c, HistParams* out) {
     const bool fresh = c.scratchSize && *c.scratchSize < kBins * 4u; // about to be allocated (zero-filled): whatever the map says about this address is history
     uint32_t* thresholds = (uint32_t*)c.scratch(kBins * 4u);
     if (!thresholds) return c.fail(-2, "histogramPerTile: cannot allocate scratch memory");
+    // (size changes: the table does not depend on the image size; a scratch that comes back at an address is caught by `fresh` before the lookup)
     static thread_local std::map<const void*, TableKey> built; // scratch memory -> what it holds (one backend per host thread)
     TableKey& key = built[(const void*)thresholds];
     if (fresh) key.valid = 0u;

@@ -481,6 +481,7 @@ __global__ void sdfBrickKernel(const uint16_t* __restrict__ src, uint16_t* __res
 struct BrickCache {
     struct Entry { const void* src = nullptr; int w = 0, h = 0, d = 0; uint64_t version = 0; size_t offset = 0; };
     const void* scratch = nullptr;
+    size_t scratchBytes = 0;                // with the base: a grown (zero-filled) scratch can come back at the address just freed
     std::vector<Entry> entries;             // per global texture slot
     std::vector<const uint16_t*> table;     // host copy of the device table
 };
@@ -506,8 +507,8 @@ static const uint16_t* const* brickedVolumeTable(const PassCtx& c) {
     if (total > ((size_t)8 << 30)) return nullptr;
     uint8_t* scratch = (uint8_t*)c.scratch(total); // grow-only; a re-allocation drops every copy
     if (!scratch) return nullptr;
-    const bool fresh = cache.scratch != (const void*)scratch || cache.entries.size() != n;
-    if (fresh) { cache.entries.assign(n, BrickCache::Entry{}); cache.table.assign(n, nullptr); cache.scratch = scratch; }
+    const bool fresh = cache.scratch != (const void*)scratch || cache.scratchBytes != *c.scratchSize || cache.entries.size() != n;
+    if (fresh) { cache.entries.assign(n, BrickCache::Entry{}); cache.table.assign(n, nullptr); cache.scratch = scratch; cache.scratchBytes = *c.scratchSize; }
     bool tableChanged = fresh;
     for (uint32_t i = 0; i < n; i++) {
         const BrickCache::Entry &w = want[i], &have = cache.entries[i];

@@ -882,7 +882,10 @@ __global__ void pcfTapsByPositionKernel(const uint16_t* __restrict__ noiseTexels
     }
 }
 struct ShadeDerived {
-    const void* scratchBase = nullptr; // the allocation the entries below describe (a re-allocated scratch starts empty)
+    // the allocation the entries below describe: base AND size. The scratch is grow-only and zero-filled when it grows, and a larger allocation can come back
+    // at the address just freed (a resize makes the records region grow): keyed on the address alone, the tables would be taken for built while they are zeros
+    const void* scratchBase = nullptr;
+    size_t scratchBytes = 0;
     struct Slot { const void* noise = nullptr; int w = 0, h = 0; uint64_t version = 0, lastUse = 0; } slots[kNoiseSlots];
     uint64_t useCounter = 0;
     const void* lut = nullptr; int lutW = 0, lutH = 0; uint64_t lutVersion = 0; // what the energy footprint was derived from
@@ -901,9 +904,10 @@ static int shadeDerivedTables(const PassCtx& c, ShadeParams* P, DirectRecords* r
     if (!scratch) return c.fail(-2, "deferredShading: cannot allocate scratch memory");
     if (records) { records->a = (uint4*)(scratch + recordsOffset); records->b = records->a + pixels; records->c = (uint32_t*)(records->b + pixels); }
     ShadeDerived& d = g_shadeDerived[(const void*)c.scratchSlot];
-    if (d.scratchBase != scratch) {
+    if (d.scratchBase != scratch || d.scratchBytes != *c.scratchSize) {
         d = ShadeDerived{};
         d.scratchBase = scratch;
+        d.scratchBytes = *c.scratchSize;
         const hipError_t e = buildPcfTapTable((float2*)scratch, c.stream);
         if (e != hipSuccess) return c.fail(-2, std::string("deferredShading: PCF tap table: ") + hipGetErrorString(e));
     }

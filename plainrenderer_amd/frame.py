@@ -91,7 +91,9 @@ class FramePipeline:
     def _check(self, rc):
         if rc != 0:
             msg = self.lib.plrf_last_error().decode() or self.lib.plr_last_error().decode()
-            raise PlrError("plrf error %d: %s" % (rc, msg))
+            err = PlrError("plrf error %d: %s" % (rc, msg))
+            err.code = rc
+            raise err
 
     def destroy(self):
         if self.handle:
@@ -215,6 +217,29 @@ class FramePipeline:
 
     def set_camera_cut(self):
         self._check(self.lib.plrf_set_camera_cut(self.handle))
+
+    # ---- live changes (include/plr_frame.h plrf_set_resolution / plrf_update_settings): recorded, applied at the start of the next frame() or by apply_changes()
+    def set_resolution(self, width, height):
+        """resize the frame (0 in either: minimized, frames render nothing); images that follow the screen come back zero-filled, the next frame is a camera cut"""
+        self._check(self.lib.plrf_set_resolution(self.handle, C.c_uint32(width), C.c_uint32(height)))
+        self.width, self.height = width, height
+        self.settings.width, self.settings.height = width, height
+
+    def update_settings(self, **overrides):
+        """change the settings the reference's UI edits (taa_*, bloom_*, sdf_half_res_trace, ..., plr_frame.h), starting from the current ones; any other field
+        that differs raises PlrError (PLR_ERR_UNSUPPORTED), width / height too (PLR_ERR_INVALID_ARGUMENT: use set_resolution)"""
+        s = PlrfSettings()
+        C.memmove(C.byref(s), C.byref(self.settings), C.sizeof(PlrfSettings))
+        for k, v in overrides.items():
+            if not hasattr(s, k):
+                raise KeyError(k)
+            setattr(s, k, v)
+        self._check(self.lib.plrf_update_settings(self.handle, C.byref(s)))
+        self.settings = s
+
+    def apply_changes(self):
+        """apply a recorded resize / settings change now, so that inputs of the new size can be uploaded before the next frame()"""
+        self._check(self.lib.plrf_apply_changes(self.handle))
 
     def frame(self, cam: Camera, delta_time=1.0 / 60.0, time=0.0):
         c = PlrfCamera()
