@@ -64,6 +64,11 @@ typedef struct plrf_settings {
      * carry a column range and the transfers are rectangles (plrf_exchange_plan_rects). With band_overlap_exchange 1 a tile behaves as with 0 (its producers
      * are never split); 2 produces the FRAME of the tile first (plr.h first_rows + first_cols). */
     uint32_t band_col_begin, band_col_end;
+    /* 1: "skyAndSunSprite.comp" right after the deferred shade (Sky::renderSky, Techniques/Sky.cpp:318-353, as one compute pass over the depth == 0 pixels of
+     * the colour buffer: the banding dither, the froxel in-scattering on the sky and the sun disc with limb darkening; geometry pixels are not touched). Off by
+     * default. Needs run_shading (plrf_create: PLR_ERR_INVALID_ARGUMENT otherwise), is not recorded while sdf_debug_mode != 0 and is fixed for the pipeline's
+     * lifetime like the other run_* flags. */
+    uint32_t run_sky;
 } plrf_settings;
 
 /* ---- band rendering: halo exchange hooks ----

@@ -48,6 +48,25 @@ PLR_DI float rand01(uint32_t& state) {
     return gclamp((float)x * u2f(0x2f800004u), 0.f, 1.f);
 }
 
+// resources/shaders/noise.inc:14-24 on a vec2 that holds converted uvec2 values: uvec3(ivec3(q.xyx)) is float -> int (truncation), reinterpreted as uint
+PLR_DI vec3 hash32(float qx, float qy) {
+    const uint32_t UI0 = 1597334673u, UI1 = 3812015801u, UI2 = 2798796415u;
+    uint32_t nx = (uint32_t)(int32_t)qx * UI0, ny = (uint32_t)(int32_t)qy * UI1, nz = (uint32_t)(int32_t)qx * UI2;
+    const uint32_t m = nx ^ ny ^ nz;
+    nx = m * UI0; ny = m * UI1; nz = m * UI2;
+    const float UIF = 1.0f / (float)0xffffffffu;
+    return vec3((float)nx, (float)ny, (float)nz) * UIF;
+}
+// resources/shaders/dither.inc:6-12, the term added to the colour: hash32(uvec2(uv * g_time)) + hash32(uvec2((uv + vec2(165, 1292)) * g_time)) - 1, in 1/255
+// units; (ux, uy) = the ivec2 argument as floats
+PLR_DI vec3 ditherRGB8Noise(float ux, float uy, float time) {
+    vec3 noise = hash32((float)(uint32_t)(ux * time), (float)(uint32_t)(uy * time));
+    noise += hash32((float)(uint32_t)((ux + 165.f) * time), (float)(uint32_t)((uy + 1292.f) * time));
+    noise = noise - 1.f;
+    noise = noise / 255.f;
+    return noise;
+}
+
 // resources/shaders/SphericalHarmonics.inc:5-15
 PLR_DI vec4 directionToSH_L1(vec3 V) {
     const float s = sqrtf(PLR_GLSL_PI);

@@ -35,6 +35,7 @@ int plrf_default_settings(plrf_settings* o, uint32_t width, uint32_t height) {
     o->run_light_matrix = d.runLightMatrix; o->volumetrics_max_distance = d.volumetricsMaxDistance; o->run_sky_luts = d.runSkyLuts; o->run_volumetrics = d.runVolumetrics; o->band_taa_history_halo = d.band.taaHistoryHalo; o->band_overlap_exchange = d.band.overlapExchange ? (d.band.rowsFirst ? 2u : 1u) : 0u;
     o->sdf_debug_mode = (uint32_t)d.sdfDebug.visualisationMode; o->sdf_debug_tile_usage_with_hiz = d.sdfDebug.showCameraTileUsageWithHiZ;
     o->sdf_debug_use_influence_radius = d.sdfDebug.useInfluenceRadiusForDebug;
+    o->run_sky = d.runSky;
     o->taa_use_separate_supersampling = d.taa.useSeparateSupersampling; o->taa_supersample_use_tonemapping = d.taa.supersampleUseTonemapping;
     // the denoiser's disc is 1.5 m in WORLD space: its reach in rows grows with the frame height, and so does the halo that keeps the band deviation
     // where it is at 2160 rows (measured at 8K in four bands, tests/test_config5_8k.py: 64 rows 98.6 %, 128 rows 99.3 %, 192 rows 99.4 % of a band's
@@ -63,6 +64,7 @@ static FramePipelineSettings toPipelineSettings(const plrf_settings* s) {
     f.runLightMatrix = s->run_light_matrix; f.volumetricsMaxDistance = s->volumetrics_max_distance; f.runSkyLuts = s->run_sky_luts; f.runVolumetrics = s->run_volumetrics; f.band.taaHistoryHalo = s->band_taa_history_halo; f.band.overlapExchange = s->band_overlap_exchange != 0; f.band.rowsFirst = s->band_overlap_exchange >= 2;
     f.sdfDebug.visualisationMode = (SDFVisualisationMode)s->sdf_debug_mode; f.sdfDebug.showCameraTileUsageWithHiZ = s->sdf_debug_tile_usage_with_hiz;
     f.sdfDebug.useInfluenceRadiusForDebug = s->sdf_debug_use_influence_radius;
+    f.runSky = s->run_sky != 0;
     f.taa.useSeparateSupersampling = s->taa_use_separate_supersampling; f.taa.supersampleUseTonemapping = s->taa_supersample_use_tonemapping;
     return f;
 }

@@ -773,6 +773,7 @@ FramePipeline::FramePipeline(const FramePipelineSettings& s) : settings(s), m_re
         if (b.tiled() && (b.colEnd > W || b.colBegin % bandAlignment != 0 || (b.colEnd % bandAlignment != 0 && b.colEnd != W)))
             throw std::runtime_error("tile columns must lie inside the frame and start/end on multiples of 64 (or at the last column)");
     } else if (s.band.tiled()) throw std::runtime_error("tile columns without band rows: set rowBegin / rowEnd too");
+    if (s.runSky && !s.runShading) throw std::runtime_error("run_sky needs run_shading: the sky pass completes the colour buffer the deferred shade writes");
     // a halo never needs to be larger than the image (PLRF_HALO_WHOLE_IMAGE: the exact mode of a partitioned frame, every GI texel a denoiser sample can
     // reach is exchanged); clamping here keeps the row arithmetic below in 32 bits
     if (settings.band.giHalo == 0xfffffffeu) { // PLRF_HALO_REQUESTED
@@ -914,6 +915,9 @@ FramePipeline::FramePipeline(const FramePipelineSettings& s) : settings(s), m_re
         d.name = "Sky lut";
         d.shaderDescription.srcPathRelative = "skyLut.comp";
         m_skyLutPass = m_be.createComputePass(d);
+        d.name = "Sky and sun sprite"; // Sky::renderSky's two raster passes as one compute pass (no reference shader: kernels/sky_background.hip)
+        d.shaderDescription.srcPathRelative = "skyAndSunSprite.comp";
+        m_skyAndSunSpritePass = m_be.createComputePass(d);
     }
     {
         // Volumetrics::init (Techniques/Volumetrics.cpp:19-117): froxel volumes of the integration volume's size; the 32^3 R8 Perlin noise is an
@@ -1153,6 +1157,20 @@ void FramePipeline::computeDeferredShading(ImageHandle colorTarget, const FrameR
                                                ImageResource(m_albedoImage, 0, 22), ImageResource(m_specularImage, 0, 23), ImageResource(m_skyLut, 0, 24)};
     for (uint32_t i = 0; i < (uint32_t)maxSunShadowCascadeCount; i++) exe.genericInfo.resources.sampledImages.push_back(ImageResource(m_shadowMaps[i], 0, 9 + i));
     exe.genericInfo.resources.uniformBuffers = {UniformBufferResource(m_volumetricsInfoBuffer, 19)};
+    dispatch8(exe, settings.width, settings.height, bandRows(settings.band.colorHalo), bandCols(settings.band.colorHalo));
+    m_be.setComputePassExecution(exe);
+}
+
+// Sky::renderSky (Techniques/Sky.cpp:318-353) on the pixels the forward pass left at depth 0: same rows and columns as the shade, so a band / tile has its
+// sky wherever it has shaded colour and needs no exchange for it
+void FramePipeline::computeSkyAndSunSprite(ImageHandle colorTarget, const FrameRenderTargets& current) {
+    ComputePassExecution exe;
+    exe.genericInfo.handle = m_skyAndSunSpritePass;
+    exe.genericInfo.resources.storageImages = {ImageResource(colorTarget, 0, 0)};
+    exe.genericInfo.resources.sampledImages = {ImageResource(current.depthBuffer, 0, 1), ImageResource(m_skyLut, 0, 2), ImageResource(m_volumetricIntegrationVolume, 0, 3),
+                                               ImageResource(m_transmissionLut, 0, 4)};
+    exe.genericInfo.resources.uniformBuffers = {UniformBufferResource(m_volumetricsInfoBuffer, 5)};
+    exe.genericInfo.resources.storageBuffers = {StorageBufferResource(m_lightBuffer, true, 6)};
     dispatch8(exe, settings.width, settings.height, bandRows(settings.band.colorHalo), bandCols(settings.band.colorHalo));
     m_be.setComputePassExecution(exe);
 }
@@ -1482,7 +1500,9 @@ void FramePipeline::prepareRenderpasses() { // RenderFrontend.cpp:313-406
         computeVolumetricLighting(m_lastDeltaTime);
     }
     if (settings.runShading) computeDeferredShading(currentRenderTarget.colorBuffer, currentRenderTarget);
-    // [sky: folded into the deferred pass' sky stand-in]
+    // renderSky (RenderFrontend.cpp:691-694, Techniques/Sky.cpp:318-353): the deferred pass writes the plain sky LUT colour on depth == 0 pixels; with runSky
+    // the sky pass overwrites those pixels with the dithered, in-scattered sky and the sun disc before anything else reads the colour buffer
+    if (settings.runShading && settings.runSky) computeSkyAndSunSprite(currentRenderTarget.colorBuffer, currentRenderTarget);
     ImageHandle currentSrc = currentRenderTarget.colorBuffer;
     bool postExchangeStarted = false;
     if (settings.runTAA && settings.taa.enabled) {
@@ -1617,7 +1637,8 @@ static const char* fixedFieldChanged(const FramePipelineSettings& a, const Frame
     if (a.shading.sunShadowCascadeCount != b.shading.sunShadowCascadeCount) return "sun_shadow_cascade_count";
     if (a.sdfTrace.additionalSunShadowMapPadding != b.sdfTrace.additionalSunShadowMapPadding) return "additional sun shadow map padding";
     if (a.runExposure != b.runExposure || a.runHiZ != b.runHiZ || a.runGI != b.runGI || a.runShading != b.runShading || a.runTAA != b.runTAA || a.runBloom != b.runBloom ||
-        a.runTonemap != b.runTonemap || a.runLightMatrix != b.runLightMatrix || a.runVolumetrics != b.runVolumetrics || a.runSkyLuts != b.runSkyLuts)
+        a.runTonemap != b.runTonemap || a.runLightMatrix != b.runLightMatrix || a.runVolumetrics != b.runVolumetrics || a.runSkyLuts != b.runSkyLuts ||
+        a.runSky != b.runSky)
         return "run_*";
     if (a.volumetricsMaxDistance != b.volumetricsMaxDistance) return "volumetrics_max_distance";
     const BandSettings &x = a.band, &y = b.band;

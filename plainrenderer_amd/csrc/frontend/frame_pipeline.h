@@ -301,6 +301,9 @@ struct FramePipelineSettings {
     // input producers recorded as compute passes instead of being uploaded by the caller
     bool runLightMatrix = false; // lightMatrix.comp after the depth pyramid (RenderFrontend.cpp:353, 840-872); in band mode the apex it reads is the all-reduced depth range of the bands (ExchangeDepthApex)
     bool runVolumetrics = false; // froxelVolumeMaterial / froxelLightScattering / volumeLightingReprojection / volumetricLightingIntegration (Volumetrics.cpp:119-243)
+    // "skyAndSunSprite.comp" behind the deferred shade: sky dither, froxel in-scattering on the sky and the sun disc (Sky::renderSky, Techniques/Sky.cpp:318-353)
+    // on the depth == 0 pixels; needs runShading, not recorded under the SDF debug view (RenderFrontend.cpp:691-694)
+    bool runSky = false;
     bool runSkyLuts = false;     // skyTransmissionLut / skyMultiscatterLut / skyLut.comp (Techniques/Sky.cpp:260-316) instead of uploaded LUTs
     float volumetricsMaxDistance = 30.f; // VolumetricsSettings::maxDistance, the last cascade's minimum far plane
 };
@@ -364,6 +367,7 @@ private:
     void computeDepthPyramid(ImageHandle depthBuffer);
     void downscaleDepth(const FrameRenderTargets& currentTarget);
     void computeDeferredShading(ImageHandle colorTarget, const FrameRenderTargets& current);
+    void computeSkyAndSunSprite(ImageHandle colorTarget, const FrameRenderTargets& current);
     void computeTonemapping(ImageHandle src);
     bool asyncPostTail() const { return true; } // bloom chain + tonemap as the frame's asynchronous tail (plr.h async_tail)
     void computeBRDFLut();
@@ -403,7 +407,8 @@ private:
     std::vector<ImageHandle> m_sdfVolumes;
     StorageBufferHandle m_histogramPerTileBuffer, m_histogramBuffer, m_lightBuffer, m_sunShadowInfoBuffer, m_depthPyramidSyncBuffer;
     RenderPassHandle m_histogramPerTilePass, m_histogramResetPass, m_histogramCombinePass, m_preExposeLightsPass, m_depthPyramidPass, m_depthDownscalePass,
-        m_deferredShadingPass, m_tonemappingPass, m_brdfLutPass, m_lightMatrixPass, m_depthApexPass, m_skyTransmissionLutPass, m_skyMultiscatterLutPass, m_skyLutPass;
+        m_deferredShadingPass, m_tonemappingPass, m_brdfLutPass, m_lightMatrixPass, m_depthApexPass, m_skyTransmissionLutPass, m_skyMultiscatterLutPass, m_skyLutPass,
+        m_skyAndSunSpritePass;
     ImageHandle m_skyMultiscatterLut, m_scatteringTransmittanceVolume, m_volumetricLightingHistory[2], m_volumeMaterialVolume, m_perlinNoise3D;
     RenderPassHandle m_froxelVolumeMaterialPass, m_froxelScatteringTransmittancePass, m_volumetricLightingIntegration, m_volumetricLightingReprojection;
     VolumetricsState m_volumetricsState;

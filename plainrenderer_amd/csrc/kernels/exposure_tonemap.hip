@@ -551,25 +551,11 @@ PLR_DI float linearTosRGB1(float l) {
     return l <= 0.0031308f ? lo : hi;
 }
 
-PLR_DI vec3 hash32(float qx, float qy) {
-    const uint32_t UI0 = 1597334673u, UI1 = 3812015801u, UI2 = 2798796415u;
-    uint32_t nx = (uint32_t)(int32_t)qx * UI0, ny = (uint32_t)(int32_t)qy * UI1, nz = (uint32_t)(int32_t)qx * UI2;
-    const uint32_t m = nx ^ ny ^ nz;
-    nx = m * UI0; ny = m * UI1; nz = m * UI2;
-    const float UIF = 1.0f / (float)0xffffffffu;
-    return vec3((float)nx, (float)ny, (float)nz) * UIF;
-}
-
 PLR_DI uint32_t tonemapPixel(uint32_t texel, int x, int y, float time) {
     const vec3 linearColor = unpackR11G11B10(texel);
     const vec3 t = ACESFitted(linearColor);
     vec3 s(linearTosRGB1(t.x), linearTosRGB1(t.y), linearTosRGB1(t.z));
-    // ditherRGB8: hash32(uvec2(uv * g_time)) + hash32(uvec2((uv + vec2(165, 1292)) * g_time)) - 1, in 1/255 units
-    vec3 noise = hash32((float)(uint32_t)((float)x * time), (float)(uint32_t)((float)y * time));
-    noise += hash32((float)(uint32_t)(((float)x + 165.f) * time), (float)(uint32_t)(((float)y + 1292.f) * time));
-    noise = noise - 1.f;
-    noise = noise / 255.f;
-    s = s + noise;
+    s = s + ditherRGB8Noise((float)x, (float)y, time); // ditherRGB8 (dither.inc:6-12; device/shading_common.h)
     // imageStore to the BGRA8 swapchain image: memory order B, G, R, A
     return encodeUnorm8(s.z) | (encodeUnorm8(s.y) << 8) | (encodeUnorm8(s.x) << 16) | (255u << 24);
 }

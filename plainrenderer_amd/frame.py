@@ -26,7 +26,7 @@ class PlrfSettings(C.Structure):
                                                                               ("sdf_debug_mode", C.c_uint32), ("sdf_debug_tile_usage_with_hiz", C.c_uint32),
                                                                               ("sdf_debug_use_influence_radius", C.c_uint32), ("band_taa_history_halo", C.c_uint32), ("run_volumetrics", C.c_uint32),
                                                                               ("run_sky_luts", C.c_uint32), ("band_overlap_exchange", C.c_uint32), ("band_col_begin", C.c_uint32),
-                                                                              ("band_col_end", C.c_uint32)]
+                                                                              ("band_col_end", C.c_uint32), ("run_sky", C.c_uint32)]
 
 
 class PlrfExchangeItem(C.Structure):
