@@ -19,6 +19,7 @@
 #include "../device/buffer_fetch.h"
 #include "upscale_quad.h"
 #include "pcf_taps.h"
+#include <cstdlib>
 #include <type_traits>
 #include <map>
 
@@ -194,7 +195,12 @@ struct ShadeParams {
     const float4* pcfTapsByPosition;
     uint32_t pcfPositions;
     const uint2* lutEnergyFootprint; // [(h - 1)][(w - 1)] of the BRDF LUT: .y of the 2 x 2 texels at (x, y), or null (lutEnergy below)
+    const uint32_t* lutEnergyNonFinite; // one word next to the footprint (null with it): non-zero if a .y half of the LUT is Inf / NaN
+    // skip what the sun cannot light (shadeDirect, "unlit pixels"): set by the launcher unless decision signatures are written or PLR_SHADE_SKIP_UNLIT=0
+    uint32_t skipUnlit;
 };
+PLR_DI float uniformValue(float x) { return u2f((uint32_t)__builtin_amdgcn_readfirstlane((int)f2u(x))); } // the first active lane's value, in a scalar register
+PLR_DI bool finiteBits(float x) { return (f2u(x) & 0x7f800000u) != 0x7f800000u; } // integer test: on a uniform value it stays on the scalar unit
 
 // The four uniform blocks a shade kernel reads are ALSO passed as top-level `const T* __restrict__` kernel arguments, and the kernel puts those into
 // its copy of ShadeParams. A pointer inside a by-value struct carries no aliasing information, so every load of a uniform field was a VECTOR
@@ -331,8 +337,39 @@ struct SurfaceTerms {
     vec3 brdfLut;                 // the LUT texel (INDIRECT_TECH 1 reads .x)
 };
 struct DirectOut { vec3 direct; float pixelDepth; vec2 noiseTexel; }; // direct = diffuseDirect + specularDirect for a sun of colour `lightColor`
+// ---- Unlit pixels (`skipUnlit`, wave-uniform: ShadeParams::skipUnlit and a finite sun, see the callers). Everything the sun contributes is a product with
+//   directLighting = (max(NdotL, 0) * sunShadow) * lightColor,  sunShadow = (lit taps) / 12 in {0, 1/12, ..., 1}: never NaN or infinite.
+// Stage 1, every instantiation: a lane with NdotL <= 0 has max(NdotL, 0) = +0 and +0 * sunShadow = +0 whatever the taps say. It skips the tap-row loads, the
+//   cascade loop and the PCF and keeps sunShadow = 0; a wave without a sun-facing lane branches over them. Nothing else reads sunShadow but the decision
+//   signature, and a signature run never skips. A NaN NdotL fails the comparison and takes the full path.
+// Stage 2, instantiations with kLobesSkippable: a lane with NdotL <= 0 or sunShadow == 0 has directLighting = +-0 in every channel (lightColor is finite), and
+//   direct = F * directLighting is +-0 as well if every factor F is finite. Such a lane skips the half vector, the sun's diffuse and specular lobes and the
+//   LUT fetch of the multiscattering lobe, and gets direct = +0. The factors, for NoL in [0, 1] (a clamp: NaN loses), r in [0.0045, 1] (the max / the clamp
+//   after geometric AA), NoV in [1e-4, 1 + 1e-6], f0 and diffuseColor in [0, 1] (8-bit texels), and the guard 1e-30 <= |V + L|^2 <= 8 on the lane - it
+//   fails for a NaN or infinite V or L and for V = -L, so behind it H is a unit vector and NoH, VoH, LoV lie in [0, 1 + 1e-6]:
+//    * diffuse 0: a constant. diffuse 1 (Disney): sums and products of the bounded terms, pow5 clamps its argument at 0. diffuse 2 (CoD WWII): the
+//      argument of its log2 is 2 / r^2 - 1 >= 1 - 2^-22 > 0, its exp2 has a non-positive exponent, its sqrt takes NoH >= 0.
+//    * the two Schlick factors: 1 - (f0 + (1 - f0) pow5(.)) with everything in [0, 1].
+//    * GGX: D's denominator 1 - NoH^2 (1 - r^2) >= r^2 - 3e-6 > 1.7e-5; Visibility's v1 + v2 >= NoV sqrt(r^2) >= 4.5e-7, its roots take values >= r^2 > 0.
+//    * multiscattering 0: 1 - energyAverage >= 1e-3 (the min with 0.999) and energyAverage >= 0.409, so the denominators 3.1415 (1 - energyAverage) and
+//      1 - fresnelAverage (1 - energyAverage) >= 0.409 are positive; energyIncoming and energyOutgoing are convex combinations of .y texels of the LUT,
+//      finite because the LUT's are (ShadeParams::lutEnergyNonFinite, checked when the footprint is derived; without a footprint the lobes are kept).
+//      multiscattering 3: the lobe is zero.
+//   Not skippable: multiscattering 1 and 2 divide by a function of a LUT texel that can be zero (rcp(0) * 0 = NaN today, and it stays NaN); diffuse 3
+//   computes diffuseBRDFIntegral, which the indirect half needs, among its lobes. They get stage 1 only.
+//   The sign of the zero: the full path may produce -0 where the skip produces +0. The callers form fma(direct, sunStrengthExposed, lightingIndirect)
+//   (sunStrengthExposed finite: `skipUnlit`) - lightingIndirect itself unless that is a zero - and then fma(that, transmittance, inScattering). inScattering
+//   is an fma chain that starts at +0 and so is never -0 (x + (+0) and an exact cancellation both give +0), hence neither is the sum: the value packed is
+//   inScattering, or +0, or a NaN from a non-finite transmittance, identically for both signs. (The encoder's choice for a whole wave depends on a -0, so
+//   "equal up to the sign of a zero" would not have been enough.) The two-launch form stores direct * transmittance in its record and adds
+//   fma(indirect, transmittance, inScattering) with inScattering rounded to fp16: the same holds for every froxel LUT without negative in-scattering.
 template <int DIFFUSE_BRDF, int MULTISCATTER, bool GEOMETRIC_AA>
-PLR_DI DirectOut shadeDirect(const ShadeParams& P, int px, int py, const ViewRay& vr, const PixelInputs& in, vec3 lightColor, SurfaceTerms* st, uint32_t* sigWord) {
+PLR_DI DirectOut shadeDirect(const ShadeParams& P, bool skipUnlit, int px, int py, const ViewRay& vr, const PixelInputs& in, vec3 lightColor, SurfaceTerms* st,
+                             uint32_t* sigWord) {
+    constexpr bool kLobesSkippable = DIFFUSE_BRDF != 3 && (MULTISCATTER == 0 || MULTISCATTER == 3);
+    // the LUT's "not finite" word, needed only where a LUT texel enters a skipped factor: fetched up front, parked in a scalar register in front of the PCF
+    uint32_t lutNonFinite = 1u;
+    if (kLobesSkippable && MULTISCATTER == 0 && skipUnlit && P.lutEnergyNonFinite) lutNonFinite = *P.lutEnergyNonFinite; // uniform
     const GlobalUbo* g = P.g;
     const Surface surf = exactSurface(g, vr.Vn, in.depth);
     const vec3 passPos = surf.passPos;
@@ -347,19 +384,18 @@ PLR_DI DirectOut shadeDirect(const ShadeParams& P, int px, int py, const ViewRay
     const vec3 diffuseColor = (1.f - metalic) * albedo;
     const vec3 N = decodeNormal(in.normal);
     const vec3 L = nrm(ld3(g->sunDirection));
+    // L is uniform but lives in vector registers (v_rsq_f32): three scalar registers carry it past the PCF to the sun's lobes instead
+    const vec3 Lu(uniformValue(L.x), uniformValue(L.y), uniformValue(L.z));
     const vec3 V = vr.Vn; // normalize(camPos - passPos) is the view ray itself
-    const vec3 H = nrm(V + L);
     if (GEOMETRIC_AA) {
         const vec3 N_U = decodeNormal(in.normalH) - N, N_V = decodeNormal(in.normalV) - N; // sign is irrelevant: only squared lengths are used
         const float variance = 0.25f * (dot(N_V, N_V) + dot(N_U, N_U));
         const float kernelRoughness2 = fmin1(2.f * variance, 0.18f);
         r = fclamp(sqrtv(r * r + kernelRoughness2), 0.f, 1.f);
     }
-    const float NoH = fmax1(dot(N, H), 0.f);
     const float NdotL = dot(N, L);
     const float NoL = fclamp(NdotL, 0.f, 1.f);
-    const float VoH = fabsf(dot(V, H));
-    const float LoV = fmax1(dot(L, V), 0.f);
+    const bool backFacing = NdotL <= 0.f; // false for a NaN
     const float NoV = fmax1(fabsf(dot(N, V)), 0.0001f);
     const vec3 f0 = vmix(vec3(0.04f), albedo, metalic);
 
@@ -379,64 +415,79 @@ PLR_DI DirectOut shadeDirect(const ShadeParams& P, int px, int py, const ViewRay
     // each, a third of all the L1 accesses of a kernel that the ablation of round 4 showed to be bound by exactly those (profiles/r04_shade_ablation.txt).
     // Indexed by the noise texel's POSITION and transposed, lane l reads 16 bytes next to lane l - 1's: four cache lines per load.
     // One code path for both tables: a uniform base and row stride (scalar registers) and one 32-bit byte offset per lane.
-    PcfTapRow tapRow;
-    {
-        const bool byPosition = P.pcfTapsByPosition != nullptr; // uniform
-        const uint8_t* base = byPosition ? (const uint8_t*)P.pcfTapsByPosition : (const uint8_t*)P.pcfTaps;
-        const uint32_t rowStride = byPosition ? P.pcfPositions * 16u : 16u;
-        const uint32_t laneOffset = byPosition ? noiseIndex * 16u : noiseByte * (uint32_t)(kPcfTaps / 2 * 16);
-        // raw buffer loads: the lane's byte offset in a VGPR, the row's in an SGPR - no 64-bit address per row on the VALU (device/buffer_fetch.h)
-        const __amdgpu_buffer_rsrc_t table = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-        for (int k = 0; k < kPcfTaps / 2; k++) {
-            const auto q = __builtin_amdgcn_raw_buffer_load_b128(table, (int)laneOffset, (int)((uint32_t)k * rowStride), 0);
-            __builtin_memcpy(&tapRow.q[k], &q, 16);
-        }
-    }
+    const bool skipLobes = kLobesSkippable && skipUnlit && (MULTISCATTER != 0 || __builtin_amdgcn_readfirstlane(lutNonFinite) == 0u); // uniform
     float sunShadow = 0.f;
-    for (bool pending = true; pending;) {
-        int c = __builtin_amdgcn_readfirstlane(cascadeIndex);
-        const bool mine = cascadeIndex == c;
-        // the optimiser would otherwise replace c by the (per-lane) cascadeIndex inside the branch it guards - equal there, but in a vector register
-        asm volatile("" : "+s"(c));
-        if (mine) {
-            const ImgView& m0 = P.shadowMaps[0];
-            ImgView shadowMap; // uniform selects (s_cselect): the struct is a kernel argument, a dynamic index would copy it to scratch memory
-            shadowMap.ptr = c == 0 ? m0.ptr : c == 1 ? P.shadowMaps[1].ptr : c == 2 ? P.shadowMaps[2].ptr : P.shadowMaps[3].ptr;
-            shadowMap.w = c == 0 ? m0.w : c == 1 ? P.shadowMaps[1].w : c == 2 ? P.shadowMaps[2].w : P.shadowMaps[3].w;
-            shadowMap.h = c == 0 ? m0.h : c == 1 ? P.shadowMaps[1].h : c == 2 ? P.shadowMaps[2].h : P.shadowMaps[3].h;
-            shadowMap.d = 1; shadowMap.fmt = F_D16;
-            sunShadow = calcShadow(passPos, shadowMap, P.shadowInfo->lightMatrices[c], P.shadowInfo->lightSpaceScale[c][0], P.shadowInfo->lightSpaceScale[c][1], tapRow);
-            pending = false;
+    if (!(skipUnlit && backFacing)) { // stage 1 of the unlit skip (above): a wave of back-facing lanes branches over the loads and the PCF
+        PcfTapRow tapRow;
+        {
+            const bool byPosition = P.pcfTapsByPosition != nullptr; // uniform
+            const uint8_t* base = byPosition ? (const uint8_t*)P.pcfTapsByPosition : (const uint8_t*)P.pcfTaps;
+            const uint32_t rowStride = byPosition ? P.pcfPositions * 16u : 16u;
+            const uint32_t laneOffset = byPosition ? noiseIndex * 16u : noiseByte * (uint32_t)(kPcfTaps / 2 * 16);
+            // raw buffer loads: the lane's byte offset in a VGPR, the row's in an SGPR - no 64-bit address per row on the VALU (device/buffer_fetch.h)
+            const __amdgpu_buffer_rsrc_t table = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7fffffff, 0x00020000);
+#pragma unroll
+            for (int k = 0; k < kPcfTaps / 2; k++) {
+                const auto q = __builtin_amdgcn_raw_buffer_load_b128(table, (int)laneOffset, (int)((uint32_t)k * rowStride), 0);
+                __builtin_memcpy(&tapRow.q[k], &q, 16);
+            }
+        }
+        for (bool pending = true; pending;) {
+            int c = __builtin_amdgcn_readfirstlane(cascadeIndex);
+            const bool mine = cascadeIndex == c;
+            // the optimiser would otherwise replace c by the (per-lane) cascadeIndex inside the branch it guards - equal there, but in a vector register
+            asm volatile("" : "+s"(c));
+            if (mine) {
+                const ImgView& m0 = P.shadowMaps[0];
+                ImgView shadowMap; // uniform selects (s_cselect): the struct is a kernel argument, a dynamic index would copy it to scratch memory
+                shadowMap.ptr = c == 0 ? m0.ptr : c == 1 ? P.shadowMaps[1].ptr : c == 2 ? P.shadowMaps[2].ptr : P.shadowMaps[3].ptr;
+                shadowMap.w = c == 0 ? m0.w : c == 1 ? P.shadowMaps[1].w : c == 2 ? P.shadowMaps[2].w : P.shadowMaps[3].w;
+                shadowMap.h = c == 0 ? m0.h : c == 1 ? P.shadowMaps[1].h : c == 2 ? P.shadowMaps[2].h : P.shadowMaps[3].h;
+                shadowMap.d = 1; shadowMap.fmt = F_D16;
+                sunShadow = calcShadow(passPos, shadowMap, P.shadowInfo->lightMatrices[c], P.shadowInfo->lightSpaceScale[c][0], P.shadowInfo->lightSpaceScale[c][1], tapRow);
+                pending = false;
+            }
         }
     }
     *sigWord = (uint32_t)cascadeIndex | ((uint32_t)(sunShadow * 12.f + 0.5f) << 2) | 64u; // cascade, lit PCF taps, geometry (oracle/oracle.h)
-    const vec3 directLighting = (fmax1(NdotL, 0.f) * sunShadow) * lightColor;
     const vec3 brdfLut = bilinearLut(P.brdfLut, r, NoV).xyz();
 
-    vec3 diffuseDirect;
+    // stage 2 of the unlit skip (above)
+    const vec3 VL = V + Lu;
+    const float VL2 = dot(VL, VL); // H = nrm(V + L) = VL * rsqf(VL2)
+    const bool unlit = skipLobes && (backFacing || sunShadow == 0.f) && VL2 >= 1e-30f && VL2 <= 8.f;
+    vec3 direct(0.f);
     vec3 diffuseBRDFIntegral(brdfLut.z);
-    if (DIFFUSE_BRDF == 0) diffuseDirect = diffuseColor * (1.f / PLR_GLSL_PI) * directLighting;
-    else if (DIFFUSE_BRDF == 1) diffuseDirect = DisneyDiffuse(diffuseColor, NoL, VoH, NoV, r) * directLighting;
-    else if (DIFFUSE_BRDF == 2) diffuseDirect = CoDWWIIDiffuse(diffuseColor, NoL, VoH, NoV, NoH, r) * directLighting;
-    else {
-        const float single = Titanfall2DiffuseSingleComponent(NoL, LoV, NoV, NoH, r);
-        diffuseDirect = diffuseColor * (single + diffuseColor * (0.1159f * r)) * directLighting;
-        float multiIntegral = 0.1159f * r * PLR_GLSL_PI * 2.f;
-        multiIntegral *= (1.f - (0.04f + 0.96f * pow5(1.f - NoV)));
-        multiIntegral *= 0.94291f;
-        diffuseBRDFIntegral = vmin(vec3(brdfLut.z) + diffuseColor * multiIntegral, vec3(1.f));
-    }
-    diffuseDirect = diffuseDirect * ((1.f - F_Schlick(f0, vec3(1.f), NoV)) * (1.f - F_Schlick(f0, vec3(1.f), NoL)));
+    if (!unlit) {
+        const vec3 H = VL * rsqf(VL2);
+        const float NoH = fmax1(dot(N, H), 0.f);
+        const float VoH = fabsf(dot(V, H));
+        const float LoV = fmax1(dot(Lu, V), 0.f);
+        const vec3 directLighting = (fmax1(NdotL, 0.f) * sunShadow) * lightColor;
+        vec3 diffuseDirect;
+        if (DIFFUSE_BRDF == 0) diffuseDirect = diffuseColor * (1.f / PLR_GLSL_PI) * directLighting;
+        else if (DIFFUSE_BRDF == 1) diffuseDirect = DisneyDiffuse(diffuseColor, NoL, VoH, NoV, r) * directLighting;
+        else if (DIFFUSE_BRDF == 2) diffuseDirect = CoDWWIIDiffuse(diffuseColor, NoL, VoH, NoV, NoH, r) * directLighting;
+        else {
+            const float single = Titanfall2DiffuseSingleComponent(NoL, LoV, NoV, NoH, r);
+            diffuseDirect = diffuseColor * (single + diffuseColor * (0.1159f * r)) * directLighting;
+            float multiIntegral = 0.1159f * r * PLR_GLSL_PI * 2.f;
+            multiIntegral *= (1.f - (0.04f + 0.96f * pow5(1.f - NoV)));
+            multiIntegral *= 0.94291f;
+            diffuseBRDFIntegral = vmin(vec3(brdfLut.z) + diffuseColor * multiIntegral, vec3(1.f));
+        }
+        diffuseDirect = diffuseDirect * ((1.f - F_Schlick(f0, vec3(1.f), NoV)) * (1.f - F_Schlick(f0, vec3(1.f), NoL)));
 
-    const vec3 singleScatteringLobe = GGXSingleScattering(r, f0, NoH, NoV, VoH, NoL);
-    const vec3 multiScatteringLobe = specularMultiscatteringLobe<MULTISCATTER>(P, r, NoL, f0, singleScatteringLobe, brdfLut);
-    const vec3 specularDirect = directLighting * (singleScatteringLobe + multiScatteringLobe);
+        const vec3 singleScatteringLobe = GGXSingleScattering(r, f0, NoH, NoV, VoH, NoL);
+        const vec3 multiScatteringLobe = specularMultiscatteringLobe<MULTISCATTER>(P, r, NoL, f0, singleScatteringLobe, brdfLut);
+        const vec3 specularDirect = directLighting * (singleScatteringLobe + multiScatteringLobe);
+        direct = diffuseDirect + specularDirect;
+    }
 
     st->N = N; st->V = V; st->f0 = f0; st->diffuseColor = diffuseColor; st->diffuseBRDFIntegral = diffuseBRDFIntegral;
     st->r = r; st->NoV = NoV; st->energyOutgoing = brdfLut.y; st->brdfLut = brdfLut;
     DirectOut o;
-    o.direct = diffuseDirect + specularDirect;
+    o.direct = direct;
     o.pixelDepth = pixelDepth;
     o.noiseTexel = noiseTexel;
     return o;
@@ -505,7 +556,10 @@ PLR_DI vec4 froxelLookup(const ShadeParams& P, float su, float sv, vec2 noiseTex
 template <int DIFFUSE_BRDF, int MULTISCATTER, bool GEOMETRIC_AA, int INDIRECT_TECH>
 PLR_DI uint32_t shadeGeometryPixel(const ShadeParams& P, int px, int py, const ViewRay& vr, const PixelInputs& in, uint32_t* sigWord) {
     SurfaceTerms st;
-    const DirectOut d = shadeDirect<DIFFUSE_BRDF, MULTISCATTER, GEOMETRIC_AA>(P, px, py, vr, in, ld3(P.light->sunColor), &st, sigWord);
+    // the unlit skip relies on 0 * x = 0: with a non-finite sun that product is NaN today, and stays NaN (uniform, scalar loads the pixel needs anyway)
+    const vec3 sunColor = ld3(P.light->sunColor);
+    const bool skipUnlit = P.skipUnlit && finiteBits(sunColor.x) && finiteBits(sunColor.y) && finiteBits(sunColor.z) && finiteBits(P.light->sunStrengthExposed);
+    const DirectOut d = shadeDirect<DIFFUSE_BRDF, MULTISCATTER, GEOMETRIC_AA>(P, skipUnlit, px, py, vr, in, sunColor, &st, sigWord);
     vec3 lightingIndirect;
     if (INDIRECT_TECH == 0) lightingIndirect = shadeIndirect<MULTISCATTER>(P, st, in.ysh, in.cocg);
     else {
@@ -717,7 +771,8 @@ __global__ __launch_bounds__(256, PLR_SHADE_WAVES) void shadeDirectKernel(ShadeP
     in.cocg = 0u;
     SurfaceTerms st;
     uint32_t sigWord;
-    const DirectOut d = shadeDirect<DIFFUSE_BRDF, MULTISCATTER, GEOMETRIC_AA>(P, px, py, vr, in, vec3(1.f), &st, &sigWord);
+    // (unit sun colour: the product with the sun's colour and exposure is the combine launch's, NaN there for a non-finite sun whether this launch skips or not)
+    const DirectOut d = shadeDirect<DIFFUSE_BRDF, MULTISCATTER, GEOMETRIC_AA>(P, P.skipUnlit != 0u, px, py, vr, in, vec3(1.f), &st, &sigWord);
     const vec4 it = froxelLookup(P, vr.su, vr.sv, d.noiseTexel, d.pixelDepth);
     const vec3 X = d.direct * it.w;
     const vec3 dci = st.diffuseColor * st.diffuseBRDFIntegral;
@@ -859,12 +914,16 @@ template <int D> static FusedKernel pickFusedMulti(int m, bool aa) {
 constexpr int kNoiseSlots = 4;
 constexpr uint32_t kMaxNoisePositions = 4096;
 constexpr size_t kNoiseSlotBytes = (size_t)kMaxNoisePositions * (kPcfTaps / 2) * sizeof(float4);
-__global__ void lutEnergyFootprintKernel(ImgView lut, uint2* __restrict__ out) {
+// *nonFinite (zeroed by the launcher) becomes non-zero if a .y half is Inf or NaN; the footprints of a LUT of at least 2 x 2 texels cover every texel
+__global__ void lutEnergyFootprintKernel(ImgView lut, uint2* __restrict__ out, uint32_t* __restrict__ nonFinite) {
     const int x = (int)(blockIdx.x * 64u + (threadIdx.x & 63u)), y = (int)(blockIdx.y * 4u + (threadIdx.x >> 6));
     if (x >= lut.w - 1 || y >= lut.h - 1) return;
     const uint2* t = (const uint2*)lut.ptr;
     auto energy = [&](int tx, int ty) { return t[(size_t)ty * (size_t)lut.w + tx].x >> 16; }; // RGBA16F texel: .y = upper half of the first word
-    out[(size_t)y * (size_t)(lut.w - 1) + x] = make_uint2(energy(x, y) | (energy(x + 1, y) << 16), energy(x, y + 1) | (energy(x + 1, y + 1) << 16));
+    const uint32_t e00 = energy(x, y), e10 = energy(x + 1, y), e01 = energy(x, y + 1), e11 = energy(x + 1, y + 1);
+    out[(size_t)y * (size_t)(lut.w - 1) + x] = make_uint2(e00 | (e10 << 16), e01 | (e11 << 16));
+    auto special = [](uint32_t h) { return (h & 0x7c00u) == 0x7c00u; };
+    if (special(e00) || special(e10) || special(e01) || special(e11)) *nonFinite = 1u;
 }
 __global__ void pcfTapsByPositionKernel(const uint16_t* __restrict__ noiseTexels, uint32_t positions, const float4* __restrict__ byValue, float4* __restrict__ byPosition) {
     const uint32_t pos = blockIdx.x * blockDim.x + threadIdx.x;
@@ -892,14 +951,15 @@ struct ShadeDerived {
 };
 static thread_local std::map<const void*, ShadeDerived> g_shadeDerived; // key = the pass's scratch slot (one backend per host thread)
 static int shadeDerivedTables(const PassCtx& c, ShadeParams* P, DirectRecords* records = nullptr) {
-    // [tap table by value | noise slots | BRDF LUT energy footprint (size follows the LUT: a larger LUT re-allocates the scratch and everything is rebuilt)
+    // [tap table by value | noise slots | BRDF LUT energy footprint (size follows the LUT: a larger LUT re-allocates the scratch and everything is rebuilt) and its flag
     //  | the direct launch's records: planes a, b, c over the colour target (only when the shade runs as two launches)]
     const ImgView& lut = P->brdfLut;
     const size_t footprintOffset = kPcfTapTableBytes + kNoiseSlots * kNoiseSlotBytes;
     const size_t footprintBytes = (size_t)(lut.w - 1) * (size_t)std::max(lut.h - 1, 1) * sizeof(uint2); // (the launcher sends LUTs narrower than two texels to the general kernel)
-    const size_t recordsOffset = (footprintOffset + footprintBytes + 255) & ~(size_t)255;
+    const size_t flagOffset = (footprintOffset + footprintBytes + 15) & ~(size_t)15; // the footprint's "a .y texel is not finite" word
+    const size_t recordsOffset = (flagOffset + 16 + 255) & ~(size_t)255;
     const size_t pixels = (size_t)P->color.w * (size_t)P->color.h;
-    const size_t total = records ? recordsOffset + pixels * 36 : footprintOffset + footprintBytes;
+    const size_t total = records ? recordsOffset + pixels * 36 : flagOffset + 16;
     uint8_t* scratch = (uint8_t*)c.scratch(total);
     if (!scratch) return c.fail(-2, "deferredShading: cannot allocate scratch memory");
     if (records) { records->a = (uint4*)(scratch + recordsOffset); records->b = records->a + pixels; records->c = (uint32_t*)(records->b + pixels); }
@@ -915,13 +975,18 @@ static int shadeDerivedTables(const PassCtx& c, ShadeParams* P, DirectRecords* r
     P->pcfTapsByPosition = nullptr;
     P->pcfPositions = 0;
     P->lutEnergyFootprint = nullptr;
+    P->lutEnergyNonFinite = nullptr;
     if (const uint64_t lutVersion = lut.h >= 2 ? contentVersionOf(lut.ptr) : 0) { // 0: the LUT may change behind the backend's back - the kernel reads the LUT itself
         if (d.lut != lut.ptr || d.lutW != lut.w || d.lutH != lut.h || d.lutVersion != lutVersion) {
-            lutEnergyFootprintKernel<<<dim3(divUp((unsigned)(lut.w - 1), 64u), divUp((unsigned)(lut.h - 1), 4u)), 256, 0, c.stream>>>(lut, (uint2*)(scratch + footprintOffset));
+            const hipError_t e = hipMemsetAsync(scratch + flagOffset, 0, 16, c.stream);
+            if (e != hipSuccess) return c.fail(-2, std::string("deferredShading: LUT energy footprint: ") + hipGetErrorString(e));
+            lutEnergyFootprintKernel<<<dim3(divUp((unsigned)(lut.w - 1), 64u), divUp((unsigned)(lut.h - 1), 4u)), 256, 0, c.stream>>>(lut, (uint2*)(scratch + footprintOffset),
+                                                                                                                                       (uint32_t*)(scratch + flagOffset));
             PLR_CHECK_LAUNCH(c);
             d.lut = lut.ptr; d.lutW = lut.w; d.lutH = lut.h; d.lutVersion = lutVersion;
         }
         P->lutEnergyFootprint = (const uint2*)(scratch + footprintOffset);
+        P->lutEnergyNonFinite = (const uint32_t*)(scratch + flagOffset);
     }
     const ImgView& noise = P->noiseTex;
     if (!noise.ptr || noise.fmt != F_RG8) return 0;
@@ -987,6 +1052,10 @@ static int shadeParamsFor(const PassCtx& c, ShadeParams* out, int* diffuseBRDF, 
     const PassCtx::ColSpan cs = c.colSpan(P.color.w);
     P.coverW = cs.x1; P.xBase = cs.x0; P.coverH = rs.y1; P.yBase = rs.y0; // columns [xBase, coverW), rows [yBase, coverH)
     P.sig = c.sigFor((size_t)P.color.w * (size_t)P.color.h);
+    // PLR_SHADE_SKIP_UNLIT=0 (read per launch: tests switch it): every pixel takes the full path, as a decision-signature run always does - its word carries
+    // the lit-tap count of every geometry pixel. Same bytes either way (shadeDirect, "unlit pixels"; tests/test_shade_unlit_skip.py)
+    const char* skipEnv = std::getenv("PLR_SHADE_SKIP_UNLIT");
+    P.skipUnlit = (!P.sig && !(skipEnv && skipEnv[0] == '0' && skipEnv[1] == 0)) ? 1u : 0u;
     *out = P;
     return 0;
 }
