@@ -8,6 +8,7 @@
 #ifndef PLR_FRAME_H
 #define PLR_FRAME_H
 #include "plr.h"
+#include "plr_sdf_bake.h" /* plr_mesh_data */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -247,6 +248,24 @@ int plrf_set_camera_cut(void* pipeline);
 int plrf_set_resolution(void* pipeline, uint32_t width, uint32_t height);
 int plrf_update_settings(void* pipeline, const plrf_settings* settings);
 int plrf_apply_changes(void* pipeline); /* apply what was recorded now: a caller uploads the new size's inputs after it */
+/* ---- mesh shadow casters: RenderFrontend::renderSunShadowCascades (RenderFrontend.cpp:354, 760-774) as the compute pass "sunShadowRaster.comp".
+ * While a pipeline has casters, every plrf_frame records sun_shadow_cascade_count executions of the pass behind the light matrices (also under sdf_debug_mode);
+ * they rasterise the draws into shadow0 .. shadow<count - 1> with whatever sunShadowInfo holds, uploaded or computed (run_light_matrix). Maps at and above the
+ * cascade count are not touched. Without casters nothing is recorded and the uploaded maps are used. The rasterisation contract - 8 sub-pixel bits, top-left
+ * rule, front faces culled, depth clamp, round-to-nearest-even Depth16, a 2^20-pixel guard band with a counted reject instead of clipping, opaque casters - is
+ * DESIGN.md "Sun shadow cascades as a compute pass".
+ * plrf_set_shadow_casters copies the meshes (positions and a uint32 triangle list each) and the draws; draw_count 0 removes the casters. PLR_ERR_INVALID_ARGUMENT,
+ * with a message that names the cause: a mesh index or a vertex index out of range, an index count that is no multiple of 3, a model matrix whose last row is not
+ * exactly (0, 0, 0, 1) (the pass does not divide by w). PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing.
+ * plrf_set_shadow_caster_transforms replaces the draws' model matrices (draw_count x 16 floats) from the next frame on, like setStorageBufferData: queued, applied
+ * in call order; a draw_count other than the casters' is PLR_ERR_INVALID_ARGUMENT.
+ * plrf_get_shadow_raster_stats: the counters of the last frame's execution for one cascade; waits for the GPU. submitted = triangles of all draws, drawn = back
+ * faces inside the guard band whose pixel box meets the map, guard_band_rejects = triangles with a non-finite or out-of-band vertex. */
+typedef struct plrf_shadow_draw { uint32_t mesh; float model_matrix[16]; } plrf_shadow_draw; /* glm column-major */
+int plrf_set_shadow_casters(void* pipeline, const plr_mesh_data* meshes, uint32_t mesh_count, const plrf_shadow_draw* draws, uint32_t draw_count);
+int plrf_set_shadow_caster_transforms(void* pipeline, const float* matrices16, uint32_t draw_count);
+typedef struct plrf_shadow_raster_stats { uint64_t triangles_submitted, triangles_drawn, guard_band_rejects; } plrf_shadow_raster_stats;
+int plrf_get_shadow_raster_stats(void* pipeline, uint32_t cascade, plrf_shadow_raster_stats* out);
 /* one iteration of the reference's main loop: record the frame, update camera/UBOs, submit (does not wait for the GPU) */
 int plrf_frame(void* pipeline, const plrf_camera* camera, float delta_time, float time);
 /* host copies of what the last plrf_frame submitted (340-byte global UBO image, 9 TAA resolve weights) */

@@ -3,6 +3,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "../../../include/plr_frame.h"
 #include "frame_pipeline.h"
@@ -87,6 +88,30 @@ int plrf_update_settings(void* p, const plrf_settings* s) {
 int plrf_apply_changes(void* p) {
     if (!p) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY(((FramePipeline*)p)->applyPendingChanges())
+}
+
+// ---- mesh shadow casters ("sunShadowRaster.comp")
+int plrf_set_shadow_casters(void* p, const plr_mesh_data* meshes, uint32_t meshCount, const plrf_shadow_draw* draws, uint32_t drawCount) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        std::vector<ShadowCasterMesh> m(meshes ? meshCount : 0u);
+        for (size_t i = 0; i < m.size(); i++) m[i] = {meshes[i].positions, meshes[i].vertex_count, meshes[i].indices, meshes[i].index_count};
+        std::vector<ShadowCasterDraw> d(draws ? drawCount : 0u);
+        for (size_t i = 0; i < d.size(); i++) { d[i].mesh = draws[i].mesh; std::memcpy(d[i].modelMatrix, draws[i].model_matrix, sizeof(d[i].modelMatrix)); }
+        if (drawCount && d.empty()) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "plrf_set_shadow_casters: draws are null");
+        ((FramePipeline*)p)->setShadowCasters(m.data(), (uint32_t)m.size(), d.data(), drawCount);
+    })
+}
+int plrf_set_shadow_caster_transforms(void* p, const float* matrices16, uint32_t drawCount) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL(((FramePipeline*)p)->setShadowCasterTransforms(matrices16, drawCount))
+}
+int plrf_get_shadow_raster_stats(void* p, uint32_t cascade, plrf_shadow_raster_stats* out) {
+    if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        const ShadowRasterStats s = ((FramePipeline*)p)->shadowRasterStats(cascade);
+        out->triangles_submitted = s.trianglesSubmitted; out->triangles_drawn = s.trianglesDrawn; out->guard_band_rejects = s.guardBandRejects;
+    })
 }
 
 int plrf_destroy(void* p) { delete (FramePipeline*)p; return PLR_OK; }

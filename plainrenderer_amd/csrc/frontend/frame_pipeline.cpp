@@ -1,10 +1,12 @@
 // See frame_pipeline.h. Pass order, bindings, specialisation constants and dispatch counts follow the cited reference code.
 #include "frame_pipeline.h"
+#include "../device/sun_shadow_raster.h"
 
 #include "../../../include/plr_image_io.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <stdexcept>
 
 namespace plrhost {
@@ -841,7 +843,7 @@ FramePipeline::FramePipeline(const FramePipelineSettings& s) : settings(s), m_re
         m_volumetricIntegrationVolume = m_be.createImage(d, nullptr, 0);
     }
     for (int i = 0; i < maxSunShadowCascadeCount; i++)
-        m_shadowMaps[i] = m_be.createImage(desc2D(s.shadowMapRes, s.shadowMapRes, ImageFormat::Depth16, ImageUsageFlags::Sampled), nullptr, 0);
+        m_shadowMaps[i] = m_be.createImage(desc2D(s.shadowMapRes, s.shadowMapRes, ImageFormat::Depth16, ImageUsageFlags::Storage | ImageUsageFlags::Sampled), nullptr, 0); // (storage: sunShadowRaster.comp writes them while casters are set)
     for (int i = 0; i < 4; i++) {
         m_noiseTextures[i] = m_be.createImage(desc2D(noiseTextureWidth, noiseTextureHeight, ImageFormat::RG8, ImageUsageFlags::Sampled), nullptr, 0);
         m_globalShaderInfo.noiseTextureIndices[i] = (int32_t)m_be.getImageGlobalTextureArrayIndex(m_noiseTextures[i]);
@@ -1234,6 +1236,125 @@ void FramePipeline::computeSunLightMatrices() { // RenderFrontend.cpp:840-872
     m_be.setComputePassExecution(exe);
 }
 
+// ---- RenderFrontend::renderSunShadowCascades (RenderFrontend.cpp:760-774, pass :1565-1590) as one compute execution per cascade ("sunShadowRaster.comp",
+// kernels/sun_shadow_raster.hip). The reference's coarse CPU frustum culling of the draws (:611-646) is not rebuilt: the set-up kernel rejects per triangle.
+void FramePipeline::renderSunShadowCascades() {
+    if (m_casterDrawCount == 0) return;
+    for (int c = 0; c < settings.shading.sunShadowCascadeCount; c++) {
+        ComputePassExecution exe;
+        exe.genericInfo.handle = m_sunShadowRasterPass[c];
+        exe.dispatchCount[0] = exe.dispatchCount[1] = exe.dispatchCount[2] = 1;
+        exe.genericInfo.resources.storageImages = {ImageResource(m_shadowMaps[c], 0, plr::sunraster::kMapBinding)};
+        exe.genericInfo.resources.storageBuffers = {StorageBufferResource(m_sunShadowInfoBuffer, true, plr::sunraster::kSunShadowInfoBinding),
+                                                    StorageBufferResource(m_casterTransforms, true, plr::sunraster::kTransformBinding),
+                                                    StorageBufferResource(m_casterPositions, true, plr::sunraster::kPositionBinding),
+                                                    StorageBufferResource(m_casterIndices, true, plr::sunraster::kIndexBinding),
+                                                    StorageBufferResource(m_casterDraws, true, plr::sunraster::kDrawBinding),
+                                                    StorageBufferResource(m_casterScratch[c], false, plr::sunraster::kScratchBinding)};
+        const plr::sunraster::PushConstants pc{m_casterDrawCount, m_casterTriangleCount};
+        exe.pushConstants = dataToCharArray(&pc, sizeof(pc));
+        m_be.setComputePassExecution(exe);
+    }
+}
+
+// a caster buffer that holds `bytes`: a new, larger one when the current is too small (the backend has no call that frees a buffer; casters change with the
+// scene, not per frame), then the contents as a queued fill (applied in call order at the next frame)
+void FramePipeline::fillCasterBuffer(StorageBufferHandle& buffer, size_t& capacity, const void* data, size_t bytes) {
+    if (capacity < bytes) {
+        StorageBufferDescription sb;
+        sb.size = (bytes + 255) & ~(size_t)255;
+        buffer = m_be.createStorageBuffer(sb);
+        capacity = sb.size;
+    }
+    if (data) m_be.setStorageBufferData(buffer, data, bytes);
+}
+
+static void refuseUnlessAffine(const float* m, uint32_t draw, const char* call) {
+    if (m[3] != 0.f || m[7] != 0.f || m[11] != 0.f || m[15] != 1.f)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": the model matrix of draw " + std::to_string(draw) +
+                                   " is not affine (its last row must be exactly (0, 0, 0, 1): the shadow pass does not divide by w)");
+}
+
+void FramePipeline::setShadowCasters(const ShadowCasterMesh* meshes, uint32_t meshCount, const ShadowCasterDraw* draws, uint32_t drawCount) {
+    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setShadowCasters: a band / tile pipeline cannot rasterise shadow casters (every partition would draw every cascade)");
+    if (drawCount == 0) { m_casterDrawCount = m_casterTriangleCount = 0; return; }
+    if (!meshes || !draws || meshCount == 0) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: draws without meshes");
+    // everything is validated before anything is changed
+    std::vector<uint32_t> firstIndex(meshCount), vertexOffset(meshCount);
+    uint64_t vertices = 0, indices = 0, triangles = 0;
+    for (uint32_t m = 0; m < meshCount; m++) {
+        const ShadowCasterMesh& mesh = meshes[m];
+        if ((mesh.vertexCount && !mesh.positions) || (mesh.indexCount && !mesh.indices)) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: mesh " + std::to_string(m) + " has null data");
+        if (mesh.indexCount % 3u != 0u)
+            throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: mesh " + std::to_string(m) + " has " + std::to_string(mesh.indexCount) + " indices, not a triangle list");
+        for (uint32_t i = 0; i < mesh.indexCount; i++)
+            if (mesh.indices[i] >= mesh.vertexCount)
+                throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: vertex index out of range: index " + std::to_string(i) + " of mesh " + std::to_string(m) + " is " +
+                                           std::to_string(mesh.indices[i]) + ", the mesh has " + std::to_string(mesh.vertexCount) + " vertices");
+        firstIndex[m] = (uint32_t)indices; vertexOffset[m] = (uint32_t)vertices;
+        vertices += mesh.vertexCount; indices += mesh.indexCount;
+    }
+    for (uint32_t d = 0; d < drawCount; d++) {
+        if (draws[d].mesh >= meshCount)
+            throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: mesh index out of range: draw " + std::to_string(d) + " names mesh " + std::to_string(draws[d].mesh) +
+                                       " of " + std::to_string(meshCount));
+        refuseUnlessAffine(draws[d].modelMatrix, d, "setShadowCasters");
+        triangles += meshes[draws[d].mesh].indexCount / 3u;
+    }
+    if (vertices == 0 || indices == 0 || triangles == 0) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: the draws hold no triangle");
+    if (vertices > 0xffffffffull || indices > 0xffffffffull || triangles > 0x7fffffffull) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: too many vertices, indices or triangles");
+    std::vector<float> positions((size_t)vertices * 3u), matrices((size_t)drawCount * 16u);
+    std::vector<uint32_t> indexData((size_t)indices);
+    std::vector<plr::sunraster::Draw> drawData(drawCount);
+    for (uint32_t m = 0; m < meshCount; m++) {
+        if (meshes[m].vertexCount) std::memcpy(positions.data() + (size_t)vertexOffset[m] * 3u, meshes[m].positions, (size_t)meshes[m].vertexCount * 12u);
+        if (meshes[m].indexCount) std::memcpy(indexData.data() + firstIndex[m], meshes[m].indices, (size_t)meshes[m].indexCount * 4u);
+    }
+    for (uint32_t d = 0; d < drawCount; d++) {
+        drawData[d] = {firstIndex[draws[d].mesh], meshes[draws[d].mesh].indexCount, vertexOffset[draws[d].mesh], d};
+        std::memcpy(matrices.data() + (size_t)d * 16u, draws[d].modelMatrix, 64);
+    }
+    if (!m_casterPassesCreated) {
+        for (uint32_t c = 0; c < 4; c++) {
+            ComputePassDescription d; // RenderFrontend.cpp:1565-1590, one pass per cascade (sunShadow.vert:8 cascadeIndex)
+            d.name = "Sun shadow cascade " + std::to_string(c);
+            d.shaderDescription.srcPathRelative = "sunShadowRaster.comp";
+            d.shaderDescription.specialisationConstants = {spec(plr::sunraster::kCascadeIndexConstant, c)};
+            m_sunShadowRasterPass[c] = m_be.createComputePass(d);
+        }
+        m_casterPassesCreated = true;
+    }
+    fillCasterBuffer(m_casterPositions, m_casterPositionBytes, positions.data(), positions.size() * sizeof(float));
+    fillCasterBuffer(m_casterIndices, m_casterIndexBytes, indexData.data(), indexData.size() * sizeof(uint32_t));
+    fillCasterBuffer(m_casterDraws, m_casterDrawBytes, drawData.data(), drawData.size() * sizeof(plr::sunraster::Draw));
+    fillCasterBuffer(m_casterTransforms, m_casterTransformBytes, matrices.data(), matrices.size() * sizeof(float));
+    for (int c = 0; c < settings.shading.sunShadowCascadeCount; c++)
+        fillCasterBuffer(m_casterScratch[c], m_casterScratchBytes[c], nullptr, plr::sunraster::scratchBytes((uint32_t)triangles));
+    m_casterDrawCount = drawCount; m_casterTriangleCount = (uint32_t)triangles;
+}
+
+void FramePipeline::setShadowCasterTransforms(const float* matrices16, uint32_t drawCount) {
+    if (drawCount != m_casterDrawCount)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasterTransforms: transform count " + std::to_string(drawCount) + " differs from the draw count " +
+                                   std::to_string(m_casterDrawCount) + " of the casters");
+    if (drawCount == 0) return;
+    if (!matrices16) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasterTransforms: matrices are null");
+    for (uint32_t d = 0; d < drawCount; d++) refuseUnlessAffine(matrices16 + (size_t)d * 16u, d, "setShadowCasterTransforms");
+    m_be.setStorageBufferData(m_casterTransforms, matrices16, (size_t)drawCount * 64u);
+}
+
+ShadowRasterStats FramePipeline::shadowRasterStats(uint32_t cascade) {
+    if (cascade >= (uint32_t)settings.shading.sunShadowCascadeCount)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "shadowRasterStats: cascade " + std::to_string(cascade) + " of " + std::to_string(settings.shading.sunShadowCascadeCount));
+    ShadowRasterStats out;
+    if (m_casterScratchBytes[cascade] == 0) return out;
+    plr::sunraster::ScratchHeader h{};
+    if (plr_download_storage_buffer(m_casterScratch[cascade].index, &h, 0, sizeof(h)) != PLR_OK) throw std::runtime_error(plr_last_error());
+    out.trianglesSubmitted = h.submitted; out.trianglesDrawn = h.drawn; out.guardBandRejects = h.guardBandRejects;
+    return out;
+}
+
 void FramePipeline::computeVolumetricLighting(float deltaTime) { // Volumetrics::computeVolumetricLighting, Techniques/Volumetrics.cpp:119-243
     m_volumetricsState.sampleOffset = radicalInverseBase2((uint32_t)m_frameIndex.mod8()) - 0.5f; // hammersley2D(frameIndexMod8).x - 0.5
     for (int i = 0; i < 3; i++) m_volumetricsState.windSampleOffset[i] += windSettings.vector[i] * windSettings.speed * deltaTime;
@@ -1403,7 +1524,7 @@ void FramePipeline::prepareRenderpasses() { // RenderFrontend.cpp:313-406
         computeExposure();
         if (settings.runSkyLuts) updateSkyLut();
         if (settings.runLightMatrix) computeSunLightMatrices();
-        // [renderSunShadowCascades: input]
+        renderSunShadowCascades(); // (RenderFrontend.cpp:331) only with mesh casters set; the uploaded maps otherwise
         SDFTraceDependencies deps = m_frustumScratch;
         deps.currentFrame = currentRenderTarget;
         deps.previousFrame = previousRenderTarget;
@@ -1437,7 +1558,7 @@ void FramePipeline::prepareRenderpasses() { // RenderFrontend.cpp:313-406
         if (perTilePyramid(settings)) computeDepthApexOfTiles(); // no apex in a per-tile pyramid: reduce (and, across bands, all-reduce) it
         computeSunLightMatrices();
     }
-    // [renderSunShadowCascades: input]
+    renderSunShadowCascades(); // (RenderFrontend.cpp:354) only with mesh casters set; the uploaded maps otherwise
     if (settings.runGI && settings.shading.indirectLightingTech == IndirectLightingTech::SDFTrace) {
         if (settings.sdfTrace.halfResTrace) downscaleDepth(currentRenderTarget);
         SDFTraceDependencies deps = m_frustumScratch; // frustum points/normals from setCameraExtrinsic (fillOutSdfGiDependencies, :1073-1090)

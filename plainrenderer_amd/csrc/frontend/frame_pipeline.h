@@ -2,7 +2,7 @@
 // (Plain/src/Runtime/Rendering/RenderFrontend.cpp:313-406 prepareRenderpasses and the compute*/init* helpers) and of its
 // technique classes (Techniques/TAA.cpp, Bloom.cpp, SDFGI.cpp), written against the RenderBackend shim in
 // include/plr_render_backend.hpp. Rasterised passes (depth prepass, shadow cascades, forward shading, sky) are inputs:
-// their outputs (G-buffer, shadow maps, LUTs) are uploaded by the caller; forward shading is replaced by the deferred
+// their outputs (G-buffer, shadow maps, LUTs) are uploaded by the caller (the cascades are rasterised by a compute pass instead while mesh casters are set); forward shading is replaced by the deferred
 // compute pass. Pass order, bindings, specialisation constants and dispatch counts are the reference's.
 #pragma once
 #include <array>
@@ -314,9 +314,24 @@ struct FramePipelineRefusal : std::runtime_error {
     FramePipelineRefusal(int c, const std::string& what) : std::runtime_error(what), code(c) {}
 };
 
+// mesh shadow casters (plr_frame.h plrf_set_shadow_casters): the fields of MeshData the shadow pass reads, and one draw of a mesh under a model matrix
+struct ShadowCasterMesh { const float* positions = nullptr; uint32_t vertexCount = 0; const uint32_t* indices = nullptr; uint32_t indexCount = 0; };
+struct ShadowCasterDraw { uint32_t mesh = 0; float modelMatrix[16] = {}; }; // glm column-major
+struct ShadowRasterStats { uint64_t trianglesSubmitted = 0, trianglesDrawn = 0, guardBandRejects = 0; };
+
 class FramePipeline {
 public:
     explicit FramePipeline(const FramePipelineSettings& s);
+    // RenderFrontend::renderSunShadowCascades (RenderFrontend.cpp:354, 760-774) as "sunShadowRaster.comp" (kernels/sun_shadow_raster.hip): while casters are set every
+    // frame records one execution per cascade behind computeSunLightMatrices, writing shadow0 .. shadow<cascade count - 1> from whatever sunShadowInfo holds; without
+    // casters the uploaded maps are used. Meshes and matrices are copied; drawCount 0 removes the casters. Refusals (FramePipelineRefusal): a mesh index or a vertex
+    // index out of range, an index count that is no multiple of 3 and a matrix whose last row is not (0, 0, 0, 1) are PLR_ERR_INVALID_ARGUMENT, a band / tile
+    // pipeline is PLR_ERR_UNSUPPORTED. A refused call changes nothing.
+    void setShadowCasters(const ShadowCasterMesh* meshes, uint32_t meshCount, const ShadowCasterDraw* draws, uint32_t drawCount);
+    // the draws' model matrices for the next frame (setStorageBufferData: applied in call order at the next frame); drawCount must be the casters' draw count
+    void setShadowCasterTransforms(const float* matrices16, uint32_t drawCount);
+    // counters of the last frame's execution for `cascade`; waits for the GPU. Zero before the first frame with casters.
+    ShadowRasterStats shadowRasterStats(uint32_t cascade);
     // RenderFrontend::setResolution (RenderFrontend.cpp:408-421): recorded, applied at the start of the next frame() (prepareNewFrame, :199-222). Every image and
     // buffer whose size follows the screen is re-created zero-filled, as the constructor creates it, and the next frame is a camera cut; a resize to the size the
     // images already have (back from minimized) keeps them and only cuts. Width or height 0: minimized, frame() renders nothing and advances nothing.
@@ -373,6 +388,8 @@ private:
     void computeBRDFLut();
     void computeDepthApexOfTiles();
     void computeSunLightMatrices();
+    void renderSunShadowCascades();
+    void fillCasterBuffer(StorageBufferHandle& buffer, size_t& capacity, const void* data, size_t bytes);
     void updateTransmissionLut();
     void computeVolumetricLighting(float deltaTime);
     void updateSkyLut();
@@ -414,6 +431,12 @@ private:
     VolumetricsState m_volumetricsState;
     float m_lastDeltaTime = 0.f;
     UniformBufferHandle m_atmosphereSettingsBuffer;
+    // mesh shadow casters: created by the first setShadowCasters (a pipeline without casters allocates and records nothing for them)
+    uint32_t m_casterDrawCount = 0, m_casterTriangleCount = 0;
+    bool m_casterPassesCreated = false;
+    RenderPassHandle m_sunShadowRasterPass[4];
+    StorageBufferHandle m_casterTransforms, m_casterPositions, m_casterIndices, m_casterDraws, m_casterScratch[4];
+    size_t m_casterTransformBytes = 0, m_casterPositionBytes = 0, m_casterIndexBytes = 0, m_casterDrawBytes = 0, m_casterScratchBytes[4] = {0, 0, 0, 0};
 public:
     AtmosphereSettings atmosphereSettings;
     VolumetricsSettings volumetricsSettings;

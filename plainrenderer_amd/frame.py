@@ -44,6 +44,18 @@ class PlrfCamera(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("forward", C.c_float * 3), ("up", C.c_float * 3), ("right", C.c_float * 3)]
 
 
+class PlrMeshData(C.Structure):  # plr_mesh_data, include/plr_sdf_bake.h
+    _fields_ = [("positions", C.POINTER(C.c_float)), ("vertex_count", C.c_uint32), ("indices", C.POINTER(C.c_uint32)), ("index_count", C.c_uint32)]
+
+
+class PlrfShadowDraw(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("model_matrix", C.c_float * 16)]
+
+
+class PlrfShadowRasterStats(C.Structure):
+    _fields_ = [("triangles_submitted", C.c_uint64), ("triangles_drawn", C.c_uint64), ("guard_band_rejects", C.c_uint64)]
+
+
 class LocalExchangeGroup:
     """shared state of the in-process transport of the native exchange (include/plr_frame.h plrf_local_group_*): one per partition, created before its ranks'
     pipelines attach (FramePipeline.attach_local_rects), destroyed after they are gone"""
@@ -240,6 +252,32 @@ class FramePipeline:
     def apply_changes(self):
         """apply a recorded resize / settings change now, so that inputs of the new size can be uploaded before the next frame()"""
         self._check(self.lib.plrf_apply_changes(self.handle))
+
+    # ---- mesh shadow casters (include/plr_frame.h plrf_set_shadow_casters): the sun shadow cascades rasterised every frame by "sunShadowRaster.comp"
+    def set_shadow_casters(self, meshes, draws):
+        """meshes: [(positions n x 3 float32, indices uint32 triangle list)], draws: [(mesh index, 16 floats, glm column-major)]; copied. No draws: the casters
+        are removed and the uploaded shadow maps are used again"""
+        pos = [np.ascontiguousarray(p, np.float32).reshape(-1, 3) for p, _ in meshes]
+        idx = [np.ascontiguousarray(i, np.uint32).reshape(-1) for _, i in meshes]
+        m = (PlrMeshData * max(len(meshes), 1))()
+        for k in range(len(meshes)):
+            m[k] = PlrMeshData(pos[k].ctypes.data_as(C.POINTER(C.c_float)), pos[k].shape[0], idx[k].ctypes.data_as(C.POINTER(C.c_uint32)), idx[k].size)
+        d = (PlrfShadowDraw * max(len(draws), 1))()
+        for k, (mesh, matrix) in enumerate(draws):
+            d[k].mesh = int(mesh)
+            d[k].model_matrix = (C.c_float * 16)(*[float(v) for v in np.asarray(matrix, np.float32).reshape(16)])
+        self._check(self.lib.plrf_set_shadow_casters(self.handle, m, C.c_uint32(len(meshes)), d, C.c_uint32(len(draws))))
+
+    def set_shadow_caster_transforms(self, matrices):
+        """one 16-float model matrix per draw, from the next frame on"""
+        a = np.ascontiguousarray(matrices, np.float32).reshape(-1, 16)
+        self._check(self.lib.plrf_set_shadow_caster_transforms(self.handle, a.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(a.shape[0])))
+
+    def shadow_raster_stats(self, cascade):
+        """(triangles submitted, triangles drawn, guard-band rejects) of the last frame's execution for the cascade; waits for the GPU"""
+        s = PlrfShadowRasterStats()
+        self._check(self.lib.plrf_get_shadow_raster_stats(self.handle, C.c_uint32(cascade), C.byref(s)))
+        return int(s.triangles_submitted), int(s.triangles_drawn), int(s.guard_band_rejects)
 
     def frame(self, cam: Camera, delta_time=1.0 / 60.0, time=0.0):
         c = PlrfCamera()
