@@ -10,8 +10,11 @@
 //     refuses anything else) and L orthographic (lightMatrix.comp:57-138)
 //   viewport 0 .. res on both axes, no Y flip, depth 0 .. 1 (VulkanCommandRecording.cpp:44-48): xf = (clip.x * 0.5 + 0.5) * res, yf likewise, z = clip.z
 //   X = rint(xf * 256), Y = rint(yf * 256), round to nearest even, int32: eight sub-pixel bits
-//   guard band: a triangle with a non-finite xf, yf or z, or |xf| or |yf| >= 2^20 pixels, is not drawn and counted as a reject (no clipping); a vertex, index
-//     or transform slot outside its buffer counts as non-finite. Inside the band every product below fits int64.
+//   guard band: a triangle with a non-finite xf, yf or z, or |xf| or |yf| >= 2^20 pixels, is not drawn and counted as a reject (no clipping). Inside the band
+//     every product below fits int64.
+//   outside a buffer: a triangle counts as submitted and as a reject, and draws nothing, when its three index slots are not all inside `indices`, when a
+//     vertex (index + vertexOffset, in 64 bits) is not inside `positions`, or when its draw's transformIndex is not inside `transforms`. A draw submits
+//     indexCount / 3 triangles (rounded down), whatever becomes of them.
 //   A = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0); Vulkan's area is -A / 2 and the front face counter-clockwise (VulkanPipeline.cpp:61), so A < 0 faces front;
 //     the pass culls FRONT faces (RenderFrontend.cpp:1576): only A > 0 is drawn
 //   pixel box: columns (Xmin + 127) >> 8 .. (Xmax - 128) >> 8 (the pixel centres 256 i + 128 inside [Xmin, Xmax]) clipped to 0 .. res - 1, rows likewise; a
@@ -19,7 +22,8 @@
 //   edges 0 -> 1, 1 -> 2, 2 -> 0; for a -> b and the pixel centre P = (256 i + 128, 256 j + 128): E = (Xb - Xa)(Py - Ya) - (Yb - Ya)(Px - Xa), int64
 //   a pixel is covered when every E > 0, or E == 0 on a top (dy == 0 && dx > 0) or left (dy < 0) edge, d = b - a: the top-left rule in a y-down frame
 //   l1 = float(E_20) / float(A), l2 = float(E_01) / float(A) (int64 -> fp32 to nearest even, IEEE divide); zf = (z0 + l1 (z1 - z0)) + l2 (z2 - z0)
-//   depth clamp on (:1578): zf to [0, 1]; code = rint(zf * 65535) as uint16
+//   depth clamp on (:1578): zf to [0, 1] as fmin(fmax(zf, 0), 1) with IEEE maxNum / minNum semantics (of a NaN and a number, the number): a NaN zf - finite
+//     vertex depths whose difference overflows, times a zero weight - stores code 0, +inf stores 65535; code = rint(zf * 65535) as uint16
 //   cleared to 0, depth test GreaterEqual (RenderPass.cpp:105, :1574): a texel is the MAXIMUM code of its fragments, 0 without any. Every texel of the map is
 //     written by every execution: the clear is part of the pass.
 //   sunShadow.frag's alpha test is left out - casters are opaque: its anisotropic repeat sampler is implementation-defined and material textures are no input here.

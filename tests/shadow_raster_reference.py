@@ -3,6 +3,11 @@ same contract independently and must agree bit for bit).
 
 Every float operation is one fp32 IEEE operation on np.float32 arrays, sums are written out left to right (no `@`, no np.sum), edge functions are int64.
 The loop is over triangles, each vectorised over its pixel box.
+
+Outside a buffer: a triangle counts as submitted and as a reject, and draws nothing, when its three index slots are not all inside `indices`, when a vertex
+(index + vertexOffset, in 64 bits) is not inside `positions`, or when its draw's transformIndex is not inside `transforms`. A draw submits indexCount // 3
+triangles, whatever becomes of them.
+The depth clamp is fmin(fmax(zf, 0), 1) with IEEE maxNum / minNum semantics (np.fmax / np.fmin): a NaN zf stores code 0, +inf stores 65535.
 """
 import numpy as np
 
@@ -59,6 +64,11 @@ def project(light_matrix, model_matrix, positions, res):
     return X, Y, z, inside
 
 
+def clamp01(zf):
+    """the depth clamp: fmin(fmax(zf, 0), 1) with IEEE maxNum / minNum semantics - of a NaN and a number the number. A NaN zf becomes 0, +inf becomes 1"""
+    return np.fmin(np.fmax(zf, F32(0.0)), F32(1.0))
+
+
 def rasterise(light_matrix, transforms, positions, indices, draws, res):
     """light_matrix: 16 floats; transforms: n x 16; positions: v x 3; indices: uint32; draws: d x 4 {firstIndex, indexCount, vertexOffset, transformIndex}.
     -> dict(map uint16 res x res, coverage int32 res x res (fragments per texel), submitted, drawn, rejects)"""
@@ -71,11 +81,21 @@ def rasterise(light_matrix, transforms, positions, indices, draws, res):
     coverage = np.zeros((res, res), np.int32)
     submitted = drawn = rejects = 0
     for first, count, vertex_offset, transform_index in draws.tolist():
-        idx = indices[first:first + count // 3 * 3].astype(np.int64).reshape(-1, 3) + vertex_offset
+        n = count // 3
+        submitted += n
+        # outside a buffer (module docstring): index slots, vertices (64-bit sums), the draw's transform slot
+        slot = first + 3 * np.arange(n, dtype=np.int64)
+        in_buffers = (slot + 3 <= indices.size) & (transform_index < transforms.shape[0])
+        idx = np.zeros((n, 3), np.int64)
+        idx[in_buffers] = indices[slot[in_buffers, None] + np.arange(3)[None, :]].astype(np.int64) + vertex_offset
+        in_buffers &= (idx < positions.shape[0]).all(axis=1)
+        rejects += int((~in_buffers).sum())
+        if not in_buffers.any():
+            continue
+        idx = idx[in_buffers]
         X, Y, z, inside = project(light_matrix, transforms[transform_index], positions[idx.reshape(-1)], res)
         X, Y, z, inside = X.reshape(-1, 3), Y.reshape(-1, 3), z.reshape(-1, 3), inside.reshape(-1, 3)
         ok = inside.all(axis=1)
-        submitted += idx.shape[0]
         rejects += int((~ok).sum())
         for t in np.flatnonzero(ok):
             x0, x1, x2 = (int(v) for v in X[t])
@@ -105,9 +125,10 @@ def rasterise(light_matrix, transforms, positions, indices, draws, res):
             l1 = E[2].astype(F32) / fa
             l2 = E[0].astype(F32) / fa
             z0 = z[t, 0]
-            dz1, dz2 = F32(z[t, 1] - z0), F32(z[t, 2] - z0)
-            zf = (z0 + l1 * dz1) + l2 * dz2
-            zf = np.minimum(np.maximum(zf, F32(0.0)), F32(1.0))
+            with np.errstate(all="ignore"):  # z1 - z0 may overflow to an infinity, and 0 * inf is a NaN
+                dz1, dz2 = F32(z[t, 1] - z0), F32(z[t, 2] - z0)
+                zf = (z0 + l1 * dz1) + l2 * dz2
+            zf = clamp01(zf)
             code = np.rint(zf * F32(65535.0)).astype(np.uint16)
             sub = depth[iy0:iy1 + 1, ix0:ix1 + 1]
             sub[...] = np.where(covered, np.maximum(sub, code), sub)

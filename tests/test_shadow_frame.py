@@ -4,6 +4,8 @@ After a frame the three cascade maps must be bit-identical to tests/shadow_raste
 (the cascade fit runs on the GPU in front of the pass), shadow3 - above the cascade count - must still hold the bytes uploaded into it, and a pipeline without
 casters must keep all four uploaded maps. All four maps are uploaded as bit patterns first. New transforms move the shadow in the next frame, draw_count 0
 stops the writes, the counters equal the reference's, a fast-set frame runs no general kernel, and the refusals return their codes and name their causes.
+Replacing the casters by a larger set (300 draws, a mesh without indices among their meshes) and then by a single draw in buffers that stay larger gives the
+reference's maps and counters in the frame after each call.
 """
 import copy
 
@@ -110,6 +112,72 @@ def test_gpu_frame_rasterises_the_casters_into_the_cascades(backend, fast):
         if fp is not None:
             fp.destroy()
         backend.setMathMode(False)
+
+
+EMPTY_MESH = (np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0]], np.float32), np.zeros(0, np.uint32))  # three vertices and no index
+
+
+def replacement_scene():
+    """the second caster set of test_gpu_frame_replaces_its_casters: mesh200's three meshes and an empty one, 300 draws in front of the camera (as
+    tools/shadow_raster_cost.py places its instances); every second draw names the empty mesh, the first and the last draw among them"""
+    if "replacement" not in _inputs:
+        s = sc.mesh_scene()
+        cam = s["cam"]
+        rng = np.random.default_rng(0x5245504C)
+        pos, fwd = np.asarray(cam.position, np.float64), np.asarray(cam.forward, np.float64)
+        right, up = np.asarray(cam.right, np.float64), np.asarray(cam.up, np.float64)
+        draws = []
+        for k in range(300):
+            d = rng.uniform(4.0, 40.0)
+            at = pos + d * fwd + rng.uniform(-0.45, 0.45) * d * right + rng.uniform(-0.2, 0.2) * d * up
+            scale = rng.uniform(0.5, 1.5, 3) * (0.15 + d / 40.0)
+            draws.append((3 if k % 2 == 0 or k == 299 else (k // 2) % 3, sc.affine(scale, rng.uniform(0, 6.28), rng.uniform(-1.0, 1.0), at)))
+        _inputs["replacement"] = (list(s["meshes"]) + [EMPTY_MESH], draws)
+    return _inputs["replacement"]
+
+
+def test_replacement_scene_is_what_it_is_for():
+    """not gpu: more than 256 draws (a second chunk of the draw lookup), empty draws at both ends and in between, and - under the light matrices the CPU fits to the
+    smoke camera, close to those the frame downloads - triangles drawn in every cascade"""
+    s = sc.mesh_scene()
+    meshes, draws = replacement_scene()
+    pos, idx, dr, tr = ref.merge_meshes(meshes, draws)
+    assert dr.shape == (300, 4) and dr[0, 1] == 0 and dr[-1, 1] == 0 and int((dr[:, 1] == 0).sum()) == 151 and int((dr[256:, 1] > 0).sum()) > 10
+    assert pos.shape[0] == sum(m[0].shape[0] for m in s["meshes"]) + 3 and idx.size == sum(m[1].size for m in s["meshes"])
+    for c in range(3):
+        r = ref.rasterise(ref.light_matrices(s["info"])[c], tr, pos, idx, dr, RES)
+        assert r["submitted"] == int((dr[:, 1] // 3).sum()) and r["drawn"] > 100 and r["map"].any()
+
+
+@pytest.mark.gpu
+def test_gpu_frame_replaces_its_casters(backend):
+    """three draws, then 300 draws over four meshes (the caster buffers grow into new handles, the scratch buffers are resized), then one draw (the buffers are
+    kept and larger than needed: the vertex, index and transform counts the launcher derives from their sizes exceed the scene's). After each replacement a frame's
+    cascades equal the reference under the downloaded light matrices and the stats agree."""
+    s, i = sc.mesh_scene(), _scene_inputs()
+    many_meshes, many_draws = replacement_scene()
+    fp = _pipeline(backend)
+    try:
+        steps = (("three draws", s["meshes"], s["draws"]), ("300 draws", many_meshes, many_draws), ("one draw", s["meshes"][1:2], [(0, s["draws"][1][1])]))
+        for f, (what, meshes, draws) in enumerate(steps):
+            fp.set_shadow_casters(meshes, draws)
+            fp.frame(i["cams"][1 + f % 2], 1.0 / 60.0, 0.5 + f / 60.0)
+            info = backend.downloadStorageBuffer(fp.storage_buffer("sunShadowInfo"), 304, dtype=np.uint8).tobytes()
+            maps = _maps(backend, fp)
+            pos, idx, dr, tr = ref.merge_meshes(meshes, draws)
+            drawn = 0
+            for c in range(3):
+                r = ref.rasterise(ref.light_matrices(info)[c], tr, pos, idx, dr, RES)
+                differing = int((maps[c] != r["map"]).sum())
+                print("shadow frame, %s, cascade %d: %d of %d texels differ, %d texels covered, counters %r (reference %r)"
+                      % (what, c, differing, RES * RES, int((r["map"] > 0).sum()), fp.shadow_raster_stats(c), (r["submitted"], r["drawn"], r["rejects"])))
+                assert differing == 0, what
+                assert fp.shadow_raster_stats(c) == (r["submitted"], r["drawn"], r["rejects"]), what
+                drawn += r["drawn"]
+            assert drawn > 0 and any(m.any() for m in maps[:3]), "the casters lie in no cascade: the test would compare cleared maps"
+            assert np.array_equal(maps[3], i["patterns"][3]), "shadow3 lies above the cascade count and was written"
+    finally:
+        fp.destroy()
 
 
 @pytest.mark.gpu

@@ -65,6 +65,72 @@ def test_depth_is_clamped_and_rounded_to_nearest_even():
     assert sc.rasterise(sc.pixel_case([tri(0.5)], 16))["map"].max() == 32768
 
 
+def test_depth_clamp_takes_the_number_of_a_nan_and_a_number():
+    """the clamp is fmin(fmax(zf, 0), 1) with IEEE maxNum / minNum semantics: a NaN zf stores code 0, +inf stores 65535. z0 = -3e38 and z1 = 3e38 are finite,
+    z1 - z0 overflows to +inf, and on edge 2 -> 0 (l1 == 0, a left edge up the pixel centres of column 4) zf = 0 * inf = NaN; beside it zf = +inf"""
+    f = np.float32
+    assert ref.clamp01(np.array([np.nan, np.inf, -np.inf, -0.5, 0.25, 1.5], f)).tolist() == [0.0, 1.0, 0.0, 0.0, 0.25, 1.0]
+    r = sc.rasterise(sc.pixel_case([[(4.5, 2.5, -3e38), (12.5, 6.5, 3e38), (4.5, 10.5, 0.5)]], 16))
+    rows = np.arange(3, 10)
+    assert (r["submitted"], r["drawn"], r["rejects"]) == (1, 1, 0), "every vertex depth is finite: no reject"
+    assert (r["coverage"][rows, 4] == 1).all() and not r["map"][rows, 4].any()
+    inner = r["coverage"] > 0
+    inner[:, 4] = False
+    assert inner.sum() > 10 and (r["map"][inner] == 65535).all()
+
+
+def test_old_and_new_clamp_agree_on_the_first_four_cases(monkeypatch):
+    """np.fmax / np.fmin instead of np.maximum / np.minimum changes no texel where zf is a number: the maps of unit96, mesh200, dense64 and big130 are what they were"""
+    import test_shadow_raster as tsr
+    new = {name: [r["map"] for _, _, r in tsr.reference(name)] for name in ("unit96", "mesh200", "dense64", "big130")}
+    monkeypatch.setattr(ref, "clamp01", lambda zf: np.minimum(np.maximum(zf, np.float32(0.0)), np.float32(1.0)))
+    for name, maps in new.items():
+        old = [sc.rasterise(case)["map"] for case, _ in tsr.CASES[name]()]
+        assert len(old) == len(maps) and all(np.array_equal(a, b) for a, b in zip(old, maps)), name
+
+
+def test_a_slot_outside_its_buffer_is_a_counted_reject():
+    """the contract's clause: a triangle counts as submitted and as a reject, and draws nothing, when its three index slots are not all inside `indices`, when a
+    vertex (index + vertexOffset, in 64 bits) is not inside `positions`, or when its draw's transformIndex is not inside `transforms`. Submitted triangles per
+    draw stay indexCount // 3."""
+    base = sc.pixel_case([[(2.0, 2.0, 0.5), (12.0, 2.0, 0.5), (12.0, 12.0, 0.5)], [(1.0, 3.0, 0.7), (9.0, 3.0, 0.7), (9.0, 14.0, 0.7)]], 16)
+    whole = sc.rasterise(base)
+    first = sc.rasterise(dict(base, draws=np.array([[0, 3, 0, 0]], np.uint32)))
+    assert (whole["submitted"], whole["drawn"], whole["rejects"]) == (2, 2, 0) and (first["submitted"], first["drawn"]) == (1, 1)
+
+    def run(**changed):
+        r = sc.rasterise(dict(base, **changed))
+        return (r["submitted"], r["drawn"], r["rejects"]), r["map"]
+
+    # the last index slot of the second triangle is one past the end (the buffer holds 5 indices); with 8 of 6 the draw still has two triangles
+    counters, out = run(indices=base["indices"][:5])
+    assert counters == (2, 1, 1) and np.array_equal(out, first["map"])
+    counters, out = run(draws=np.array([[0, 8, 0, 0]], np.uint32))
+    assert counters == (2, 2, 0) and np.array_equal(out, whole["map"])
+    counters, out = run(draws=np.array([[0, 9, 0, 0]], np.uint32))
+    assert counters == (3, 2, 1) and np.array_equal(out, whole["map"])
+    counters, _ = run(draws=np.array([[7, 6, 0, 0]], np.uint32))  # a draw that starts behind the buffer
+    assert counters == (2, 0, 2)
+    # a vertex equal to the vertex count: through the index, through vertexOffset, and not wrapped into the buffer by 32-bit arithmetic
+    idx = base["indices"].copy()
+    idx[5] = 6
+    counters, out = run(indices=idx)
+    assert counters == (2, 1, 1) and np.array_equal(out, first["map"])
+    counters, out = run(indices=np.array([0, 1, 2, 0, 1, 2], np.uint32), draws=np.array([[0, 3, 0, 0], [3, 3, 4, 0]], np.uint32))
+    assert counters == (2, 1, 1) and np.array_equal(out, first["map"])
+    idx[5] = 0xFFFFFFFF
+    counters, out = run(indices=idx, draws=np.array([[0, 3, 0, 0], [3, 3, 3, 0]], np.uint32))  # 0xFFFFFFFF + 3 is vertex 2 in 32 bits
+    assert counters == (2, 1, 1) and np.array_equal(out, first["map"])
+    # transformIndex equal to the transform count: the whole draw
+    counters, out = run(draws=np.array([[0, 3, 0, 0], [3, 3, 0, 1]], np.uint32))
+    assert counters == (2, 1, 1) and np.array_equal(out, first["map"])
+    counters, out = run(draws=np.array([[0, 6, 0, 1]], np.uint32))
+    assert counters == (2, 0, 2) and not out.any()
+    # no buffer at all
+    counters, out = run(positions=np.zeros((0, 3), np.float32))
+    assert counters == (2, 0, 2) and not out.any()
+
+
 def test_the_shadow_caster_entry_points_are_exported():
     from plainrenderer_amd import backend
     lib = backend._load()
