@@ -167,15 +167,16 @@ int PassCtx::needGlobal() const {
     return 0;
 }
 void* PassCtx::scratch(size_t bytes) const {
-    if (!scratchSlot) return nullptr;
-    if (*scratchSize < bytes) {
-        if (*scratchSlot) { hipStreamSynchronize(stream); hipFree(*scratchSlot); }
-        *scratchSlot = nullptr;
-        if (hipMalloc(scratchSlot, bytes) != hipSuccess) { *scratchSize = 0; return nullptr; }
-        hipMemsetAsync(*scratchSlot, 0, bytes, stream);
-        *scratchSize = bytes;
+    if (!passScratch) return nullptr;
+    PassScratch& s = *passScratch;
+    if (s.bytes < bytes) {
+        if (s.dev) { hipStreamSynchronize(stream); hipFree(s.dev); }
+        s = PassScratch{}; // what the launcher knew about the old memory goes with it
+        if (hipMalloc(&s.dev, bytes) != hipSuccess) return nullptr;
+        hipMemsetAsync(s.dev, 0, bytes, stream);
+        s.bytes = bytes;
     }
-    return *scratchSlot;
+    return s.dev;
 }
 
 // ---------------------------------------------------------------- resources
@@ -217,8 +218,7 @@ struct PassRes {
     std::vector<SpecConstant> spec;
     LaunchFn fn = nullptr, fast = nullptr;
     bool readsBindless = false;
-    void* scratch = nullptr;
-    size_t scratchSize = 0;
+    PassScratch scratch;
 };
 
 // one resource an execution touches, for the hazard analysis of the stream scheduler: key = base address of the allocation
@@ -247,6 +247,7 @@ struct FillOrder {
     size_t stagingOffset;
 };
 
+struct EarlyPlan { size_t at = 0, group = 0, count = 0; const FusionEntry* f = nullptr; hipEvent_t done = nullptr; bool launched = false; }; // planEarlyParts below
 struct Backend {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -334,6 +335,7 @@ struct Backend {
     uint64_t mainOps = 0, tailStartOps = ~0ull;
     bool tailStartCoversLate = false, lateLaunchedThisFrame = false;
     std::vector<const void*> lastFillDsts; // destinations of the buffer fills flushed for the frame being launched
+    std::vector<EarlyPlan> earlyPlans;     // of the frame being launched: filled and consumed inside one launchAll
 
     std::vector<Access> tailPending;
     bool asyncTail = true;               // plr_set_async_tail
@@ -566,7 +568,6 @@ static bool sameDesc(const plr_image_desc& a, const plr_image_desc& b) { return 
 int launchSkyLutProbe(const ImgView& lut, const float* dirs, float* out, int64_t n); // kernels_fast/stream_fast.hip
 int launchSamplerProbe(const ImgView& view, int filter, int address, const float* coords, float* out, int64_t n); // kernels/probes.hip
 
-
 static bool sameView(const ImgView& a, const ImgView& b) { return a.ptr == b.ptr && a.w == b.w && a.h == b.h && a.d == b.d && a.fmt == b.fmt; }
 int launchOverTwoRowRanges(const PassCtx* const* ctxs, size_t count, LaunchFn single) {
     if (count != 2) return kUseGeneralKernel;
@@ -574,7 +575,7 @@ int launchOverTwoRowRanges(const PassCtx* const* ctxs, size_t count, LaunchFn si
     const PassCtx& b = *ctxs[1];
     if (a.sampledMask != b.sampledMask || a.storageMask != b.storageMask || a.sbufMask != b.sbufMask || a.ubufMask != b.ubufMask || a.push != b.push || a.spec != b.spec ||
         a.dispatch[0] != b.dispatch[0] || a.base[0] != b.base[0] || a.dispatch[2] != b.dispatch[2] || a.validRows[0] != b.validRows[0] || a.validRows[1] != b.validRows[1] ||
-        a.validCols[0] != b.validCols[0] || a.validCols[1] != b.validCols[1] || a.extraCountY || b.extraCountY || a.scratchSlot != b.scratchSlot)
+        a.validCols[0] != b.validCols[0] || a.validCols[1] != b.validCols[1] || a.extraCountY || b.extraCountY || a.passScratch != b.passScratch)
         return kUseGeneralKernel;
     for (int i = 0; i < kMaxBindings; i++) {
         if (a.hasSampled(i) && !sameView(a.sampled[i], b.sampled[i])) return kUseGeneralKernel;
@@ -724,7 +725,7 @@ int plr_shutdown(void) {
     freeImage(g->swapchain);
     for (auto& b : g->ubufs) if (b.dev) hipFree(b.dev);
     for (auto& b : g->sbufs) if (b.dev) hipFree(b.dev);
-    for (auto& p : g->passes) if (p->scratch) hipFree(p->scratch);
+    for (auto& p : g->passes) if (p->scratch.dev) hipFree(p->scratch.dev);
     if (g->debugSig) hipFree(g->debugSig);
     for (auto ev : g->passEvents) hipEventDestroy(ev);
     for (auto ev : g->orderEvents) hipEventDestroy(ev);
@@ -1382,8 +1383,7 @@ static void prepareCtx(Execution& x, hipStream_t stream, const GlobalUbo* global
     x.ctx.bindlessCount = (uint32_t)g->images.size();
     x.ctx.spec = &p.spec;
     x.ctx.err = &g_err;
-    x.ctx.scratchSlot = &p.scratch;
-    x.ctx.scratchSize = &p.scratchSize;
+    x.ctx.passScratch = &p.scratch;
     x.ctx.debugSig = g->debugSig;
     x.ctx.debugSigWords = g->debugSigWords;
     x.ctx.passName = p.name.c_str();
@@ -1495,8 +1495,6 @@ static int launchExecution(Execution& x, hipStream_t stream, const GlobalUbo* gl
 // compute execution lies between that position and the sequence: something to run beside. launchEarlyPartsAt(i) issues the plans of position i on the early
 // stream before execution i is launched; tryFusedLaunch makes the launch stream wait for the part's event and tells the launcher (PassCtx::earlyPartDone).
 // (the plans are rebuilt from the recorded executions by every launchAll: no address outlives the frame, a resize cannot leave one stale)
-struct EarlyPlan { size_t at = 0, group = 0, count = 0; const FusionEntry* f = nullptr; hipEvent_t done = nullptr; bool launched = false; };
-static thread_local std::vector<EarlyPlan> g_earlyPlans;
 static bool fusionNamesMatch(const FusionEntry& f, size_t i, size_t n) {
     const size_t m = f.shaders.size();
     if (i + m > n || m > 8) return false;
@@ -1507,7 +1505,7 @@ static bool fusionNamesMatch(const FusionEntry& f, size_t i, size_t n) {
     return true;
 }
 static void planEarlyParts(const GlobalUbo* globalPtr) {
-    g_earlyPlans.clear();
+    g->earlyPlans.clear();
     if (!g->earlyParts || !g->fusion || g->mathMode != PLR_MATH_FAST || g->debugSig || g->overlap || !g->earlyStream) return;
     const size_t n = g->executions.size();
     std::vector<const void*> reads;
@@ -1559,12 +1557,12 @@ static void planEarlyParts(const GlobalUbo* globalPtr) {
         if (tailHazard || (g->earlyParts < 2 && (at >= i || beside == 0))) continue;
         EarlyPlan plan;
         plan.at = at; plan.group = i; plan.count = m; plan.f = f;
-        g_earlyPlans.push_back(plan);
+        g->earlyPlans.push_back(plan);
         i += m - 1;
     }
 }
 static int launchEarlyPartsAt(size_t index, const GlobalUbo* globalPtr, bool timed) {
-    for (EarlyPlan& plan : g_earlyPlans) {
+    for (EarlyPlan& plan : g->earlyPlans) {
         if (plan.at != index || plan.launched) continue;
         // order the early stream behind what the part depends on: everything launched so far in this frame - or, at the frame's start, the previous frame's late
         // part, which read the scratch memory this part overwrites: the tail's start event of that frame covers it for free (an event record is a barrier packet
@@ -1617,7 +1615,7 @@ static int tryFusedLaunch(size_t i, size_t last, hipStream_t stream, const Globa
         if (n > 8) continue;
         for (size_t k = 0; k < n; k++) { prepareCtx(g->executions[i + k], stream, globalPtr); ctxs[k] = &g->executions[i + k].ctx; }
         EarlyPlan* early = nullptr;
-        for (EarlyPlan& plan : g_earlyPlans) if (plan.launched && plan.group == i && plan.f == &f) early = &plan;
+        for (EarlyPlan& plan : g->earlyPlans) if (plan.launched && plan.group == i && plan.f == &f) early = &plan;
         if (early) {
             HIP_TRY(hipStreamWaitEvent(stream, early->done, 0));
             for (size_t k = 0; k < n; k++) g->executions[i + k].ctx.earlyPartDone = true;

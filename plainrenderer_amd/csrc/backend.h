@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -23,6 +24,12 @@ struct BufferBinding {
     size_t size = 0;
     bool readOnly = false;
 };
+
+// A pass's persistent device scratch and what its launcher knows about the contents; the pass owns both (PassRes, backend.cpp) and plr_shutdown frees them with it.
+// The memory only grows and is zero-filled when it is (re)allocated (PassCtx::scratch). The same (re)allocation drops `state`, and PassCtx::scratchState<T>() default-
+// constructs the next one: a default-constructed T means "the scratch holds zeros", and a launcher sets a field of its T once the launch that built the table succeeded.
+struct ScratchState { virtual ~ScratchState() = default; };
+struct PassScratch { void* dev = nullptr; size_t bytes = 0; std::unique_ptr<ScratchState> state; };
 
 // Everything a pass launcher needs, with handles already resolved to HBM addresses.
 struct PassCtx {
@@ -90,8 +97,7 @@ struct PassCtx {
     uint64_t frameSerial = 0;             // serial of this plr_render_frame call, unique in the process: lets a pass's host-side bookkeeping tell this frame's entries from stale ones
     const std::vector<SpecConstant>* spec = nullptr;
     std::string* err = nullptr;
-    void** scratchSlot = nullptr;         // persistent per-pass scratch (device memory, grow-only)
-    size_t* scratchSize = nullptr;
+    PassScratch* passScratch = nullptr;   // persistent per-pass scratch (device memory, grow-only) and the launcher's record of its contents
     // decision signatures (plr_debug_set_decision_signature, plr.h): when set, the kernels that support it write one word per output pixel
     uint32_t* debugSig = nullptr;
     size_t debugSigWords = 0;
@@ -148,6 +154,12 @@ struct PassCtx {
     int needUbuf(int binding, size_t minSize, const char* what) const;
     int needGlobal() const;
     void* scratch(size_t bytes) const;
+    template <class T> T* scratchState() const { // (PassScratch above; a pass's scratch has one layout, hence one T: null, with the error recorded, for another)
+        if (passScratch && !passScratch->state) passScratch->state.reset(new T());
+        T* s = passScratch ? dynamic_cast<T*>(passScratch->state.get()) : nullptr;
+        if (!s) fail(-1, "scratchState: this pass has no scratch, or keeps a scratch state of another type");
+        return s;
+    }
     // pass timing (plr_set_pass_timing): a pass that launches an auxiliary kernel before its main one calls this between the two, so the
     // auxiliary part is reported as its own entry "<pass name> (<label>)" and the pass entry times the main kernel alone
     void splitTiming(const char* label) const;

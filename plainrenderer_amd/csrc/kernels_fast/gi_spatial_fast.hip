@@ -30,7 +30,6 @@
 #include "../device/buffer_fetch.h"
 #include "fused_gi.h"
 #include <cstdlib>
-#include <map>
 #include <utility>
 #include <vector>
 #include <type_traits>
@@ -445,15 +444,29 @@ __global__ __launch_bounds__(256) void spatialFilterFastKernel(ImgView outYSH, I
     if (SIG) { sig[2 * idx] = sampleParityX; sig[2 * idx + 1] = sampleParityY; }
 }
 
-// scratch of a filter pass: [sample tables | packed texels of the whole input image]
+// scratch of a filter pass: [sample tables | packed texels of the whole input image], and what the host knows about it
 constexpr size_t kSpatialTableBytes = 4096;
 static_assert(sizeof(float) * kSampleKeys * kSampleTableFloats <= kSpatialTableBytes, "sample tables");
-static uint8_t* spatialScratch(const PassCtx& c, bool sameGrid) {
+// what of the packed copy the producer of the input filled this frame: rectangles (whole rows in band rendering, a tile's rectangle in tile rendering). Across a
+// resize: valid for one frame (frameSerial) and one source image address only, and the rectangles are clipped to the consumer's current image - nothing carries over
+struct PackRect { int x0, y0, x1, y1; };
+struct PackedRects {
+    uint64_t frameSerial = 0;
+    const void* source = nullptr;             // the Y_SH image the texels were packed from
+    std::vector<PackRect> rects;
+};
+struct SpatialState : ScratchState { bool tablesBuilt = false; PackedRects packed; };
+static int spatialScratch(const PassCtx& c, bool sameGrid, uint8_t** out) { // 0 and *out = the scratch with its sample tables built, or an error
     const size_t packedBytes = sameGrid ? (size_t)c.sampled[2].w * (size_t)c.sampled[2].h * 16u : 0u;
-    const bool freshScratch = c.scratchSize && *c.scratchSize < kSpatialTableBytes + packedBytes;
-    uint8_t* scratch = (uint8_t*)c.scratch(kSpatialTableBytes + packedBytes);
-    if (scratch && freshScratch) spatialSampleTableKernel<<<1, 256, 0, c.stream>>>((float*)scratch);
-    return scratch;
+    *out = (uint8_t*)c.scratch(kSpatialTableBytes + packedBytes);
+    if (!*out) return c.fail(-2, "filterIndirectDiffuseSpatial: cannot allocate scratch memory");
+    SpatialState* state = c.scratchState<SpatialState>();
+    if (state && !state->tablesBuilt) {
+        spatialSampleTableKernel<<<1, 256, 0, c.stream>>>((float*)*out);
+        PLR_CHECK_LAUNCH(c);
+        state->tablesBuilt = true;
+    }
+    return state ? 0 : -1;
 }
 
 int spatialFilterPackTarget(const PassCtx& c, SpatialPackTarget* out) {
@@ -463,24 +476,12 @@ int spatialFilterPackTarget(const PassCtx& c, SpatialPackTarget* out) {
     // every reason for which THIS pass's launcher hands the execution to the general kernel must also be a "no" here: a producer that was promised a packed-texel
     // consumer may leave the unpacked image unwritten (fusion level 2), and the general kernel reads the image
     if (!c.global || !c.globalHost) return kUseGeneralKernel;
-    uint8_t* scratch = spatialScratch(c, true);
-    if (!scratch) return c.fail(-2, "filterIndirectDiffuseSpatial: cannot allocate scratch memory");
+    uint8_t* scratch = nullptr;
+    if (int rc = spatialScratch(c, true, &scratch)) return rc;
     out->packed = (uint4*)(scratch + kSpatialTableBytes);
     out->depth = c.sampled[4];
     return 0;
 }
-
-// ---- what of a filter pass's packed copy its producer filled this frame: rectangles (whole rows in band rendering, a tile's rectangle in tile rendering).
-// Host-side bookkeeping, one entry per filter pass = per scratch slot; the backend is one instance per host thread. Across a resize: an entry is valid for one frame
-// (frameSerial), one source image address and one packed copy address only, and the rectangles are clipped to the consumer's current image - nothing carries over
-struct PackRect { int x0, y0, x1, y1; };
-struct PackedRects {
-    uint64_t frameSerial = 0;
-    const void* source = nullptr;             // the Y_SH image the texels were packed from
-    const void* packed = nullptr;             // the packed copy they were written to (a re-allocated scratch invalidates the entry)
-    std::vector<PackRect> rects;
-};
-static thread_local std::map<const void*, PackedRects> g_packedRects;
 
 int spatialPackTargetOfConsumer(const PassCtx& producer, int outY, int outC, SpatialPackTarget* out) {
     const PassCtx* f = producer.consumer;
@@ -492,12 +493,10 @@ int spatialPackTargetOfConsumer(const PassCtx& producer, int outY, int outC, Spa
 }
 void spatialNotePackedRect(const PassCtx& producer, int x0, int y0, int x1, int y1) {
     const PassCtx* f = producer.consumer;
-    if (!f || !f->scratchSlot || y1 <= y0 || x1 <= x0) return;
-    PackedRects& e = g_packedRects[(const void*)f->scratchSlot];
-    const void* packed = *f->scratchSlot ? (const uint8_t*)*f->scratchSlot + kSpatialTableBytes : nullptr;
-    if (e.frameSerial != producer.frameSerial || e.source != f->sampled[2].ptr || e.packed != packed) {
-        e.frameSerial = producer.frameSerial; e.source = f->sampled[2].ptr; e.packed = packed; e.rects.clear();
-    }
+    SpatialState* state = f && f->passScratch && y1 > y0 && x1 > x0 ? f->scratchState<SpatialState>() : nullptr;
+    if (!state) return;
+    PackedRects& e = state->packed;
+    if (e.frameSerial != producer.frameSerial || e.source != f->sampled[2].ptr) e = PackedRects{producer.frameSerial, f->sampled[2].ptr, {}};
     e.rects.push_back({x0, y0, x1, y1});
     countFusedExecutions(1);
 }
@@ -507,11 +506,10 @@ void spatialNotePackedRows(const PassCtx& producer, int y0, int y1) {
 }
 // the rectangle `all` minus what the producer packed this frame, as at most four rectangles (more: the caller packs `all` whole; the producer's texels
 // are then written a second time with the same values)
-static int unpackedRects(const PassCtx& c, const void* packed, PackRect all, PackRect out[4]) {
+static int unpackedRects(const PassCtx& c, const PackedRects& done, PackRect all, PackRect out[4]) {
     std::vector<PackRect> rest{all};
-    auto it = c.scratchSlot ? g_packedRects.find((const void*)c.scratchSlot) : g_packedRects.end();
-    if (it != g_packedRects.end() && it->second.frameSerial == c.frameSerial && it->second.source == c.sampled[2].ptr && it->second.packed == packed) {
-        for (const PackRect& r : it->second.rects) {
+    if (done.frameSerial == c.frameSerial && done.source == c.sampled[2].ptr) {
+        for (const PackRect& r : done.rects) {
             std::vector<PackRect> next;
             for (const PackRect& q : rest) {
                 if (r.x1 <= q.x0 || r.x0 >= q.x1 || r.y1 <= q.y0 || r.y0 >= q.y1) { next.push_back(q); continue; }
@@ -567,9 +565,8 @@ static int launchSpatialFilterFast(const PassCtx& c) {
     const dim3 grid = xcdWalkGrid2(tilesX, tilesY, chunksPerXcd, splitX);
     // half-res trace: depth and GI images share the texel grid (one texel index serves all gathers, and the packed path applies)
     const bool sameGrid = c.sampled[4].w == c.sampled[2].w && c.sampled[4].h == c.sampled[2].h;
-    uint8_t* scratch = spatialScratch(c, sameGrid);
-    if (!scratch) return c.fail(-2, "filterIndirectDiffuseSpatial: cannot allocate scratch memory");
-    PLR_CHECK_LAUNCH(c);
+    uint8_t* scratch = nullptr;
+    if (int rc = spatialScratch(c, sameGrid, &scratch)) return rc;
     float* tables = (float*)scratch;
     uint4* packed = (uint4*)(scratch + kSpatialTableBytes);
     int validLo, validHi, validLoX, validHiX;
@@ -598,7 +595,7 @@ static int launchSpatialFilterFast(const PassCtx& c) {
         const int marginX = requested ? 0 : std::max({128, x0 - validLoX, validHiX - w});
         const int q0 = tiled ? std::max({x0 - marginX, 0, validLoX}) : 0, q1 = tiled ? std::min({w + marginX, (int)c.sampled[2].w, validHiX}) : (int)c.sampled[2].w;
         PackRect todo[4];
-        const int nTodo = p1 > p0 && q1 > q0 && requestPhase != 2 ? unpackedRects(c, packed, PackRect{q0, p0, q1, p1}, todo) : 0; // (phase 2: phase 1 packed the rectangle)
+        const int nTodo = p1 > p0 && q1 > q0 && requestPhase != 2 ? unpackedRects(c, c.scratchState<SpatialState>()->packed, PackRect{q0, p0, q1, p1}, todo) : 0; // (phase 2: phase 1 packed the rectangle)
         if (c.sampled[4].fmt != F_R16F && c.sampled[4].fmt != F_D32) return c.fail(-4, "filterIndirectDiffuseSpatial: depthTexture must be R16_sFloat or Depth32");
         if (nTodo) {
             PackRects pr{};
@@ -652,6 +649,7 @@ static int launchSpatialFilterFast(const PassCtx& c) {
 }
 PLR_REGISTER_SHADER_FAST("filterIndirectDiffuseSpatial.comp", launchSpatialFilterFast);
 
+struct RequestScratchState : ScratchState { bool ready = false; }; // sample tables built, byte maps zeroed
 // ---- giSampleRequests.comp (no reference counterpart; the request-list GI exchange of a partitioned frame, plr_frame.h PLRF_HALO_REQUESTED): for the rectangle of
 // trace pixels it is dispatched over - recorded like the spatial filter execution it precedes: same dispatch, valid_rows / valid_cols = the rank's own rectangle - sets
 // the bit of every texel OUTSIDE that rectangle a disc sample of filterIndirectDiffuseSpatial.comp (specialisation constant 0 = its filterIndex) lands on.
@@ -678,14 +676,19 @@ static int launchGiSampleRequestsImpl(const PassCtx& c, const PassCtx* second) {
     const uint32_t bytePitch = rowWords * 32u;
     const size_t byteMapBytes = (size_t)bytePitch * (size_t)depth.h;
     const size_t scratchBytes = kSpatialTableBytes + 2 * byteMapBytes;
-    const bool freshScratch = c.scratchSize && *c.scratchSize < scratchBytes;
     uint8_t* scratch = (uint8_t*)c.scratch(scratchBytes);
     if (!scratch) return c.fail(-2, "giSampleRequests: cannot allocate scratch memory");
-    if (freshScratch) spatialSampleTableKernel<<<1, 256, 0, c.stream>>>((float*)scratch);
+    RequestScratchState* state = c.scratchState<RequestScratchState>();
+    if (!state) return -1;
     uint8_t* byteMap = scratch + kSpatialTableBytes;
     uint8_t* byteMap2 = second ? byteMap + byteMapBytes : nullptr;
-    // (both maps are zero between frames: requestBytesToBitsKernel clears what a pass set)
-    if (freshScratch && hipMemsetAsync(byteMap, 0, 2 * byteMapBytes, c.stream) != hipSuccess) return c.fail(-2, "giSampleRequests: hipMemsetAsync");
+    if (!state->ready) {
+        spatialSampleTableKernel<<<1, 256, 0, c.stream>>>((float*)scratch);
+        PLR_CHECK_LAUNCH(c);
+        // (both maps are zero between frames: requestBytesToBitsKernel clears what a pass set)
+        if (hipMemsetAsync(byteMap, 0, 2 * byteMapBytes, c.stream) != hipSuccess) return c.fail(-2, "giSampleRequests: hipMemsetAsync");
+        state->ready = true;
+    }
     auto clearBitmaps = [&]() {
         if (hipMemsetAsync(c.sbuf[6].ptr, 0, bitmapBytes, c.stream) != hipSuccess) return false;
         return !second || hipMemsetAsync(second->sbuf[6].ptr, 0, bitmapBytes, c.stream) == hipSuccess;
@@ -696,7 +699,6 @@ static int launchGiSampleRequestsImpl(const PassCtx& c, const PassCtx* second) {
     const int chunksPerXcd = std::max(1, (tilesY * TYv + 272) / 544);
     const int chunkRows = xcdChunkRows(tilesY, chunksPerXcd) | (1 << 16); // (rows | splitX << 16: the kernel's xcdWalk2)
     const dim3 grid = xcdWalkGrid(tilesX, tilesY, chunksPerXcd);
-    PLR_CHECK_LAUNCH(c);
     int validLo, validHi, validLoX, validHiX;
     c.validRowRange(depth.h, &validLo, &validHi);
     c.validColRange(depth.w, &validLoX, &validHiX);

@@ -20,7 +20,6 @@
 #include "../device/sdf_bricks.h"
 #include "fused_gi.h"
 #include <cstdlib>
-#include <map>
 #include <vector>
 
 namespace plr {
@@ -477,23 +476,19 @@ __global__ void sdfBrickKernel(const uint16_t* __restrict__ src, uint16_t* __res
     dst[slot] = src[((size_t)z * h + y) * w + x];
 }
 
-
-struct BrickCache {
+struct BrickCache : ScratchState {
     struct Entry { const void* src = nullptr; int w = 0, h = 0, d = 0; uint64_t version = 0; size_t offset = 0; };
-    const void* scratch = nullptr;
-    size_t scratchBytes = 0;                // with the base: a grown (zero-filled) scratch can come back at the address just freed
     std::vector<Entry> entries;             // per global texture slot
     std::vector<const uint16_t*> table;     // host copy of the device table
 };
-// -> device table (slot -> bricked copy or null), or null: no copies (a host the backend cannot read the texture table of, out of memory).
+// *out = device table (slot -> bricked copy or null), or null: no copies (a host the backend cannot read the texture table of, out of memory). 0, or an error.
 // A copy is (re)built when its image is new, resized, moved or has new contents (contentVersionOf: uploads, passes that write it); an image whose address was
 // handed out (plr_get_image_device_pointer) is never cached and is marched in its image layout.
-static const uint16_t* const* brickedVolumeTable(const PassCtx& c) {
-    if (!c.bindlessHost || c.bindlessCount == 0 || !c.scratchSlot) return nullptr;
+static int brickedVolumeTable(const PassCtx& c, const uint16_t* const** out) {
+    *out = nullptr;
+    if (!c.bindlessHost || c.bindlessCount == 0) return 0;
     const uint32_t n = c.bindlessCount;
     auto align = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
-    static thread_local std::map<void**, BrickCache> caches; // one backend per host thread; keyed by the pass's scratch slot
-    BrickCache& cache = caches[c.scratchSlot];
     std::vector<BrickCache::Entry> want(n);
     size_t total = align((size_t)n * sizeof(void*));
     for (uint32_t i = 0; i < n; i++) {
@@ -504,28 +499,31 @@ static const uint16_t* const* brickedVolumeTable(const PassCtx& c) {
         want[i].src = v.ptr; want[i].w = v.w; want[i].h = v.h; want[i].d = v.d; want[i].version = version; want[i].offset = total;
         total += align(brickedTexelCount(v.w, v.h, v.d) * sizeof(uint16_t));
     }
-    if (total > ((size_t)8 << 30)) return nullptr;
+    if (total > ((size_t)8 << 30)) return 0;
     uint8_t* scratch = (uint8_t*)c.scratch(total); // grow-only; a re-allocation drops every copy
-    if (!scratch) return nullptr;
-    const bool fresh = cache.scratch != (const void*)scratch || cache.scratchBytes != *c.scratchSize || cache.entries.size() != n;
-    if (fresh) { cache.entries.assign(n, BrickCache::Entry{}); cache.table.assign(n, nullptr); cache.scratch = scratch; cache.scratchBytes = *c.scratchSize; }
+    if (!scratch) return 0;
+    BrickCache* cache = c.scratchState<BrickCache>();
+    if (!cache) return -1;
+    const bool fresh = cache->entries.size() != n;
+    if (fresh) { cache->entries.assign(n, BrickCache::Entry{}); cache->table.assign(n, nullptr); }
     bool tableChanged = fresh;
     for (uint32_t i = 0; i < n; i++) {
-        const BrickCache::Entry &w = want[i], &have = cache.entries[i];
+        const BrickCache::Entry &w = want[i], &have = cache->entries[i];
         const uint16_t* copy = w.src ? (const uint16_t*)(scratch + w.offset) : nullptr;
         if (w.src && (have.src != w.src || have.w != w.w || have.h != w.h || have.d != w.d || have.version != w.version || have.offset != w.offset)) {
             const size_t slots = brickedTexelCount(w.w, w.h, w.d);
             sdfBrickKernel<<<(unsigned)divUp((unsigned)slots, 256u), 256, 0, c.stream>>>((const uint16_t*)w.src, (uint16_t*)(scratch + w.offset), w.w, w.h, w.d);
-            if (hipGetLastError() != hipSuccess) return nullptr;
+            if (hipGetLastError() != hipSuccess) return 0;
         }
-        cache.entries[i] = w;
-        if (cache.table[i] != copy) { cache.table[i] = copy; tableChanged = true; }
+        cache->entries[i] = w;
+        if (cache->table[i] != copy) { cache->table[i] = copy; tableChanged = true; }
     }
     if (tableChanged) { // rare (start-up, a new volume): the table's host copy must outlive the transfer
-        if (hipMemcpyAsync(scratch, cache.table.data(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, c.stream) != hipSuccess) return nullptr;
-        if (hipStreamSynchronize(c.stream) != hipSuccess) return nullptr;
+        if (hipMemcpyAsync(scratch, cache->table.data(), (size_t)n * sizeof(void*), hipMemcpyHostToDevice, c.stream) != hipSuccess) return 0;
+        if (hipStreamSynchronize(c.stream) != hipSuccess) return 0;
     }
-    return (const uint16_t* const*)scratch;
+    *out = (const uint16_t* const*)scratch;
+    return 0;
 }
 
 static int launchImpl(const PassCtx& c) {
@@ -593,7 +591,7 @@ static int launchImpl(const PassCtx& c) {
             // (2: as 1, and a launch that cannot take the variant is an error - how the test knows the variant ran)
             const char* bricksEnv = std::getenv("PLR_TRACE_BRICKS");
             const int bricksMode = bricksEnv ? std::atoi(bricksEnv) : 0;
-            if (bricksMode >= 1 && strict && !perLane) brickedVolumes = brickedVolumeTable(c);
+            if (bricksMode >= 1 && strict && !perLane) if (int rc = brickedVolumeTable(c, &brickedVolumes)) return rc;
             if (bricksMode >= 2 && !brickedVolumes) return c.fail(-1, "sdfDiffuseTrace: PLR_TRACE_BRICKS=2 but this launch cannot march bricked volumes");
             if (brickedVolumes) sdfDiffuseTraceFastKernel<true, false, F_R16F, false, true><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS);
             else if (strict && perLane) sdfDiffuseTraceFastKernel<true, false, F_R16F, true><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS);

@@ -21,7 +21,6 @@
 #include "pcf_taps.h"
 #include <cstdlib>
 #include <type_traits>
-#include <map>
 
 namespace plr {
 
@@ -940,16 +939,12 @@ __global__ void pcfTapsByPositionKernel(const uint16_t* __restrict__ noiseTexels
         byPosition[(uint32_t)k * positions + pos] = make_float4(taps[i0].x, taps[i0].y, taps[i1].x, taps[i1].y);
     }
 }
-struct ShadeDerived {
-    // the allocation the entries below describe: base AND size. The scratch is grow-only and zero-filled when it grows, and a larger allocation can come back
-    // at the address just freed (a resize makes the records region grow): keyed on the address alone, the tables would be taken for built while they are zeros
-    const void* scratchBase = nullptr;
-    size_t scratchBytes = 0;
+struct ShadeDerived : ScratchState {
+    bool tapTableBuilt = false; // the by-value table at the start of the scratch
     struct Slot { const void* noise = nullptr; int w = 0, h = 0; uint64_t version = 0, lastUse = 0; } slots[kNoiseSlots];
     uint64_t useCounter = 0;
     const void* lut = nullptr; int lutW = 0, lutH = 0; uint64_t lutVersion = 0; // what the energy footprint was derived from
 };
-static thread_local std::map<const void*, ShadeDerived> g_shadeDerived; // key = the pass's scratch slot (one backend per host thread)
 static int shadeDerivedTables(const PassCtx& c, ShadeParams* P, DirectRecords* records = nullptr) {
     // [tap table by value | noise slots | BRDF LUT energy footprint (size follows the LUT: a larger LUT re-allocates the scratch and everything is rebuilt) and its flag
     //  | the direct launch's records: planes a, b, c over the colour target (only when the shade runs as two launches)]
@@ -963,13 +958,12 @@ static int shadeDerivedTables(const PassCtx& c, ShadeParams* P, DirectRecords* r
     uint8_t* scratch = (uint8_t*)c.scratch(total);
     if (!scratch) return c.fail(-2, "deferredShading: cannot allocate scratch memory");
     if (records) { records->a = (uint4*)(scratch + recordsOffset); records->b = records->a + pixels; records->c = (uint32_t*)(records->b + pixels); }
-    ShadeDerived& d = g_shadeDerived[(const void*)c.scratchSlot];
-    if (d.scratchBase != scratch || d.scratchBytes != *c.scratchSize) {
-        d = ShadeDerived{};
-        d.scratchBase = scratch;
-        d.scratchBytes = *c.scratchSize;
+    ShadeDerived* d = c.scratchState<ShadeDerived>();
+    if (!d) return -1;
+    if (!d->tapTableBuilt) {
         const hipError_t e = buildPcfTapTable((float2*)scratch, c.stream);
         if (e != hipSuccess) return c.fail(-2, std::string("deferredShading: PCF tap table: ") + hipGetErrorString(e));
+        d->tapTableBuilt = true;
     }
     P->pcfTaps = (const float4*)scratch;
     P->pcfTapsByPosition = nullptr;
@@ -977,13 +971,13 @@ static int shadeDerivedTables(const PassCtx& c, ShadeParams* P, DirectRecords* r
     P->lutEnergyFootprint = nullptr;
     P->lutEnergyNonFinite = nullptr;
     if (const uint64_t lutVersion = lut.h >= 2 ? contentVersionOf(lut.ptr) : 0) { // 0: the LUT may change behind the backend's back - the kernel reads the LUT itself
-        if (d.lut != lut.ptr || d.lutW != lut.w || d.lutH != lut.h || d.lutVersion != lutVersion) {
+        if (d->lut != lut.ptr || d->lutW != lut.w || d->lutH != lut.h || d->lutVersion != lutVersion) {
             const hipError_t e = hipMemsetAsync(scratch + flagOffset, 0, 16, c.stream);
             if (e != hipSuccess) return c.fail(-2, std::string("deferredShading: LUT energy footprint: ") + hipGetErrorString(e));
             lutEnergyFootprintKernel<<<dim3(divUp((unsigned)(lut.w - 1), 64u), divUp((unsigned)(lut.h - 1), 4u)), 256, 0, c.stream>>>(lut, (uint2*)(scratch + footprintOffset),
                                                                                                                                        (uint32_t*)(scratch + flagOffset));
             PLR_CHECK_LAUNCH(c);
-            d.lut = lut.ptr; d.lutW = lut.w; d.lutH = lut.h; d.lutVersion = lutVersion;
+            d->lut = lut.ptr; d->lutW = lut.w; d->lutH = lut.h; d->lutVersion = lutVersion;
         }
         P->lutEnergyFootprint = (const uint2*)(scratch + footprintOffset);
         P->lutEnergyNonFinite = (const uint32_t*)(scratch + flagOffset);
@@ -994,17 +988,17 @@ static int shadeDerivedTables(const PassCtx& c, ShadeParams* P, DirectRecords* r
     const uint64_t positions = (uint64_t)noise.w * (uint64_t)noise.h;
     if (version == 0 || positions > kMaxNoisePositions) return 0;
     ShadeDerived::Slot* slot = nullptr;
-    for (auto& s : d.slots) if (s.noise == noise.ptr && s.w == noise.w && s.h == noise.h && s.version == version) slot = &s;
+    for (auto& s : d->slots) if (s.noise == noise.ptr && s.w == noise.w && s.h == noise.h && s.version == version) slot = &s;
     if (!slot) {
-        slot = &d.slots[0];
-        for (auto& s : d.slots) if (s.lastUse < slot->lastUse) slot = &s; // least recently used
-        float4* dst = (float4*)(scratch + kPcfTapTableBytes + (size_t)(slot - d.slots) * kNoiseSlotBytes);
+        slot = &d->slots[0];
+        for (auto& s : d->slots) if (s.lastUse < slot->lastUse) slot = &s; // least recently used
+        float4* dst = (float4*)(scratch + kPcfTapTableBytes + (size_t)(slot - d->slots) * kNoiseSlotBytes);
         pcfTapsByPositionKernel<<<divUp((unsigned)positions, 256u), 256, 0, c.stream>>>((const uint16_t*)noise.ptr, (uint32_t)positions, (const float4*)scratch, dst);
         PLR_CHECK_LAUNCH(c);
         slot->noise = noise.ptr; slot->w = noise.w; slot->h = noise.h; slot->version = version;
     }
-    slot->lastUse = ++d.useCounter;
-    P->pcfTapsByPosition = (const float4*)(scratch + kPcfTapTableBytes + (size_t)(slot - d.slots) * kNoiseSlotBytes);
+    slot->lastUse = ++d->useCounter;
+    P->pcfTapsByPosition = (const float4*)(scratch + kPcfTapTableBytes + (size_t)(slot - d->slots) * kNoiseSlotBytes);
     P->pcfPositions = (uint32_t)positions;
     return 0;
 }
