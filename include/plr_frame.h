@@ -266,6 +266,34 @@ int plrf_set_shadow_casters(void* pipeline, const plr_mesh_data* meshes, uint32_
 int plrf_set_shadow_caster_transforms(void* pipeline, const float* matrices16, uint32_t draw_count);
 typedef struct plrf_shadow_raster_stats { uint64_t triangles_submitted, triangles_drawn, guard_band_rejects; } plrf_shadow_raster_stats;
 int plrf_get_shadow_raster_stats(void* pipeline, uint32_t cascade, plrf_shadow_raster_stats* out);
+/* ---- scene meshes: RenderFrontend::renderDepthPrepass (RenderFrontend.cpp:351, 792-802) as the compute pass "depthPrepassRaster.comp".
+ * While a pipeline has a scene, every plrf_frame records one execution of the pass in front of the light matrices and the depth pyramid (also under
+ * sdf_debug_mode). It rasterises the draws with the pipeline's own jittered viewProjection into the CURRENT frame's depth<i> and motion<i> and into normal, albedo
+ * and specular, and writes every texel of the five images (depth 0 = sky where nothing is drawn); what the caller uploaded to them is overwritten, and a resize
+ * needs no re-upload of the G-buffer. Without a scene nothing is recorded, created or allocated and the uploaded G-buffer is used. The rasterisation contract -
+ * Sutherland-Hodgman clipping against the near plane and a 32-NDC guard volume, 8 sub-pixel bits, top-left rule, back faces culled with a counter-clockwise front
+ * face, reverse-Z Depth32 with GreaterEqual and the later triangle winning a tie, perspective-correct fp64 attributes, opaque meshes, one constant material per
+ * draw - is DESIGN.md "Depth prepass as a compute pass".
+ * plrf_scene_mesh: positions and optional normals (3 floats per vertex; NULL, or a vertex normal of exactly (0, 0, 0): the triangle's face normal
+ * normalize(cross(v0 - v2, v0 - v1)) of the model-space positions) and a uint32 triangle list. plrf_scene_draw: a mesh under a model matrix with the two RGBA8
+ * texels (R in the low byte) every pixel of the draw stores to albedo and specular.
+ * plrf_set_scene_meshes copies everything; draw_count 0 removes the scene and the uploaded G-buffer is used again. PLR_ERR_INVALID_ARGUMENT, with a message that
+ * names the cause: a mesh index or a vertex index out of range, an index count that is no multiple of 3, a non-finite matrix element. PLR_ERR_UNSUPPORTED: a
+ * band / tile pipeline, for every call, a removal (draw_count 0) included - it could only be a no-op there. A refused call changes nothing.
+ * plrf_set_scene_mesh_transforms replaces the draws' model matrices (draw_count x 16 floats) from the next frame on; a draw_count other than the scene's is
+ * PLR_ERR_INVALID_ARGUMENT. A draw's previous model matrix (motion vectors) is the one the last recorded frame used; on the first frame after
+ * plrf_set_scene_meshes and after a camera cut it equals the current one.
+ * plrf_get_prepass_raster_stats: the counters of the last frame's execution for the scene now set; waits for the GPU. All zero while no scene is set (also after a
+ * removal) and before the first frame of a newly set scene. submitted = triangles of all draws, clipped = triangles the clip
+ * changed, subtriangles_drawn = front-facing sub-triangles whose pixel box meets the frame, rejects = triangles outside their buffers or with a non-finite clip
+ * coordinate plus sub-triangles with a vertex w <= 0 or outside the 2^20-pixel band. The storage buffer "mainPassMatrices" (plrf_get_storage_buffer) holds the
+ * {model, mvp, mvpPrevious} the last frame wrote, 48 floats per draw. */
+typedef struct plrf_scene_mesh { const float* positions; const float* normals; uint32_t vertex_count; const uint32_t* indices; uint32_t index_count; } plrf_scene_mesh;
+typedef struct plrf_scene_draw { uint32_t mesh; float model_matrix[16]; uint32_t albedo_rgba8, specular_rgba8; } plrf_scene_draw; /* glm column-major */
+int plrf_set_scene_meshes(void* pipeline, const plrf_scene_mesh* meshes, uint32_t mesh_count, const plrf_scene_draw* draws, uint32_t draw_count);
+int plrf_set_scene_mesh_transforms(void* pipeline, const float* matrices16, uint32_t draw_count);
+typedef struct plrf_prepass_raster_stats { uint64_t triangles_submitted, triangles_clipped, subtriangles_drawn, rejects; } plrf_prepass_raster_stats;
+int plrf_get_prepass_raster_stats(void* pipeline, plrf_prepass_raster_stats* out);
 /* one iteration of the reference's main loop: record the frame, update camera/UBOs, submit (does not wait for the GPU) */
 int plrf_frame(void* pipeline, const plrf_camera* camera, float delta_time, float time);
 /* host copies of what the last plrf_frame submitted (340-byte global UBO image, 9 TAA resolve weights) */

@@ -1,0 +1,52 @@
+// "depthPrepassRaster.comp": what the launcher (kernels/depth_prepass_raster.hip) and the frame pipeline (frontend/frame_pipeline.cpp) share - the pass record's
+// bindings, the layout of its buffers and of its scratch buffer. Plain C++: no device code here.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "sun_shadow_raster.h"
+
+namespace plr {
+namespace prepass {
+
+// the pass record (DESIGN.md "Depth prepass as a compute pass")
+constexpr int kTransformBinding = 0, kPositionBinding = 1, kNormalBinding = 2, kIndexBinding = 3, kDrawBinding = 4, kScratchBinding = 5;                  // storage buffers
+constexpr int kDepthBinding = 0, kMotionBinding = 1, kNormalImageBinding = 2, kAlbedoBinding = 3, kSpecularBinding = 4;                                   // storage images
+struct PushConstants { uint32_t drawCount, triangleCount; };
+struct Draw { uint32_t firstIndex, indexCount, vertexOffset, transformIndex, albedo, specular; }; // albedo, specular: RGBA8 texels as they are stored
+struct MainPassMatrices { float model[16], mvp[16], mvpPrevious[16]; };                            // glm column-major (RenderFrontend.cpp:581-585)
+static_assert(sizeof(Draw) == 24 && sizeof(MainPassMatrices) == 192, "pass buffer layouts");
+
+constexpr int kTileSize = sunraster::kTileSize;          // 64 x 64 64-bit keys: 32 KB of LDS per workgroup
+constexpr int kMaxResolution = sunraster::kMaxResolution;
+constexpr uint32_t kMaxTriangles = 1u << 28;             // 6 sub-triangles each still count in 32 bits
+constexpr uint32_t kMaxSubTriangles = 6;                 // a triangle clipped by five planes has at most 8 vertices
+constexpr float kGuardNdc = 32.f;                        // the four side planes of the clip volume: |x|, |y| <= 32 w
+
+// scratch: header, one {draw, triangle within the draw} per submitted triangle (the resolve finds a winner's vertices through it), then one 4-byte tile
+// rectangle and one set-up record per sub-triangle slot, 6 slots per triangle: nothing can overflow
+struct alignas(8) ScratchHeader {
+    uint32_t cursor;     // sub-triangles appended = entries of the two arrays } one 64-bit word for the set-up kernel's atomic
+    uint32_t submitted;  // triangles the draws hold                            }
+    uint32_t drawn;      // = cursor, copied by the tile kernel
+    uint32_t rejects;    // triangles outside their buffers or with a non-finite clip component, and sub-triangles with a vertex w <= 0 or outside the 2^20-pixel band
+    uint32_t clipped;    // triangles the clip changed
+    uint32_t pad[11];
+};
+static_assert(sizeof(ScratchHeader) == 64, "ScratchHeader layout");
+
+struct TriangleOrigin { uint32_t draw, local; };
+struct alignas(16) Record {
+    sunraster::SetupRecord s; // the sub-triangle with vertices 1 and 2 exchanged: A > 0, the shadow contract's record
+    uint32_t t;               // the triangle's number in submission order
+    uint32_t pad[3];
+};
+static_assert(sizeof(Record) == 96, "Record layout");
+
+constexpr size_t originOffset() { return sizeof(ScratchHeader); }
+constexpr size_t rectOffset(uint32_t triangleCount) { return (originOffset() + (size_t)triangleCount * sizeof(TriangleOrigin) + 15u) & ~(size_t)15u; }
+constexpr size_t recordOffset(uint32_t triangleCount) { return (rectOffset(triangleCount) + (size_t)triangleCount * kMaxSubTriangles * 4u + 15u) & ~(size_t)15u; }
+constexpr size_t scratchBytes(uint32_t triangleCount) { return recordOffset(triangleCount) + (size_t)triangleCount * kMaxSubTriangles * sizeof(Record); }
+
+} // namespace prepass
+} // namespace plr

@@ -114,6 +114,33 @@ int plrf_get_shadow_raster_stats(void* p, uint32_t cascade, plrf_shadow_raster_s
     })
 }
 
+// ---- scene meshes ("depthPrepassRaster.comp")
+int plrf_set_scene_meshes(void* p, const plrf_scene_mesh* meshes, uint32_t meshCount, const plrf_scene_draw* draws, uint32_t drawCount) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        std::vector<SceneMesh> m(meshes ? meshCount : 0u);
+        for (size_t i = 0; i < m.size(); i++) m[i] = {meshes[i].positions, meshes[i].normals, meshes[i].vertex_count, meshes[i].indices, meshes[i].index_count};
+        std::vector<SceneDraw> d(draws ? drawCount : 0u);
+        for (size_t i = 0; i < d.size(); i++) {
+            d[i].mesh = draws[i].mesh; d[i].albedo = draws[i].albedo_rgba8; d[i].specular = draws[i].specular_rgba8;
+            std::memcpy(d[i].modelMatrix, draws[i].model_matrix, sizeof(d[i].modelMatrix));
+        }
+        if (drawCount && d.empty()) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "plrf_set_scene_meshes: draws are null");
+        ((FramePipeline*)p)->setSceneMeshes(m.data(), (uint32_t)m.size(), d.data(), drawCount);
+    })
+}
+int plrf_set_scene_mesh_transforms(void* p, const float* matrices16, uint32_t drawCount) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL(((FramePipeline*)p)->setSceneMeshTransforms(matrices16, drawCount))
+}
+int plrf_get_prepass_raster_stats(void* p, plrf_prepass_raster_stats* out) {
+    if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        const PrepassRasterStats s = ((FramePipeline*)p)->prepassRasterStats();
+        out->triangles_submitted = s.trianglesSubmitted; out->triangles_clipped = s.trianglesClipped; out->subtriangles_drawn = s.subtrianglesDrawn; out->rejects = s.rejects;
+    })
+}
+
 int plrf_destroy(void* p) { delete (FramePipeline*)p; return PLR_OK; }
 
 int plrf_get_image(void* p, const char* name, plr_image_handle* out) {

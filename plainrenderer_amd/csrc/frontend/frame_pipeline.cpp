@@ -1,5 +1,6 @@
 // See frame_pipeline.h. Pass order, bindings, specialisation constants and dispatch counts follow the cited reference code.
 #include "frame_pipeline.h"
+#include "../device/depth_prepass_raster.h"
 #include "../device/sun_shadow_raster.h"
 
 #include "../../../include/plr_image_io.h"
@@ -998,6 +999,7 @@ bool FramePipeline::storageBuffer(const std::string& n, StorageBufferHandle* out
     else if (n == "histogramPerTile") *out = m_histogramPerTileBuffer;
     else if (n == "light") *out = m_lightBuffer;
     else if (n == "sunShadowInfo") *out = m_sunShadowInfoBuffer;
+    else if (n == "mainPassMatrices" && m_sceneMatrices.bytes) *out = m_sceneMatrices.handle; // (exists once a scene was set)
     else if (n == "sdfInstances") *out = m_sdfGi.m_sdfInstanceBuffer;
     else if (n == "sdfCulledInstances") *out = m_sdfGi.m_sdfCameraFrustumCulledInstances;
     else if (n == "sdfCulledTiles") *out = m_sdfGi.m_sdfCameraCulledTiles;
@@ -1355,6 +1357,87 @@ ShadowRasterStats FramePipeline::shadowRasterStats(uint32_t cascade) {
     return out;
 }
 
+// ---- RenderFrontend::renderDepthPrepass (RenderFrontend.cpp:792-802, pass :1717-1735) as one compute execution ("depthPrepassRaster.comp",
+// kernels/depth_prepass_raster.hip). No frustum culling of the draws on the host (:565-569): the set-up kernel clips and rejects per triangle.
+void FramePipeline::renderDepthPrepass(const FrameRenderTargets& current) {
+    if (m_sceneDrawCount == 0) return;
+    namespace pp = plr::prepass;
+    ComputePassExecution exe;
+    exe.genericInfo.handle = m_depthPrepassRasterPass;
+    exe.dispatchCount[0] = exe.dispatchCount[1] = exe.dispatchCount[2] = 1;
+    exe.genericInfo.resources.storageImages = {ImageResource(current.depthBuffer, 0, pp::kDepthBinding), ImageResource(current.motionBuffer, 0, pp::kMotionBinding),
+                                               ImageResource(m_worldSpaceNormalImage, 0, pp::kNormalImageBinding), ImageResource(m_albedoImage, 0, pp::kAlbedoBinding),
+                                               ImageResource(m_specularImage, 0, pp::kSpecularBinding)};
+    exe.genericInfo.resources.storageBuffers = {StorageBufferResource(m_sceneMatrices.handle, true, pp::kTransformBinding), StorageBufferResource(m_scenePositions.handle, true, pp::kPositionBinding),
+                                                StorageBufferResource(m_sceneNormals.handle, true, pp::kNormalBinding), StorageBufferResource(m_sceneIndices.handle, true, pp::kIndexBinding),
+                                                StorageBufferResource(m_sceneDraws.handle, true, pp::kDrawBinding), StorageBufferResource(m_sceneScratch.handle, false, pp::kScratchBinding)};
+    const pp::PushConstants pc{m_sceneDrawCount, m_sceneTriangleCount};
+    exe.pushConstants = dataToCharArray(&pc, sizeof(pc));
+    m_be.setComputePassExecution(exe);
+    m_sceneRecorded = true;
+}
+
+// MainPassMatrices per draw (RenderFrontend.cpp:581-585): {model, mvp = viewProjection * model, mvpPrevious = viewProjectionPrevious * previousModel}. A draw's
+// previous model matrix is the one the last recorded frame used (obj.previousModelMatrix, :584); the current one on the first frame of a scene and on a camera cut
+void FramePipeline::updateMainPassMatrices() {
+    if (m_sceneDrawCount == 0) return;
+    if (!m_scenePreviousValid || m_globalShaderInfo.cameraCut) m_scenePreviousModel = m_sceneModel;
+    std::vector<plr::prepass::MainPassMatrices> matrices(m_sceneDrawCount);
+    for (uint32_t d = 0; d < m_sceneDrawCount; d++) {
+        Mat4 model, previous;
+        std::memcpy(model.m, m_sceneModel.data() + (size_t)d * 16u, 64);
+        std::memcpy(previous.m, m_scenePreviousModel.data() + (size_t)d * 16u, 64);
+        const Mat4 mvp = mul(m_globalShaderInfo.viewProjection, model), mvpPrevious = mul(m_globalShaderInfo.viewProjectionPrevious, previous);
+        std::memcpy(matrices[d].model, model.m, 64); std::memcpy(matrices[d].mvp, mvp.m, 64); std::memcpy(matrices[d].mvpPrevious, mvpPrevious.m, 64);
+    }
+    m_be.setStorageBufferData(m_sceneMatrices.handle, matrices.data(), matrices.size() * sizeof(matrices[0]));
+    m_scenePreviousModel = m_sceneModel;
+    m_scenePreviousValid = true;
+}
+
+void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const SceneDraw* draws, uint32_t drawCount) {
+    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneMeshes: a band / tile pipeline cannot rasterise scene meshes (a partition would have to rasterise only its own rectangle)");
+    if (drawCount == 0) { m_sceneDrawCount = m_sceneTriangleCount = 0; m_scenePreviousValid = m_sceneRecorded = false; return; }
+    const PackedScene packed = packSceneMeshes(meshes, meshCount, draws, drawCount); // validates everything before anything is changed
+    if (!m_scenePassCreated) {
+        ComputePassDescription d; // RenderFrontend.cpp:1717-1735
+        d.name = "Depth prepass";
+        d.shaderDescription.srcPathRelative = "depthPrepassRaster.comp";
+        m_depthPrepassRasterPass = m_be.createComputePass(d);
+        m_scenePassCreated = true;
+    }
+    auto fill = [&](SceneBuffer& b, const void* data, size_t bytes) { fillCasterBuffer(b.handle, b.bytes, data, bytes); };
+    fill(m_scenePositions, packed.positions.data(), packed.positions.size() * sizeof(float));
+    fill(m_sceneNormals, packed.normals.data(), packed.normals.size() * sizeof(float));
+    fill(m_sceneIndices, packed.indices.data(), packed.indices.size() * sizeof(uint32_t));
+    fill(m_sceneDraws, packed.draws.data(), packed.draws.size() * sizeof(uint32_t));
+    fill(m_sceneMatrices, nullptr, (size_t)drawCount * sizeof(plr::prepass::MainPassMatrices)); // filled by every frame
+    fill(m_sceneScratch, nullptr, plr::prepass::scratchBytes(packed.triangleCount));
+    m_sceneModel = packed.models;
+    m_scenePreviousValid = m_sceneRecorded = false;
+    m_sceneDrawCount = drawCount; m_sceneTriangleCount = packed.triangleCount;
+}
+
+void FramePipeline::setSceneMeshTransforms(const float* matrices16, uint32_t drawCount) {
+    if (drawCount != m_sceneDrawCount)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setSceneMeshTransforms: transform count " + std::to_string(drawCount) + " differs from the draw count " +
+                                   std::to_string(m_sceneDrawCount) + " of the scene");
+    if (drawCount == 0) return;
+    if (!matrices16) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setSceneMeshTransforms: matrices are null");
+    refuseNonFiniteMatrices(matrices16, drawCount, "setSceneMeshTransforms");
+    m_sceneModel.assign(matrices16, matrices16 + (size_t)drawCount * 16u);
+}
+
+PrepassRasterStats FramePipeline::prepassRasterStats() {
+    PrepassRasterStats out;
+    if (m_sceneDrawCount == 0 || !m_sceneRecorded) return out; // no scene, or no frame since it was set: the scratch header is not this scene's
+    plr::prepass::ScratchHeader h{};
+    if (plr_download_storage_buffer(m_sceneScratch.handle.index, &h, 0, sizeof(h)) != PLR_OK) throw std::runtime_error(plr_last_error());
+    out.trianglesSubmitted = h.submitted; out.trianglesClipped = h.clipped; out.subtrianglesDrawn = h.drawn; out.rejects = h.rejects;
+    return out;
+}
+
 void FramePipeline::computeVolumetricLighting(float deltaTime) { // Volumetrics::computeVolumetricLighting, Techniques/Volumetrics.cpp:119-243
     m_volumetricsState.sampleOffset = radicalInverseBase2((uint32_t)m_frameIndex.mod8()) - 0.5f; // hammersley2D(frameIndexMod8).x - 0.5
     for (int i = 0; i < 3; i++) m_volumetricsState.windSampleOffset[i] += windSettings.vector[i] * windSettings.speed * deltaTime;
@@ -1517,7 +1600,7 @@ void FramePipeline::prepareRenderpasses() { // RenderFrontend.cpp:313-406
     if (settings.sdfDebug.visualisationMode != SDFVisualisationMode::None) { // RenderFrontend.cpp:321-340
         if (bandMode) throw std::runtime_error("the SDF debug visualisation is not supported in band rendering");
         for (auto& items : m_exchangeItems) items.clear();
-        // [renderDepthPrepass: input]
+        renderDepthPrepass(currentRenderTarget); // (RenderFrontend.cpp:322) only with scene meshes set; the uploaded G-buffer otherwise
         computeDepthPyramid(currentRenderTarget.depthBuffer);
         computeColorBufferHistogram(m_postProcessBuffers[0]);
         if (settings.runSkyLuts) updateTransmissionLut();
@@ -1552,7 +1635,7 @@ void FramePipeline::prepareRenderpasses() { // RenderFrontend.cpp:313-406
         computeExposure();
     } else if (settings.runSkyLuts) updateTransmissionLut();
     if (settings.runSkyLuts) updateSkyLut();
-    // [renderDepthPrepass: input]
+    renderDepthPrepass(currentRenderTarget); // (RenderFrontend.cpp:351) only with scene meshes set; the uploaded G-buffer otherwise
     if (settings.runHiZ) computeDepthPyramid(currentRenderTarget.depthBuffer);
     if (settings.runLightMatrix && settings.runHiZ) {
         if (perTilePyramid(settings)) computeDepthApexOfTiles(); // no apex in a per-tile pyramid: reduce (and, across bands, all-reduce) it
@@ -1869,6 +1952,7 @@ void FramePipeline::frame(const CameraExtrinsic& camera, float deltaTime, float 
     m_be.prepareForDrawcallRecording();
     // App::runUpdate, App.cpp:64-74
     setCameraExtrinsic(camera);
+    updateMainPassMatrices(); // (RenderFrontend.cpp:581-585) from the jittered viewProjection / viewProjectionPrevious the global UBO gets
     updateGlobalShaderInfo(deltaTime, time);
     // RenderFrontend::renderFrame, RenderFrontend.cpp:685-705: the GPU-visible frame index lags the CPU one
     m_globalShaderInfo.frameIndex++;

@@ -2,7 +2,7 @@
 // (Plain/src/Runtime/Rendering/RenderFrontend.cpp:313-406 prepareRenderpasses and the compute*/init* helpers) and of its
 // technique classes (Techniques/TAA.cpp, Bloom.cpp, SDFGI.cpp), written against the RenderBackend shim in
 // include/plr_render_backend.hpp. Rasterised passes (depth prepass, shadow cascades, forward shading, sky) are inputs:
-// their outputs (G-buffer, shadow maps, LUTs) are uploaded by the caller (the cascades are rasterised by a compute pass instead while mesh casters are set); forward shading is replaced by the deferred
+// their outputs (G-buffer, shadow maps, LUTs) are uploaded by the caller (the cascades are rasterised by a compute pass instead while mesh casters are set, the G-buffer while scene meshes are set); forward shading is replaced by the deferred
 // compute pass. Pass order, bindings, specialisation constants and dispatch counts are the reference's.
 #pragma once
 #include <array>
@@ -318,6 +318,20 @@ struct FramePipelineRefusal : std::runtime_error {
 struct ShadowCasterMesh { const float* positions = nullptr; uint32_t vertexCount = 0; const uint32_t* indices = nullptr; uint32_t indexCount = 0; };
 struct ShadowCasterDraw { uint32_t mesh = 0; float modelMatrix[16] = {}; }; // glm column-major
 struct ShadowRasterStats { uint64_t trianglesSubmitted = 0, trianglesDrawn = 0, guardBandRejects = 0; };
+// scene meshes (plr_frame.h plrf_set_scene_meshes): a mesh with optional vertex normals (null: face normals), and one draw of a mesh under a model matrix with
+// the draw's constant material, two RGBA8 texels as the albedo and specular images store them
+struct SceneMesh { const float* positions = nullptr; const float* normals = nullptr; uint32_t vertexCount = 0; const uint32_t* indices = nullptr; uint32_t indexCount = 0; };
+struct SceneDraw { uint32_t mesh = 0; float modelMatrix[16] = {}; uint32_t albedo = 0, specular = 0; }; // glm column-major
+struct PrepassRasterStats { uint64_t trianglesSubmitted = 0, trianglesClipped = 0, subtrianglesDrawn = 0, rejects = 0; };
+// what setSceneMeshes validates and packs, without a backend: the buffers of "depthPrepassRaster.comp" (device/depth_prepass_raster.h). Throws FramePipelineRefusal.
+struct PackedScene {
+    std::vector<float> positions, normals, models; // 3 floats per vertex (normals: zeros for a mesh without), 16 floats per draw
+    std::vector<uint32_t> indices;
+    std::vector<uint32_t> draws;                   // 6 words per draw: {firstIndex, indexCount, vertexOffset, transformIndex, albedo, specular}
+    uint32_t triangleCount = 0;
+};
+PackedScene packSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const SceneDraw* draws, uint32_t drawCount);
+void refuseNonFiniteMatrices(const float* matrices16, uint32_t drawCount, const char* call);
 
 class FramePipeline {
 public:
@@ -332,6 +346,17 @@ public:
     void setShadowCasterTransforms(const float* matrices16, uint32_t drawCount);
     // counters of the last frame's execution for `cascade`; waits for the GPU. Zero before the first frame with casters.
     ShadowRasterStats shadowRasterStats(uint32_t cascade);
+    // RenderFrontend::renderDepthPrepass (RenderFrontend.cpp:351, 792-802) as "depthPrepassRaster.comp" (kernels/depth_prepass_raster.hip): while a scene is set every
+    // frame records one execution in front of the depth pyramid (also under the SDF debug view) that writes the current render target's depth and motion and the
+    // normal, albedo and specular images from the pipeline's own camera matrices and jitter; without a scene the uploaded G-buffer is used. Everything is
+    // copied; drawCount 0 removes the scene. Refusals (FramePipelineRefusal): a mesh index or a vertex index out of range, an index count that is no multiple of
+    // 3 and a non-finite matrix element are PLR_ERR_INVALID_ARGUMENT, a band / tile pipeline is PLR_ERR_UNSUPPORTED. A refused call changes nothing.
+    void setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const SceneDraw* draws, uint32_t drawCount);
+    // the draws' model matrices from the next frame on; a draw's previous model matrix is the one the last recorded frame used (on the first frame after
+    // setSceneMeshes and after a camera cut: the current one). drawCount must be the scene's draw count
+    void setSceneMeshTransforms(const float* matrices16, uint32_t drawCount);
+    // counters of the last frame's execution for the scene now set; waits for the GPU. Zero while no scene is set and before the first frame of a newly set scene.
+    PrepassRasterStats prepassRasterStats();
     // RenderFrontend::setResolution (RenderFrontend.cpp:408-421): recorded, applied at the start of the next frame() (prepareNewFrame, :199-222). Every image and
     // buffer whose size follows the screen is re-created zero-filled, as the constructor creates it, and the next frame is a camera cut; a resize to the size the
     // images already have (back from minimized) keeps them and only cuts. Width or height 0: minimized, frame() renders nothing and advances nothing.
@@ -389,6 +414,8 @@ private:
     void computeDepthApexOfTiles();
     void computeSunLightMatrices();
     void renderSunShadowCascades();
+    void renderDepthPrepass(const FrameRenderTargets& current);
+    void updateMainPassMatrices();
     void fillCasterBuffer(StorageBufferHandle& buffer, size_t& capacity, const void* data, size_t bytes);
     void updateTransmissionLut();
     void computeVolumetricLighting(float deltaTime);
@@ -437,6 +464,14 @@ private:
     RenderPassHandle m_sunShadowRasterPass[4];
     StorageBufferHandle m_casterTransforms, m_casterPositions, m_casterIndices, m_casterDraws, m_casterScratch[4];
     size_t m_casterTransformBytes = 0, m_casterPositionBytes = 0, m_casterIndexBytes = 0, m_casterDrawBytes = 0, m_casterScratchBytes[4] = {0, 0, 0, 0};
+    // scene meshes: created by the first setSceneMeshes (a pipeline without a scene allocates and records nothing for them). A buffer and the capacity that
+    // describes it are one object
+    struct SceneBuffer { StorageBufferHandle handle; size_t bytes = 0; };
+    uint32_t m_sceneDrawCount = 0, m_sceneTriangleCount = 0;
+    bool m_scenePassCreated = false, m_scenePreviousValid = false, m_sceneRecorded = false; // recorded: a frame has run the pass for the scene now set
+    RenderPassHandle m_depthPrepassRasterPass;
+    SceneBuffer m_sceneMatrices, m_scenePositions, m_sceneNormals, m_sceneIndices, m_sceneDraws, m_sceneScratch;
+    std::vector<float> m_sceneModel, m_scenePreviousModel; // 16 floats per draw: what the next frame uses, what the last recorded frame used
 public:
     AtmosphereSettings atmosphereSettings;
     VolumetricsSettings volumetricsSettings;

@@ -1,0 +1,583 @@
+// "depthPrepassRaster.comp": the depth prepass as a compute pass - RenderFrontend::renderDepthPrepass (RenderFrontend.cpp:351, 792-802; pass description
+// :1717-1735; depthPrepass.vert / depthPrepass.frag) for opaque meshes with one constant material per draw: the current frame's depth (Depth32), motion
+// (RG16_sNorm), world-space normal, albedo and specular (RGBA8) in one execution. One kernel family serves both math modes: every decision is an integer one.
+// PLR_BUILD_FLAGS: -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
+//
+// THE RASTERISATION CONTRACT (DESIGN.md "Depth prepass as a compute pass"; tests/prepass_raster_reference.py implements it independently and all five images and
+// all counters must agree bit for bit). fp32 IEEE, no contraction, correctly rounded divide and sqrt, except where fp64 (IEEE, no contraction) is named.
+// A draw {firstIndex, indexCount, vertexOffset, transformIndex, albedo, specular} submits indexCount / 3 triangles (rounded down); triangle t is the t-th in
+// submission order over all draws. transforms[transformIndex] = {model, mvp, mvpPrevious}, glm column-major.
+//   outside a buffer: a triangle is a counted reject and draws nothing when its three index slots are not all inside `indices`, when a vertex (index +
+//     vertexOffset, in 64 bits) is not inside `positions` AND `normals`, or when transformIndex is not inside `transforms`
+//   clip = mvp * (p, 1), four components, each m[0][i] x + m[1][i] y + m[2][i] z + m[3][i] summed left to right. A triangle with a non-finite clip
+//     component is a counted reject.
+//   clipping, Sutherland-Hodgman, five planes in this order with d(v) = w - z (near; reverse Z, depth clamp off), 32 w - x, 32 w + x, 32 w - y, 32 w + y (32 w
+//     is one multiply). A vertex is inside when d >= 0. The polygon starts as (v0, v1, v2); for every plane, for i = 0 .. n - 1 with a = poly[i],
+//     b = poly[(i + 1) mod n]: a is emitted when it is inside; when exactly one of a, b is inside, the vertex on the edge is emitted behind it, always computed
+//     from the inside vertex I towards the outside vertex O: t = d_I / (d_I - d_O), v = I + t (O - I) per component (x, y, z, w). Two triangles that share an
+//     edge get the identical vertex. The output of plane k (0 .. 4) holds at most 4 + k vertices; what rounding might produce beyond that is dropped. A
+//     triangle counts as clipped when any of its polygon's vertices was outside any plane. A polygon of fewer than 3 vertices draws nothing; otherwise it is
+//     fanned from its first vertex: sub-triangle k = (poly[0], poly[k + 1], poly[k + 2]), at most 6. The far plane is a per-fragment rule (below).
+//   per sub-triangle vertex: it must have w > 0; ndc = (x / w, y / w), z = clip.z / w; xf = (ndc.x * 0.5 + 0.5) * width, yf = (ndc.y * 0.5 + 0.5) * height,
+//     no Y flip; |xf| and |yf| must be < 2^20 and z finite (a NaN fails). A sub-triangle with a vertex that fails is a counted reject.
+//   X = rint(xf * 256), Y = rint(yf * 256), int32. A = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0) in int64. Cull mode Back with a counter-clockwise front face
+//     (:1729, VulkanPipeline.cpp:61): only A < 0 is drawn. Such a sub-triangle is rasterised as (v0, v2, v1) - area -A > 0 - by the shadow contract word for
+//     word: pixel box (Xmin + 127) >> 8 .. (Xmax - 128) >> 8 clipped to the image (an empty box: not drawn, not counted), edge functions in int64 at the pixel
+//     centres (256 i + 128, 256 j + 128), the top-left rule, l1 = float(E_20) / float(A'), l2 = float(E_01) / float(A'), zf = (z0 + l1 (z1' - z0)) + l2 (z2' - z0)
+//     with 1' = 2 and 2' = 1. Every sub-triangle with a non-empty box counts as drawn.
+//   a fragment is kept when zf > 0 (a NaN and everything at or beyond the far plane is dropped: depth 0 is the sky's code); it is not clamped
+//   visibility: attachments cleared to 0, depth test GreaterEqual, depth write on (:1726-1727), primitives in order: a pixel's winner is the MAXIMUM of the
+//     64-bit keys (bits(zf) << 32) | t of its fragments. All sub-triangles of one triangle share t; of two fragments at bit-equal depth the later t wins.
+//   a pixel without a fragment gets depth 0, motion (0, 0), and 0 in all four channels of normal, albedo and specular. Every texel of all five images is written
+//     by every execution: the clear is part of the pass.
+//   attributes of the winner, once per pixel (i, j), from the ORIGINAL triangle, in fp64: P = ((2 i + 1) / width - 1, (2 j + 1) / height - 1, 1), V_k = the fp32
+//     clip (x, y, w) of original vertex k promoted; det(A, B, C) = (A.x (B.y C.w - B.w C.y) - A.y (B.x C.w - B.w C.x)) + A.w (B.x C.y - B.y C.x);
+//     e0 = det(P, V1, V2), e1 = det(P, V2, V0), e2 = det(P, V0, V1); s = (e0 + e1) + e2; b_k = e_k / s; s zero or non-finite: b = (1, 0, 0).
+//     Sums over k below are (b0 a0 + b1 a1) + b2 a2.
+//   normal: the stored vertex normal, or where all three of its components are 0 (a mesh given without normals) the face normal normalize(cross(p0 - p2,
+//     p0 - p1)) of the model-space positions, fp64; N_k = normalize(mat3(model) * normal_k), component r = (m[0][r] x + m[1][r] y) + m[2][r] z; n = normalize(
+//     sum b_k N_k); every normalize is v / sqrt((x x + y y) + z z), and (0, 0, 0) where that length is not a finite number > 0. n is rounded once to fp32, then
+//     n * 0.5 + 0.5 (fp32, two operations) is stored by the image contract's UNORM8 rule with alpha 255; a zero n therefore stores 128, 128, 128.
+//   motion (.frag:34-40): ndcCurrent = P.xy + currentFrameCameraJitter (the pixel centre, not passPos.xy / passPos.w: the same in real arithmetic);
+//     prev_k = mvpPrevious * (p_k, 1) in fp32 as above, promoted; ndcPrevious = (sum b_k prev_k.x, sum b_k prev_k.y) / sum b_k prev_k.w + previousFrameCameraJitter;
+//     m = (ndcPrevious - ndcCurrent) * 0.5, rounded to fp32; code = rint(fmin(fmax(m, -1), 1) * 32767) as int16, 0 for a NaN. A previous w sum that is not a
+//     finite number > 0 stores (0, 0). Both jitters come from the global UBO.
+//   albedo, specular: the two RGBA8 words of the winner's draw.
+//   counters: submitted (triangles of all draws), clipped, drawn (sub-triangles), rejects (triangles and sub-triangles, as above).
+//   depthPrepass.frag's alpha test is left out - all meshes are opaque - and material textures are no input here.
+//
+// Two kernels. SET-UP: a lane per triangle finds its draw (block-wide prefix sum, LDS bisection), transforms, clips (the polygon lives in LDS, a column per lane),
+// projects, snaps, culls and boxes; the block's sub-triangles are appended through one 64-bit atomic per block to a dense array of 4-byte tile rectangles and an
+// array of records that carry t. TILES: a 256-thread block per 64 x 64 tile keeps the tile's 64-bit keys in LDS (32 KB); each wave reads 256 rectangles per step
+// and queues those that touch its tile; a hit whose box inside the tile is at most 4 x 4 pixels is rasterised by its lane, larger ones by the whole wave in
+// 8 x 8 stamps, in int32 where the triangle is narrow; LDS 64-bit atomic max. RESOLVE: behind the barrier a lane per pixel finds the winner's draw, fetches its
+// three vertices, evaluates the fp64 attributes and stores the five images, a wave per row segment of 64 four-byte texels (256 contiguous bytes per image).
+// Every tile scans every rectangle: no bins in this version. No global atomics on the targets.
+#include <algorithm>
+
+#include "../backend.h"
+#include "../device/depth_prepass_raster.h"
+#include "../device/detmath.h"
+#include "../device/raster_coverage.h"
+
+namespace plr {
+namespace prepass {
+
+using rastercov::edgeAt00;
+using rastercov::topOrLeft;
+using sunraster::kNarrowFlag;
+using sunraster::kNarrowSpan;
+using sunraster::SetupRecord;
+
+struct SetupParams {
+    const float* transforms; const float* positions; const uint32_t* indices; const Draw* draws;
+    ScratchHeader* header; TriangleOrigin* origins; uint32_t* rects; Record* records;
+    uint32_t drawCount, triangleCount, capacity, transformCount, vertexCount, indexCount;
+    int32_t width, height;
+};
+
+PLR_DI float planeDistance(int plane, float x, float y, float z, float w) {
+    switch (plane) {
+    case 0: return w - z;
+    case 1: return kGuardNdc * w - x;
+    case 2: return kGuardNdc * w + x;
+    case 3: return kGuardNdc * w - y;
+    default: return kGuardNdc * w + y;
+    }
+}
+
+// one Sutherland-Hodgman step of this lane's polygon: src (n vertices) -> dst (at most `cap`), both LDS arrays [slot * 4 + component][thread]
+PLR_DI int clipPolygon(const float (*src)[256], int n, float (*dst)[256], int cap, int plane, uint32_t tid, bool& changed) {
+    int m = 0;
+    for (int i = 0; i < n; i++) {
+        const int j = i + 1 == n ? 0 : i + 1;
+        const float ax = src[i * 4 + 0][tid], ay = src[i * 4 + 1][tid], az = src[i * 4 + 2][tid], aw = src[i * 4 + 3][tid];
+        const float bx = src[j * 4 + 0][tid], by = src[j * 4 + 1][tid], bz = src[j * 4 + 2][tid], bw = src[j * 4 + 3][tid];
+        const float da = planeDistance(plane, ax, ay, az, aw), db = planeDistance(plane, bx, by, bz, bw);
+        const bool ina = da >= 0.f, inb = db >= 0.f;
+        if (!ina) changed = true;
+        if (ina && m < cap) {
+            dst[m * 4 + 0][tid] = ax; dst[m * 4 + 1][tid] = ay; dst[m * 4 + 2][tid] = az; dst[m * 4 + 3][tid] = aw;
+            m++;
+        }
+        if (ina != inb && m < cap) { // from the inside vertex towards the outside one
+            const float ix = ina ? ax : bx, iy = ina ? ay : by, iz = ina ? az : bz, iw = ina ? aw : bw;
+            const float ox = ina ? bx : ax, oy = ina ? by : ay, oz = ina ? bz : az, ow = ina ? bw : aw;
+            const float di = ina ? da : db, dout = ina ? db : da;
+            const float t = di / (di - dout);
+            dst[m * 4 + 0][tid] = ix + t * (ox - ix); dst[m * 4 + 1][tid] = iy + t * (oy - iy);
+            dst[m * 4 + 2][tid] = iz + t * (oz - iz); dst[m * 4 + 3][tid] = iw + t * (ow - iw);
+            m++;
+        }
+    }
+    return m;
+}
+
+// clip = M * (p, 1) for a glm column-major matrix, component i
+PLR_DI float clipComponent(const float* M, int i, float x, float y, float z) { return ((M[0 * 4 + i] * x + M[1 * 4 + i] * y) + M[2 * 4 + i] * z) + M[3 * 4 + i]; }
+
+// sub-triangle (0, k + 1, k + 2) of the projected polygon in `poly` ({X, Y as int bits, z, ok}): 0 nothing, 1 a reject, 2 a record (with its tile rectangle)
+PLR_DI int setupSubTriangle(const float (*poly)[256], int k, uint32_t tid, int32_t width, int32_t height, SetupRecord* rec, uint32_t* rect) {
+    const int slot[3] = {0, k + 2, k + 1}; // vertices 1 and 2 exchanged: a front face (A < 0) has A' = -A > 0
+    int32_t X[3], Y[3];
+    float z[3];
+    bool ok = true;
+    for (int v = 0; v < 3; v++) {
+        X[v] = (int32_t)f2u(poly[slot[v] * 4 + 0][tid]); Y[v] = (int32_t)f2u(poly[slot[v] * 4 + 1][tid]);
+        z[v] = poly[slot[v] * 4 + 2][tid];
+        ok = ok && f2u(poly[slot[v] * 4 + 3][tid]) != 0u;
+    }
+    if (!ok) return 1;
+    const int64_t area = (int64_t)(X[1] - X[0]) * (int64_t)(Y[2] - Y[0]) - (int64_t)(X[2] - X[0]) * (int64_t)(Y[1] - Y[0]);
+    if (area <= 0) return 0;
+    const int32_t xmin = min(X[0], min(X[1], X[2])), xmax = max(X[0], max(X[1], X[2]));
+    const int32_t ymin = min(Y[0], min(Y[1], Y[2])), ymax = max(Y[0], max(Y[1], Y[2]));
+    const int32_t ix0 = max(0, (xmin + 127) >> 8), ix1 = min(width - 1, (xmax - 128) >> 8);
+    const int32_t iy0 = max(0, (ymin + 127) >> 8), iy1 = min(height - 1, (ymax - 128) >> 8);
+    if (ix0 > ix1 || iy0 > iy1) return 0;
+    if (rec) {
+        SetupRecord& r = *rec;
+        r.x0 = X[0]; r.y0 = Y[0]; r.x1 = X[1]; r.y1 = Y[1]; r.x2 = X[2]; r.y2 = Y[2];
+        r.boxMin = (uint32_t)ix0 | ((uint32_t)iy0 << 16); r.boxMax = (uint32_t)ix1 | ((uint32_t)iy1 << 16);
+        r.e01 = edgeAt00(X[0], Y[0], X[1], Y[1]); r.e12 = edgeAt00(X[1], Y[1], X[2], Y[2]); r.e20 = edgeAt00(X[2], Y[2], X[0], Y[0]);
+        r.area = area;
+        r.z0 = z[0]; r.dz1 = z[1] - z[0]; r.dz2 = z[2] - z[0];
+        r.topLeft = (topOrLeft(X[1] - X[0], Y[1] - Y[0]) ? 1u : 0u) | (topOrLeft(X[2] - X[1], Y[2] - Y[1]) ? 2u : 0u) | (topOrLeft(X[0] - X[2], Y[0] - Y[2]) ? 4u : 0u);
+        if (xmax - xmin < kNarrowSpan && ymax - ymin < kNarrowSpan) r.topLeft |= kNarrowFlag;
+        *rect = (uint32_t)(ix0 >> 6) | ((uint32_t)(iy0 >> 6) << 8) | ((uint32_t)(ix1 >> 6) << 16) | ((uint32_t)(iy1 >> 6) << 24);
+    }
+    return 2;
+}
+
+__global__ __launch_bounds__(256) void depthPrepassSetupKernel(SetupParams p) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, tid = threadIdx.x;
+    // the draw that holds triangle t, as in the shadow pass: the block walks the draws 256 at a time, a block-wide prefix sum of their triangle counts gives
+    // the chunk's boundaries in LDS and each lane bisects them
+    __shared__ uint32_t chunkEnd[256];
+    __shared__ uint32_t waveTotal[4];
+    // the lane's polygon, [slot * 4 + component][thread]: planes 0, 2 and 4 write polyA (at most 4, 6, 8 vertices), the input and planes 1 and 3 polyB (3, 5, 7)
+    __shared__ float polyA[32][256];
+    __shared__ float polyB[28][256];
+    const uint32_t wave = threadIdx.x >> 6;
+    const uint32_t lastOfBlock = min(blockIdx.x * 256u + 255u, p.triangleCount - 1u);
+    bool found = false;
+    uint32_t drawIndex = 0, local = 0, running = 0;
+    for (uint32_t chunk = 0; chunk < p.drawCount; chunk += 256u) {
+        const uint32_t d = chunk + threadIdx.x;
+        uint32_t sum = d < p.drawCount ? p.draws[d].indexCount / 3u : 0u;
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t up = (uint32_t)__shfl_up((int)sum, off);
+            if ((int)lane >= off) sum += up;
+        }
+        if (lane == 63u) waveTotal[wave] = sum;
+        __syncthreads();
+        for (uint32_t w = 0; w < wave; w++) sum += waveTotal[w];
+        chunkEnd[threadIdx.x] = running + sum;
+        __syncthreads();
+        const uint32_t end = chunkEnd[255];
+        if (!found && t < p.triangleCount && t < end) {
+            uint32_t lo = 0, hi = 255; // the first k with t < chunkEnd[k]
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (t < chunkEnd[mid]) hi = mid; else lo = mid + 1u;
+            }
+            // (a raw record whose draws' triangle counts wrap 32 bits makes the boundaries non-monotone: a slot at or past drawCount is never loaded from)
+            if (chunk + lo < p.drawCount) {
+                found = true;
+                drawIndex = chunk + lo;
+                local = t - (lo ? chunkEnd[lo - 1u] : running);
+            }
+        }
+        running = end;
+        __syncthreads();
+        if (running > lastOfBlock) break; // (block-uniform) every triangle of the block has its draw
+    }
+    uint32_t rejects = 0;
+    bool clipped = false;
+    int n = 0; // vertices of the clipped and projected polygon in polyA
+    if (found) {
+        p.origins[t] = TriangleOrigin{drawIndex, local};
+        const Draw draw = p.draws[drawIndex];
+        const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)local * 3u;
+        bool inBuffers = at + 3u <= (uint64_t)p.indexCount && draw.transformIndex < p.transformCount;
+        uint64_t v[3] = {0, 0, 0};
+        if (inBuffers)
+            for (int k = 0; k < 3; k++) {
+                v[k] = (uint64_t)p.indices[at + k] + (uint64_t)draw.vertexOffset;
+                inBuffers = inBuffers && v[k] < (uint64_t)p.vertexCount;
+            }
+        if (!inBuffers) rejects = 1;
+        else {
+            const float* M = p.transforms + (size_t)draw.transformIndex * 48u + 16u; // mvp
+            bool finite = true;
+            for (int k = 0; k < 3; k++) {
+                const float* q = p.positions + v[k] * 3u;
+                const float x = q[0], y = q[1], z = q[2];
+                for (int i = 0; i < 4; i++) {
+                    const float c = clipComponent(M, i, x, y, z);
+                    finite = finite && fabsf(c) < __builtin_inff(); // (a NaN fails the comparison)
+                    polyB[k * 4 + i][tid] = c;
+                }
+            }
+            if (!finite) rejects = 1;
+            else {
+                n = clipPolygon(polyB, 3, polyA, 4, 0, tid, clipped);
+                n = clipPolygon(polyA, n, polyB, 5, 1, tid, clipped);
+                n = clipPolygon(polyB, n, polyA, 6, 2, tid, clipped);
+                n = clipPolygon(polyA, n, polyB, 7, 3, tid, clipped);
+                n = clipPolygon(polyB, n, polyA, 8, 4, tid, clipped);
+                if (n < 3) n = 0;
+                const float wf = (float)p.width, hf = (float)p.height;
+                for (int i = 0; i < n; i++) { // project in place: {X, Y (int bits), z, ok}
+                    const float x = polyA[i * 4 + 0][tid], y = polyA[i * 4 + 1][tid], z = polyA[i * 4 + 2][tid], w = polyA[i * 4 + 3][tid];
+                    const float nx = x / w, ny = y / w, nz = z / w;
+                    const float xf = (nx * 0.5f + 0.5f) * wf, yf = (ny * 0.5f + 0.5f) * hf;
+                    const bool ok = w > 0.f && fabsf(xf) < sunraster::kGuardBandPixels && fabsf(yf) < sunraster::kGuardBandPixels && fabsf(nz) < __builtin_inff();
+                    polyA[i * 4 + 0][tid] = u2f(ok ? (uint32_t)(int32_t)__builtin_rintf(xf * 256.f) : 0u);
+                    polyA[i * 4 + 1][tid] = u2f(ok ? (uint32_t)(int32_t)__builtin_rintf(yf * 256.f) : 0u);
+                    polyA[i * 4 + 2][tid] = nz;
+                    polyA[i * 4 + 3][tid] = u2f(ok ? 1u : 0u);
+                }
+            }
+        }
+    }
+    // pass 1: which sub-triangles survive
+    uint32_t surviveMask = 0;
+    for (int k = 0; k + 2 < n; k++) {
+        const int what = setupSubTriangle(polyA, k, tid, p.width, p.height, nullptr, nullptr);
+        if (what == 1) rejects++;
+        if (what == 2) surviveMask |= 1u << k;
+    }
+    const uint32_t mine = (uint32_t)__popc(surviveMask);
+    // one 64-bit atomic per block hands it a run of slots (the low word is the cursor) and counts its triangles (the high word); a lane appends 0 .. 6
+    // records, so the block's prefix sum is over counts
+    __shared__ uint32_t waveSurvivors[4], blockFound, blockRejects, blockClipped, blockBase;
+    if (threadIdx.x == 0) blockFound = blockRejects = blockClipped = 0u;
+    uint32_t incl = mine;
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)incl, off);
+        if ((int)lane >= off) incl += up;
+    }
+    if (lane == 63u) waveSurvivors[wave] = incl;
+    __syncthreads();
+    const unsigned long long foundMask = __ballot(found), clippedMask = __ballot(clipped);
+    if (lane == 0) { atomicAdd(&blockFound, (uint32_t)__popcll(foundMask)); atomicAdd(&blockClipped, (uint32_t)__popcll(clippedMask)); }
+    if (rejects) atomicAdd(&blockRejects, rejects);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t survivors = waveSurvivors[0] + waveSurvivors[1] + waveSurvivors[2] + waveSurvivors[3];
+        const unsigned long long old = atomicAdd((unsigned long long*)&p.header->cursor, (unsigned long long)survivors | ((unsigned long long)blockFound << 32));
+        blockBase = (uint32_t)old;
+        if (blockRejects) atomicAdd(&p.header->rejects, blockRejects);
+        if (blockClipped) atomicAdd(&p.header->clipped, blockClipped);
+    }
+    __syncthreads();
+    uint32_t slot = blockBase + incl - mine;
+    for (uint32_t w = 0; w < wave; w++) slot += waveSurvivors[w];
+    // pass 2: the records
+    for (int k = 0; k + 2 < n; k++) {
+        if (!((surviveMask >> k) & 1u)) continue;
+        Record rec{};
+        uint32_t rect = 0;
+        setupSubTriangle(polyA, k, tid, p.width, p.height, &rec.s, &rect);
+        rec.t = t;
+        if (slot < p.capacity) { // (always: at most 6 per triangle and the launcher sized the arrays for that many)
+            p.rects[slot] = rect;
+            p.records[slot] = rec;
+        }
+        slot++;
+    }
+}
+
+struct TileParams {
+    ScratchHeader* header; const TriangleOrigin* origins; const uint32_t* rects; const Record* records;
+    const float* transforms; const float* positions; const float* normals; const uint32_t* indices; const Draw* draws;
+    const GlobalUbo* global;
+    float* depth; uint32_t* motion; uint32_t* normal; uint32_t* albedo; uint32_t* specular;
+    uint32_t capacity, triangleCount;
+    int32_t width, height;
+};
+
+typedef unsigned long long Key;
+
+PLR_DI void keepFragment(float zf, uint32_t t, Key* cell) {
+    if (!(zf > 0.f)) return; // at or beyond the far plane, or a NaN
+    atomicMax(cell, ((Key)f2u(zf) << 32) | (Key)t);
+}
+
+// one fragment of sub-triangle r at pixel (px, py); tile: the block's 64 x 64 keys, (ox, oy) its first pixel
+PLR_DI void prepassFragment(const SetupRecord& r, uint32_t t, int64_t sx01, int64_t sy01, int64_t sx12, int64_t sy12, int64_t sx20, int64_t sy20, float fa, int px, int py, Key* tile, int ox, int oy) {
+    const int64_t e01 = r.e01 + (int64_t)px * sx01 + (int64_t)py * sy01;
+    const int64_t e12 = r.e12 + (int64_t)px * sx12 + (int64_t)py * sy12;
+    const int64_t e20 = r.e20 + (int64_t)px * sx20 + (int64_t)py * sy20;
+    if (!rastercov::covered(e01, e12, e20, r.topLeft)) return;
+    const float l1 = (float)e20 / fa, l2 = (float)e01 / fa;
+    keepFragment((r.z0 + l1 * r.dz1) + l2 * r.dz2, t, &tile[(py - oy) * kTileSize + (px - ox)]);
+}
+
+// the same fragment for a sub-triangle whose snapped vertices span less than 2^15 sub-pixel units on both axes (kNarrowFlag): the contract's int64 values fit
+// int32 and 24-bit multiplies (sun_shadow_raster.hip)
+PLR_DI void prepassFragmentNarrow(const SetupRecord& r, uint32_t t, float fa, int px, int py, Key* tile, int ox, int oy) {
+    const int32_t Px = px * 256 + 128, Py = py * 256 + 128;
+    const int32_t e01 = __mul24(r.x1 - r.x0, Py - r.y0) - __mul24(r.y1 - r.y0, Px - r.x0);
+    const int32_t e12 = __mul24(r.x2 - r.x1, Py - r.y1) - __mul24(r.y2 - r.y1, Px - r.x1);
+    const int32_t e20 = __mul24(r.x0 - r.x2, Py - r.y2) - __mul24(r.y0 - r.y2, Px - r.x2);
+    if (!rastercov::covered(e01, e12, e20, r.topLeft)) return;
+    const float l1 = (float)e20 / fa, l2 = (float)e01 / fa;
+    keepFragment((r.z0 + l1 * r.dz1) + l2 * r.dz2, t, &tile[(py - oy) * kTileSize + (px - ox)]);
+}
+
+// E(i, j) = E(0, 0) + i (-256 dy) + j (256 dx) for the pixel centre (256 i + 128, 256 j + 128)
+#define PLR_PREPASS_STEPS(r)                                                                                                                            \
+    const int64_t sx01 = -256ll * (int64_t)((r).y1 - (r).y0), sy01 = 256ll * (int64_t)((r).x1 - (r).x0);                                                \
+    const int64_t sx12 = -256ll * (int64_t)((r).y2 - (r).y1), sy12 = 256ll * (int64_t)((r).x2 - (r).x1);                                                \
+    const int64_t sx20 = -256ll * (int64_t)((r).y0 - (r).y2), sy20 = 256ll * (int64_t)((r).x0 - (r).x2);                                                \
+    const float fa = (float)(r).area
+
+// the record lane `src` holds, in every lane (src is wave-uniform)
+PLR_DI Record broadcastRecord(const Record& r, int src) {
+    union Words { Record rec; int w[sizeof(Record) / 4]; };
+    Words in, out;
+    in.rec = r;
+    for (size_t k = 0; k < sizeof(Record) / 4; k++) out.w[k] = __builtin_amdgcn_readlane(in.w[k], src);
+    return out.rec;
+}
+
+struct D3 { double x, y, z; };
+PLR_DI double det3(D3 a, D3 b, D3 c) { return (a.x * (b.y * c.z - b.z * c.y) - a.y * (b.x * c.z - b.z * c.x)) + a.z * (b.x * c.y - b.y * c.x); }
+PLR_DI double weighted(const double b[3], double a0, double a1, double a2) { return (b[0] * a0 + b[1] * a1) + b[2] * a2; }
+PLR_DI D3 normalized(D3 v) {
+    const double len = __builtin_sqrt((v.x * v.x + v.y * v.y) + v.z * v.z);
+    if (!(len > 0.0 && len < __builtin_inf())) return D3{0.0, 0.0, 0.0};
+    return D3{v.x / len, v.y / len, v.z / len};
+}
+PLR_DI uint32_t snorm16(float m) {
+    if (m != m) return 0u;
+    return (uint32_t)(int32_t)__builtin_rintf(fminf(fmaxf(m, -1.f), 1.f) * 32767.f) & 0xffffu;
+}
+PLR_DI uint32_t unorm8Half(float n) { // n * 0.5 + 0.5 under the image contract's UNORM8 rule
+    const float v = n * 0.5f + 0.5f;
+    if (v != v) return 0u;
+    return (uint32_t)(int32_t)__builtin_rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.f);
+}
+
+// the winner's attributes at pixel (x, y): motion, normal and the draw's two material words
+PLR_DI void resolvePixel(const TileParams& p, uint32_t t, int x, int y, uint32_t* motion, uint32_t* normal, uint32_t* albedo, uint32_t* specular) {
+    const TriangleOrigin o = p.origins[t];
+    const Draw draw = p.draws[o.draw];
+    const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)o.local * 3u;
+    const float* T = p.transforms + (size_t)draw.transformIndex * 48u;
+    const float *model = T, *mvp = T + 16, *mvpPrevious = T + 32;
+    float pos[3][3], nrm[3][3];
+    D3 V[3], prev[3];
+    for (int k = 0; k < 3; k++) {
+        const uint64_t v = (uint64_t)p.indices[at + k] + (uint64_t)draw.vertexOffset;
+        for (int c = 0; c < 3; c++) { pos[k][c] = p.positions[v * 3u + c]; nrm[k][c] = p.normals[v * 3u + c]; }
+        V[k] = D3{(double)clipComponent(mvp, 0, pos[k][0], pos[k][1], pos[k][2]), (double)clipComponent(mvp, 1, pos[k][0], pos[k][1], pos[k][2]),
+                  (double)clipComponent(mvp, 3, pos[k][0], pos[k][1], pos[k][2])};
+        prev[k] = D3{(double)clipComponent(mvpPrevious, 0, pos[k][0], pos[k][1], pos[k][2]), (double)clipComponent(mvpPrevious, 1, pos[k][0], pos[k][1], pos[k][2]),
+                     (double)clipComponent(mvpPrevious, 3, pos[k][0], pos[k][1], pos[k][2])};
+    }
+    const D3 P{(double)(2 * x + 1) / (double)p.width - 1.0, (double)(2 * y + 1) / (double)p.height - 1.0, 1.0};
+    const double e0 = det3(P, V[1], V[2]), e1 = det3(P, V[2], V[0]), e2 = det3(P, V[0], V[1]);
+    const double s = (e0 + e1) + e2;
+    double b[3] = {1.0, 0.0, 0.0};
+    if (s != 0.0 && __builtin_fabs(s) < __builtin_inf()) { b[0] = e0 / s; b[1] = e1 / s; b[2] = e2 / s; }
+    // normal
+    D3 face{0.0, 0.0, 0.0};
+    {
+        const D3 a{(double)pos[0][0] - (double)pos[2][0], (double)pos[0][1] - (double)pos[2][1], (double)pos[0][2] - (double)pos[2][2]};
+        const D3 c{(double)pos[0][0] - (double)pos[1][0], (double)pos[0][1] - (double)pos[1][1], (double)pos[0][2] - (double)pos[1][2]};
+        face = normalized(D3{a.y * c.z - a.z * c.y, a.z * c.x - a.x * c.z, a.x * c.y - a.y * c.x});
+    }
+    D3 N[3];
+    for (int k = 0; k < 3; k++) {
+        D3 in{(double)nrm[k][0], (double)nrm[k][1], (double)nrm[k][2]};
+        if (nrm[k][0] == 0.f && nrm[k][1] == 0.f && nrm[k][2] == 0.f) in = face;
+        N[k] = normalized(D3{((double)model[0] * in.x + (double)model[4] * in.y) + (double)model[8] * in.z, ((double)model[1] * in.x + (double)model[5] * in.y) + (double)model[9] * in.z,
+                             ((double)model[2] * in.x + (double)model[6] * in.y) + (double)model[10] * in.z});
+    }
+    const D3 nn = normalized(D3{weighted(b, N[0].x, N[1].x, N[2].x), weighted(b, N[0].y, N[1].y, N[2].y), weighted(b, N[0].z, N[1].z, N[2].z)});
+    *normal = unorm8Half((float)nn.x) | (unorm8Half((float)nn.y) << 8) | (unorm8Half((float)nn.z) << 16) | (255u << 24);
+    // motion
+    const double ws = weighted(b, prev[0].z, prev[1].z, prev[2].z);
+    uint32_t code = 0u;
+    if (ws > 0.0 && ws < __builtin_inf()) {
+        const double xs = weighted(b, prev[0].x, prev[1].x, prev[2].x), ys = weighted(b, prev[0].y, prev[1].y, prev[2].y);
+        const double px = xs / ws + (double)p.global->previousFrameCameraJitter[0], py = ys / ws + (double)p.global->previousFrameCameraJitter[1];
+        const double cx = P.x + (double)p.global->currentFrameCameraJitter[0], cy = P.y + (double)p.global->currentFrameCameraJitter[1];
+        code = snorm16((float)((px - cx) * 0.5)) | (snorm16((float)((py - cy) * 0.5)) << 16);
+    }
+    *motion = code;
+    *albedo = draw.albedo;
+    *specular = draw.specular;
+}
+
+__global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
+    __shared__ Key tile[kTileSize * kTileSize];
+    __shared__ uint32_t hitQueue[4][256]; // per wave: the entries of the current step that touch the tile
+    const int tx = (int)blockIdx.x, ty = (int)blockIdx.y;
+    const int ox = tx * kTileSize, oy = ty * kTileSize;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t i = threadIdx.x; i < (uint32_t)(kTileSize * kTileSize); i += 256u) tile[i] = 0ull;
+    __syncthreads();
+    const uint32_t n = min(p.header->cursor, p.capacity);
+    const int tx1 = min(ox + kTileSize - 1, p.width - 1), ty1 = min(oy + kTileSize - 1, p.height - 1); // the tile's pixels inside the image
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.header->drawn = n;
+    // the scan of the shadow pass: a wave reads 256 rectangles per step (four per lane, one 16-byte load: the array is padded to that), queues the indices of
+    // those that touch its tile in LDS and takes the queue 64 at a time, a record per lane
+    uint32_t* queue = hitQueue[wave];
+    const unsigned long long lanesBelow = (1ull << lane) - 1ull;
+    auto touches = [&](uint32_t rc) { return (int)(rc & 255u) <= tx && tx <= (int)((rc >> 16) & 255u) && (int)((rc >> 8) & 255u) <= ty && ty <= (int)(rc >> 24); };
+    for (uint32_t base = wave * 256u; base < n; base += 1024u) {
+        const uint32_t i0 = base + lane * 4u;
+        uint4 rc = make_uint4(0u, 0u, 0u, 0u);
+        if (i0 < n) rc = *(const uint4*)(p.rects + i0);
+        const bool h0 = i0 < n && touches(rc.x), h1 = i0 + 1u < n && touches(rc.y), h2 = i0 + 2u < n && touches(rc.z), h3 = i0 + 3u < n && touches(rc.w);
+        const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1), m2 = __ballot(h2), m3 = __ballot(h3);
+        const uint32_t c0 = (uint32_t)__popcll(m0), c1 = c0 + (uint32_t)__popcll(m1), c2 = c1 + (uint32_t)__popcll(m2), total = c2 + (uint32_t)__popcll(m3);
+        if (total == 0u) continue;
+        if (h0) queue[(uint32_t)__popcll(m0 & lanesBelow)] = i0;
+        if (h1) queue[c0 + (uint32_t)__popcll(m1 & lanesBelow)] = i0 + 1u;
+        if (h2) queue[c1 + (uint32_t)__popcll(m2 & lanesBelow)] = i0 + 2u;
+        if (h3) queue[c2 + (uint32_t)__popcll(m3 & lanesBelow)] = i0 + 3u;
+        __builtin_amdgcn_wave_barrier(); // (one wave: its LDS operations execute in order)
+        for (uint32_t k = 0; k < total; k += 64u) {
+            bool hit = k + lane < total;
+            int bx0 = 0, by0 = 0, bx1 = -1, by1 = -1;
+            Record rr{};
+            if (hit) {
+                rr = p.records[queue[k + lane]];
+                bx0 = max((int)(rr.s.boxMin & 0xffffu), ox); by0 = max((int)(rr.s.boxMin >> 16), oy);
+                bx1 = min((int)(rr.s.boxMax & 0xffffu), tx1); by1 = min((int)(rr.s.boxMax >> 16), ty1);
+                hit = bx0 <= bx1 && by0 <= by1;
+            }
+            const bool small = hit && bx1 - bx0 < 4 && by1 - by0 < 4;
+            if (small) { // its lane walks the <= 16 pixels
+                const SetupRecord& r = rr.s;
+                if (r.topLeft & kNarrowFlag) {
+                    const float fa = (float)(int32_t)r.area;
+                    for (int py = by0; py <= by1; py++)
+                        for (int px = bx0; px <= bx1; px++) prepassFragmentNarrow(r, rr.t, fa, px, py, tile, ox, oy);
+                } else {
+                    PLR_PREPASS_STEPS(r);
+                    for (int py = by0; py <= by1; py++)
+                        for (int px = bx0; px <= bx1; px++) prepassFragment(r, rr.t, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, tile, ox, oy);
+                }
+            }
+            unsigned long long large = __ballot(hit && !small);
+            while (large) { // the whole wave walks the box in 8 x 8 stamps, with the record broadcast from the lane that holds it
+                const int src = __ffsll((long long)large) - 1;
+                large &= large - 1ull;
+                const Record ur = broadcastRecord(rr, src);
+                const SetupRecord& u = ur.s;
+                const int lx0 = __builtin_amdgcn_readlane(bx0, src), ly0 = __builtin_amdgcn_readlane(by0, src);
+                const int lx1 = __builtin_amdgcn_readlane(bx1, src), ly1 = __builtin_amdgcn_readlane(by1, src);
+                if (u.topLeft & kNarrowFlag) { // (wave-uniform)
+                    const float fa = (float)(int32_t)u.area;
+                    for (int sy = ly0; sy <= ly1; sy += 8)
+                        for (int sx = lx0; sx <= lx1; sx += 8) {
+                            const int px = sx + (int)(lane & 7u), py = sy + (int)(lane >> 3);
+                            if (px <= lx1 && py <= ly1) prepassFragmentNarrow(u, ur.t, fa, px, py, tile, ox, oy);
+                        }
+                } else {
+                    PLR_PREPASS_STEPS(u);
+                    for (int sy = ly0; sy <= ly1; sy += 8)
+                        for (int sx = lx0; sx <= lx1; sx += 8) {
+                            const int px = sx + (int)(lane & 7u), py = sy + (int)(lane >> 3);
+                            if (px <= lx1 && py <= ly1) prepassFragment(u, ur.t, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, tile, ox, oy);
+                        }
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    // resolve: a lane per pixel, a wave per tile row - 64 four-byte texels, 256 contiguous bytes of every image per store instruction
+    for (uint32_t i = threadIdx.x; i < (uint32_t)(kTileSize * kTileSize); i += 256u) {
+        const int y = oy + (int)(i >> 6), x = ox + (int)(i & 63u);
+        if (y >= p.height || x >= p.width) continue;
+        const Key key = tile[i];
+        uint32_t motion = 0u, normal = 0u, albedo = 0u, specular = 0u;
+        const uint32_t t = (uint32_t)key;
+        if (key != 0ull && t < p.triangleCount) resolvePixel(p, t, x, y, &motion, &normal, &albedo, &specular);
+        const size_t at = (size_t)y * (size_t)p.width + (size_t)x;
+        p.depth[at] = u2f((uint32_t)(key >> 32));
+        p.motion[at] = motion; p.normal[at] = normal; p.albedo[at] = albedo; p.specular[at] = specular;
+    }
+}
+
+static int launchDepthPrepassRaster(const PassCtx& c) {
+    if (c.push.size() < sizeof(PushConstants)) return c.fail(-1, "depthPrepassRaster: push constants {drawCount, triangleCount} missing");
+    PushConstants pc;
+    std::memcpy(&pc, c.push.data(), sizeof(pc));
+    if (c.dispatch[0] != 1u || c.dispatch[1] != 1u || c.dispatch[2] != 1u || c.base[0] != 0u || c.base[1] != 0u)
+        return c.fail(-1, "depthPrepassRaster: the dispatch is {1, 1, 1} (the launcher derives its grids from the push constants and the images)");
+    if (pc.triangleCount > kMaxTriangles) return c.fail(-1, "depthPrepassRaster: triangleCount " + std::to_string(pc.triangleCount) + " exceeds 2^28");
+    if ((pc.drawCount == 0u) != (pc.triangleCount == 0u)) return c.fail(-1, "depthPrepassRaster: drawCount and triangleCount must both be zero or both be non-zero");
+    if (int rc = c.needGlobal()) return rc;
+    if (int rc = c.needSbuf(kTransformBinding, 0, "depthPrepassRaster transforms (MainPassMatrices[]: model, mvp, mvpPrevious)")) return rc;
+    if (int rc = c.needSbuf(kPositionBinding, 0, "depthPrepassRaster positions (3 floats per vertex)")) return rc;
+    if (int rc = c.needSbuf(kNormalBinding, 0, "depthPrepassRaster normals (3 floats per vertex)")) return rc;
+    if (int rc = c.needSbuf(kIndexBinding, 0, "depthPrepassRaster indices (uint32 triangle list)")) return rc;
+    if (int rc = c.needSbuf(kDrawBinding, (size_t)pc.drawCount * sizeof(Draw), "depthPrepassRaster draws {firstIndex, indexCount, vertexOffset, transformIndex, albedo, specular}")) return rc;
+    if (int rc = c.needSbuf(kScratchBinding, scratchBytes(pc.triangleCount),
+                            "depthPrepassRaster scratch (align16(align16(64 + 8 triangleCount) + 24 triangleCount) + 576 triangleCount bytes: 6 sub-triangles per triangle)"))
+        return rc;
+    if (c.sbuf[kScratchBinding].readOnly) return c.fail(-4, "depthPrepassRaster: the scratch buffer (binding 5) is bound read-only");
+    if (int rc = c.needStorage(kDepthBinding, F_D32, "depthPrepassRaster depth")) return rc;
+    if (int rc = c.needStorage(kMotionBinding, F_RG16SN, "depthPrepassRaster motion")) return rc;
+    if (int rc = c.needStorage(kNormalImageBinding, F_RGBA8, "depthPrepassRaster world-space normal")) return rc;
+    if (int rc = c.needStorage(kAlbedoBinding, F_RGBA8, "depthPrepassRaster albedo")) return rc;
+    if (int rc = c.needStorage(kSpecularBinding, F_RGBA8, "depthPrepassRaster specular")) return rc;
+    const ImgView depth = c.storage[kDepthBinding];
+    if (depth.w < 1 || depth.h < 1 || depth.w > kMaxResolution || depth.h > kMaxResolution || depth.d > 1)
+        return c.fail(-4, "depthPrepassRaster: the depth image is " + std::to_string(depth.w) + " x " + std::to_string(depth.h) + ", it must be 2D and at most 16384 x 16384");
+    for (int b : {kMotionBinding, kNormalImageBinding, kAlbedoBinding, kSpecularBinding}) {
+        if (c.storage[b].w != depth.w || c.storage[b].h != depth.h || c.storage[b].d > 1)
+            return c.fail(-4, "depthPrepassRaster: the five images must have one size; storage binding " + std::to_string(b) + " is " + std::to_string(c.storage[b].w) + " x " +
+                                  std::to_string(c.storage[b].h) + ", depth is " + std::to_string(depth.w) + " x " + std::to_string(depth.h));
+        for (int o = 0; o < b; o++)
+            if (c.storage[o].ptr == c.storage[b].ptr) return c.fail(-4, "depthPrepassRaster: one image is bound at two storage bindings");
+    }
+    for (int b : {kTransformBinding, kPositionBinding, kNormalBinding, kIndexBinding, kDrawBinding})
+        if (c.sbuf[b].ptr == c.sbuf[kScratchBinding].ptr) return c.fail(-4, "depthPrepassRaster: the scratch buffer is also bound as an input");
+
+    uint8_t* scratch = (uint8_t*)c.sbuf[kScratchBinding].ptr;
+    if (hipMemsetAsync(scratch, 0, sizeof(ScratchHeader), c.stream) != hipSuccess) return c.fail(-2, "depthPrepassRaster: clearing the scratch header failed");
+    const uint32_t capacity = pc.triangleCount * kMaxSubTriangles;
+    if (pc.triangleCount) {
+        SetupParams s{};
+        s.transforms = (const float*)c.sbuf[kTransformBinding].ptr; s.positions = (const float*)c.sbuf[kPositionBinding].ptr;
+        s.indices = (const uint32_t*)c.sbuf[kIndexBinding].ptr; s.draws = (const Draw*)c.sbuf[kDrawBinding].ptr;
+        s.header = (ScratchHeader*)scratch; s.origins = (TriangleOrigin*)(scratch + originOffset());
+        s.rects = (uint32_t*)(scratch + rectOffset(pc.triangleCount)); s.records = (Record*)(scratch + recordOffset(pc.triangleCount));
+        s.drawCount = pc.drawCount; s.triangleCount = pc.triangleCount; s.capacity = capacity;
+        s.transformCount = (uint32_t)std::min<size_t>(c.sbuf[kTransformBinding].size / sizeof(MainPassMatrices), 0xffffffffu);
+        s.vertexCount = (uint32_t)std::min<size_t>(std::min(c.sbuf[kPositionBinding].size, c.sbuf[kNormalBinding].size) / 12u, 0xffffffffu);
+        s.indexCount = (uint32_t)std::min<size_t>(c.sbuf[kIndexBinding].size / 4u, 0xffffffffu);
+        s.width = depth.w; s.height = depth.h;
+        depthPrepassSetupKernel<<<divUp(pc.triangleCount, 256u), 256, 0, c.stream>>>(s);
+        PLR_CHECK_LAUNCH(c);
+        c.splitTiming("set-up");
+    }
+    TileParams t{};
+    t.header = (ScratchHeader*)scratch; t.origins = (const TriangleOrigin*)(scratch + originOffset());
+    t.rects = (const uint32_t*)(scratch + rectOffset(pc.triangleCount)); t.records = (const Record*)(scratch + recordOffset(pc.triangleCount));
+    t.transforms = (const float*)c.sbuf[kTransformBinding].ptr; t.positions = (const float*)c.sbuf[kPositionBinding].ptr; t.normals = (const float*)c.sbuf[kNormalBinding].ptr;
+    t.indices = (const uint32_t*)c.sbuf[kIndexBinding].ptr; t.draws = (const Draw*)c.sbuf[kDrawBinding].ptr;
+    t.global = c.global;
+    t.depth = (float*)depth.ptr; t.motion = (uint32_t*)c.storage[kMotionBinding].ptr; t.normal = (uint32_t*)c.storage[kNormalImageBinding].ptr;
+    t.albedo = (uint32_t*)c.storage[kAlbedoBinding].ptr; t.specular = (uint32_t*)c.storage[kSpecularBinding].ptr;
+    t.capacity = capacity; t.triangleCount = pc.triangleCount; t.width = depth.w; t.height = depth.h;
+    depthPrepassTileKernel<<<dim3(divUp((unsigned)depth.w, (unsigned)kTileSize), divUp((unsigned)depth.h, (unsigned)kTileSize)), 256, 0, c.stream>>>(t);
+    PLR_CHECK_LAUNCH(c);
+    return 0;
+}
+
+} // namespace prepass
+static int depth_prepass_raster_launch(const PassCtx& c) { return prepass::launchDepthPrepassRaster(c); }
+static int depth_prepass_raster_launch_fast(const PassCtx& c) { return prepass::launchDepthPrepassRaster(c); }
+PLR_REGISTER_SHADER("depthPrepassRaster.comp", depth_prepass_raster_launch);
+PLR_REGISTER_SHADER_FAST("depthPrepassRaster.comp", depth_prepass_raster_launch_fast);
+} // namespace plr

@@ -36,6 +36,7 @@
 
 #include "../backend.h"
 #include "../device/detmath.h"
+#include "../device/raster_coverage.h"
 #include "../device/sun_shadow_raster.h"
 
 namespace plr {
@@ -48,8 +49,8 @@ struct SetupParams {
     int32_t res;
 };
 
-PLR_DI bool topOrLeft(int32_t dx, int32_t dy) { return (dy == 0 && dx > 0) || dy < 0; }
-PLR_DI int64_t edgeAt00(int32_t xa, int32_t ya, int32_t xb, int32_t yb) { return (int64_t)(xb - xa) * (int64_t)(128 - ya) - (int64_t)(yb - ya) * (int64_t)(128 - xa); }
+using rastercov::edgeAt00; // the coverage rules are shared with "depthPrepassRaster.comp" (device/raster_coverage.h)
+using rastercov::topOrLeft;
 
 __global__ __launch_bounds__(256) void sunShadowSetupKernel(SetupParams p) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;

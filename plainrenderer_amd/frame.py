@@ -56,6 +56,19 @@ class PlrfShadowRasterStats(C.Structure):
     _fields_ = [("triangles_submitted", C.c_uint64), ("triangles_drawn", C.c_uint64), ("guard_band_rejects", C.c_uint64)]
 
 
+class PlrfSceneMesh(C.Structure):
+    _fields_ = [("positions", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)), ("vertex_count", C.c_uint32), ("indices", C.POINTER(C.c_uint32)),
+                ("index_count", C.c_uint32)]
+
+
+class PlrfSceneDraw(C.Structure):
+    _fields_ = [("mesh", C.c_uint32), ("model_matrix", C.c_float * 16), ("albedo_rgba8", C.c_uint32), ("specular_rgba8", C.c_uint32)]
+
+
+class PlrfPrepassRasterStats(C.Structure):
+    _fields_ = [("triangles_submitted", C.c_uint64), ("triangles_clipped", C.c_uint64), ("subtriangles_drawn", C.c_uint64), ("rejects", C.c_uint64)]
+
+
 class LocalExchangeGroup:
     """shared state of the in-process transport of the native exchange (include/plr_frame.h plrf_local_group_*): one per partition, created before its ranks'
     pipelines attach (FramePipeline.attach_local_rects), destroyed after they are gone"""
@@ -278,6 +291,37 @@ class FramePipeline:
         s = PlrfShadowRasterStats()
         self._check(self.lib.plrf_get_shadow_raster_stats(self.handle, C.c_uint32(cascade), C.byref(s)))
         return int(s.triangles_submitted), int(s.triangles_drawn), int(s.guard_band_rejects)
+
+    # ---- scene meshes (include/plr_frame.h plrf_set_scene_meshes): the G-buffer rasterised every frame by "depthPrepassRaster.comp"
+    def set_scene_meshes(self, meshes, draws):
+        """meshes: [(positions n x 3 float32, normals n x 3 float32 or None, indices uint32 triangle list)], draws: [(mesh index, 16 floats glm column-major,
+        albedo RGBA8 word, specular RGBA8 word)]; copied. No draws: the scene is removed and the uploaded G-buffer is used again"""
+        pos = [np.ascontiguousarray(m[0], np.float32).reshape(-1, 3) for m in meshes]
+        nrm = [None if m[1] is None else np.ascontiguousarray(m[1], np.float32).reshape(-1, 3) for m in meshes]
+        idx = [np.ascontiguousarray(m[2], np.uint32).reshape(-1) for m in meshes]
+        m = (PlrfSceneMesh * max(len(meshes), 1))()
+        for k in range(len(meshes)):
+            if nrm[k] is not None and nrm[k].shape != pos[k].shape:
+                raise ValueError("mesh %d has %d normals for %d vertices" % (k, nrm[k].shape[0], pos[k].shape[0]))
+            m[k] = PlrfSceneMesh(pos[k].ctypes.data_as(C.POINTER(C.c_float)), None if nrm[k] is None else nrm[k].ctypes.data_as(C.POINTER(C.c_float)), pos[k].shape[0],
+                                 idx[k].ctypes.data_as(C.POINTER(C.c_uint32)), idx[k].size)
+        d = (PlrfSceneDraw * max(len(draws), 1))()
+        for k, (mesh, matrix, albedo, specular) in enumerate(draws):
+            d[k].mesh = int(mesh)
+            d[k].model_matrix = (C.c_float * 16)(*[float(v) for v in np.asarray(matrix, np.float32).reshape(16)])
+            d[k].albedo_rgba8, d[k].specular_rgba8 = int(albedo), int(specular)
+        self._check(self.lib.plrf_set_scene_meshes(self.handle, m, C.c_uint32(len(meshes)), d, C.c_uint32(len(draws))))
+
+    def set_scene_mesh_transforms(self, matrices):
+        """one 16-float model matrix per draw, from the next frame on"""
+        a = np.ascontiguousarray(matrices, np.float32).reshape(-1, 16)
+        self._check(self.lib.plrf_set_scene_mesh_transforms(self.handle, a.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(a.shape[0])))
+
+    def prepass_raster_stats(self):
+        """(triangles submitted, triangles clipped, sub-triangles drawn, rejects) of the last frame's execution; waits for the GPU"""
+        s = PlrfPrepassRasterStats()
+        self._check(self.lib.plrf_get_prepass_raster_stats(self.handle, C.byref(s)))
+        return int(s.triangles_submitted), int(s.triangles_clipped), int(s.subtriangles_drawn), int(s.rejects)
 
     def frame(self, cam: Camera, delta_time=1.0 / 60.0, time=0.0):
         c = PlrfCamera()

@@ -1,0 +1,149 @@
+"""The scene mesh entry points at the C boundary and the tests' own rasteriser (tests/prepass_raster_reference.py) against hand-computed cases; no GPU."""
+import ctypes as C
+
+import numpy as np
+
+import prepass_raster_cases as pc
+import prepass_raster_reference as ref
+from shadow_raster_cases import quad
+
+F32 = np.float32
+
+
+def counters(r):
+    return r["submitted"], r["clipped"], r["drawn"], r["rejects"]
+
+
+def test_diagonal_through_pixel_centres_covers_every_centre_once():
+    """the shadow contract's fill rule, mirrored: corners on pixel centres, split along the diagonal through the centres (k + 0.5, k + 0.5); every centre strictly
+    inside belongs to exactly one of the two front faces, and the diagonal to the upper-right half (for the rasterised (v0, v2, v1) it is a left edge)"""
+    r = pc.rasterise(pc.pixel_case([quad(2.5, 2.5, 10.5, 10.5, 0.25, 0.75)], 16, 16))
+    assert counters(r) == (2, 0, 2, 0)
+    assert (r["coverage"][3:10, 3:10] == 1).all() and r["coverage"].max() == 1
+    k = np.arange(3, 10)
+    assert (r["depth"][k, k] == F32(0.25)).all() and (r["depth"][5, 6:10] == F32(0.25)).all() and (r["depth"][6:10, 5] == F32(0.75)).all()
+
+
+def test_axis_aligned_quad_owns_its_top_row_and_left_column_only():
+    r = pc.rasterise(pc.pixel_case([quad(2.5, 3.5, 11.5, 9.5, 0.5, 0.5)], 16, 12))
+    expect = np.zeros((12, 16), np.int32)
+    expect[3:9, 2:11] = 1
+    assert np.array_equal(r["coverage"], expect)
+
+
+def test_back_faces_are_culled_and_depth_is_stored_as_it_is():
+    tri = [(2.0, 2.0, 0.3), (12.0, 2.0, 0.3), (12.0, 12.0, 0.3)]
+    front, back = pc.rasterise(pc.pixel_case([[tri]], 16, 16)), pc.rasterise(pc.pixel_case([[tri]], 16, 16, keep_winding=(0,)))
+    assert counters(front) == (1, 0, 1, 0) and counters(back) == (1, 0, 0, 0) and not back["keys"].any()
+    covered = front["coverage"] > 0
+    assert covered.sum() == 55 and (front["depth"][covered] == F32(0.3)).all() and (front["depth"][~covered] == 0).all()
+    assert (front["albedo"][covered] == pc.material(0)[0]).all() and (front["specular"][covered] == pc.material(0)[1]).all()
+    assert not front["albedo"][~covered].any() and not front["normal"][~covered].any() and not front["motion"].any()
+
+
+def test_the_far_plane_is_a_per_fragment_rule():
+    """z runs from 0.5 at x = 2 to -0.5 at x = 12: zf <= 0 from x = 7 on, so of the pixel centres 2.5 .. 11.5 only 2.5 .. 6.5 keep a fragment"""
+    r = pc.rasterise(pc.pixel_case([[[(2.0, 2.0, 0.5), (12.0, 2.0, -0.5), (12.0, 12.0, -0.5)], [(2.0, 2.0, 0.5), (12.0, 12.0, -0.5), (2.0, 12.0, 0.5)]]], 16, 16))
+    assert counters(r) == (2, 0, 2, 0)
+    assert r["coverage"][2:12, 2:7].all() and not r["coverage"][:, 7:].any()
+    assert r["depth"][5, 2] == F32(0.45)
+
+
+def test_the_later_triangle_wins_a_tie():
+    tri = [(2.0, 2.0, 0.5), (12.0, 2.0, 0.5), (12.0, 12.0, 0.5)]
+    r = pc.rasterise(pc.pixel_case([[tri], [tri]], 16, 16))
+    covered = r["coverage"] > 0
+    assert (r["coverage"][covered] == 2).all() and (r["albedo"][covered] == pc.material(1)[0]).all()
+    assert ((r["keys"][covered] & np.uint64(0xFFFFFFFF)) == 1).all()
+
+
+def test_clipping_by_hand():
+    """a triangle under an identity matrix with one vertex at x = 40: the plane 32 w - x cuts edges 0 -> 1 and 1 -> 2. The new vertices come from the inside
+    vertex: on 0 -> 1, t = 32 / (32 + 8) = 0.8, y = -0.5 + 0.8 * 0.25"""
+    tri = np.array([[0.0, -0.5, 0.5, 1.0], [40.0, -0.25, 0.5, 1.0], [0.0, 0.5, 0.5, 1.0]], F32)
+    poly, clipped = ref.clip_triangle(tri)
+    assert clipped and len(poly) == 4
+    t = F32(32.0) / F32(F32(32.0) - F32(-8.0))
+    assert np.array_equal(poly[0], tri[0]) and np.array_equal(poly[3], tri[2])
+    assert poly[1][0] == F32(0.0) + t * F32(40.0) and poly[1][1] == F32(-0.5) + t * F32(0.25)
+    t2 = F32(32.0) / F32(F32(32.0) - F32(-8.0))  # from vertex 2 (inside, d = 32) towards vertex 1 (outside, d = -8)
+    assert poly[2][1] == F32(0.5) + t2 * F32(F32(-0.25) - F32(0.5))
+    inside, unchanged = ref.clip_triangle(np.array([[0.0, 0.0, 0.5, 1.0], [1.0, 0.0, 0.5, 1.0], [0.0, 1.0, 0.5, 1.0]], F32))
+    assert not unchanged and len(inside) == 3
+    behind, was = ref.clip_triangle(np.array([[0.0, 0.0, 2.0, 1.0], [1.0, 0.0, 2.0, 1.0], [0.0, 1.0, 2.0, 1.0]], F32))  # z > w everywhere: in front of near
+    assert was and behind == []
+
+
+def test_a_shared_clipped_edge_gets_the_identical_vertex_whatever_the_winding():
+    a, b = np.array([0.3, 0.2, 0.9, 1.0], F32), np.array([-0.4, 0.7, 0.5, -0.2], F32)  # b is behind the camera and outside the near plane
+    c, d = np.array([0.9, 0.9, 0.5, 1.0], F32), np.array([-0.9, -0.5, 0.5, 1.0], F32)
+    p1, _ = ref.clip_triangle(np.stack([a, b, c]))
+    p2, _ = ref.clip_triangle(np.stack([b, a, d]))
+    on_edge = lambda poly: {tuple(v.tolist()) for v in poly if abs(float(v[3] - v[2])) < 1e-6}
+    assert on_edge(p1) & on_edge(p2), "both triangles hold the vertex where a -> b meets the near plane, bit for bit"
+
+
+def test_attributes_by_hand():
+    """one triangle under an identity matrix whose previous matrix shifts x by 0.25 NDC: motion.x = 0.125 -> rint(0.125 * 32767) = 4096, motion.y = 0; with a
+    current jitter of 0.125 the shift from the jittered centre is 0.125: code 2048. The face normal of a screen-aligned front face is +z (reverse Z: towards the viewer): stored (128, 128, 255, 255)"""
+    previous = pc.IDENTITY.copy()
+    previous[12] = 0.25
+    tri = [(2.0, 2.0, 0.5), (12.0, 2.0, 0.5), (12.0, 12.0, 0.5)]
+    r = pc.rasterise(pc.pixel_case([[tri]], 16, 16, previous=previous))
+    covered = r["coverage"] > 0
+    assert (r["motion"][covered, 0] == 4096).all() and not r["motion"][covered, 1].any()
+    assert np.all(r["weights"] >= -1e-12) and np.allclose(r["weights"].sum(axis=1), 1.0, atol=1e-12)
+    code = np.unique(r["normal"][covered])
+    assert code.size == 1 and code[0] == 0xFFFF8080, hex(int(code[0]))
+    case = pc.pixel_case([[tri]], 16, 16, previous=previous)
+    case["jitter_current"], case["jitter_previous"] = (0.125, 0.0), (0.0, -0.0625)
+    r = pc.rasterise(case)
+    assert (r["motion"][covered, 0] == 2048).all() and (r["motion"][covered, 1] == -1024).all(), "((P + 0.25) - (P + 0.125)) / 2 and (-0.0625 - 0) / 2"
+
+
+def test_vertex_normals_are_interpolated_and_transformed():
+    """normals (1, 0, 0), (0, 1, 0), (0, 0, 1) under a model matrix that is a rotation x -> y -> z -> x: at the centroid pixel n = (1, 1, 1) / sqrt 3 -> 0.7887 -> 201"""
+    model = pc.glm([[0, 0, 1, 0], [1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, 1]])
+    case = pc.pixel_case([[[(1.5, 1.5, 0.5), (13.5, 1.5, 0.5), (1.5, 13.5, 0.5)]]], 16, 16, keep_winding=())
+    case["transforms"][0, 0:16] = model
+    case["normals"] = np.eye(3, dtype=F32)
+    r = pc.rasterise(case)
+    assert r["coverage"][5, 5] == 1 and r["normal"][5, 5] == (201 | (201 << 8) | (201 << 16) | (255 << 24))
+
+
+def test_the_outside_of_the_generated_meshes_is_the_drawn_side():
+    """a sphere 6 in front of the camera: with the index order plainrenderer_amd.meshes emits, the near hemisphere is drawn (reverse Z: the larger depths); reversed,
+    the far one. The stored normal of the centre pixel then points at the camera: -z"""
+    from plainrenderer_amd import meshes
+    raw = meshes.uv_sphere(1.25, segments=28, rings=14)
+    model = pc.glm(np.array([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 6.0], [0, 0, 0, 1]]))
+    out = {}
+    for name, idx in (("emitted", np.asarray(raw[1], np.uint32)), ("reversed", pc.reversed_winding(raw[1]))):
+        out[name] = pc.rasterise(pc.perspective_case(64, 64, [(raw[0], None, idx)], [(0, model)], pc.camera()))
+    covered = out["emitted"]["coverage"] > 0
+    assert covered.sum() > 1000 and np.array_equal(covered, out["reversed"]["coverage"] > 0)
+    assert (out["emitted"]["depth"][covered] > out["reversed"]["depth"][covered]).all()
+    n = out["emitted"]["normal"][32, 32]
+    assert (n >> 16) & 0xFF < 16 and abs(int(n & 0xFF) - 128) < 24 and abs(int((n >> 8) & 0xFF) - 128) < 24
+
+
+def test_matrices_follow_the_pipelines_product():
+    a, b = np.arange(16, dtype=F32) * F32(0.37) - F32(2.0), np.cos(np.arange(16, dtype=F32))
+    want = (a.reshape(4, 4).T.astype(np.float64) @ b.reshape(4, 4).T.astype(np.float64)).T.reshape(16)
+    assert np.allclose(ref.mat_mul(a, b), want, rtol=1e-5, atol=1e-5)
+    m = ref.main_pass_matrices(a, b, [pc.IDENTITY], [pc.IDENTITY])
+    assert m.shape == (1, 48) and np.array_equal(m[0, :16], pc.IDENTITY) and np.array_equal(m[0, 16:32], ref.mat_mul(a, pc.IDENTITY))
+
+
+def test_the_scene_mesh_entry_points_are_exported():
+    from plainrenderer_amd import backend
+    lib = backend._load()
+    for name in ("plrf_set_scene_meshes", "plrf_set_scene_mesh_transforms", "plrf_get_prepass_raster_stats"):
+        assert getattr(lib, name) is not None
+    from plainrenderer_amd.frame import PlrfPrepassRasterStats, PlrfSceneDraw, PlrfSceneMesh
+    assert C.sizeof(PlrfSceneDraw) == 76 and C.sizeof(PlrfPrepassRasterStats) == 32 and C.sizeof(PlrfSceneMesh) == 40
+
+
+def test_the_shader_is_registered():
+    from plainrenderer_amd import supported_shaders
+    assert "depthPrepassRaster.comp" in supported_shaders()

@@ -1,0 +1,123 @@
+"""What the depth prepass costs as a compute pass ("depthPrepassRaster.comp", plrf_set_scene_meshes) in bench.py's 4K frame.
+
+    python tools/prepass_raster_cost.py [--out FILE] [--frames N] [--instances K]
+
+One process, one build. The scene is the instance set of tools/shadow_raster_cost.py: the three meshes of tests/shadow_raster_cases.py (box, uv_sphere, torus:
+1496 triangles) instanced K times (default 202: about 100 k triangles) over the view frustum in front of bench.py's camera, rasterised into the 3840 x 2160
+G-buffer. By hipEvent (plr_set_pass_timing), averaged over --frames frames: the set-up kernel and the tile kernel (rasterisation and resolve), with the pass'
+counters and, from a host-side projection of the triangles the clip leaves unchanged, how their rectangles spread over the 64 x 64 tiles (the busiest tile
+bounds the tile kernel). The same with every instance shrunk to 1 / 20, where the tile kernel's time is its scan of the rectangle list and its resolve.
+It also reports that a frame WITHOUT scene meshes records the passes and runs the general kernels it did before a scene was ever set.
+The report goes to stdout and to --out.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+W, H = 3840, 2160
+sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests"), os.path.dirname(os.path.abspath(__file__))]
+
+
+def tile_hits(matrices, meshes, draws):
+    """(mean, largest, touched) number of unclipped front-facing triangles whose tile rectangle touches a tile"""
+    import prepass_raster_reference as ref
+    nx, ny = (W + 63) // 64, (H + 63) // 64
+    grid = np.zeros((ny + 1, nx + 1), np.int64)
+    for d, (mesh, _, _, _) in enumerate(draws):
+        pos, _, idx = meshes[mesh]
+        clip = ref.transform4(matrices[d, 16:32], pos[idx.astype(np.int64)]).reshape(-1, 3, 4)
+        inside = np.isfinite(clip).all(axis=(1, 2))
+        for plane in range(5):
+            inside &= (ref.plane_distance(plane, clip) >= 0).all(axis=1)
+        X, Y, _, ok = ref.project(clip[inside].reshape(-1, 4), W, H)
+        X, Y, ok = X.reshape(-1, 3), Y.reshape(-1, 3), ok.reshape(-1, 3).all(axis=1)
+        area = (X[:, 1] - X[:, 0]) * (Y[:, 2] - Y[:, 0]) - (X[:, 2] - X[:, 0]) * (Y[:, 1] - Y[:, 0])
+        x0, x1 = np.maximum((X.min(1) + 127) >> 8, 0), np.minimum((X.max(1) - 128) >> 8, W - 1)
+        y0, y1 = np.maximum((Y.min(1) + 127) >> 8, 0), np.minimum((Y.max(1) - 128) >> 8, H - 1)
+        keep = ok & (area < 0) & (x0 <= x1) & (y0 <= y1)
+        tx0, tx1, ty0, ty1 = x0[keep] >> 6, x1[keep] >> 6, y0[keep] >> 6, y1[keep] >> 6
+        np.add.at(grid, (ty0, tx0), 1); np.add.at(grid, (ty1 + 1, tx1 + 1), 1)
+        np.add.at(grid, (ty0, tx1 + 1), -1); np.add.at(grid, (ty1 + 1, tx0), -1)
+    hits = grid.cumsum(0).cumsum(1)[:ny, :nx]
+    return float(hits.mean()), int(hits.max()), int((hits > 0).sum())
+
+
+def pass_times(be, fp, cams, first, frames):
+    """-> ({pass name: mean us} of the prepass, number of timed entries of the last frame)"""
+    be.setPassTiming(True)
+    acc, entries = {}, 0
+    for i in range(frames + 1):
+        fp.frame(cams[first + i], 1.0 / 60.0, 0.5)
+        be.waitForGPUIdle()
+        if i == 0:
+            continue
+        timings = be.getRenderpassTimings()
+        entries = len(timings)
+        for name, ms in timings:
+            if name.startswith("Depth prepass"):
+                acc.setdefault(name, []).append(ms * 1e3)
+    be.setPassTiming(False)
+    return {k: float(np.mean(v)) for k, v in acc.items()}, entries
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=40)
+    ap.add_argument("--instances", type=int, default=202)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    import torch  # noqa: F401  (first: it brings its own HIP runtime)
+    import bench
+    import prepass_raster_cases as pc
+    import shadow_raster_cost
+    from plainrenderer_amd import RenderBackend
+    from plainrenderer_amd.frame import FramePipeline
+    args = argparse.Namespace(steps=a.frames * 6 + 20, warmup=5, profile_frames=0, grid=16, sdf_res=64, shadow_res=2048, scene="default")
+    be = RenderBackend(W, H, device=0)
+    fp = FramePipeline(be, W, H, shadow_map_res=2048)
+    _, cams, inputs = bench.build_scene(args, "cuda:0", W, H, None)
+    inputs.upload(fp)
+    lines = ["# python tools/prepass_raster_cost.py: bench.py's scene at %d x %d, fast kernel set, %d frames per figure" % (W, H, a.frames)]
+    cursor = 1
+    for i in range(args.warmup):
+        fp.frame(cams[cursor + i], 1.0 / 60.0, 0.5)
+    cursor += args.warmup
+    _, entries_before = pass_times(be, fp, cams, cursor, 2)
+    general_before = be.getGeneralKernelExecutions()
+    cursor += 3
+    tiles = ((W + 63) // 64) * ((H + 63) // 64)
+    lines.append("%-26s %9s %9s %9s %8s %8s %13s %11s %10s" % ("scene", "submitted", "drawn", "clipped", "rejects", "covered", "busiest tile", "set-up us", "tiles us"))
+    for label, shrink in (("meshes at scale", 1.0), ("meshes shrunk to 1 / 20", 0.05)):
+        raw, draws = shadow_raster_cost.instances(cams[1], a.instances, shrink)
+        meshes = [pc.mesh_arrays(m, k != 0) for k, m in enumerate(raw)]
+        scene_draws = [(m, t, *pc.material(d)) for d, (m, t) in enumerate(draws)]
+        fp.set_scene_meshes(meshes, scene_draws)
+        times, _ = pass_times(be, fp, cams, cursor, a.frames)
+        cursor += a.frames + 1
+        submitted, clipped, drawn, rejects = fp.prepass_raster_stats()
+        matrices = be.downloadStorageBuffer(fp.storage_buffer("mainPassMatrices"), 192 * len(draws), dtype=np.float32).reshape(-1, 48)
+        covered = max(int((be.downloadImage(fp.image("depth%d" % t), 0, np.float32) > 0).sum()) for t in (0, 1))
+        mean_hits, max_hits, touched = tile_hits(matrices, meshes, scene_draws)
+        lines.append("%-26s %9d %9d %9d %8d %8d %13d %11.2f %10.2f" % (label, submitted, drawn, clipped, rejects, covered, max_hits, times.get("Depth prepass (set-up)", float("nan")),
+                                                                 times.get("Depth prepass", float("nan"))))
+        lines.append("  %d draws; %d of %d tiles touched, %.1f rectangles per tile on average" % (len(draws), touched, tiles, mean_hits))
+    general_with = be.getGeneralKernelExecutions()
+    fp.set_scene_meshes([], [])
+    _, entries_after = pass_times(be, fp, cams, cursor, 2)
+    general_after = be.getGeneralKernelExecutions()
+    lines.append("general-kernel executions of the last frame: %d before a scene was set, %d with the scene, %d after it was removed" % (general_before[0], general_with[0], general_after[0]))
+    lines.append("timed pass entries of a frame: %d before a scene was set, %d after it was removed" % (entries_before, entries_after))
+    text = "\n".join(lines) + "\n"
+    sys.stdout.write(text)
+    if a.out:
+        with open(a.out, "w") as fh:
+            fh.write(text)
+    fp.destroy()
+    be.shutdown()
+
+
+if __name__ == "__main__":
+    main()
