@@ -51,9 +51,9 @@ def make_case(width, height, transforms, positions, indices, draws, normals=None
                 jitter_previous=tuple(float(F32(v)) for v in jitter_previous))
 
 
-def rasterise(case):
+def rasterise(case, diagnostics=False):
     return ref.rasterise(case["transforms"], case["positions"], case["normals"], case["indices"], case["draws"], case["width"], case["height"],
-                         case["jitter_current"], case["jitter_previous"])
+                         case["jitter_current"], case["jitter_previous"], diagnostics=diagnostics)
 
 
 def identity_matrices(count=1, previous=None):

@@ -114,9 +114,12 @@ def _snorm16(m):
     return np.where(np.isnan(m), 0, code).astype(np.int16)
 
 
-def rasterise(transforms, positions, normals, indices, draws, width, height, jitter_current=(0.0, 0.0), jitter_previous=(0.0, 0.0)):
+def rasterise(transforms, positions, normals, indices, draws, width, height, jitter_current=(0.0, 0.0), jitter_previous=(0.0, 0.0), diagnostics=False):
     """-> dict(depth float32 h x w, motion int16 h x w x 2, normal / albedo / specular uint32 h x w, keys uint64 h x w, coverage int32 h x w (kept fragments
-    per pixel), weights float64 n x 3 (the barycentrics of the pixels with a winner, row-major order), submitted, clipped, drawn, rejects)"""
+    per pixel), weights float64 n x 3 (the barycentrics of the pixels with a winner, row-major order), submitted, clipped, drawn, rejects).
+    diagnostics: also polygons [(t, vertices of its clipped polygon)] for every triangle that reaches the clipper, fan_drawn [(t, fan index, (ix0, iy0, ix1,
+    iy1), (x span, y span in sub-pixel units))] for every sub-triangle counted as drawn, in submission order, and fan_rejected [(t, fan index)]. An added output:
+    nothing else depends on it"""
     width, height = int(width), int(height)
     transforms = np.asarray(transforms, F32).reshape(-1, 48)
     positions = np.asarray(positions, F32).reshape(-1, 3)
@@ -128,6 +131,7 @@ def rasterise(transforms, positions, normals, indices, draws, width, height, jit
     coverage = np.zeros((height, width), np.int32)
     submitted = clipped_count = drawn = rejects = 0
     origin_draw, origin_vertices = [], []  # per submitted triangle: its draw and its three vertices (-1 where it is outside its buffers)
+    polygons, fan_drawn, fan_rejected = [], [], []
     t_next = 0
     for d, (first, count, vertex_offset, transform_index, _, _) in enumerate(draws.tolist()):
         n = count // 3
@@ -160,6 +164,8 @@ def rasterise(transforms, positions, normals, indices, draws, width, height, jit
             else:
                 poly, was_clipped = clip_triangle(clip[k])
             clipped_count += int(was_clipped)
+            if diagnostics:
+                polygons.append((t, len(poly)))
             if len(poly) < 3:
                 continue
             X, Y, z, ok = project(np.stack(poly), width, height)
@@ -167,6 +173,8 @@ def rasterise(transforms, positions, normals, indices, draws, width, height, jit
                 corners = (0, s + 1, s + 2)
                 if not all(ok[c] for c in corners):
                     rejects += 1
+                    if diagnostics:
+                        fan_rejected.append((t, s))
                     continue
                 (x0, x1, x2), (y0, y1, y2) = (int(X[c]) for c in corners), (int(Y[c]) for c in corners)
                 area = (x1 - x0) * (y2 - y0) - (x2 - x0) * (y1 - y0)
@@ -182,6 +190,8 @@ def rasterise(transforms, positions, normals, indices, draws, width, height, jit
                 if ix0 > ix1 or iy0 > iy1:
                     continue
                 drawn += 1
+                if diagnostics:
+                    fan_drawn.append((t, s, (ix0, iy0, ix1, iy1), (max(x0, x1, x2) - min(x0, x1, x2), max(y0, y1, y2) - min(y0, y1, y2))))
                 px = (np.arange(ix0, ix1 + 1, dtype=np.int64) * 256 + 128)[None, :]
                 py = (np.arange(iy0, iy1 + 1, dtype=np.int64) * 256 + 128)[:, None]
                 covered = np.ones((iy1 - iy0 + 1, ix1 - ix0 + 1), bool)
@@ -206,6 +216,8 @@ def rasterise(transforms, positions, normals, indices, draws, width, height, jit
                 sub[...] = np.where(keep, np.maximum(sub, key), sub)
                 coverage[iy0:iy1 + 1, ix0:ix1 + 1] += keep
     out = dict(keys=keys, coverage=coverage, submitted=submitted, clipped=clipped_count, drawn=drawn, rejects=rejects)
+    if diagnostics:
+        out.update(polygons=polygons, fan_drawn=fan_drawn, fan_rejected=fan_rejected)
     out["depth"] = (keys >> np.uint64(32)).astype(np.uint32).view(F32)
     motion = np.zeros((height, width, 2), np.int16)
     normal = np.zeros((height, width), np.uint32)

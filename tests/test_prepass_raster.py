@@ -21,9 +21,23 @@ header). The global UBO holds the case's two jitters and nothing else. Cases, th
   draws700    136 x 136: the shadow test's draw-lookup executions
   nothing     72 x 40: no draws; only culled; only rejects. The images are still cleared
   small_frames  1 x 1, 7 x 5, 63 x 65, 65 x 63
-The largest image (16384 wide, 3 rows: tile indices 0, 127, 128 and 255) has a test of its own.
+The contract clause by clause, where the cases above do not reach:
+  octagon     96 x 64: a triangle that crosses the near plane and all four guard planes, clipped to 8 vertices, in its three front-facing vertex orders at three
+              depths that each win somewhere, as it is and translated twice so that every fan index 0 .. 5 is drawn; and as an execution of its own a 6- and
+              a 7-vertex polygon under the near_clip camera
+  sub_rejects 96 x 64: counted rejects of sub-triangles - a vertex (0, 0, 0, 0), inside all five planes and failing w > 0; a vertex whose z / w overflows to
+              -inf; a clipped triangle of which one sub-triangle is a reject and the other is drawn, in both orders; a visible triangle behind them
+  motion_edges  72 x 40, non-zero jitters: motion saturated at +-32767, a previous w sum of -1 and of 0, a NaN previous x, and one code below +1
+  normal_edges  72 x 40: a singular mat3(model) (128, 128, 128), vertex normals that interpolate through zero, inf / NaN / 1e30 normals, normals that are not
+              unit length under scale and shear, and the face normal under the same model
+  denormal_depth  64 x 64: constant depths 1e-41, the least denormal and the least normal, ties among them, and a ramp that the far rule cuts inside the
+              denormal range
+  lane_int64  96 x 80: two thin triangles of span 35008 whose boxes are 64 x 4 in one tile and 3 x 4 in the next: 64-bit edge functions on the lane path
+  crowded_large  64 x 64, one tile: 200 triangles of about 10 x 10 pixels and 50 small ones in one 256-rectangle step - more than 64 wave-path hits
+The largest images (16384 wide and 3 rows, 3 wide and 16384 rows: tile indices 0, 127, 128 and 255 on either axis) have tests of their own.
 """
 import struct
+import time
 
 import numpy as np
 import pytest
@@ -177,15 +191,190 @@ def _small_frames():
     return out
 
 
+
+def _grouped_case(width, height, transforms, groups, normals=None, **jitters):
+    """one draw per group (transformIndex, triangles of three model-space positions), vertices in submission order"""
+    positions = np.asarray([v for _, tris in groups for tri in tris for v in tri], F32).reshape(-1, 3)
+    draws, first = [], 0
+    for transform_index, tris in groups:
+        draws.append([first, 3 * len(tris), 0, transform_index])
+        first += 3 * len(tris)
+    return pc.make_case(width, height, transforms, positions, np.arange(positions.shape[0]), draws, normals, **jitters)
+
+
+def _matrices(mvp, model=pc.IDENTITY, previous=None):
+    return np.concatenate([np.asarray(model, F32).reshape(16), np.asarray(mvp, F32).reshape(16), np.asarray(mvp if previous is None else previous, F32).reshape(16)])
+
+
+# clip = (x, y, 0.05, z): w is the model-space z and the clip z a constant, so the near plane w >= z is the model-space plane z = 0.05. In (x, y, w) the triangle
+# lies in the plane x + y - 50 (w - 1) = 45; cut at the near plane it is the NDC diamond (45, 0), (0, 45), (-50, 0), (0, -50), which the guard square |x|, |y| <= 32
+# cuts at all four corners: an octagon, two vertices on every side. On screen w = 5 / (50 - (u + v)), about 0.1.
+OCTAGON_S = 45.0 / 42.5
+OCTAGON = ((45.0, 0.0, 1.0), (0.0, 45.0, 1.0), (-2.5 * OCTAGON_S, -2.5 * OCTAGON_S, 1.0 - 0.95 * OCTAGON_S))
+OCTAGON_FRONT = ((0, 2, 1), (1, 0, 2), (2, 1, 0))  # the three vertex orders that face front
+# the shape as it is, and translated in NDC (x + dx w, y + dy w) by less than the 13 that keep all four corners cut (half a unit more or less on either axis still
+# gives 8 vertices): the fan starts at another place relative to the screen, and the boxes of sub-triangles 0, 1 and 5 reach it
+OCTAGON_OFFSETS = ((0.0, 0.0), (-8.0, 6.0), (8.0, 10.0))
+OCTAGON_COUNTERS = ((3, 3, 9, 0), (3, 3, 11, 0), (3, 3, 11, 0))
+OCTAGON_FANS = (((2, 3, 4), (2, 3, 4), (2, 3, 4)), ((0, 1, 2, 3, 4), (2, 3, 4), (2, 3, 4)), ((1, 2, 3, 4), (2, 3, 4), (2, 3, 4, 5)))
+# found by a random search under the near_clip camera: rng = np.random.default_rng(0x4F435447), per trial np.round(rng.uniform((-40, -40, -2), (40, 40, 12), (3, 3)), 3),
+# the first trial whose polygon has 6 (trial 282) and 7 (trial 616) vertices, at least 2 drawn sub-triangles, no reject and more than 300 pixels
+HEXAGON = ((9.489, -4.831, -1.397), (-20.575, 27.834, 7.088), (-25.875, -8.528, 1.056))
+HEPTAGON = ((23.335, -36.792, 1.611), (-11.845, 25.58, -1.096), (-21.067, -35.488, 6.209))
+
+
+def octagon_mvp(k, dx=0.0, dy=0.0):
+    """clip = (x + dx z, y + dy z, a z + b, z): depth a + b / w, for k = 0 exactly (x, y, 0.05, z). The three lines in q = 1 / w have slopes b = 0.05, 0.0495 and
+    0.049 (the near plane w >= a w + b hardly moves); lines 0 and 2 cross at the q of the screen centre, q0 = (50 + dx + dy) / 5, and line 1 lies 0.00005 above
+    that crossing: it is the nearest where |q - q0| < 0.1, on a screen where q varies by +- 0.4"""
+    q0 = (50.0 + dx + dy) / 5.0
+    a, b = ((0.0, 0.05), (0.0005 * q0 + 0.00005, 0.0495), (0.001 * q0, 0.049))[k]
+    return pc.glm([[1, 0, dx, 0], [0, 1, dy, 0], [0, 0, a, b], [0, 0, 1, 0]])
+
+
+def _octagon():
+    out = []
+    for dx, dy in OCTAGON_OFFSETS:
+        transforms = np.stack([_matrices(octagon_mvp(k, dx, dy)) for k in range(3)])
+        out.append(_grouped_case(96, 64, transforms, [(k, [[OCTAGON[i] for i in order]]) for k, order in enumerate(OCTAGON_FRONT)]))
+    cam = pc.camera(**NEAR_CAMERA)
+    vp = np.asarray(cam.view_projection(), F32).reshape(16)
+    out.append(_grouped_case(96, 64, ref.main_pass_matrices(vp, vp, [pc.IDENTITY]), [(0, [HEXAGON, HEPTAGON])]))
+    return out
+
+
+W_ZERO = ((0.0, 0.0, 0.0), (0.5, 0.0, 1.0), (0.0, 0.5, 1.0))          # under clip = (x, y, 0.05 z, z) its first vertex is (0, 0, 0, 0)
+Z_OVERFLOW = ((0.0, 0.0, 1e-30), (0.5, 0.0, 1.0), (0.0, 0.5, 1.0))    # under clip = (x, y, 1e30 z - 1e30, z) its first vertex has z = -1e30, w = 1e-30
+# under clip = (x, y, -4e8, z): the middle vertex, at the apex of the clip volume (NDC (-0.9, -0.9)) with z / w = -4e38, overflows. The third vertex is outside
+# 32 w - x; the vertex the clipper puts on the edge from the middle one towards it has w = 3.6e-29 and z / w = -1.1e37, finite. The polygon is (v0, v1, that vertex,
+# the one on v2 -> v0): sub-triangle 0 is a reject and sub-triangle 1 is not; in the reversed order the polygon ends with v1 and sub-triangle 1 is the reject
+Z_OVERFLOW_PARTLY = ((-0.9, 0.5, 1.0), (-0.9e-30, -0.9e-30, 1e-30), (40.0, -0.5, 1.0))
+VISIBLE_BEHIND = ((-0.9, -0.8, 2.0), (0.9, -0.8, 2.0), (0.0, 0.9, 2.0))
+
+
+def _rotations(tri):
+    return [[tri[(k + i) % 3] for i in range(3)] for k in range(3)]
+
+
+def _sub_rejects():
+    flat = pc.glm([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0.05, 0], [0, 0, 1, 0]])
+    steep = pc.glm([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1e30, -1e30], [0, 0, 1, 0]])
+    deep = pc.glm([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, -4e8], [0, 0, 1, 0]])
+    transforms = np.stack([_matrices(flat), _matrices(steep), _matrices(deep)])
+    visible = _both_windings(VISIBLE_BEHIND)
+    return [_grouped_case(96, 64, transforms, [(0, _both_windings(W_ZERO) + visible), (1, _both_windings(Z_OVERFLOW)), (2, _rotations(Z_OVERFLOW_PARTLY) + _rotations(Z_OVERFLOW_PARTLY[::-1])), (0, visible)])]
+
+
+def _with_draw_transforms(case, transforms):
+    """the case with one transform per draw"""
+    case = dict(case, transforms=np.asarray(transforms, F32).reshape(-1, 48), draws=case["draws"].copy())
+    assert case["transforms"].shape[0] == case["draws"].shape[0]
+    case["draws"][:, 3] = np.arange(case["draws"].shape[0])
+    return case
+
+
+def _columns(count, width, height, z=0.5):
+    """`count` triangles side by side, one per draw: each 12 pixels wide and height - 4 tall"""
+    step = width // count
+    return [[[(1.0 + step * k, 2.0, z), (13.0 + step * k, 2.0, z), (13.0 + step * k, height - 2.0, z)]] for k in range(count)]
+
+
+MOTION_JITTER, MOTION_JITTER_PREVIOUS = (0.004, -0.003), (-0.002, -0.003)  # y: the same in both frames, so the draw with a NaN x stores 0 in y as well
+MOTION_BELOW_ONE = 1.0 - 0.7 / 32767.0  # m * 32767 = 32766.3: code 32766
+MOTION_BEYOND_ONE = 1.0 + 0.7 / 32767.0
+
+
+def _translated(tx, ty):
+    m = pc.IDENTITY.copy()
+    m[12], m[13] = tx, ty
+    return m
+
+
+def _motion_edges():
+    negated, zero_w, nan_x = pc.IDENTITY.copy(), pc.IDENTITY.copy(), pc.IDENTITY.copy()
+    negated[15], zero_w[15], nan_x[12] = -1.0, 0.0, np.nan
+    # m = (translation + previous jitter - current jitter) / 2
+    jx, jy = MOTION_JITTER_PREVIOUS[0] - MOTION_JITTER[0], MOTION_JITTER_PREVIOUS[1] - MOTION_JITTER[1]
+    edge = _translated(2.0 * MOTION_BELOW_ONE - jx, -2.0 * MOTION_BEYOND_ONE - jy)
+    previous = [_translated(3.0, -3.0), negated, zero_w, nan_x, edge]
+    case = _with_draw_transforms(pc.pixel_case(_columns(5, 72, 40), 72, 40), [_matrices(pc.IDENTITY, previous=p) for p in previous])
+    case["jitter_current"], case["jitter_previous"] = tuple(float(F32(v)) for v in MOTION_JITTER), tuple(float(F32(v)) for v in MOTION_JITTER_PREVIOUS)
+    return [case]
+
+
+SHEAR_MODEL = pc.glm([[1.5, 0.4, 0.25, 0.0], [0.0, 0.7, 0.3, 0.0], [0.2, 0.0, 2.0, 0.0], [0.0, 0.0, 0.0, 1.0]])
+
+
+def _normal_edges():
+    singular = pc.IDENTITY.copy()
+    singular[[0, 5, 10]] = 0.0
+    models = [singular, pc.IDENTITY, pc.IDENTITY, SHEAR_MODEL, SHEAR_MODEL]
+    columns = _columns(5, 72, 40)
+    # draw 1 from y = 2.5 to 32.5, NDC -0.875 and 0.625: the weight of its lower vertex is 1/2 on the pixel centres of row 17, NDC -0.125, all three exact in binary
+    columns[1] = [[(15.0, 2.5, 0.5), (27.0, 2.5, 0.5), (27.0, 32.5, 0.5)]]
+    case = _with_draw_transforms(pc.pixel_case(columns, 72, 40), [_matrices(pc.IDENTITY, model=m) for m in models])
+    normals = np.zeros((15, 3), F32)
+    normals[0:3] = (0.0, 0.0, 1.0)                                              # draw 0: any normal under the singular model
+    normals[3:6] = [(0.0, 0.0, 1.0), (0.0, 0.0, -1.0), (0.0, 0.0, 1.0)]         # draw 1: interpolates through zero
+    normals[6:9] = [(np.inf, 0.0, 0.0), (0.0, np.nan, 0.0), (0.0, 0.0, 1e30)]   # draw 2: only the third normalises to a non-zero vector
+    normals[9:12] = [(0.3, 0.4, 2.0), (1.0, 2.0, -0.5), (-3.0, 0.25, 0.75)]     # draw 3: not unit length, under scale and shear
+    case["normals"] = normals                                                   # draw 4: no stored normals, the face normal under the same model
+    return [case]
+
+
+DENORMAL_SMALL, DENORMAL_LEAST, NORMAL_LEAST = 1e-41, 1.4e-45, 1.1754944e-38
+DENORMAL_TWO = 2.8e-45  # two units of the least denormal
+
+
+def _denormal_depth():
+    flat = lambda x, y, z, size=28.0: [(x, y, z), (x + size, y, z), (x + size, y + size, z)]
+    tris = [flat(2.0, 2.0, DENORMAL_SMALL), flat(34.0, 2.0, DENORMAL_LEAST), flat(2.0, 34.0, NORMAL_LEAST),
+            [(34.0, 34.0, DENORMAL_SMALL), (62.0, 34.0, -DENORMAL_SMALL), (62.0, 62.0, -DENORMAL_SMALL)],  # zf <= 0 from x = 48 on
+            flat(12.0, 4.0, DENORMAL_LEAST, 12.0), flat(44.0, 4.0, DENORMAL_TWO, 12.0)]  # over the first: it loses; over the second: it wins by one unit
+    return [pc.pixel_case([tris], 64, 64)]
+
+
+# thin, span 136.75 pixels = 35008 sub-pixel units: 64 x 4 pixels in the first tile and 3 x 4 in the next one. The second is its transpose across y = 64
+LANE_INT64_ROW = [(-70.0, 10.0, 0.3), (66.75, 10.0, 0.6), (66.75, 13.5, 0.7)]
+LANE_INT64_COLUMN = [(10.0, -70.0, 0.4), (13.5, 66.75, 0.8), (10.0, 66.75, 0.5)]
+
+
+def _lane_int64():
+    return [pc.pixel_case([[LANE_INT64_ROW, LANE_INT64_COLUMN]], 96, 80)]
+
+
+CROWDED_LARGE, CROWDED_SMALL = 200, 50
+
+
+def _crowded_large():
+    """250 consecutive triangles of one draw in one tile: one block of the set-up kernel, so the records are in submission order, and one 256-rectangle step of
+    the tile kernel's first wave. Right triangles with legs of 9 to 12 pixels (the wave path) and, at 50 random places among them, of 2 to 3.5 pixels (the lane
+    path); corners on the quarter-pixel grid, a random depth per vertex"""
+    rng = np.random.default_rng(0x43524F57)
+    n = CROWDED_LARGE + CROWDED_SMALL
+    small = np.zeros(n, bool)
+    small[rng.permutation(n)[:CROWDED_SMALL]] = True
+    tris = []
+    for k in range(n):
+        leg = np.rint(rng.uniform((2.0, 2.0), (3.5, 3.5)) * 4) / 4 if small[k] else np.rint(rng.uniform((9.0, 9.0), (12.0, 12.0)) * 4) / 4
+        x, y = np.rint(rng.uniform((-2.0, -2.0), (54.0, 54.0)) * 4) / 4
+        z = rng.uniform(0.1, 0.9, 3)
+        tris.append([(x, y, z[0]), (x + leg[0], y, z[1]), (x + leg[0], y + leg[1], z[2])])
+    return [pc.pixel_case([tris], 64, 64)]
+
+
 CASES = {"unit96x80": _unit96x80, "ties": _ties, "fans": _fans, "near_clip": _near_clip, "behind_and_beyond": _behind_and_beyond, "mesh130x70": _mesh130x70,
-         "far_tiny": _far_tiny, "dense64": _dense64, "draws700": _draws700, "nothing": _nothing, "small_frames": _small_frames}
+         "far_tiny": _far_tiny, "dense64": _dense64, "draws700": _draws700, "nothing": _nothing, "small_frames": _small_frames,
+         "octagon": _octagon, "sub_rejects": _sub_rejects, "motion_edges": _motion_edges, "normal_edges": _normal_edges, "denormal_depth": _denormal_depth,
+         "lane_int64": _lane_int64, "crowded_large": _crowded_large}
+FIRST_ROUND = ("unit96x80", "ties", "fans", "near_clip", "behind_and_beyond", "mesh130x70", "far_tiny", "dense64", "draws700", "nothing", "small_frames")
 _reference_cache = {}
 
 
 def reference(name):
-    """[(case, reference result)], computed once per case and shared by the modes; callers must not modify it"""
+    """[(case, reference result with its diagnostic lists)], computed once per case and shared by the modes; callers must not modify it"""
     if name not in _reference_cache:
-        _reference_cache[name] = [(case, pc.rasterise(case)) for case in CASES[name]()]
+        _reference_cache[name] = [(case, pc.rasterise(case, diagnostics=True)) for case in CASES[name]()]
     return _reference_cache[name]
 
 
@@ -348,9 +537,163 @@ def _check_small_frames(runs):
     assert runs[3][1]["coverage"][:, 63:65].max() >= 2 and runs[2][1]["coverage"][63:65, :].max() >= 2
 
 
+
+def _fan_indices(r, t=None):
+    return tuple(f[1] for f in r["fan_drawn"] if t is None or f[0] == t)
+
+
+def _check_octagon(runs):
+    assert len(runs) == 4
+    reached = set()
+    for k, (case, r) in enumerate(runs[:3]):
+        assert r["polygons"] == [(0, 8), (1, 8), (2, 8)], "every rotation is clipped to 8 vertices: %r" % (r["polygons"],)
+        assert counters(r) == OCTAGON_COUNTERS[k] and not r["fan_rejected"]
+        assert tuple(_fan_indices(r, t) for t in range(3)) == OCTAGON_FANS[k]
+        assert (r["coverage"] == 3).all(), "each of the three octagons covers every pixel exactly once"
+        alone = pc.rasterise(dict(case, draws=case["draws"][:1]))
+        assert (alone["coverage"] == 1).all() and counters(alone)[:2] == (1, 1), "the sub-triangles of one fan partition the %d pixels" % alone["coverage"].size
+        own = owner(r)
+        assert all((own == t).sum() > 1000 for t in range(3)), "every rotation is seen"
+        reached |= set(_fan_indices(r))
+    assert counters(runs[0][1]) == (3, 3, 9, 0) and np.array_equal(runs[0][0]["transforms"][0, 16:32], pc.glm([[1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 0, 0.05], [0, 0, 1, 0]]))
+    case, r = runs[3]
+    assert r["polygons"] == [(0, 6), (1, 7)] and counters(r) == (2, 2, 6, 0) and (_fan_indices(r, 0), _fan_indices(r, 1)) == ((0, 1, 2), (1, 2, 3))
+    own = owner(r)
+    assert (own == 0).sum() > 1000 and (own == 1).sum() > 1000
+    reached |= set(_fan_indices(r))
+    # (sub-triangles 0 and 5 of an octagon on the guard square hold three consecutive vertices of it and cannot contain a point within 1 of the centre: they
+    # reach the screen with their boxes only. They are set up, counted and walked; a wrong record would show as coverage that is not there)
+    assert reached == {0, 1, 2, 3, 4, 5}, "every fan index is drawn somewhere in the case"
+    for order in ((0, 1, 2), (0, 2, 1), (1, 0, 2), (1, 2, 0), (2, 0, 1), (2, 1, 0)):
+        poly, clipped = ref.clip_triangle(ref.transform4(octagon_mvp(0), np.asarray([OCTAGON[i] for i in order], F32)))
+        assert clipped and len(poly) == 8
+
+
+def _check_sub_rejects(runs):
+    case, r = runs[0]
+    assert counters(r) == (14, 6, 4, 13)
+    assert r["polygons"] == [(t, 3) for t in range(6)] + [(t, 4) for t in range(6, 12)] + [(12, 3), (13, 3)]
+    for winding in range(2):  # the issue's two triangles alone, in either winding: submitted 1, clipped 0, drawn 0, rejects 1
+        for first, transform_index in ((0, 0), (12, 1)):
+            alone = pc.rasterise(dict(case, draws=pc.draws6([[first + 3 * winding, 3, 0, transform_index]])))
+            assert counters(alone) == (1, 0, 0, 1)
+    clip = ref.transform4(case["transforms"][0, 16:32], case["positions"][0:3])
+    assert not clip[0].any() and all(ref.plane_distance(plane, clip[0]) >= 0 for plane in range(5)), "(0, 0, 0, 0) is inside all five planes"
+    assert not ref.project(clip, 96, 64)[3][0], "and fails w > 0"
+    clip = ref.transform4(case["transforms"][1, 16:32], case["positions"][12:15])
+    with np.errstate(all="ignore"):
+        assert np.isfinite(clip).all() and clip[0, 2] < F32(-9e29) and 0 < clip[0, 3] < F32(2e-30) and clip[0, 2] / clip[0, 3] == -np.inf
+    assert all(ref.plane_distance(plane, clip[0]) >= 0 for plane in range(5)), "z / w overflows inside the near plane"
+    rejected, drawn = set(r["fan_rejected"]), {(f[0], f[1]) for f in r["fan_drawn"]}
+    assert rejected == {(0, 0), (1, 0), (4, 0), (5, 0), (6, 0), (7, 0), (7, 1), (8, 0), (8, 1), (9, 0), (10, 0), (10, 1), (11, 1)}
+    assert drawn == {(3, 0), (9, 1), (11, 0), (13, 0)}, "triangles 9 and 11 hold a reject and a drawn sub-triangle, in either order"
+    own = owner(r)
+    assert set(np.unique(own).tolist()) == {-1, 13} and (own == 13).sum() > 500 and (r["coverage"][own == 13] == 2).all(), \
+        "the visible triangle behind them, drawn in both draws: the later one wins the tie"
+
+
+def _motion_of(r, t):
+    return np.unique(r["motion"][owner(r) == t].reshape(-1, 2), axis=0).tolist()
+
+
+def _check_motion_edges(runs):
+    case, r = runs[0]
+    assert counters(r) == (5, 0, 5, 0) and all((owner(r) == t).sum() == 222 for t in range(5))
+    assert all(v != 0 for v in case["jitter_current"] + case["jitter_previous"]) and case["jitter_current"] != case["jitter_previous"]
+    assert _motion_of(r, 0) == [[32767, -32767]], "m = (1.5, -1.5) saturates"
+    assert _motion_of(r, 1) == [[0, 0]] and _motion_of(r, 2) == [[0, 0]], "a previous w sum of -1 and of 0"
+    assert _motion_of(r, 3) == [[0, 0]], "a NaN x stores 0; y has the same jitter in both frames"
+    assert _motion_of(r, 4) == [[32766, -32767]], "one code below +1, and just beyond -1"
+    previous = case["transforms"][:, 32:48]
+    assert previous[1, 15] == -1 and previous[2, 15] == 0 and not previous[2, [3, 7, 11]].any() and np.isnan(previous[3, 12]) and np.isnan(previous[3]).sum() == 1
+    assert (case["transforms"][:, :32] == np.tile(pc.IDENTITY, 2)).all(), "identity current matrices"
+
+
+def _check_normal_edges(runs):
+    case, r = runs[0]
+    own = owner(r)
+    words = lambda t: set(np.unique(r["normal"][own == t]).tolist())
+    assert counters(r) == (5, 0, 5, 0)
+    assert words(0) == {0xFF808080} and (own == 0).sum() == 222, "a singular mat3(model): n = 0"
+    assert words(1) == {0xFF008080, 0xFF808080, 0xFFFF8080}, "(0, 0, 1) and (0, 0, -1) interpolate through zero: z codes 0, 128 and 255"
+    assert words(2) == {0xFF008080, 0xFFFF8080}, "only the 1e30 normal normalises to a non-zero vector: +z, or -z where rounding leaves its weight below zero"
+    assert len(words(3)) > 100, "normals of three lengths and directions through scale and shear: a word of its own for almost every pixel"
+    assert len(words(4)) == 1 and words(4) != {0xFFFF8080}, "the face normal (0, 0, 1) through the sheared mat3"
+    m = case["transforms"][3, :16].reshape(4, 4).T[:3, :3].astype(np.float64)
+    want = m @ np.array([0.0, 0.0, 1.0])
+    want /= np.linalg.norm(want)
+    got = np.array([(words(4).copy().pop() >> s) & 0xFF for s in (0, 8, 16)])
+    assert np.abs(got - np.rint((want * 0.5 + 0.5) * 255)).max() <= 1 and abs(want[0]) > 0.05
+    assert np.array_equal(case["transforms"][4, :16], case["transforms"][3, :16]) and not case["normals"][12:15].any()
+    lengths = np.linalg.norm(case["normals"][9:12].astype(np.float64), axis=1)
+    assert (np.abs(lengths - 1.0) > 0.5).all(), "stored normals that are not unit length"
+
+
+DENORMAL_LIMIT = 0x00800000  # the bits of the least normal float
+
+
+def _check_denormal_depth(runs):
+    case, r = runs[0]
+    bits, own = r["depth"].view(np.uint32), owner(r)
+    assert counters(r) == (6, 0, 6, 0)
+    assert F32(DENORMAL_LEAST).view(np.uint32) == 1 and F32(DENORMAL_TWO).view(np.uint32) == 2 and F32(NORMAL_LEAST).view(np.uint32) == DENORMAL_LIMIT
+    assert 1 < F32(DENORMAL_SMALL).view(np.uint32) < DENORMAL_LIMIT
+    for t, z, pixels in ((0, DENORMAL_SMALL, 406), (1, DENORMAL_LEAST, 328), (2, NORMAL_LEAST, 406), (5, DENORMAL_TWO, 78)):
+        assert (own == t).sum() == pixels and (r["depth"][own == t] == F32(z)).all(), "a constant denormal depth is kept and stored as it is"
+    assert not (own == 4).any() and (r["coverage"][2:16, 12:24].max() == 2), "the least denormal loses to 1e-41, and wins nowhere else"
+    ramp = own == 3
+    assert ramp.sum() > 80 and (bits[ramp] > 0).all() and (bits[ramp] < F32(DENORMAL_SMALL).view(np.uint32)).all() and len(np.unique(bits[ramp])) >= 10
+    assert ramp[:, :48].sum() == ramp.sum() and ramp[35, 47], "the far rule cuts the ramp at x = 48, inside the denormal range"
+    kept = r["keys"] != 0
+    assert ((bits[kept] < DENORMAL_LIMIT).sum() > 800) and (bits[kept] != 0).all(), "no kept depth is 0"
+
+
+def _tiles_of(tri, width, height):
+    """by hand from ref.project and the box formula: per 64 x 64 tile the triangle's box reaches, (tile, box inside the tile, pixels it keeps there, snapped span)"""
+    case = pc.pixel_case([[tri]], width, height)
+    X, Y, _, ok = ref.project(np.concatenate([case["positions"], np.ones((3, 1), F32)], axis=1), width, height)
+    assert ok.all()
+    ix0, ix1 = max(0, (int(X.min()) + 127) >> 8), min(width - 1, (int(X.max()) - 128) >> 8)
+    iy0, iy1 = max(0, (int(Y.min()) + 127) >> 8), min(height - 1, (int(Y.max()) - 128) >> 8)
+    kept = pc.rasterise(case)["coverage"]
+    out = []
+    for ty in range(iy0 >> 6, (iy1 >> 6) + 1):
+        for tx in range(ix0 >> 6, (ix1 >> 6) + 1):
+            bx0, bx1, by0, by1 = max(ix0, 64 * tx), min(ix1, 64 * tx + 63), max(iy0, 64 * ty), min(iy1, 64 * ty + 63)
+            out.append(((tx, ty), (bx1 - bx0 + 1, by1 - by0 + 1), int(kept[by0:by1 + 1, bx0:bx1 + 1].sum()), max(int(X.max() - X.min()), int(Y.max() - Y.min()))))
+    return out
+
+
+def _check_lane_int64(runs):
+    case, r = runs[0]
+    assert counters(r) == (2, 0, 2, 0) and (owner(r) == 0).sum() > 100 and (owner(r) == 1).sum() > 100
+    row, column = _tiles_of(LANE_INT64_ROW, 96, 80), _tiles_of(LANE_INT64_COLUMN, 96, 80)
+    assert [(tile, box) for tile, box, _, _ in row] == [((0, 0), (64, 4)), ((1, 0), (3, 4))]
+    assert [(tile, box) for tile, box, _, _ in column] == [((0, 0), (4, 64)), ((0, 1), (4, 3))]
+    for tiles in (row, column):
+        assert all(span >= NARROW_SPAN and kept > 0 for _, _, kept, span in tiles), "64-bit edge functions in both tiles, and pixels kept in both"
+        (_, large, _, _), (_, small, kept, _) = tiles
+        assert max(large) > 4 and max(small) <= 4 and kept >= 5, "the wave path in the first tile, the lane path in the next one"
+    c = r["coverage"]
+    assert c[10:14, 64:67].sum() >= 5 and c[64:67, 10:14].sum() >= 5
+
+
+def _check_crowded_large(runs):
+    case, r = runs[0]
+    assert counters(r) == (250, 0, 250, 0) and case["draws"].shape[0] == 1 and case["width"] == case["height"] == 64
+    first = r["fan_drawn"][:256]
+    assert [f[0] for f in first] == list(range(250)), "one set-up block: the records are in submission order, all within the first 256-rectangle step"
+    large = [max(x1 - x0, y1 - y0) >= 4 for _, _, (x0, y0, x1, y1), _ in first]
+    assert sum(large) >= 150 and len(large) - sum(large) >= 40, "%d boxes larger than 4 x 4 (the wave path), %d lane-path boxes among them" % (sum(large), len(large) - sum(large))
+    assert max(sum(large[k:k + 64]) for k in range(0, 256, 64)) < 64 and sum(large[64:]) > 100, "wave-path hits in the second and later rounds of 64"
+    own = owner(r)
+    assert len(np.unique(own[own >= 0])) >= 100 and r["coverage"].max() >= 8, "winners interleave"
+
+
 CASE_CHECKS = {"unit96x80": _check_unit96x80, "ties": _check_ties, "fans": _check_fans, "near_clip": _check_near_clip, "behind_and_beyond": _check_behind_and_beyond,
                "mesh130x70": _check_mesh130x70, "far_tiny": _check_far_tiny, "dense64": _check_dense64, "draws700": _check_draws700, "nothing": _check_nothing,
-               "small_frames": _check_small_frames}
+               "small_frames": _check_small_frames, "octagon": _check_octagon, "sub_rejects": _check_sub_rejects, "motion_edges": _check_motion_edges,
+               "normal_edges": _check_normal_edges, "denormal_depth": _check_denormal_depth, "lane_int64": _check_lane_int64, "crowded_large": _check_crowded_large}
 
 
 def check_case_is_what_it_is_for(name):
@@ -376,8 +719,10 @@ def globals_with_jitter(case):
 FORMATS = (ImageFormat.Depth32, ImageFormat.RG16_sNorm, ImageFormat.RGBA8, ImageFormat.RGBA8, ImageFormat.RGBA8)
 
 
-def gpu_prepass(be, case, scratch=None, formats=FORMATS, sizes=None):
-    """one execution through the C-ABI with the test's own buffers -> (dict of the five images as uint32 h x w, (submitted, clipped, drawn, rejects))"""
+def gpu_prepass(be, case, scratch=None, formats=FORMATS, sizes=None, dispatch=(1, 1, 1), push=None, scratch_read_only=False, same_image=None, scratch_as_input=None):
+    """one execution through the C-ABI with the test's own buffers -> (dict of the five images as uint32 h x w, (submitted, clipped, drawn, rejects)).
+    For the refusals: `scratch` its size in bytes, `formats` and `sizes` of the five images, `dispatch`, `push` the push constant bytes, `scratch_read_only`,
+    `same_image` (a, b): storage binding b gets the image of binding a, `scratch_as_input`: the input binding that gets the scratch buffer as well"""
     import passes
     w, h = case["width"], case["height"]
     triangles = int((case["draws"][:, 1] // 3).sum())
@@ -390,11 +735,17 @@ def gpu_prepass(be, case, scratch=None, formats=FORMATS, sizes=None):
     buffers.append(be.createStorageBuffer(nbytes, b"\xa5" * nbytes))
     images = [be.createImage(image_desc_2d(*(sizes[k] if sizes else (w, h)), fmt), prefill_pattern((sizes[k][0] * sizes[k][1]) if sizes else w * h, 17 * k + 3))
               for k, fmt in enumerate(formats)]
+    if same_image is not None:
+        images[same_image[1]] = images[same_image[0]]
+    bound = list(buffers)
+    if scratch_as_input is not None:
+        bound[scratch_as_input] = buffers[5]
     p = be.createComputePass("depthPrepassRaster.comp", [], "Depth prepass")
     be.newFrame()
     be.setComputePassExecution(ComputePassExecution(p, RenderPassResources(
-        storageImages=[ImageResource(img, 0, k) for k, img in enumerate(images)], storageBuffers=[StorageBufferResource(b, i != 5, i) for i, b in enumerate(buffers)]),
-        struct.pack("<2I", case["draws"].shape[0], triangles), (1, 1, 1)))
+        storageImages=[ImageResource(img, 0, k) for k, img in enumerate(images)],
+        storageBuffers=[StorageBufferResource(b, i != 5 or scratch_read_only, i) for i, b in enumerate(bound)]),
+        struct.pack("<2I", case["draws"].shape[0], triangles) if push is None else push, tuple(dispatch)))
     be.prepareForDrawcallRecording()
     be.renderFrame()
     out = {name: be.downloadImage(img, 0, np.uint32).reshape(h, w).copy() for name, img in zip(IMAGES, images)}
@@ -432,8 +783,11 @@ def test_gpu_prepass_raster_is_bit_identical_to_the_reference(backend, name, fas
     backend.setMathMode(fast)
     try:
         for k, (case, r) in enumerate(reference(name)):
+            start = time.perf_counter()
             out, counted = gpu_prepass(backend, case)
+            seconds = time.perf_counter() - start
             general = backend.getGeneralKernelExecutions()
+            print("prepass raster %s[%d] %s: upload, pass and download %.2f ms" % (name, k, "fast" if fast else "exact", 1e3 * seconds))
             compare("%s[%d] %s" % (name, k, "fast" if fast else "exact"), out, counted, r)
             if fast:
                 assert general[0] == 0, "the fast set ran a general kernel: %r" % (general,)
@@ -475,9 +829,47 @@ def test_gpu_prepass_raster_reaches_the_largest_width(backend):
     compare("largest image %d x %d" % (LARGEST_WIDTH, LARGEST_HEIGHT), out, counted, r)
 
 
+TALLEST_WIDTH, TALLEST_HEIGHT = 3, 16384
+
+
+def _tallest():
+    """the widest image's triangles transposed, second and third vertex exchanged so that they face front again"""
+    tris = [[(-0.75, 64.0 * ty + 10.5, 0.3 + 0.002 * ty), (3.5, 64.0 * ty + 30.25, 0.4), (0.25, 64.0 * ty + 80.5, 0.5)] for ty in LARGEST_TILES]
+    return pc.pixel_case([tris], TALLEST_WIDTH, TALLEST_HEIGHT)
+
+
+def check_tallest_is_what_it_is_for():
+    if "tallest" not in _reference_cache:
+        case = _tallest()
+        _reference_cache["tallest"] = (case, pc.rasterise(case))
+    case, r = _reference_cache["tallest"]
+    assert counters(r) == (4, 0, 4, 0), "all four face front"
+    for ty in LARGEST_TILES:
+        assert r["coverage"][64 * ty:64 * ty + 64].any() and (ty == 255 or r["coverage"][64 * ty + 64:64 * ty + 128].any())
+    assert r["coverage"][TALLEST_HEIGHT - 1].any()
+    return case, r
+
+
+def test_tallest_image_case_is_what_it_is_for():
+    """not gpu: the input conditions of the GPU test below"""
+    check_tallest_is_what_it_is_for()
+
+
+@pytest.mark.gpu
+def test_gpu_prepass_raster_reaches_the_largest_height(backend):
+    """16384 texels tall = 256 tile rows: the tile rectangle keeps its rows in bits 8 .. 15 and 24 .. 31, rows 128 and above set the top bit of each; one math mode"""
+    case, r = check_tallest_is_what_it_is_for()
+    start = time.perf_counter()
+    out, counted = gpu_prepass(backend, case)
+    print("prepass raster tallest image: upload, pass and download %.2f ms" % (1e3 * (time.perf_counter() - start)))
+    compare("tallest image %d x %d" % (TALLEST_WIDTH, TALLEST_HEIGHT), out, counted, r)
+
+
 @pytest.mark.gpu
 def test_gpu_launcher_refuses_what_it_cannot_run(backend):
-    """fails loudly: a scratch buffer too small for the triangle count (the message states the size formula), a depth image that is not Depth32, images of two sizes"""
+    """fails loudly: a scratch buffer too small for the triangle count (the message states the size formula), a depth image that is not Depth32, images of two sizes,
+    images wider than the largest, another dispatch, push constants that are short or contradict themselves or count too many triangles, a scratch buffer that is
+    read-only or also an input, one image at two bindings. A refusal leaves nothing behind: the next execution is bit-identical to the reference"""
     from plainrenderer_amd.backend import PlrError
     case = _unit96x80()[0]
     with pytest.raises(PlrError, match="scratch.*576 triangleCount"):
@@ -486,3 +878,26 @@ def test_gpu_launcher_refuses_what_it_cannot_run(backend):
         gpu_prepass(backend, case, formats=(ImageFormat.R16_sFloat,) + FORMATS[1:])
     with pytest.raises(PlrError, match="one size"):
         gpu_prepass(backend, case, sizes=[(96, 80), (96, 80), (96, 80), (96, 64), (96, 80)])
+    with pytest.raises(PlrError, match="at most 16384"):
+        gpu_prepass(backend, case, sizes=[(16385, 1)] * 5)
+    for dispatch in ((2, 1, 1), (1, 3, 1), (1, 1, 2)):
+        with pytest.raises(PlrError, match=r"the dispatch is \{1, 1, 1\}"):
+            gpu_prepass(backend, case, dispatch=dispatch)
+    for counts in ((0, 3), (1, 0)):
+        with pytest.raises(PlrError, match="both be zero or both be non-zero"):
+            gpu_prepass(backend, case, push=struct.pack("<2I", *counts))
+    with pytest.raises(PlrError, match=r"triangleCount 268435457 exceeds 2\^28"):  # (before the scratch size is looked at: the scratch buffer is the case's own)
+        gpu_prepass(backend, case, push=struct.pack("<2I", 1, (1 << 28) + 1))
+    with pytest.raises(PlrError, match="scratch buffer.*bound read-only"):
+        gpu_prepass(backend, case, scratch_read_only=True)
+    with pytest.raises(PlrError, match="one image is bound at two storage bindings"):
+        gpu_prepass(backend, case, same_image=(2, 3))
+    with pytest.raises(PlrError, match="scratch buffer is also bound as an input"):
+        gpu_prepass(backend, case, scratch_as_input=1)
+    for short in (b"", struct.pack("<I", 1), struct.pack("<2I", 1, 17)[:7]):
+        with pytest.raises(PlrError, match="push constants.*missing"):
+            gpu_prepass(backend, case, push=short)
+    check_case_is_what_it_is_for("unit96x80")
+    case, r = reference("unit96x80")[0]
+    out, counted = gpu_prepass(backend, case)
+    compare("unit96x80 after the refusals", out, counted, r)
