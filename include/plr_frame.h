@@ -273,7 +273,7 @@ int plrf_get_shadow_raster_stats(void* pipeline, uint32_t cascade, plrf_shadow_r
  * needs no re-upload of the G-buffer. Without a scene nothing is recorded, created or allocated and the uploaded G-buffer is used. The rasterisation contract -
  * Sutherland-Hodgman clipping against the near plane and a 32-NDC guard volume, 8 sub-pixel bits, top-left rule, back faces culled with a counter-clockwise front
  * face, reverse-Z Depth32 with GreaterEqual and the later triangle winning a tie, perspective-correct fp64 attributes, opaque meshes, one constant material per
- * draw - is DESIGN.md "Depth prepass as a compute pass".
+ * draw unless plrf_set_scene_textures (below) gives it textures - is DESIGN.md "Depth prepass as a compute pass".
  * plrf_scene_mesh: positions and optional normals (3 floats per vertex; NULL, or a vertex normal of exactly (0, 0, 0): the triangle's face normal
  * normalize(cross(v0 - v2, v0 - v1)) of the model-space positions) and a uint32 triangle list. plrf_scene_draw: a mesh under a model matrix with the two RGBA8
  * texels (R in the low byte) every pixel of the draw stores to albedo and specular.
@@ -292,6 +292,24 @@ typedef struct plrf_scene_mesh { const float* positions; const float* normals; u
 typedef struct plrf_scene_draw { uint32_t mesh; float model_matrix[16]; uint32_t albedo_rgba8, specular_rgba8; } plrf_scene_draw; /* glm column-major */
 int plrf_set_scene_meshes(void* pipeline, const plrf_scene_mesh* meshes, uint32_t mesh_count, const plrf_scene_draw* draws, uint32_t draw_count);
 int plrf_set_scene_mesh_transforms(void* pipeline, const float* matrices16, uint32_t draw_count);
+/* ---- material textures of the scene meshes: depthPrepass.frag / triangle.frag's albedoTexture and specularTexture sampled per pixel with the interpolated UV and
+ * g_mipBias (DESIGN.md "Material textures in the depth prepass": the sampling contract in integers and IEEE operations - repeat addressing, isotropic trilinear
+ * filtering with 8 sub-texel and 8 level-fraction bits, forward-difference derivatives of the triangle's own plane, round half even; no alpha test, no normal map).
+ * plrf_scene_texture: RGBA8 texels, R in the low byte, row-major; mip_count >= 1: that many levels back to back, level l being max(1, width >> l) x
+ * max(1, height >> l); mip_count 0: level 0 only and the host builds the full chain, each texel the rounded mean (a + b + c + d + 2) >> 2 of the level below at
+ * (min(2x, W - 1) | min(2x + 1, W - 1), min(2y, H - 1) | min(2y + 1, H - 1)). plrf_scene_material, one per draw: the texture an output samples, or PLRF_NO_TEXTURE
+ * for the draw's constant albedo_rgba8 / specular_rgba8 word. mesh_uvs[k]: 2 floats per vertex of mesh k, NULL (the array or an entry): all (0, 0).
+ * plrf_set_scene_textures needs a scene; mesh_count and draw_count must be the scene's. Everything is copied and takes effect with the next frame, in call order.
+ * texture_count 0 removes textures and materials (the other arguments are not looked at), and so does every plrf_set_scene_meshes; they survive
+ * plrf_set_scene_mesh_transforms, plrf_set_resolution and plrf_update_settings. Visibility, depth, motion, normal and the counters never depend on textures.
+ * PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: no scene set, a count mismatch, a texture size of 0 or above 16384, too many mips for the size,
+ * NULL texels, a material index that is neither PLRF_NO_TEXTURE nor < texture_count, more than 2^28 texels in total, a non-finite UV. PLR_ERR_UNSUPPORTED: a band /
+ * tile pipeline. A refused call changes nothing. */
+#define PLRF_NO_TEXTURE 0xffffffffu
+typedef struct plrf_scene_texture { const uint32_t* texels; uint32_t width, height, mip_count; } plrf_scene_texture;
+typedef struct plrf_scene_material { uint32_t albedo_texture, specular_texture; } plrf_scene_material;
+int plrf_set_scene_textures(void* pipeline, const plrf_scene_texture* textures, uint32_t texture_count, const float* const* mesh_uvs, uint32_t mesh_count,
+                            const plrf_scene_material* materials, uint32_t draw_count);
 typedef struct plrf_prepass_raster_stats { uint64_t triangles_submitted, triangles_clipped, subtriangles_drawn, rejects; } plrf_prepass_raster_stats;
 int plrf_get_prepass_raster_stats(void* pipeline, plrf_prepass_raster_stats* out);
 /* one iteration of the reference's main loop: record the frame, update camera/UBOs, submit (does not wait for the GPU) */

@@ -133,6 +133,17 @@ int plrf_set_scene_mesh_transforms(void* p, const float* matrices16, uint32_t dr
     if (!p) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY_REFUSAL(((FramePipeline*)p)->setSceneMeshTransforms(matrices16, drawCount))
 }
+int plrf_set_scene_textures(void* p, const plrf_scene_texture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount,
+                            const plrf_scene_material* materials, uint32_t drawCount) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        std::vector<SceneTexture> t(textures ? textureCount : 0u);
+        for (size_t i = 0; i < t.size(); i++) t[i] = {textures[i].texels, textures[i].width, textures[i].height, textures[i].mip_count};
+        std::vector<SceneMaterial> m(materials ? drawCount : 0u);
+        for (size_t i = 0; i < m.size(); i++) m[i] = {materials[i].albedo_texture, materials[i].specular_texture};
+        ((FramePipeline*)p)->setSceneTextures(t.empty() ? nullptr : t.data(), textureCount, meshUvs, meshCount, m.empty() ? nullptr : m.data(), drawCount);
+    })
+}
 int plrf_get_prepass_raster_stats(void* p, plrf_prepass_raster_stats* out) {
     if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY_REFUSAL({

@@ -329,9 +329,28 @@ struct PackedScene {
     std::vector<uint32_t> indices;
     std::vector<uint32_t> draws;                   // 6 words per draw: {firstIndex, indexCount, vertexOffset, transformIndex, albedo, specular}
     uint32_t triangleCount = 0;
+    std::vector<uint32_t> meshVertexCounts;        // per mesh, in the order the positions are packed: what packSceneTextures lays the UVs out by
 };
 PackedScene packSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const SceneDraw* draws, uint32_t drawCount);
 void refuseNonFiniteMatrices(const float* matrices16, uint32_t drawCount, const char* call);
+// material textures of the scene meshes (plr_frame.h plrf_set_scene_textures): RGBA8 texels, R in the low byte; mipCount levels back to back, or 0: level 0
+// only and the host builds the full chain. A material names a texture per output or kNoSceneTexture
+constexpr uint32_t kNoSceneTexture = 0xffffffffu;
+struct SceneTexture { const uint32_t* texels = nullptr; uint32_t width = 0, height = 0, mipCount = 0; };
+struct SceneMaterial { uint32_t albedoTexture = kNoSceneTexture, specularTexture = kNoSceneTexture; };
+// what setSceneTextures validates and packs, without a backend: the four extra buffers of a textured "depthPrepassRaster.comp" (device/depth_prepass_raster.h)
+struct PackedTextures {
+    std::vector<float> uvs;          // 2 floats per vertex of the packed scene, zeros for a mesh given without
+    std::vector<uint32_t> materials; // 2 words per draw
+    std::vector<uint32_t> textures;  // 4 words per texture: {texelOffset, width, height, mipCount}
+    std::vector<uint32_t> texels;
+};
+// sceneMeshVertexCounts / sceneDrawCount: of the scene the pipeline holds (sceneMeshCount 0: none). Throws FramePipelineRefusal.
+PackedTextures packSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials,
+                                 uint32_t drawCount, const uint32_t* sceneMeshVertexCounts, uint32_t sceneMeshCount, uint32_t sceneDrawCount);
+// appends levels 1 .. of the full chain of a width x height level 0 (already the last `width * height` texels of `texels`): level l + 1 texel (x, y) per channel
+// is (a + b + c + d + 2) >> 2 of the level-l texels at (min(2x, W - 1) | min(2x + 1, W - 1), min(2y, H - 1) | min(2y + 1, H - 1))
+void appendMipChain(std::vector<uint32_t>& texels, uint32_t width, uint32_t height);
 
 class FramePipeline {
 public:
@@ -355,6 +374,12 @@ public:
     // the draws' model matrices from the next frame on; a draw's previous model matrix is the one the last recorded frame used (on the first frame after
     // setSceneMeshes and after a camera cut: the current one). drawCount must be the scene's draw count
     void setSceneMeshTransforms(const float* matrices16, uint32_t drawCount);
+    // material textures for the scene now set (DESIGN.md "Material textures in the depth prepass"): from the next frame on the pass is recorded with the third
+    // push-constant word and bindings 6 - 9, and a draw whose material names a texture stores the sampled texel instead of its constant word. meshUvs[k]: 2 floats
+    // per vertex of mesh k, null: all (0, 0). Everything is copied. textureCount 0 removes them (whatever the other arguments are); setSceneMeshes drops them
+    // too. Refusals: no scene, a mesh or draw count other than the scene's, a texture size of 0 or above 16384, too many mips, null texels, a material index out
+    // of range, more than 2^28 texels, a non-finite UV are PLR_ERR_INVALID_ARGUMENT; a band / tile pipeline is PLR_ERR_UNSUPPORTED. A refused call changes nothing.
+    void setSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount);
     // counters of the last frame's execution for the scene now set; waits for the GPU. Zero while no scene is set and before the first frame of a newly set scene.
     PrepassRasterStats prepassRasterStats();
     // RenderFrontend::setResolution (RenderFrontend.cpp:408-421): recorded, applied at the start of the next frame() (prepareNewFrame, :199-222). Every image and
@@ -471,6 +496,10 @@ private:
     bool m_scenePassCreated = false, m_scenePreviousValid = false, m_sceneRecorded = false; // recorded: a frame has run the pass for the scene now set
     RenderPassHandle m_depthPrepassRasterPass;
     SceneBuffer m_sceneMatrices, m_scenePositions, m_sceneNormals, m_sceneIndices, m_sceneDraws, m_sceneScratch;
+    // material textures: created by the first setSceneTextures; 0 textures = the untextured pass record
+    uint32_t m_sceneTextureCount = 0;
+    std::vector<uint32_t> m_sceneMeshVertexCounts;
+    SceneBuffer m_sceneUvs, m_sceneMaterials, m_sceneTextures, m_sceneTexels;
     std::vector<float> m_sceneModel, m_scenePreviousModel; // 16 floats per draw: what the next frame uses, what the last recorded frame used
 public:
     AtmosphereSettings atmosphereSettings;

@@ -1,5 +1,6 @@
-// Validation and packing of scene meshes for "depthPrepassRaster.comp" (FramePipeline::setSceneMeshes): host code without a backend call, so that a stand-alone
-// program can run it under a sanitizer (tools/scene_packing_check.cpp).
+// Validation and packing of scene meshes and their material textures for "depthPrepassRaster.comp" (FramePipeline::setSceneMeshes, setSceneTextures): host code
+// without a backend call, so that a stand-alone program can run it under a sanitizer (tools/scene_packing_check.cpp, tools/scene_texture_check.cpp).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -65,6 +66,86 @@ PackedScene packSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const S
         std::memcpy(out.models.data() + (size_t)d * 16u, draws[d].modelMatrix, 64);
     }
     out.triangleCount = (uint32_t)triangles;
+    out.meshVertexCounts.resize(meshCount);
+    for (uint32_t m = 0; m < meshCount; m++) out.meshVertexCounts[m] = meshes[m].vertexCount;
+    return out;
+}
+
+void appendMipChain(std::vector<uint32_t>& texels, uint32_t width, uint32_t height) {
+    size_t src = texels.size() - (size_t)width * height;
+    for (uint32_t w = width, h = height; w > 1u || h > 1u;) {
+        const uint32_t nw = w > 1u ? w >> 1 : 1u, nh = h > 1u ? h >> 1 : 1u;
+        const size_t dst = texels.size();
+        texels.resize(dst + (size_t)nw * nh);
+        for (uint32_t y = 0; y < nh; y++) {
+            const uint32_t y0 = std::min(2u * y, h - 1u), y1 = std::min(2u * y + 1u, h - 1u);
+            for (uint32_t x = 0; x < nw; x++) {
+                const uint32_t x0 = std::min(2u * x, w - 1u), x1 = std::min(2u * x + 1u, w - 1u);
+                const uint32_t a = texels[src + (size_t)y0 * w + x0], b = texels[src + (size_t)y0 * w + x1], c = texels[src + (size_t)y1 * w + x0], d = texels[src + (size_t)y1 * w + x1];
+                uint32_t word = 0;
+                for (int k = 0; k < 32; k += 8) word |= ((((a >> k) & 255u) + ((b >> k) & 255u) + ((c >> k) & 255u) + ((d >> k) & 255u) + 2u) >> 2) << k;
+                texels[dst + (size_t)y * nw + x] = word;
+            }
+        }
+        src = dst; w = nw; h = nh;
+    }
+}
+
+// everything is validated before anything is built
+PackedTextures packSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials,
+                                 uint32_t drawCount, const uint32_t* sceneMeshVertexCounts, uint32_t sceneMeshCount, uint32_t sceneDrawCount) {
+    namespace pp = plr::prepass;
+    const std::string call = "setSceneTextures";
+    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
+    if (sceneDrawCount == 0) refuse("no scene set (plrf_set_scene_meshes comes first)");
+    if (meshCount != sceneMeshCount) refuse("mesh count " + std::to_string(meshCount) + " differs from the mesh count " + std::to_string(sceneMeshCount) + " of the scene");
+    if (drawCount != sceneDrawCount) refuse("draw count " + std::to_string(drawCount) + " differs from the draw count " + std::to_string(sceneDrawCount) + " of the scene");
+    if (!textures || !materials) refuse("textures or materials are null");
+    uint64_t total = 0;
+    for (uint32_t t = 0; t < textureCount; t++) {
+        const SceneTexture& tex = textures[t];
+        if (tex.width < 1u || tex.height < 1u || tex.width > pp::kMaxTextureSize || tex.height > pp::kMaxTextureSize)
+            refuse("texture size out of range: texture " + std::to_string(t) + " is " + std::to_string(tex.width) + " x " + std::to_string(tex.height) + ", each side must be 1 .. 16384");
+        const uint32_t full = pp::fullMipCount(tex.width, tex.height);
+        if (tex.mipCount > full)
+            refuse("too many mips: texture " + std::to_string(t) + " (" + std::to_string(tex.width) + " x " + std::to_string(tex.height) + ") has " + std::to_string(tex.mipCount) + " levels, at most " + std::to_string(full));
+        if (!tex.texels) refuse("null texels: texture " + std::to_string(t));
+        const uint32_t levels = tex.mipCount ? tex.mipCount : full;
+        for (uint32_t l = 0; l < levels; l++) total += (uint64_t)std::max(1u, tex.width >> l) * std::max(1u, tex.height >> l);
+    }
+    for (uint32_t d = 0; d < drawCount; d++)
+        for (uint32_t index : {materials[d].albedoTexture, materials[d].specularTexture})
+            if (index != kNoSceneTexture && index >= textureCount)
+                refuse("material texture index out of range: draw " + std::to_string(d) + " names texture " + std::to_string(index) + " of " + std::to_string(textureCount));
+    if (total > pp::kMaxTexels) refuse("too many texels: " + std::to_string(total) + " in all levels of all textures, at most 2^28");
+    uint64_t vertices = 0;
+    for (uint32_t m = 0; m < meshCount; m++) {
+        if (meshUvs && meshUvs[m])
+            for (size_t i = 0; i < (size_t)sceneMeshVertexCounts[m] * 2u; i++)
+                if (!std::isfinite(meshUvs[m][i]))
+                    refuse("non-finite UV: vertex " + std::to_string(i / 2u) + " of mesh " + std::to_string(m));
+        vertices += sceneMeshVertexCounts[m];
+    }
+    PackedTextures out;
+    out.uvs.assign((size_t)vertices * 2u, 0.f);
+    size_t at = 0;
+    for (uint32_t m = 0; m < meshCount; m++) {
+        if (meshUvs && meshUvs[m] && sceneMeshVertexCounts[m]) std::memcpy(out.uvs.data() + at, meshUvs[m], (size_t)sceneMeshVertexCounts[m] * 8u);
+        at += (size_t)sceneMeshVertexCounts[m] * 2u;
+    }
+    out.materials.resize((size_t)drawCount * 2u);
+    for (uint32_t d = 0; d < drawCount; d++) { out.materials[2u * d] = materials[d].albedoTexture; out.materials[2u * d + 1u] = materials[d].specularTexture; }
+    out.textures.resize((size_t)textureCount * 4u);
+    out.texels.reserve((size_t)total);
+    for (uint32_t t = 0; t < textureCount; t++) {
+        const SceneTexture& tex = textures[t];
+        const pp::Texture entry{(uint32_t)out.texels.size(), tex.width, tex.height, tex.mipCount ? tex.mipCount : pp::fullMipCount(tex.width, tex.height)};
+        std::memcpy(out.textures.data() + (size_t)t * 4u, &entry, sizeof(entry));
+        size_t given = 0;
+        for (uint32_t l = 0; l < std::max(1u, tex.mipCount); l++) given += (size_t)std::max(1u, tex.width >> l) * std::max(1u, tex.height >> l);
+        out.texels.insert(out.texels.end(), tex.texels, tex.texels + given);
+        if (tex.mipCount == 0) appendMipChain(out.texels, tex.width, tex.height);
+    }
     return out;
 }
 

@@ -42,9 +42,31 @@
 //     prev_k = mvpPrevious * (p_k, 1) in fp32 as above, promoted; ndcPrevious = (sum b_k prev_k.x, sum b_k prev_k.y) / sum b_k prev_k.w + previousFrameCameraJitter;
 //     m = (ndcPrevious - ndcCurrent) * 0.5, rounded to fp32; code = rint(fmin(fmax(m, -1), 1) * 32767) as int16, 0 for a NaN. A previous w sum that is not a
 //     finite number > 0 stores (0, 0). Both jitters come from the global UBO.
-//   albedo, specular: the two RGBA8 words of the winner's draw.
+//   albedo, specular: the two RGBA8 words of the winner's draw, or for a draw that names a texture the sampled texel (THE SAMPLING CONTRACT below).
 //   counters: submitted (triangles of all draws), clipped, drawn (sub-triangles), rejects (triangles and sub-triangles, as above).
-//   depthPrepass.frag's alpha test is left out - all meshes are opaque - and material textures are no input here.
+//   depthPrepass.frag's alpha test is left out - all meshes are opaque.
+//
+// THE SAMPLING CONTRACT (DESIGN.md "Material textures in the depth prepass"; tests/prepass_texture_reference.py implements it independently, bit for bit). Only
+// an execution whose third push-constant word textureCount is > 0 samples, and only the albedo and specular words of a winner pixel change; visibility, depth,
+// motion, normal and the counters do not. fp64 IEEE without contraction where named, fp32 IEEE elsewhere.
+//   texture store: `texels` holds uint32 RGBA8 texels, R in the low byte: all textures, each with all its levels back to back and unpadded; level l is row-major
+//     W_l x H_l with W_l = max(1, W_0 >> l), H_l likewise. `textures` holds {texelOffset (in texels), width, height, mipCount} per texture; an entry is usable when
+//     1 <= width, height <= 16384 and 1 <= mipCount <= floor(log2(max(width, height))) + 1. `materials` holds {albedoTexture, specularTexture} per draw, 0xffffffff
+//     = none. A word that is none, is >= textureCount or names an unusable entry makes that output the draw's constant word. A texel whose 64-bit address is
+//     outside `texels` reads 0.
+//   uv: `uvs` holds 2 floats per vertex, indexed like positions; a vertex outside `uvs` has (0, 0). u(P) = (b0 u0 + b1 u1) + b2 u2 in fp64 with the b of the
+//     pixel centre P, v likewise. If u or v is not finite or |.| >= 2^20, both are taken as 0 for the taps.
+//   derivatives, without a quad or a neighbouring pixel's triangle: the same triangle's b by the same formula ((1, 0, 0) fallback included) at
+//     P_x = ((2 (i + 1) + 1) / width - 1, P.y, 1) and P_y = (P.x, (2 (j + 1) + 1) / height - 1, 1). Per texture with its W_0, H_0 as fp64:
+//     ax = ((u(P_x) - u(P)) W_0, (v(P_x) - v(P)) H_0) from the raw u, v (before the validity rule), ay likewise with P_y; rx = ax.x^2 + ax.y^2, ry likewise;
+//     rho2 = rx > ry ? rx : ry, exactly that expression.
+//   level, fp32: r = (float)rho2; lod = 0.5f det_log2f(r) + g_mipBias; where !(lod > 0), lod = 0 (also a NaN); where lod > mipCount - 1, lod = that;
+//     q = (int)floorf(lod * 256.f + 0.5f), L0 = q >> 8, fw = q & 255, L1 = min(L0 + 1, mipCount - 1).
+//   taps, in integers (8 sub-texel bits), per level with dimensions (W, H): Tu = (int64)floor((u W - 0.5) 256 + 0.5) in fp64; x0 = Tu >> 8 (arithmetic),
+//     fx = Tu & 255, x1 = x0 + 1, both wrapped to [0, W) by a non-negative modulo (repeat); y0, fy, y1 likewise with v and H. Per channel
+//     S_l = (256 - fx)(256 - fy) c00 + fx (256 - fy) c10 + (256 - fx) fy c01 + fx fy c11; S = (256 - fw) S_L0 + fw S_L1 (<= 255 * 2^24: fits uint32); the stored
+//     code is (S + 2^23 - 1 + ((S >> 24) & 1)) >> 24, round half even. All four channels, alpha included; albedo is filtered in code space.
+//   Isotropic trilinear filtering stands in for the implementation-defined anisotropic sampler; there is no alpha test and no normal map.
 //
 // Two kernels. SET-UP: a lane per triangle finds its draw (block-wide prefix sum, LDS bisection), transforms, clips (the polygon lives in LDS, a column per lane),
 // projects, snaps, culls and boxes; the block's sub-triangles are appended through one 64-bit atomic per block to a dense array of 4-byte tile rectangles and an
@@ -52,7 +74,10 @@
 // and queues those that touch its tile; a hit whose box inside the tile is at most 4 x 4 pixels is rasterised by its lane, larger ones by the whole wave in
 // 8 x 8 stamps, in int32 where the triangle is narrow; LDS 64-bit atomic max. RESOLVE: behind the barrier a lane per pixel finds the winner's draw, fetches its
 // three vertices, evaluates the fp64 attributes and stores the five images, a wave per row segment of 64 four-byte texels (256 contiguous bytes per image).
-// Every tile scans every rectangle: no bins in this version. No global atomics on the targets.
+// Every tile scans every rectangle: no bins in this version. No global atomics on the targets. The tile kernel is a template over kTextured: the launcher picks
+// the instantiation by textureCount, and only the textured one holds the sampling code (the other is the kernel it was before textures, instruction for
+// instruction). Its resolve fetches the winner's vertices once for the three barycentric evaluations, samples nothing for a draw without a usable texture, and
+// computes every texel, UV and table address in 64 bits and checks it against its buffer before the load.
 #include <algorithm>
 
 #include "../backend.h"
@@ -289,6 +314,11 @@ __global__ __launch_bounds__(256) void depthPrepassSetupKernel(SetupParams p) {
     }
 }
 
+struct TextureInputs {
+    const float* uvs; const Material* materials; const Texture* textures; const uint32_t* texels;
+    uint64_t uvVertexCount, texelCount;
+    uint32_t drawCount, textureCount;
+};
 struct TileParams {
     ScratchHeader* header; const TriangleOrigin* origins; const uint32_t* rects; const Record* records;
     const float* transforms; const float* positions; const float* normals; const uint32_t* indices; const Draw* draws;
@@ -296,6 +326,7 @@ struct TileParams {
     float* depth; uint32_t* motion; uint32_t* normal; uint32_t* albedo; uint32_t* specular;
     uint32_t capacity, triangleCount;
     int32_t width, height;
+    TextureInputs tex; // a textured execution only (behind everything else: the untextured kernel's argument offsets stay)
 };
 
 typedef unsigned long long Key;
@@ -361,8 +392,86 @@ PLR_DI uint32_t unorm8Half(float n) { // n * 0.5 + 0.5 under the image contract'
     return (uint32_t)(int32_t)__builtin_rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.f);
 }
 
-// the winner's attributes at pixel (x, y): motion, normal and the draw's two material words
-PLR_DI void resolvePixel(const TileParams& p, uint32_t t, int x, int y, uint32_t* motion, uint32_t* normal, uint32_t* albedo, uint32_t* specular) {
+// ---- material textures (the sampling contract)
+// b of the same triangle at another point, by resolvePixel's formula
+PLR_DI void barycentricsAt(D3 P, const D3 V[3], double b[3]) {
+    const double e0 = det3(P, V[1], V[2]), e1 = det3(P, V[2], V[0]), e2 = det3(P, V[0], V[1]);
+    const double s = (e0 + e1) + e2;
+    b[0] = 1.0; b[1] = 0.0; b[2] = 0.0;
+    if (s != 0.0 && __builtin_fabs(s) < __builtin_inf()) { b[0] = e0 / s; b[1] = e1 / s; b[2] = e2 / s; }
+}
+
+// t mod n in [0, n) for |t| < 2^35 and 1 <= n <= 2^14: t / n is an integer or at least 2^-14 away from one, 16 times the spacing of fp64 at 2^34, so the floor
+// of the fp64 quotient is the exact one (a 64-bit integer division costs an order of magnitude more instructions)
+PLR_DI int wrapRepeat(int64_t t, int n) {
+    const double q = __builtin_floor((double)t / (double)n);
+    return (int)(t - (int64_t)q * (int64_t)n);
+}
+
+struct TexelSums { uint32_t c[4]; }; // per channel: 16 bits of weight on 8 bits of code
+
+// the four taps of one level (dimensions w x h, first texel at `base`), weighted; every address in 64 bits and checked against texelCount before its load
+PLR_DI TexelSums bilinearTaps(const uint32_t* texels, uint64_t texelCount, uint64_t base, int w, int h, double u, double v) {
+    const int64_t Tu = (int64_t)__builtin_floor((u * (double)w - 0.5) * 256.0 + 0.5), Tv = (int64_t)__builtin_floor((v * (double)h - 0.5) * 256.0 + 0.5);
+    const uint32_t fx = (uint32_t)(Tu & 255), fy = (uint32_t)(Tv & 255);
+    const int x0 = wrapRepeat(Tu >> 8, w), y0 = wrapRepeat(Tv >> 8, h);
+    const int x1 = x0 + 1 == w ? 0 : x0 + 1, y1 = y0 + 1 == h ? 0 : y0 + 1;
+    auto fetch = [&](int x, int y) {
+        const uint64_t at = base + (uint64_t)y * (uint64_t)w + (uint64_t)x;
+        return at < texelCount ? texels[at] : 0u;
+    };
+    const uint32_t c00 = fetch(x0, y0), c10 = fetch(x1, y0), c01 = fetch(x0, y1), c11 = fetch(x1, y1);
+    const uint32_t w00 = (256u - fx) * (256u - fy), w10 = fx * (256u - fy), w01 = (256u - fx) * fy, w11 = fx * fy;
+    TexelSums out;
+    for (int k = 0; k < 4; k++)
+        out.c[k] = w00 * ((c00 >> (8 * k)) & 255u) + w10 * ((c10 >> (8 * k)) & 255u) + w01 * ((c01 >> (8 * k)) & 255u) + w11 * ((c11 >> (8 * k)) & 255u);
+    return out;
+}
+
+// one trilinear sample of `texture`: (u, v) for the taps, (dudx, dvdx) and (dudy, dvdy) the raw forward differences
+PLR_DI uint32_t sampleTexture(const TextureInputs& tex, Texture texture, double u, double v, double dudx, double dvdx, double dudy, double dvdy, float mipBias) {
+    const double w0 = (double)texture.width, h0 = (double)texture.height;
+    const double axx = dudx * w0, axy = dvdx * h0, ayx = dudy * w0, ayy = dvdy * h0;
+    const double rx = axx * axx + axy * axy, ry = ayx * ayx + ayy * ayy;
+    const double rho2 = rx > ry ? rx : ry;
+    const float r = (float)rho2;
+    float lod = 0.5f * det_log2f(r) + mipBias;
+    if (!(lod > 0.f)) lod = 0.f;
+    const float top = (float)(texture.mipCount - 1u);
+    if (lod > top) lod = top;
+    const int q = (int)__builtin_floorf(lod * 256.f + 0.5f);
+    const int L0 = q >> 8, L1 = min(L0 + 1, (int)texture.mipCount - 1);
+    const uint32_t fw = (uint32_t)(q & 255);
+    uint64_t base = texture.texelOffset;
+    for (int l = 0; l < L0; l++) base += (uint64_t)max(1u, texture.width >> l) * (uint64_t)max(1u, texture.height >> l);
+    const int w = (int)max(1u, texture.width >> L0), h = (int)max(1u, texture.height >> L0);
+    const TexelSums s0 = bilinearTaps(tex.texels, tex.texelCount, base, w, h, u, v);
+    TexelSums s1{{0u, 0u, 0u, 0u}};
+    if (fw != 0u) { // (with fw == 0 the upper level has no weight; with L1 == L0 it is the same level again)
+        const uint64_t base1 = L1 == L0 ? base : base + (uint64_t)w * (uint64_t)h;
+        s1 = bilinearTaps(tex.texels, tex.texelCount, base1, (int)max(1u, texture.width >> L1), (int)max(1u, texture.height >> L1), u, v);
+    }
+    uint32_t word = 0u;
+    for (int k = 0; k < 4; k++) {
+        const uint32_t S = (256u - fw) * s0.c[k] + fw * s1.c[k];
+        word |= ((S + 0x7fffffu + ((S >> 24) & 1u)) >> 24) << (8 * k);
+    }
+    return word;
+}
+
+// the table entry `index` names when it is usable: inside the table, 1 <= width, height <= 16384, 1 <= mipCount <= floor(log2(max(width, height))) + 1
+PLR_DI bool usableTexture(const TextureInputs& tex, uint32_t index, Texture* out) {
+    if (index == kNoTexture || index >= tex.textureCount) return false;
+    const Texture t = tex.textures[index];
+    if (t.width < 1u || t.height < 1u || t.width > kMaxTextureSize || t.height > kMaxTextureSize) return false;
+    if (t.mipCount < 1u || t.mipCount > 32u - (uint32_t)__clz(max(t.width, t.height))) return false;
+    *out = t;
+    return true;
+}
+
+// the winner's attributes at pixel (x, y): motion, normal and the draw's two material words (kTextured: the sampled texel where its material names a texture)
+template <bool kTextured>
+PLR_DI void resolvePixel(const TileParams& p, const TextureInputs& tex, uint32_t t, int x, int y, uint32_t* motion, uint32_t* normal, uint32_t* albedo, uint32_t* specular) {
     const TriangleOrigin o = p.origins[t];
     const Draw draw = p.draws[o.draw];
     const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)o.local * 3u;
@@ -370,8 +479,10 @@ PLR_DI void resolvePixel(const TileParams& p, uint32_t t, int x, int y, uint32_t
     const float *model = T, *mvp = T + 16, *mvpPrevious = T + 32;
     float pos[3][3], nrm[3][3];
     D3 V[3], prev[3];
+    uint64_t vertex[3];
     for (int k = 0; k < 3; k++) {
         const uint64_t v = (uint64_t)p.indices[at + k] + (uint64_t)draw.vertexOffset;
+        vertex[k] = v;
         for (int c = 0; c < 3; c++) { pos[k][c] = p.positions[v * 3u + c]; nrm[k][c] = p.normals[v * 3u + c]; }
         V[k] = D3{(double)clipComponent(mvp, 0, pos[k][0], pos[k][1], pos[k][2]), (double)clipComponent(mvp, 1, pos[k][0], pos[k][1], pos[k][2]),
                   (double)clipComponent(mvp, 3, pos[k][0], pos[k][1], pos[k][2])};
@@ -411,8 +522,32 @@ PLR_DI void resolvePixel(const TileParams& p, uint32_t t, int x, int y, uint32_t
     *motion = code;
     *albedo = draw.albedo;
     *specular = draw.specular;
+    if constexpr (kTextured) {
+        if (o.draw >= tex.drawCount) return;
+        const Material material = tex.materials[o.draw];
+        Texture albedoTexture, specularTexture;
+        const bool sampleAlbedo = usableTexture(tex, material.albedoTexture, &albedoTexture), sampleSpecular = usableTexture(tex, material.specularTexture, &specularTexture);
+        if (!sampleAlbedo && !sampleSpecular) return;
+        double tu[3], tv[3];
+        for (int k = 0; k < 3; k++) {
+            const bool inside = vertex[k] < tex.uvVertexCount;
+            tu[k] = inside ? (double)tex.uvs[vertex[k] * 2u] : 0.0;
+            tv[k] = inside ? (double)tex.uvs[vertex[k] * 2u + 1u] : 0.0;
+        }
+        double bx[3], by[3];
+        barycentricsAt(D3{(double)(2 * (x + 1) + 1) / (double)p.width - 1.0, P.y, 1.0}, V, bx);
+        barycentricsAt(D3{P.x, (double)(2 * (y + 1) + 1) / (double)p.height - 1.0, 1.0}, V, by);
+        double u = weighted(b, tu[0], tu[1], tu[2]), v = weighted(b, tv[0], tv[1], tv[2]);
+        const double dudx = weighted(bx, tu[0], tu[1], tu[2]) - u, dvdx = weighted(bx, tv[0], tv[1], tv[2]) - v;
+        const double dudy = weighted(by, tu[0], tu[1], tu[2]) - u, dvdy = weighted(by, tv[0], tv[1], tv[2]) - v;
+        if (!(__builtin_fabs(u) < 1048576.0 && __builtin_fabs(v) < 1048576.0)) u = v = 0.0; // (a NaN fails the comparison)
+        const float mipBias = p.global->mipBias;
+        if (sampleAlbedo) *albedo = sampleTexture(tex, albedoTexture, u, v, dudx, dvdx, dudy, dvdy, mipBias);
+        if (sampleSpecular) *specular = sampleTexture(tex, specularTexture, u, v, dudx, dvdx, dudy, dvdy, mipBias);
+    }
 }
 
+template <bool kTextured>
 __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
     __shared__ Key tile[kTileSize * kTileSize];
     __shared__ uint32_t hitQueue[4][256]; // per wave: the entries of the current step that touch the tile
@@ -420,6 +555,11 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
     const int ox = tx * kTileSize, oy = ty * kTileSize;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint32_t i = threadIdx.x; i < (uint32_t)(kTileSize * kTileSize); i += 256u) tile[i] = 0ull;
+    // the textured resolve takes its inputs from LDS: held in scalar registers from the kernel's entry they would be spilled across the scan, which needs them all
+    __shared__ TextureInputs sharedTex;
+    if constexpr (kTextured) {
+        if (threadIdx.x == 0) sharedTex = p.tex;
+    }
     __syncthreads();
     const uint32_t n = min(p.header->cursor, p.capacity);
     const int tx1 = min(ox + kTileSize - 1, p.width - 1), ty1 = min(oy + kTileSize - 1, p.height - 1); // the tile's pixels inside the image
@@ -494,13 +634,15 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
     }
     __syncthreads();
     // resolve: a lane per pixel, a wave per tile row - 64 four-byte texels, 256 contiguous bytes of every image per store instruction
+    TextureInputs tex{};
+    if constexpr (kTextured) tex = sharedTex;
     for (uint32_t i = threadIdx.x; i < (uint32_t)(kTileSize * kTileSize); i += 256u) {
         const int y = oy + (int)(i >> 6), x = ox + (int)(i & 63u);
         if (y >= p.height || x >= p.width) continue;
         const Key key = tile[i];
         uint32_t motion = 0u, normal = 0u, albedo = 0u, specular = 0u;
         const uint32_t t = (uint32_t)key;
-        if (key != 0ull && t < p.triangleCount) resolvePixel(p, t, x, y, &motion, &normal, &albedo, &specular);
+        if (key != 0ull && t < p.triangleCount) resolvePixel<kTextured>(p, tex, t, x, y, &motion, &normal, &albedo, &specular);
         const size_t at = (size_t)y * (size_t)p.width + (size_t)x;
         p.depth[at] = u2f((uint32_t)(key >> 32));
         p.motion[at] = motion; p.normal[at] = normal; p.albedo[at] = albedo; p.specular[at] = specular;
@@ -509,8 +651,8 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
 
 static int launchDepthPrepassRaster(const PassCtx& c) {
     if (c.push.size() < sizeof(PushConstants)) return c.fail(-1, "depthPrepassRaster: push constants {drawCount, triangleCount} missing");
-    PushConstants pc;
-    std::memcpy(&pc, c.push.data(), sizeof(pc));
+    TexturedPushConstants pc{};
+    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0
     if (c.dispatch[0] != 1u || c.dispatch[1] != 1u || c.dispatch[2] != 1u || c.base[0] != 0u || c.base[1] != 0u)
         return c.fail(-1, "depthPrepassRaster: the dispatch is {1, 1, 1} (the launcher derives its grids from the push constants and the images)");
     if (pc.triangleCount > kMaxTriangles) return c.fail(-1, "depthPrepassRaster: triangleCount " + std::to_string(pc.triangleCount) + " exceeds 2^28");
@@ -524,6 +666,12 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
     if (int rc = c.needSbuf(kScratchBinding, scratchBytes(pc.triangleCount),
                             "depthPrepassRaster scratch (align16(align16(64 + 8 triangleCount) + 24 triangleCount) + 576 triangleCount bytes: 6 sub-triangles per triangle)"))
         return rc;
+    if (pc.textureCount) {
+        if (int rc = c.needSbuf(kUvBinding, 0, "depthPrepassRaster uvs (2 floats per vertex)")) return rc;
+        if (int rc = c.needSbuf(kMaterialBinding, (size_t)pc.drawCount * sizeof(Material), "depthPrepassRaster materials {albedoTexture, specularTexture} per draw")) return rc;
+        if (int rc = c.needSbuf(kTextureBinding, (size_t)pc.textureCount * sizeof(Texture), "depthPrepassRaster textures {texelOffset, width, height, mipCount}")) return rc;
+        if (int rc = c.needSbuf(kTexelBinding, 0, "depthPrepassRaster texels (RGBA8, every texture's levels back to back)")) return rc;
+    }
     if (c.sbuf[kScratchBinding].readOnly) return c.fail(-4, "depthPrepassRaster: the scratch buffer (binding 5) is bound read-only");
     if (int rc = c.needStorage(kDepthBinding, F_D32, "depthPrepassRaster depth")) return rc;
     if (int rc = c.needStorage(kMotionBinding, F_RG16SN, "depthPrepassRaster motion")) return rc;
@@ -542,6 +690,9 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
     }
     for (int b : {kTransformBinding, kPositionBinding, kNormalBinding, kIndexBinding, kDrawBinding})
         if (c.sbuf[b].ptr == c.sbuf[kScratchBinding].ptr) return c.fail(-4, "depthPrepassRaster: the scratch buffer is also bound as an input");
+    if (pc.textureCount)
+        for (int b : {kUvBinding, kMaterialBinding, kTextureBinding, kTexelBinding})
+            if (c.sbuf[b].ptr == c.sbuf[kScratchBinding].ptr) return c.fail(-4, "depthPrepassRaster: the scratch buffer is also bound as an input");
 
     uint8_t* scratch = (uint8_t*)c.sbuf[kScratchBinding].ptr;
     if (hipMemsetAsync(scratch, 0, sizeof(ScratchHeader), c.stream) != hipSuccess) return c.fail(-2, "depthPrepassRaster: clearing the scratch header failed");
@@ -570,7 +721,15 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
     t.depth = (float*)depth.ptr; t.motion = (uint32_t*)c.storage[kMotionBinding].ptr; t.normal = (uint32_t*)c.storage[kNormalImageBinding].ptr;
     t.albedo = (uint32_t*)c.storage[kAlbedoBinding].ptr; t.specular = (uint32_t*)c.storage[kSpecularBinding].ptr;
     t.capacity = capacity; t.triangleCount = pc.triangleCount; t.width = depth.w; t.height = depth.h;
-    depthPrepassTileKernel<<<dim3(divUp((unsigned)depth.w, (unsigned)kTileSize), divUp((unsigned)depth.h, (unsigned)kTileSize)), 256, 0, c.stream>>>(t);
+    const dim3 tiles(divUp((unsigned)depth.w, (unsigned)kTileSize), divUp((unsigned)depth.h, (unsigned)kTileSize));
+    if (pc.textureCount) {
+        t.tex.uvs = (const float*)c.sbuf[kUvBinding].ptr; t.tex.materials = (const Material*)c.sbuf[kMaterialBinding].ptr;
+        t.tex.textures = (const Texture*)c.sbuf[kTextureBinding].ptr; t.tex.texels = (const uint32_t*)c.sbuf[kTexelBinding].ptr;
+        t.tex.uvVertexCount = c.sbuf[kUvBinding].size / 8u; t.tex.texelCount = c.sbuf[kTexelBinding].size / 4u;
+        t.tex.drawCount = pc.drawCount; t.tex.textureCount = pc.textureCount;
+        depthPrepassTileKernel<true><<<tiles, 256, 0, c.stream>>>(t);
+    } else
+        depthPrepassTileKernel<false><<<tiles, 256, 0, c.stream>>>(t);
     PLR_CHECK_LAUNCH(c);
     return 0;
 }

@@ -65,6 +65,17 @@ class PlrfSceneDraw(C.Structure):
     _fields_ = [("mesh", C.c_uint32), ("model_matrix", C.c_float * 16), ("albedo_rgba8", C.c_uint32), ("specular_rgba8", C.c_uint32)]
 
 
+NO_TEXTURE = 0xFFFFFFFF  # PLRF_NO_TEXTURE
+
+
+class PlrfSceneTexture(C.Structure):
+    _fields_ = [("texels", C.POINTER(C.c_uint32)), ("width", C.c_uint32), ("height", C.c_uint32), ("mip_count", C.c_uint32)]
+
+
+class PlrfSceneMaterial(C.Structure):
+    _fields_ = [("albedo_texture", C.c_uint32), ("specular_texture", C.c_uint32)]
+
+
 class PlrfPrepassRasterStats(C.Structure):
     _fields_ = [("triangles_submitted", C.c_uint64), ("triangles_clipped", C.c_uint64), ("subtriangles_drawn", C.c_uint64), ("rejects", C.c_uint64)]
 
@@ -316,6 +327,27 @@ class FramePipeline:
         """one 16-float model matrix per draw, from the next frame on"""
         a = np.ascontiguousarray(matrices, np.float32).reshape(-1, 16)
         self._check(self.lib.plrf_set_scene_mesh_transforms(self.handle, a.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(a.shape[0])))
+
+    def set_scene_textures(self, textures, mesh_uvs, materials):
+        """textures: [(texels uint32 RGBA8 with R in the low byte, width, height, mip_count)] - mip_count levels back to back, or 0: level 0 only and the host builds
+        the full chain; mesh_uvs: one n x 2 float32 array or None per mesh of the scene; materials: one (albedo texture, specular texture) per draw, NO_TEXTURE for
+        the draw's constant word. Copied; from the next frame on. No textures: they are removed"""
+        tex = [np.ascontiguousarray(t[0], np.uint32).reshape(-1) for t in textures]
+        uvs = [None if u is None else np.ascontiguousarray(u, np.float32).reshape(-1, 2) for u in mesh_uvs]
+        t = (PlrfSceneTexture * max(len(textures), 1))()
+        for k, (_, width, height, mips) in enumerate(textures):
+            valid = 0 < width <= 16384 and 0 < height <= 16384 and mips <= max(int(width), int(height)).bit_length()  # (otherwise the call refuses and reads nothing)
+            need = sum(max(1, int(width) >> l) * max(1, int(height) >> l) for l in range(max(1, int(mips)))) if valid else 0
+            if tex[k].size and tex[k].size < need:  # (no texels at all: NULL, which the call refuses)
+                raise ValueError("texture %d has %d texels for %d x %d with %d levels" % (k, tex[k].size, width, height, mips))
+            t[k] = PlrfSceneTexture(tex[k].ctypes.data_as(C.POINTER(C.c_uint32)) if tex[k].size else None, int(width), int(height), int(mips))
+        u = (C.POINTER(C.c_float) * max(len(uvs), 1))()
+        for k, a in enumerate(uvs):
+            u[k] = None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+        m = (PlrfSceneMaterial * max(len(materials), 1))()
+        for k, (albedo, specular) in enumerate(materials):
+            m[k] = PlrfSceneMaterial(int(albedo), int(specular))
+        self._check(self.lib.plrf_set_scene_textures(self.handle, t, C.c_uint32(len(textures)), u, C.c_uint32(len(uvs)), m, C.c_uint32(len(materials))))
 
     def prepass_raster_stats(self):
         """(triangles submitted, triangles clipped, sub-triangles drawn, rejects) of the last frame's execution; waits for the GPU"""

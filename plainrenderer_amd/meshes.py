@@ -2,6 +2,10 @@
 
 Winding: the bake derives the triangle normal as normalize(cross(v0 - v2, v0 - v1)) (reference AssetPipeline/SceneSDF.cpp:273),
 the negative of the counter-clockwise normal, so triangles are emitted clockwise seen from outside and that normal points outward.
+
+with_uvs=True makes uv_sphere, box and torus return a third array, n x 2 float32 texture coordinates per vertex, in [0, 1]: (segment / segments, ring / rings) on the
+sphere, the face grid's (i / subdiv, j / subdiv) on every box face, (segment / segments, side / sides) on the torus. Vertices are not duplicated for them: the sphere's and
+the torus' last column of quads shares its far vertices with the first column, so the coordinate runs back to 0 across that one column (a seam).
 """
 import numpy as np
 
@@ -19,7 +23,11 @@ def _finish(positions, tris, outward_ref=None):
     return positions, tris[keep].reshape(-1)
 
 
-def uv_sphere(radius=1.0, segments=24, rings=12, centre=(0.0, 0.0, 0.0)):
+def _with_uvs(mesh, uvs, with_uvs):
+    return mesh + (np.asarray(uvs, np.float32).reshape(-1, 2),) if with_uvs else mesh
+
+
+def uv_sphere(radius=1.0, segments=24, rings=12, centre=(0.0, 0.0, 0.0), with_uvs=False):
     pos = []
     for r in range(rings + 1):
         th = np.pi * r / rings
@@ -33,10 +41,10 @@ def uv_sphere(radius=1.0, segments=24, rings=12, centre=(0.0, 0.0, 0.0)):
             c = (r + 1) * segments + s; d = (r + 1) * segments + (s + 1) % segments
             tris += [(a, b, c), (b, d, c)]
     p = np.asarray(pos, np.float32) + np.asarray(centre, np.float32)
-    return _finish(p, tris)
+    return _with_uvs(_finish(p, tris), [(s / segments, r / rings) for r in range(rings + 1) for s in range(segments)], with_uvs)
 
 
-def box(half=(1.0, 1.0, 1.0), centre=(0.0, 0.0, 0.0), subdiv=2):
+def box(half=(1.0, 1.0, 1.0), centre=(0.0, 0.0, 0.0), subdiv=2, with_uvs=False):
     """Axis-aligned box, each face a subdiv x subdiv grid of quads."""
     half = np.asarray(half, np.float32)
     pos, tris = [], []
@@ -56,10 +64,10 @@ def box(half=(1.0, 1.0, 1.0), centre=(0.0, 0.0, 0.0), subdiv=2):
                     a = base + i * (subdiv + 1) + j; b = a + 1; c = a + subdiv + 1; d = c + 1
                     tris += [(a, b, c), (b, d, c)]
     p = np.asarray(pos, np.float32) + np.asarray(centre, np.float32)
-    return _finish(p, tris)
+    return _with_uvs(_finish(p, tris), [(i / subdiv, j / subdiv) for _ in range(6) for i in range(subdiv + 1) for j in range(subdiv + 1)], with_uvs)
 
 
-def torus(major=1.5, minor=0.5, segments=24, sides=12, centre=(0.0, 0.0, 0.0)):
+def torus(major=1.5, minor=0.5, segments=24, sides=12, centre=(0.0, 0.0, 0.0), with_uvs=False):
     pos, tris = [], []
     for i in range(segments):
         a = 2.0 * np.pi * i / segments
@@ -83,7 +91,7 @@ def torus(major=1.5, minor=0.5, segments=24, sides=12, centre=(0.0, 0.0, 0.0)):
         out[:, [0, 2]] = xz / np.maximum(n, 1e-9) * major
         return out
     positions, idx = _finish(p, tris, outward_ref=ring_centre)
-    return positions + c3, idx
+    return _with_uvs((positions + c3, idx), [(i / segments, j / sides) for i in range(segments) for j in range(sides)], with_uvs)
 
 
 def bounds(positions):
