@@ -294,7 +294,7 @@ int plrf_set_scene_meshes(void* pipeline, const plrf_scene_mesh* meshes, uint32_
 int plrf_set_scene_mesh_transforms(void* pipeline, const float* matrices16, uint32_t draw_count);
 /* ---- material textures of the scene meshes: depthPrepass.frag / triangle.frag's albedoTexture and specularTexture sampled per pixel with the interpolated UV and
  * g_mipBias (DESIGN.md "Material textures in the depth prepass": the sampling contract in integers and IEEE operations - repeat addressing, isotropic trilinear
- * filtering with 8 sub-texel and 8 level-fraction bits, forward-difference derivatives of the triangle's own plane, round half even; no alpha test, no normal map).
+ * filtering with 8 sub-texel and 8 level-fraction bits, forward-difference derivatives of the triangle's own plane, round half even; no normal map; the alpha test: plrf_set_scene_alpha_cutoffs below).
  * plrf_scene_texture: RGBA8 texels, R in the low byte, row-major; mip_count >= 1: that many levels back to back, level l being max(1, width >> l) x
  * max(1, height >> l); mip_count 0: level 0 only and the host builds the full chain, each texel the rounded mean (a + b + c + d + 2) >> 2 of the level below at
  * (min(2x, W - 1) | min(2x + 1, W - 1), min(2y, H - 1) | min(2y + 1, H - 1)). plrf_scene_material, one per draw: the texture an output samples, or PLRF_NO_TEXTURE
@@ -310,6 +310,19 @@ typedef struct plrf_scene_texture { const uint32_t* texels; uint32_t width, heig
 typedef struct plrf_scene_material { uint32_t albedo_texture, specular_texture; } plrf_scene_material;
 int plrf_set_scene_textures(void* pipeline, const plrf_scene_texture* textures, uint32_t texture_count, const float* const* mesh_uvs, uint32_t mesh_count,
                             const plrf_scene_material* materials, uint32_t draw_count);
+/* ---- alpha-tested cutouts: depthPrepass.frag:27-30 (sample the albedo texture's alpha with g_mipBias, discard below 0.5) as a per-draw cutoff code 0 .. 255
+ * (DESIGN.md "Alpha-tested cutouts in the depth prepass"). 0 is opaque; PLRF_ALPHA_CUTOFF_REFERENCE (128) is the reference's test, a / 255 < 0.5 <=> a <= 127.
+ * The alpha code of a fragment is bits 24 - 31 of the albedo word the sampling contract yields for its triangle at that pixel (the draw's constant albedo_rgba8
+ * where its material names no albedo texture); a fragment whose alpha code is below its draw's cutoff is no fragment: depth, motion, normal, albedo, specular
+ * and everything downstream see what is behind it, or the sky. The counters of plrf_get_prepass_raster_stats do not depend on alpha.
+ * plrf_set_scene_alpha_cutoffs needs a scene with textures set; draw_count must be the scene's. The values are copied and take effect with the next frame, in
+ * call order. draw_count 0 removes them, and so does every plrf_set_scene_meshes and every plrf_set_scene_textures; they survive
+ * plrf_set_scene_mesh_transforms, plrf_set_resolution and plrf_update_settings. While all cutoffs are 0, or none are set, every frame is what it is without this
+ * call. PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: no scene set, no textures set, a count mismatch, NULL cutoffs with a non-zero count, a
+ * value above 255. PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing. The sun shadow pass has no alpha test: a cutout casts its
+ * quad's shadow. */
+#define PLRF_ALPHA_CUTOFF_REFERENCE 128u
+int plrf_set_scene_alpha_cutoffs(void* pipeline, const uint32_t* cutoffs, uint32_t draw_count);
 typedef struct plrf_prepass_raster_stats { uint64_t triangles_submitted, triangles_clipped, subtriangles_drawn, rejects; } plrf_prepass_raster_stats;
 int plrf_get_prepass_raster_stats(void* pipeline, plrf_prepass_raster_stats* out);
 /* one iteration of the reference's main loop: record the frame, update camera/UBOs, submit (does not wait for the GPU) */

@@ -12,9 +12,11 @@ namespace prepass {
 // the pass record (DESIGN.md "Depth prepass as a compute pass")
 constexpr int kTransformBinding = 0, kPositionBinding = 1, kNormalBinding = 2, kIndexBinding = 3, kDrawBinding = 4, kScratchBinding = 5;                  // storage buffers
 constexpr int kUvBinding = 6, kMaterialBinding = 7, kTextureBinding = 8, kTexelBinding = 9; // storage buffers of a textured execution (textureCount > 0)
+constexpr int kAlphaCutoffBinding = 10; // storage buffer of an alpha-tested execution (alphaTest != 0): one uint32 cutoff code per draw
 constexpr int kDepthBinding = 0, kMotionBinding = 1, kNormalImageBinding = 2, kAlbedoBinding = 3, kSpecularBinding = 4;                                   // storage images
 struct PushConstants { uint32_t drawCount, triangleCount; };
 struct TexturedPushConstants { uint32_t drawCount, triangleCount, textureCount; }; // the optional third word: 0, or absent, is the untextured pass
+struct AlphaPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest; }; // the optional fourth word: 0, or absent, is the pass without the alpha test
 struct Draw { uint32_t firstIndex, indexCount, vertexOffset, transformIndex, albedo, specular; }; // albedo, specular: RGBA8 texels as they are stored
 struct MainPassMatrices { float model[16], mvp[16], mvpPrevious[16]; };                            // glm column-major (RenderFrontend.cpp:581-585)
 // material textures ("The sampling contract"): `texels` holds RGBA8 texels, R in the low byte, every texture's levels back to back and unpadded; level l is
@@ -24,6 +26,9 @@ struct Material { uint32_t albedoTexture, specularTexture; };       // per draw;
 constexpr uint32_t kNoTexture = 0xffffffffu;
 constexpr uint32_t kMaxTextureSize = 16384;
 constexpr uint64_t kMaxTexels = 1ull << 28;                         // what plrf_set_scene_textures accepts in total
+// the alpha test ("The alpha test contract"): a draw's cutoff code c, 0 = opaque; a fragment passes when its alpha code is >= c. The kernel uses min(word, 256):
+// a word above 255 discards every fragment of the draw
+constexpr uint32_t kAlphaCutoffOpaque = 0, kAlphaCutoffReference = 128, kAlphaCutoffDiscardAll = 256;
 static_assert(sizeof(Texture) == 16 && sizeof(Material) == 8, "texture buffer layouts");
 // the levels a width x height texture can have: floor(log2(max(width, height))) + 1
 constexpr uint32_t fullMipCount(uint32_t width, uint32_t height) {

@@ -144,6 +144,10 @@ int plrf_set_scene_textures(void* p, const plrf_scene_texture* textures, uint32_
         ((FramePipeline*)p)->setSceneTextures(t.empty() ? nullptr : t.data(), textureCount, meshUvs, meshCount, m.empty() ? nullptr : m.data(), drawCount);
     })
 }
+int plrf_set_scene_alpha_cutoffs(void* p, const uint32_t* cutoffs, uint32_t drawCount) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL(((FramePipeline*)p)->setSceneAlphaCutoffs(cutoffs, drawCount))
+}
 int plrf_get_prepass_raster_stats(void* p, plrf_prepass_raster_stats* out) {
     if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY_REFUSAL({

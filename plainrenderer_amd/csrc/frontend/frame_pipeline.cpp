@@ -1371,12 +1371,15 @@ void FramePipeline::renderDepthPrepass(const FrameRenderTargets& current) {
     exe.genericInfo.resources.storageBuffers = {StorageBufferResource(m_sceneMatrices.handle, true, pp::kTransformBinding), StorageBufferResource(m_scenePositions.handle, true, pp::kPositionBinding),
                                                 StorageBufferResource(m_sceneNormals.handle, true, pp::kNormalBinding), StorageBufferResource(m_sceneIndices.handle, true, pp::kIndexBinding),
                                                 StorageBufferResource(m_sceneDraws.handle, true, pp::kDrawBinding), StorageBufferResource(m_sceneScratch.handle, false, pp::kScratchBinding)};
-    const pp::TexturedPushConstants pc{m_sceneDrawCount, m_sceneTriangleCount, m_sceneTextureCount};
-    exe.pushConstants = dataToCharArray(&pc, m_sceneTextureCount ? sizeof(pc) : sizeof(pp::PushConstants)); // without textures: the 8-byte record
+    const bool alphaTested = m_sceneAlphaTested && m_sceneTextureCount;
+    const pp::AlphaPushConstants pc{m_sceneDrawCount, m_sceneTriangleCount, m_sceneTextureCount, alphaTested ? 1u : 0u};
+    // without textures: the 8-byte record; without a cutoff other than 0: the 12-byte one
+    exe.pushConstants = dataToCharArray(&pc, alphaTested ? sizeof(pc) : m_sceneTextureCount ? sizeof(pp::TexturedPushConstants) : sizeof(pp::PushConstants));
     if (m_sceneTextureCount) {
         auto& buffers = exe.genericInfo.resources.storageBuffers;
         buffers.push_back(StorageBufferResource(m_sceneUvs.handle, true, pp::kUvBinding)); buffers.push_back(StorageBufferResource(m_sceneMaterials.handle, true, pp::kMaterialBinding));
         buffers.push_back(StorageBufferResource(m_sceneTextures.handle, true, pp::kTextureBinding)); buffers.push_back(StorageBufferResource(m_sceneTexels.handle, true, pp::kTexelBinding));
+        if (alphaTested) buffers.push_back(StorageBufferResource(m_sceneAlphaCutoffs.handle, true, pp::kAlphaCutoffBinding));
     }
     m_be.setComputePassExecution(exe);
     m_sceneRecorded = true;
@@ -1403,7 +1406,12 @@ void FramePipeline::updateMainPassMatrices() {
 void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const SceneDraw* draws, uint32_t drawCount) {
     if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneMeshes: a band / tile pipeline cannot rasterise scene meshes (a partition would have to rasterise only its own rectangle)");
-    if (drawCount == 0) { m_sceneDrawCount = m_sceneTriangleCount = m_sceneTextureCount = 0; m_scenePreviousValid = m_sceneRecorded = false; m_sceneMeshVertexCounts.clear(); return; }
+    if (drawCount == 0) {
+        m_sceneDrawCount = m_sceneTriangleCount = m_sceneTextureCount = 0;
+        m_scenePreviousValid = m_sceneRecorded = m_sceneAlphaTested = false;
+        m_sceneMeshVertexCounts.clear();
+        return;
+    }
     const PackedScene packed = packSceneMeshes(meshes, meshCount, draws, drawCount); // validates everything before anything is changed
     if (!m_scenePassCreated) {
         ComputePassDescription d; // RenderFrontend.cpp:1717-1735
@@ -1424,12 +1432,13 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
     m_sceneDrawCount = drawCount; m_sceneTriangleCount = packed.triangleCount;
     m_sceneMeshVertexCounts = packed.meshVertexCounts;
     m_sceneTextureCount = 0; // the textures belonged to the scene that was replaced
+    m_sceneAlphaTested = false; // and so did the cutoffs
 }
 
 void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {
     if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneTextures: a band / tile pipeline cannot rasterise scene meshes");
-    if (textureCount == 0) { m_sceneTextureCount = 0; return; }
+    if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = false; return; }
     const PackedTextures packed = packSceneTextures(textures, textureCount, meshUvs, meshCount, materials, drawCount, m_sceneMeshVertexCounts.data(),
                                                     (uint32_t)m_sceneMeshVertexCounts.size(), m_sceneDrawCount); // validates everything before anything is changed
     auto fill = [&](SceneBuffer& b, const std::vector<uint32_t>& data) { fillCasterBuffer(b.handle, b.bytes, data.data(), data.size() * sizeof(uint32_t)); };
@@ -1438,6 +1447,16 @@ void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t text
     fill(m_sceneTextures, packed.textures);
     fill(m_sceneTexels, packed.texels);
     m_sceneTextureCount = textureCount;
+    m_sceneAlphaTested = false; // the cutoffs belonged to the materials that were replaced
+}
+
+void FramePipeline::setSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawCount) {
+    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneAlphaCutoffs: a band / tile pipeline cannot rasterise scene meshes");
+    if (drawCount == 0) { m_sceneAlphaTested = false; return; }
+    const PackedAlphaCutoffs packed = packSceneAlphaCutoffs(cutoffs, drawCount, m_sceneDrawCount, m_sceneTextureCount); // validates everything before anything is changed
+    fillCasterBuffer(m_sceneAlphaCutoffs.handle, m_sceneAlphaCutoffs.bytes, packed.cutoffs.data(), packed.cutoffs.size() * sizeof(uint32_t));
+    m_sceneAlphaTested = packed.tested;
 }
 
 void FramePipeline::setSceneMeshTransforms(const float* matrices16, uint32_t drawCount) {

@@ -348,6 +348,13 @@ struct PackedTextures {
 // sceneMeshVertexCounts / sceneDrawCount: of the scene the pipeline holds (sceneMeshCount 0: none). Throws FramePipelineRefusal.
 PackedTextures packSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials,
                                  uint32_t drawCount, const uint32_t* sceneMeshVertexCounts, uint32_t sceneMeshCount, uint32_t sceneDrawCount);
+// what setSceneAlphaCutoffs validates and packs, without a backend: binding 10 of an alpha-tested "depthPrepassRaster.comp", one cutoff code per draw
+struct PackedAlphaCutoffs {
+    std::vector<uint32_t> cutoffs;
+    bool tested = false; // a cutoff other than 0: only then the frame records the fourth push-constant word
+};
+// sceneDrawCount / sceneTextureCount: of the scene and the textures the pipeline holds. Throws FramePipelineRefusal.
+PackedAlphaCutoffs packSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawCount, uint32_t sceneDrawCount, uint32_t sceneTextureCount);
 // appends levels 1 .. of the full chain of a width x height level 0 (already the last `width * height` texels of `texels`): level l + 1 texel (x, y) per channel
 // is (a + b + c + d + 2) >> 2 of the level-l texels at (min(2x, W - 1) | min(2x + 1, W - 1), min(2y, H - 1) | min(2y + 1, H - 1))
 void appendMipChain(std::vector<uint32_t>& texels, uint32_t width, uint32_t height);
@@ -380,6 +387,12 @@ public:
     // too. Refusals: no scene, a mesh or draw count other than the scene's, a texture size of 0 or above 16384, too many mips, null texels, a material index out
     // of range, more than 2^28 texels, a non-finite UV are PLR_ERR_INVALID_ARGUMENT; a band / tile pipeline is PLR_ERR_UNSUPPORTED. A refused call changes nothing.
     void setSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount);
+    // alpha-tested cutouts for the scene and textures now set (DESIGN.md "Alpha-tested cutouts in the depth prepass"): one cutoff code 0 .. 255 per draw, 0 =
+    // opaque, 128 = the reference's alpha < 0.5 -> discard. From the next frame on, while a cutoff is not 0, the pass is recorded with the fourth push-constant word
+    // and binding 10, and a fragment whose sampled albedo alpha code is below its draw's cutoff is no fragment. Copied. drawCount 0 removes them; setSceneMeshes
+    // and setSceneTextures drop them too. Refusals: no scene, no textures, a count other than the scene's, null cutoffs, a value above 255 are
+    // PLR_ERR_INVALID_ARGUMENT; a band / tile pipeline is PLR_ERR_UNSUPPORTED. A refused call changes nothing.
+    void setSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawCount);
     // counters of the last frame's execution for the scene now set; waits for the GPU. Zero while no scene is set and before the first frame of a newly set scene.
     PrepassRasterStats prepassRasterStats();
     // RenderFrontend::setResolution (RenderFrontend.cpp:408-421): recorded, applied at the start of the next frame() (prepareNewFrame, :199-222). Every image and
@@ -500,6 +513,9 @@ private:
     uint32_t m_sceneTextureCount = 0;
     std::vector<uint32_t> m_sceneMeshVertexCounts;
     SceneBuffer m_sceneUvs, m_sceneMaterials, m_sceneTextures, m_sceneTexels;
+    // alpha cutoffs: created by the first setSceneAlphaCutoffs; not tested = the pass record without the fourth push-constant word
+    bool m_sceneAlphaTested = false;
+    SceneBuffer m_sceneAlphaCutoffs;
     std::vector<float> m_sceneModel, m_scenePreviousModel; // 16 floats per draw: what the next frame uses, what the last recorded frame used
 public:
     AtmosphereSettings atmosphereSettings;

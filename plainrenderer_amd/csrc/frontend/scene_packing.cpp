@@ -1,5 +1,6 @@
-// Validation and packing of scene meshes and their material textures for "depthPrepassRaster.comp" (FramePipeline::setSceneMeshes, setSceneTextures): host code
-// without a backend call, so that a stand-alone program can run it under a sanitizer (tools/scene_packing_check.cpp, tools/scene_texture_check.cpp).
+// Validation and packing of scene meshes, their material textures and their alpha cutoffs for "depthPrepassRaster.comp" (FramePipeline::setSceneMeshes,
+// setSceneTextures, setSceneAlphaCutoffs): host code without a backend call, so that a stand-alone program can run it under a sanitizer
+// (tools/scene_packing_check.cpp, tools/scene_texture_check.cpp, tools/scene_alpha_check.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -146,6 +147,23 @@ PackedTextures packSceneTextures(const SceneTexture* textures, uint32_t textureC
         out.texels.insert(out.texels.end(), tex.texels, tex.texels + given);
         if (tex.mipCount == 0) appendMipChain(out.texels, tex.width, tex.height);
     }
+    return out;
+}
+
+// everything is validated before anything is built
+PackedAlphaCutoffs packSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawCount, uint32_t sceneDrawCount, uint32_t sceneTextureCount) {
+    const std::string call = "setSceneAlphaCutoffs";
+    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
+    if (sceneDrawCount == 0) refuse("no scene set (plrf_set_scene_meshes comes first)");
+    if (sceneTextureCount == 0) refuse("no textures set (plrf_set_scene_textures comes first: the alpha of a fragment is its albedo sample)");
+    if (drawCount != sceneDrawCount) refuse("cutoff count " + std::to_string(drawCount) + " differs from the draw count " + std::to_string(sceneDrawCount) + " of the scene");
+    if (!cutoffs) refuse("cutoffs are null");
+    PackedAlphaCutoffs out;
+    for (uint32_t d = 0; d < drawCount; d++) {
+        if (cutoffs[d] > 255u) refuse("cutoff out of range: draw " + std::to_string(d) + " has " + std::to_string(cutoffs[d]) + ", a cutoff code is 0 (opaque) .. 255");
+        out.tested = out.tested || cutoffs[d] != plr::prepass::kAlphaCutoffOpaque;
+    }
+    out.cutoffs.assign(cutoffs, cutoffs + drawCount);
     return out;
 }
 

@@ -44,7 +44,7 @@
 //     finite number > 0 stores (0, 0). Both jitters come from the global UBO.
 //   albedo, specular: the two RGBA8 words of the winner's draw, or for a draw that names a texture the sampled texel (THE SAMPLING CONTRACT below).
 //   counters: submitted (triangles of all draws), clipped, drawn (sub-triangles), rejects (triangles and sub-triangles, as above).
-//   depthPrepass.frag's alpha test is left out - all meshes are opaque.
+//   depthPrepass.frag's alpha test (:27-30): THE ALPHA TEST CONTRACT below; without it all meshes are opaque.
 //
 // THE SAMPLING CONTRACT (DESIGN.md "Material textures in the depth prepass"; tests/prepass_texture_reference.py implements it independently, bit for bit). Only
 // an execution whose third push-constant word textureCount is > 0 samples, and only the albedo and specular words of a winner pixel change; visibility, depth,
@@ -66,7 +66,23 @@
 //     fx = Tu & 255, x1 = x0 + 1, both wrapped to [0, W) by a non-negative modulo (repeat); y0, fy, y1 likewise with v and H. Per channel
 //     S_l = (256 - fx)(256 - fy) c00 + fx (256 - fy) c10 + (256 - fx) fy c01 + fx fy c11; S = (256 - fw) S_L0 + fw S_L1 (<= 255 * 2^24: fits uint32); the stored
 //     code is (S + 2^23 - 1 + ((S >> 24) & 1)) >> 24, round half even. All four channels, alpha included; albedo is filtered in code space.
-//   Isotropic trilinear filtering stands in for the implementation-defined anisotropic sampler; there is no alpha test and no normal map.
+//   Isotropic trilinear filtering stands in for the implementation-defined anisotropic sampler; there is no normal map.
+//
+// THE ALPHA TEST CONTRACT (DESIGN.md "Alpha-tested cutouts in the depth prepass"; tests/prepass_alpha_reference.py implements it independently, bit for bit). Only an
+// execution whose fourth push-constant word alphaTest is != 0 tests (it needs textureCount > 0 and storage buffer 10 `alphaCutoffs`, one uint32 per draw).
+//   per-draw cutoff: draw d has the cutoff code c = min(alphaCutoffs[d], 256). c = 0 is opaque; the reference's alpha < 0.5 -> discard is c = 128 (a / 255 < 0.5 <=>
+//     a <= 127); a word above 255 gives c = 256, which no alpha code reaches: every fragment of the draw is discarded (255 keeps a = 255).
+//   alpha of a fragment: a fragment of triangle t at pixel (i, j) has the alpha code a(t, i, j) = bits 24 - 31 of exactly the albedo word the sampling contract
+//     yields for triangle t at that pixel: the same b at P, P_x, P_y from the ORIGINAL triangle, the same UV validity rule, level selection with g_mipBias, taps
+//     and round-half-even; for a draw whose albedo material word names no usable texture, bits 24 - 31 of the draw's constant albedo word. It depends on (t, i, j)
+//     only - not on the sub-triangle of the clipped fan that produced the fragment, nor on any other fragment.
+//   visibility: a pixel's winner is the maximum key over its fragments that pass coverage, the zf > 0 rule and a(t, i, j) >= c: one clause added to the visibility
+//     rule above, nothing else of it changes. A pixel whose fragments all fail is sky (depth 0, all images 0). Depth, motion, normal, albedo and specular of a
+//     winner are computed as before; consequently every winner pixel of a draw has a stored albedo.a >= c. The four counters do not depend on alpha: drawn still
+//     counts sub-triangles with a non-empty box.
+//   freedom for the kernel: the result is a maximum, so a kernel may skip the alpha evaluation of a fragment whose key is not above the cell's current value; the
+//     image does not change. (There is no counter of discarded fragments: it would forbid exactly that.)
+//   sunShadow.frag's alpha test is not part of this pass: shadow casters have no UVs or materials, and a cutout casts its quad's shadow.
 //
 // Two kernels. SET-UP: a lane per triangle finds its draw (block-wide prefix sum, LDS bisection), transforms, clips (the polygon lives in LDS, a column per lane),
 // projects, snaps, culls and boxes; the block's sub-triangles are appended through one 64-bit atomic per block to a dense array of 4-byte tile rectangles and an
@@ -77,7 +93,11 @@
 // Every tile scans every rectangle: no bins in this version. No global atomics on the targets. The tile kernel is a template over kTextured: the launcher picks
 // the instantiation by textureCount, and only the textured one holds the sampling code (the other is the kernel it was before textures, instruction for
 // instruction). Its resolve fetches the winner's vertices once for the three barycentric evaluations, samples nothing for a draw without a usable texture, and
-// computes every texel, UV and table address in 64 bits and checks it against its buffer before the load.
+// computes every texel, UV and table address in 64 bits and checks it against its buffer before the load. A third instantiation (kTextured && kAlphaTest, picked by
+// alphaTest) holds the alpha test: per step of 64 records every lane finds its record's draw, cutoff, texture, V_k and UVs - once per record, all 64 chains of
+// loads at once - and leaves them in LDS; a record of an opaque draw takes the path it takes in the other two; the lane path and the wave path of a tested record
+// queue the fragments whose key is above their cell (the early out), and the wave samples 64 queued fragments at a time, one per lane. That kernel takes all its
+// arguments from LDS. The other two instantiations and the set-up kernel are the kernels they were, instruction for instruction.
 #include <algorithm>
 
 #include "../backend.h"
@@ -327,6 +347,7 @@ struct TileParams {
     uint32_t capacity, triangleCount;
     int32_t width, height;
     TextureInputs tex; // a textured execution only (behind everything else: the untextured kernel's argument offsets stay)
+    const uint32_t* alphaCutoffs; // an alpha-tested execution only: tex.drawCount words
 };
 
 typedef unsigned long long Key;
@@ -336,26 +357,40 @@ PLR_DI void keepFragment(float zf, uint32_t t, Key* cell) {
     atomicMax(cell, ((Key)f2u(zf) << 32) | (Key)t);
 }
 
-// one fragment of sub-triangle r at pixel (px, py); tile: the block's 64 x 64 keys, (ox, oy) its first pixel
-PLR_DI void prepassFragment(const SetupRecord& r, uint32_t t, int64_t sx01, int64_t sy01, int64_t sx12, int64_t sy12, int64_t sx20, int64_t sy20, float fa, int px, int py, Key* tile, int ox, int oy) {
+// coverage and depth of sub-triangle r at pixel (px, py): false where the pixel centre is not covered
+PLR_DI bool fragmentDepth(const SetupRecord& r, int64_t sx01, int64_t sy01, int64_t sx12, int64_t sy12, int64_t sx20, int64_t sy20, float fa, int px, int py, float* zf) {
     const int64_t e01 = r.e01 + (int64_t)px * sx01 + (int64_t)py * sy01;
     const int64_t e12 = r.e12 + (int64_t)px * sx12 + (int64_t)py * sy12;
     const int64_t e20 = r.e20 + (int64_t)px * sx20 + (int64_t)py * sy20;
-    if (!rastercov::covered(e01, e12, e20, r.topLeft)) return;
+    if (!rastercov::covered(e01, e12, e20, r.topLeft)) return false;
     const float l1 = (float)e20 / fa, l2 = (float)e01 / fa;
-    keepFragment((r.z0 + l1 * r.dz1) + l2 * r.dz2, t, &tile[(py - oy) * kTileSize + (px - ox)]);
+    *zf = (r.z0 + l1 * r.dz1) + l2 * r.dz2;
+    return true;
+}
+
+// one fragment of sub-triangle r at pixel (px, py); tile: the block's 64 x 64 keys, (ox, oy) its first pixel
+PLR_DI void prepassFragment(const SetupRecord& r, uint32_t t, int64_t sx01, int64_t sy01, int64_t sx12, int64_t sy12, int64_t sx20, int64_t sy20, float fa, int px, int py, Key* tile, int ox, int oy) {
+    float zf;
+    if (!fragmentDepth(r, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, &zf)) return;
+    keepFragment(zf, t, &tile[(py - oy) * kTileSize + (px - ox)]);
 }
 
 // the same fragment for a sub-triangle whose snapped vertices span less than 2^15 sub-pixel units on both axes (kNarrowFlag): the contract's int64 values fit
 // int32 and 24-bit multiplies (sun_shadow_raster.hip)
-PLR_DI void prepassFragmentNarrow(const SetupRecord& r, uint32_t t, float fa, int px, int py, Key* tile, int ox, int oy) {
+PLR_DI bool fragmentDepthNarrow(const SetupRecord& r, float fa, int px, int py, float* zf) {
     const int32_t Px = px * 256 + 128, Py = py * 256 + 128;
     const int32_t e01 = __mul24(r.x1 - r.x0, Py - r.y0) - __mul24(r.y1 - r.y0, Px - r.x0);
     const int32_t e12 = __mul24(r.x2 - r.x1, Py - r.y1) - __mul24(r.y2 - r.y1, Px - r.x1);
     const int32_t e20 = __mul24(r.x0 - r.x2, Py - r.y2) - __mul24(r.y0 - r.y2, Px - r.x2);
-    if (!rastercov::covered(e01, e12, e20, r.topLeft)) return;
+    if (!rastercov::covered(e01, e12, e20, r.topLeft)) return false;
     const float l1 = (float)e20 / fa, l2 = (float)e01 / fa;
-    keepFragment((r.z0 + l1 * r.dz1) + l2 * r.dz2, t, &tile[(py - oy) * kTileSize + (px - ox)]);
+    *zf = (r.z0 + l1 * r.dz1) + l2 * r.dz2;
+    return true;
+}
+PLR_DI void prepassFragmentNarrow(const SetupRecord& r, uint32_t t, float fa, int px, int py, Key* tile, int ox, int oy) {
+    float zf;
+    if (!fragmentDepthNarrow(r, fa, px, py, &zf)) return;
+    keepFragment(zf, t, &tile[(py - oy) * kTileSize + (px - ox)]);
 }
 
 // E(i, j) = E(0, 0) + i (-256 dy) + j (256 dx) for the pixel centre (256 i + 128, 256 j + 128)
@@ -411,6 +446,7 @@ PLR_DI int wrapRepeat(int64_t t, int n) {
 struct TexelSums { uint32_t c[4]; }; // per channel: 16 bits of weight on 8 bits of code
 
 // the four taps of one level (dimensions w x h, first texel at `base`), weighted; every address in 64 bits and checked against texelCount before its load
+template <int kFirst = 0>
 PLR_DI TexelSums bilinearTaps(const uint32_t* texels, uint64_t texelCount, uint64_t base, int w, int h, double u, double v) {
     const int64_t Tu = (int64_t)__builtin_floor((u * (double)w - 0.5) * 256.0 + 0.5), Tv = (int64_t)__builtin_floor((v * (double)h - 0.5) * 256.0 + 0.5);
     const uint32_t fx = (uint32_t)(Tu & 255), fy = (uint32_t)(Tv & 255);
@@ -423,12 +459,14 @@ PLR_DI TexelSums bilinearTaps(const uint32_t* texels, uint64_t texelCount, uint6
     const uint32_t c00 = fetch(x0, y0), c10 = fetch(x1, y0), c01 = fetch(x0, y1), c11 = fetch(x1, y1);
     const uint32_t w00 = (256u - fx) * (256u - fy), w10 = fx * (256u - fy), w01 = (256u - fx) * fy, w11 = fx * fy;
     TexelSums out;
-    for (int k = 0; k < 4; k++)
+    for (int k = kFirst; k < 4; k++)
         out.c[k] = w00 * ((c00 >> (8 * k)) & 255u) + w10 * ((c10 >> (8 * k)) & 255u) + w01 * ((c01 >> (8 * k)) & 255u) + w11 * ((c11 >> (8 * k)) & 255u);
     return out;
 }
 
-// one trilinear sample of `texture`: (u, v) for the taps, (dudx, dvdx) and (dudy, dvdy) the raw forward differences
+// one trilinear sample of `texture`: (u, v) for the taps, (dudx, dvdx) and (dudy, dvdy) the raw forward differences. kFirst: the first channel computed - 3 is
+// the alpha-only sample of the coverage path, whose bits 24 - 31 are those of the full word because every channel is filtered by itself
+template <int kFirst = 0>
 PLR_DI uint32_t sampleTexture(const TextureInputs& tex, Texture texture, double u, double v, double dudx, double dvdx, double dudy, double dvdy, float mipBias) {
     const double w0 = (double)texture.width, h0 = (double)texture.height;
     const double axx = dudx * w0, axy = dvdx * h0, ayx = dudy * w0, ayy = dvdy * h0;
@@ -445,14 +483,14 @@ PLR_DI uint32_t sampleTexture(const TextureInputs& tex, Texture texture, double 
     uint64_t base = texture.texelOffset;
     for (int l = 0; l < L0; l++) base += (uint64_t)max(1u, texture.width >> l) * (uint64_t)max(1u, texture.height >> l);
     const int w = (int)max(1u, texture.width >> L0), h = (int)max(1u, texture.height >> L0);
-    const TexelSums s0 = bilinearTaps(tex.texels, tex.texelCount, base, w, h, u, v);
+    const TexelSums s0 = bilinearTaps<kFirst>(tex.texels, tex.texelCount, base, w, h, u, v);
     TexelSums s1{{0u, 0u, 0u, 0u}};
     if (fw != 0u) { // (with fw == 0 the upper level has no weight; with L1 == L0 it is the same level again)
         const uint64_t base1 = L1 == L0 ? base : base + (uint64_t)w * (uint64_t)h;
-        s1 = bilinearTaps(tex.texels, tex.texelCount, base1, (int)max(1u, texture.width >> L1), (int)max(1u, texture.height >> L1), u, v);
+        s1 = bilinearTaps<kFirst>(tex.texels, tex.texelCount, base1, (int)max(1u, texture.width >> L1), (int)max(1u, texture.height >> L1), u, v);
     }
     uint32_t word = 0u;
-    for (int k = 0; k < 4; k++) {
+    for (int k = kFirst; k < 4; k++) {
         const uint32_t S = (256u - fw) * s0.c[k] + fw * s1.c[k];
         word |= ((S + 0x7fffffu + ((S >> 24) & 1u)) >> 24) << (8 * k);
     }
@@ -467,6 +505,30 @@ PLR_DI bool usableTexture(const TextureInputs& tex, uint32_t index, Texture* out
     if (t.mipCount < 1u || t.mipCount > 32u - (uint32_t)__clz(max(t.width, t.height))) return false;
     *out = t;
     return true;
+}
+
+// the alpha test's V_k, UV fetch and sample point: resolvePixel<true>'s expressions, operation for operation, built from the same barycentricsAt, weighted and
+// clipComponent. (resolvePixel keeps its own text: with these three helpers factored out of it the compiler allocated the textured instantiation's registers
+// differently, and that kernel's instruction stream is held to its previous one. The tests compare the two paths bit for bit.)
+PLR_DI D3 clipXYW(const float* M, const float* q) {
+    return D3{(double)clipComponent(M, 0, q[0], q[1], q[2]), (double)clipComponent(M, 1, q[0], q[1], q[2]), (double)clipComponent(M, 3, q[0], q[1], q[2])};
+}
+PLR_DI void fetchUv(const TextureInputs& tex, uint64_t vertex, double* u, double* v) { // a vertex outside `uvs` has (0, 0)
+    const bool inside = vertex < tex.uvVertexCount;
+    *u = inside ? (double)tex.uvs[vertex * 2u] : 0.0;
+    *v = inside ? (double)tex.uvs[vertex * 2u + 1u] : 0.0;
+}
+struct UvSample { double u, v, dudx, dvdx, dudy, dvdy; }; // (u, v) validated for the taps, the forward differences raw
+PLR_DI UvSample uvSampleAt(D3 P, const double b[3], const D3 V[3], const double tu[3], const double tv[3], int x, int y, int width, int height) {
+    double bx[3], by[3];
+    barycentricsAt(D3{(double)(2 * (x + 1) + 1) / (double)width - 1.0, P.y, 1.0}, V, bx);
+    barycentricsAt(D3{P.x, (double)(2 * (y + 1) + 1) / (double)height - 1.0, 1.0}, V, by);
+    UvSample s;
+    s.u = weighted(b, tu[0], tu[1], tu[2]); s.v = weighted(b, tv[0], tv[1], tv[2]);
+    s.dudx = weighted(bx, tu[0], tu[1], tu[2]) - s.u; s.dvdx = weighted(bx, tv[0], tv[1], tv[2]) - s.v;
+    s.dudy = weighted(by, tu[0], tu[1], tu[2]) - s.u; s.dvdy = weighted(by, tv[0], tv[1], tv[2]) - s.v;
+    if (!(__builtin_fabs(s.u) < 1048576.0 && __builtin_fabs(s.v) < 1048576.0)) s.u = s.v = 0.0; // (a NaN fails the comparison)
+    return s;
 }
 
 // the winner's attributes at pixel (x, y): motion, normal and the draw's two material words (kTextured: the sampled texel where its material names a texture)
@@ -547,8 +609,130 @@ PLR_DI void resolvePixel(const TileParams& p, const TextureInputs& tex, uint32_t
     }
 }
 
-template <bool kTextured>
+// ---- the alpha test (the alpha test contract)
+// what the fragments of one record need, found once per record through origins[t].draw -> alphaCutoffs[draw]
+struct AlphaRecord {
+    uint32_t cutoff; // kAlphaCutoffOpaque: every fragment passes (an opaque draw, or a constant alpha >= c); kAlphaCutoffDiscardAll: none does; else the sample decides
+    Texture texture; // } of a sampled record only
+    uint32_t t;      // }
+    D3 V[3];         // }
+    double tu[3], tv[3];
+};
+constexpr uint32_t kAlphaRecordWords = 36;
+static_assert(sizeof(AlphaRecord) == kAlphaRecordWords * 4, "AlphaRecord is moved through LDS word by word");
+PLR_DI bool alphaSampled(uint32_t cutoff) { return cutoff != kAlphaCutoffOpaque && cutoff != kAlphaCutoffDiscardAll; }
+struct AlphaInputs { const uint32_t* cutoffs; float mipBias; };
+
+PLR_DI void alphaOfRecord(const TileParams& p, const TextureInputs& tex, const uint32_t* cutoffs, uint32_t t, AlphaRecord& a) {
+    a.cutoff = kAlphaCutoffOpaque;
+    if (t >= p.triangleCount) return; // (never: the set-up kernel wrote t)
+    const TriangleOrigin o = p.origins[t];
+    if (o.draw >= tex.drawCount) return; // (never: cutoffs, materials and draws hold drawCount entries)
+    const uint32_t c = min(cutoffs[o.draw], kAlphaCutoffDiscardAll);
+    if (c == kAlphaCutoffOpaque || c == kAlphaCutoffDiscardAll) { a.cutoff = c; return; }
+    const Draw draw = p.draws[o.draw];
+    if (!usableTexture(tex, tex.materials[o.draw].albedoTexture, &a.texture)) { // the draw's constant word decides for all its fragments
+        a.cutoff = (draw.albedo >> 24) >= c ? kAlphaCutoffOpaque : kAlphaCutoffDiscardAll;
+        return;
+    }
+    // the vertices are inside their buffers: the set-up kernel made a record of this triangle (resolvePixel relies on the same)
+    const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)o.local * 3u;
+    const float* mvp = p.transforms + (size_t)draw.transformIndex * 48u + 16u;
+    uint64_t vertex[3];
+    for (int k = 0; k < 3; k++) {
+        vertex[k] = (uint64_t)p.indices[at + k] + (uint64_t)draw.vertexOffset;
+        float pos[3];
+        for (int c3 = 0; c3 < 3; c3++) pos[c3] = p.positions[vertex[k] * 3u + c3];
+        a.V[k] = clipXYW(mvp, pos);
+    }
+    for (int k = 0; k < 3; k++) fetchUv(tex, vertex[k], &a.tu[k], &a.tv[k]);
+    a.cutoff = c;
+    a.t = t;
+}
+
+// a(t, i, j): bits 24 - 31 of the albedo word the resolve would store for this triangle at pixel (x, y) - the same functions in the same order
+PLR_DI uint32_t fragmentAlpha(const TextureInputs& tex, const AlphaRecord& a, float mipBias, int x, int y, int width, int height) {
+    const D3 P{(double)(2 * x + 1) / (double)width - 1.0, (double)(2 * y + 1) / (double)height - 1.0, 1.0};
+    double b[3];
+    barycentricsAt(P, a.V, b);
+    const UvSample uv = uvSampleAt(P, b, a.V, a.tu, a.tv, x, y, width, height);
+    return sampleTexture<3>(tex, a.texture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias) >> 24;
+}
+
+// THE ALPHA-TESTED SCAN. A sample costs far more than coverage, a stamp of a triangle's box or a lane's 4 x 4 box is seldom full, and the loads that lead to a
+// record's vertices depend on one another. So per step of 64 records every lane finds the alpha data of ITS record at once (one chain of loads per step, not
+// per record) and leaves it in LDS (`records`: word-major, a column per lane); the lane path and the wave path then only QUEUE their candidates - fragments that
+// passed coverage, zf > 0 and the early out - with the slot of their record (in LDS, `queue`), and the wave samples 64 candidates at a time, one per lane, and
+// what is left at the end of the step.
+struct Candidate { uint32_t xy; float zf; uint32_t slot; }; // x | y << 16 (the frame is at most 16384 wide and high); slot: the lane that holds the record
+constexpr uint32_t kCandidateSlots = 128;                   // fewer than 64 pending + at most 64 of one push
+
+struct AlphaScan {
+    Candidate* queue;                 // this wave's kCandidateSlots entries
+    uint32_t (*records)[64];          // this wave's kAlphaRecordWords x 64 words
+    const TextureInputs* tex;
+    float mipBias;
+    int width, height;
+    Key* tile;
+    int ox, oy;
+    uint32_t lane;
+    uint32_t pending;                 // (wave-uniform)
+
+    PLR_DI void store(const AlphaRecord& a) {
+        union { AlphaRecord r; uint32_t w[kAlphaRecordWords]; } u;
+        u.r = a;
+        for (uint32_t k = 0; k < kAlphaRecordWords; k++) records[k][lane] = u.w[k];
+    }
+    // A fragment whose key is not above its cell is dropped before the sample: the result is a maximum, so the image is the same (the plain read is a filter,
+    // the atomic decides)
+    PLR_DI void sample(uint32_t count) {
+        if (lane < count) {
+            const uint32_t xy = queue[lane].xy, slot = queue[lane].slot;
+            const float zf = queue[lane].zf;
+            union { AlphaRecord r; uint32_t w[kAlphaRecordWords]; } u;
+            for (uint32_t k = 0; k < kAlphaRecordWords; k++) u.w[k] = records[k][slot];
+            const int px = (int)(xy & 0xffffu), py = (int)(xy >> 16);
+            Key* cell = &tile[(py - oy) * kTileSize + (px - ox)];
+            const Key key = ((Key)f2u(zf) << 32) | (Key)u.r.t;
+            if (key > *cell && fragmentAlpha(*tex, u.r, mipBias, px, py, width, height) >= u.r.cutoff) atomicMax(cell, key);
+        }
+    }
+    // called by the whole wave: the lanes with `candidate` append theirs; a full wave of candidates is sampled at once
+    PLR_DI void push(bool candidate, int px, int py, float zf, uint32_t slot) {
+        const unsigned long long mask = __ballot(candidate);
+        if (mask == 0ull) return;
+        if (candidate) {
+            Candidate& c = queue[pending + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))];
+            c.xy = (uint32_t)px | ((uint32_t)py << 16); c.zf = zf; c.slot = slot;
+        }
+        pending += (uint32_t)__popcll(mask);
+        __builtin_amdgcn_wave_barrier(); // (one wave: its LDS operations execute in order)
+        if (pending >= 64u) {
+            sample(64u);
+            pending -= 64u;
+            uint32_t xy = 0u, slot = 0u;
+            float zf = 0.f;
+            if (lane < pending) { xy = queue[64u + lane].xy; zf = queue[64u + lane].zf; slot = queue[64u + lane].slot; }
+            __builtin_amdgcn_wave_barrier();
+            if (lane < pending) { queue[lane].xy = xy; queue[lane].zf = zf; queue[lane].slot = slot; }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    PLR_DI void flush() {
+        sample(pending);
+        pending = 0u;
+        __builtin_amdgcn_wave_barrier();
+    }
+    // is the fragment of sub-triangle r (of triangle t) at (px, py) a candidate?
+    PLR_DI bool candidateAt(const SetupRecord& r, uint32_t t, int64_t sx01, int64_t sy01, int64_t sx12, int64_t sy12, int64_t sx20, int64_t sy20, float fa, int px, int py, float* zf) const {
+        const bool covered = (r.topLeft & kNarrowFlag) ? fragmentDepthNarrow(r, fa, px, py, zf) : fragmentDepth(r, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, zf);
+        return covered && *zf > 0.f && (((Key)f2u(*zf) << 32) | (Key)t) > tile[(py - oy) * kTileSize + (px - ox)];
+    }
+};
+
+template <bool kTextured, bool kAlphaTest = false>
 __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
+    static_assert(kTextured || !kAlphaTest, "the alpha of a fragment is a texture sample");
     __shared__ Key tile[kTileSize * kTileSize];
     __shared__ uint32_t hitQueue[4][256]; // per wave: the entries of the current step that touch the tile
     const int tx = (int)blockIdx.x, ty = (int)blockIdx.y;
@@ -557,13 +741,23 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
     for (uint32_t i = threadIdx.x; i < (uint32_t)(kTileSize * kTileSize); i += 256u) tile[i] = 0ull;
     // the textured resolve takes its inputs from LDS: held in scalar registers from the kernel's entry they would be spilled across the scan, which needs them all
     __shared__ TextureInputs sharedTex;
+    __shared__ AlphaInputs sharedAlpha; // the alpha-tested scan's, for the same reason
+    __shared__ Candidate candidates[4][kCandidateSlots];           // } per wave (the alpha-tested kernel only): AlphaScan
+    __shared__ uint32_t alphaRecords[4][kAlphaRecordWords][64];    // }
     if constexpr (kTextured) {
         if (threadIdx.x == 0) sharedTex = p.tex;
     }
+    // the alpha-tested kernel takes ALL its arguments from LDS: its scan needs the resolve's buffers too, and held in scalar registers from the kernel's entry
+    // thirty of them were spilled
+    __shared__ TileParams sharedParams;
+    if constexpr (kAlphaTest) {
+        if (threadIdx.x == 0) { sharedAlpha = AlphaInputs{p.alphaCutoffs, p.global->mipBias}; sharedParams = p; }
+    }
     __syncthreads();
-    const uint32_t n = min(p.header->cursor, p.capacity);
-    const int tx1 = min(ox + kTileSize - 1, p.width - 1), ty1 = min(oy + kTileSize - 1, p.height - 1); // the tile's pixels inside the image
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.header->drawn = n;
+    const TileParams& q = *(kAlphaTest ? &sharedParams : &p);
+    const uint32_t n = min(q.header->cursor, q.capacity);
+    const int tx1 = min(ox + kTileSize - 1, q.width - 1), ty1 = min(oy + kTileSize - 1, q.height - 1); // the tile's pixels inside the image
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) q.header->drawn = n;
     // the scan of the shadow pass: a wave reads 256 rectangles per step (four per lane, one 16-byte load: the array is padded to that), queues the indices of
     // those that touch its tile in LDS and takes the queue 64 at a time, a record per lane
     uint32_t* queue = hitQueue[wave];
@@ -572,7 +766,7 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
     for (uint32_t base = wave * 256u; base < n; base += 1024u) {
         const uint32_t i0 = base + lane * 4u;
         uint4 rc = make_uint4(0u, 0u, 0u, 0u);
-        if (i0 < n) rc = *(const uint4*)(p.rects + i0);
+        if (i0 < n) rc = *(const uint4*)(q.rects + i0);
         const bool h0 = i0 < n && touches(rc.x), h1 = i0 + 1u < n && touches(rc.y), h2 = i0 + 2u < n && touches(rc.z), h3 = i0 + 3u < n && touches(rc.w);
         const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1), m2 = __ballot(h2), m3 = __ballot(h3);
         const uint32_t c0 = (uint32_t)__popcll(m0), c1 = c0 + (uint32_t)__popcll(m1), c2 = c1 + (uint32_t)__popcll(m2), total = c2 + (uint32_t)__popcll(m3);
@@ -587,13 +781,36 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
             int bx0 = 0, by0 = 0, bx1 = -1, by1 = -1;
             Record rr{};
             if (hit) {
-                rr = p.records[queue[k + lane]];
+                rr = q.records[queue[k + lane]];
                 bx0 = max((int)(rr.s.boxMin & 0xffffu), ox); by0 = max((int)(rr.s.boxMin >> 16), oy);
                 bx1 = min((int)(rr.s.boxMax & 0xffffu), tx1); by1 = min((int)(rr.s.boxMax >> 16), ty1);
                 hit = bx0 <= bx1 && by0 <= by1;
             }
             const bool small = hit && bx1 - bx0 < 4 && by1 - by0 < 4;
-            if (small) { // its lane walks the <= 16 pixels
+            uint32_t myCutoff = kAlphaCutoffOpaque; // (kAlphaTest: of this lane's record; opaque: the record takes the paths below as they are)
+            AlphaScan scan{candidates[wave], alphaRecords[wave], &sharedTex, 0.f, 0, 0, tile, ox, oy, lane, 0u};
+            if constexpr (kAlphaTest) {
+                scan.mipBias = sharedAlpha.mipBias; scan.width = q.width; scan.height = q.height;
+                if (hit) { // every lane's record at once: its draw's cutoff and, where the sample decides, its texture, V_k and UVs
+                    AlphaRecord a;
+                    alphaOfRecord(q, sharedTex, sharedAlpha.cutoffs, rr.t, a);
+                    myCutoff = a.cutoff;
+                    if (alphaSampled(a.cutoff)) scan.store(a);
+                }
+                __builtin_amdgcn_wave_barrier();
+                const bool laneTested = small && alphaSampled(myCutoff);
+                if (__ballot(laneTested)) { // the lane path of the sampled records: the <= 16 pixels of every lane's box in step, so that the candidates can be queued
+                    PLR_PREPASS_STEPS(rr.s); // (fa: a narrow record's area fits int32, so the int64 conversion gives prepassFragmentNarrow's value)
+                    for (int o = 0; o < 16; o++) {
+                        const int px = bx0 + (o & 3), py = by0 + (o >> 2);
+                        float zf = 0.f;
+                        const bool candidate = laneTested && px <= bx1 && py <= by1 && scan.candidateAt(rr.s, rr.t, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, &zf);
+                        scan.push(candidate, px, py, zf, lane);
+                    }
+                }
+            }
+            const bool untested = myCutoff == kAlphaCutoffOpaque;
+            if (small && untested) { // its lane walks the <= 16 pixels
                 const SetupRecord& r = rr.s;
                 if (r.topLeft & kNarrowFlag) {
                     const float fa = (float)(int32_t)r.area;
@@ -613,6 +830,22 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
                 const SetupRecord& u = ur.s;
                 const int lx0 = __builtin_amdgcn_readlane(bx0, src), ly0 = __builtin_amdgcn_readlane(by0, src);
                 const int lx1 = __builtin_amdgcn_readlane(bx1, src), ly1 = __builtin_amdgcn_readlane(by1, src);
+                if constexpr (kAlphaTest) {
+                    const uint32_t cutoff = (uint32_t)__builtin_amdgcn_readlane((int)myCutoff, src); // (wave-uniform)
+                    if (cutoff != kAlphaCutoffOpaque) {
+                        if (cutoff != kAlphaCutoffDiscardAll) { // the stamps queue their candidates with the slot of the record's lane
+                            PLR_PREPASS_STEPS(u);
+                            for (int sy = ly0; sy <= ly1; sy += 8)
+                                for (int sx = lx0; sx <= lx1; sx += 8) {
+                                    const int px = sx + (int)(lane & 7u), py = sy + (int)(lane >> 3);
+                                    float zf = 0.f;
+                                    const bool candidate = px <= lx1 && py <= ly1 && scan.candidateAt(u, ur.t, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, &zf);
+                                    scan.push(candidate, px, py, zf, (uint32_t)src);
+                                }
+                        }
+                        continue;
+                    }
+                }
                 if (u.topLeft & kNarrowFlag) { // (wave-uniform)
                     const float fa = (float)(int32_t)u.area;
                     for (int sy = ly0; sy <= ly1; sy += 8)
@@ -629,6 +862,7 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
                         }
                 }
             }
+            if constexpr (kAlphaTest) scan.flush(); // before the next step's records replace these
         }
         __builtin_amdgcn_wave_barrier();
     }
@@ -638,21 +872,21 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
     if constexpr (kTextured) tex = sharedTex;
     for (uint32_t i = threadIdx.x; i < (uint32_t)(kTileSize * kTileSize); i += 256u) {
         const int y = oy + (int)(i >> 6), x = ox + (int)(i & 63u);
-        if (y >= p.height || x >= p.width) continue;
+        if (y >= q.height || x >= q.width) continue;
         const Key key = tile[i];
         uint32_t motion = 0u, normal = 0u, albedo = 0u, specular = 0u;
         const uint32_t t = (uint32_t)key;
-        if (key != 0ull && t < p.triangleCount) resolvePixel<kTextured>(p, tex, t, x, y, &motion, &normal, &albedo, &specular);
-        const size_t at = (size_t)y * (size_t)p.width + (size_t)x;
-        p.depth[at] = u2f((uint32_t)(key >> 32));
-        p.motion[at] = motion; p.normal[at] = normal; p.albedo[at] = albedo; p.specular[at] = specular;
+        if (key != 0ull && t < q.triangleCount) resolvePixel<kTextured>(q, tex, t, x, y, &motion, &normal, &albedo, &specular);
+        const size_t at = (size_t)y * (size_t)q.width + (size_t)x;
+        q.depth[at] = u2f((uint32_t)(key >> 32));
+        q.motion[at] = motion; q.normal[at] = normal; q.albedo[at] = albedo; q.specular[at] = specular;
     }
 }
 
 static int launchDepthPrepassRaster(const PassCtx& c) {
     if (c.push.size() < sizeof(PushConstants)) return c.fail(-1, "depthPrepassRaster: push constants {drawCount, triangleCount} missing");
-    TexturedPushConstants pc{};
-    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0
+    AlphaPushConstants pc{};
+    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0; 12: alphaTest 0
     if (c.dispatch[0] != 1u || c.dispatch[1] != 1u || c.dispatch[2] != 1u || c.base[0] != 0u || c.base[1] != 0u)
         return c.fail(-1, "depthPrepassRaster: the dispatch is {1, 1, 1} (the launcher derives its grids from the push constants and the images)");
     if (pc.triangleCount > kMaxTriangles) return c.fail(-1, "depthPrepassRaster: triangleCount " + std::to_string(pc.triangleCount) + " exceeds 2^28");
@@ -671,6 +905,10 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
         if (int rc = c.needSbuf(kMaterialBinding, (size_t)pc.drawCount * sizeof(Material), "depthPrepassRaster materials {albedoTexture, specularTexture} per draw")) return rc;
         if (int rc = c.needSbuf(kTextureBinding, (size_t)pc.textureCount * sizeof(Texture), "depthPrepassRaster textures {texelOffset, width, height, mipCount}")) return rc;
         if (int rc = c.needSbuf(kTexelBinding, 0, "depthPrepassRaster texels (RGBA8, every texture's levels back to back)")) return rc;
+    }
+    if (pc.alphaTest) {
+        if (pc.textureCount == 0u) return c.fail(-1, "depthPrepassRaster: alphaTest is set and textureCount is 0 (the alpha of a fragment is its albedo sample: the alpha test needs textures)");
+        if (int rc = c.needSbuf(kAlphaCutoffBinding, (size_t)pc.drawCount * 4u, "depthPrepassRaster alphaCutoffs (one uint32 cutoff code per draw)")) return rc;
     }
     if (c.sbuf[kScratchBinding].readOnly) return c.fail(-4, "depthPrepassRaster: the scratch buffer (binding 5) is bound read-only");
     if (int rc = c.needStorage(kDepthBinding, F_D32, "depthPrepassRaster depth")) return rc;
@@ -693,6 +931,8 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
     if (pc.textureCount)
         for (int b : {kUvBinding, kMaterialBinding, kTextureBinding, kTexelBinding})
             if (c.sbuf[b].ptr == c.sbuf[kScratchBinding].ptr) return c.fail(-4, "depthPrepassRaster: the scratch buffer is also bound as an input");
+    if (pc.alphaTest && c.sbuf[kAlphaCutoffBinding].ptr == c.sbuf[kScratchBinding].ptr)
+        return c.fail(-4, "depthPrepassRaster: the scratch buffer is also bound as an input (binding 10, alphaCutoffs)");
 
     uint8_t* scratch = (uint8_t*)c.sbuf[kScratchBinding].ptr;
     if (hipMemsetAsync(scratch, 0, sizeof(ScratchHeader), c.stream) != hipSuccess) return c.fail(-2, "depthPrepassRaster: clearing the scratch header failed");
@@ -727,7 +967,11 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
         t.tex.textures = (const Texture*)c.sbuf[kTextureBinding].ptr; t.tex.texels = (const uint32_t*)c.sbuf[kTexelBinding].ptr;
         t.tex.uvVertexCount = c.sbuf[kUvBinding].size / 8u; t.tex.texelCount = c.sbuf[kTexelBinding].size / 4u;
         t.tex.drawCount = pc.drawCount; t.tex.textureCount = pc.textureCount;
-        depthPrepassTileKernel<true><<<tiles, 256, 0, c.stream>>>(t);
+        if (pc.alphaTest) {
+            t.alphaCutoffs = (const uint32_t*)c.sbuf[kAlphaCutoffBinding].ptr;
+            depthPrepassTileKernel<true, true><<<tiles, 256, 0, c.stream>>>(t);
+        } else
+            depthPrepassTileKernel<true><<<tiles, 256, 0, c.stream>>>(t);
     } else
         depthPrepassTileKernel<false><<<tiles, 256, 0, c.stream>>>(t);
     PLR_CHECK_LAUNCH(c);

@@ -66,6 +66,7 @@ class PlrfSceneDraw(C.Structure):
 
 
 NO_TEXTURE = 0xFFFFFFFF  # PLRF_NO_TEXTURE
+ALPHA_CUTOFF_REFERENCE = 128  # PLRF_ALPHA_CUTOFF_REFERENCE
 
 
 class PlrfSceneTexture(C.Structure):
@@ -348,6 +349,13 @@ class FramePipeline:
         for k, (albedo, specular) in enumerate(materials):
             m[k] = PlrfSceneMaterial(int(albedo), int(specular))
         self._check(self.lib.plrf_set_scene_textures(self.handle, t, C.c_uint32(len(textures)), u, C.c_uint32(len(uvs)), m, C.c_uint32(len(materials))))
+
+    def set_scene_alpha_cutoffs(self, cutoffs):
+        """one alpha cutoff code 0 .. 255 per draw of the scene (0: opaque, ALPHA_CUTOFF_REFERENCE = 128: the reference's alpha < 0.5 -> discard); needs textures.
+        Copied; from the next frame on. No cutoffs: they are removed"""
+        a = np.ascontiguousarray(cutoffs, np.uint32).reshape(-1)
+        self.lib.plrf_set_scene_alpha_cutoffs.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]
+        self._check(self.lib.plrf_set_scene_alpha_cutoffs(self.handle, a.ctypes.data_as(C.POINTER(C.c_uint32)) if a.size else None, C.c_uint32(a.size)))
 
     def prepass_raster_stats(self):
         """(triangles submitted, triangles clipped, sub-triangles drawn, rejects) of the last frame's execution; waits for the GPU"""

@@ -1,6 +1,6 @@
 """What the depth prepass costs as a compute pass ("depthPrepassRaster.comp", plrf_set_scene_meshes) in bench.py's 4K frame.
 
-    python tools/prepass_raster_cost.py [--out FILE] [--frames N] [--instances K] [--textured]
+    python tools/prepass_raster_cost.py [--out FILE] [--frames N] [--instances K] [--textured | --alpha]
 
 One process, one build. The scene is the instance set of tools/shadow_raster_cost.py: the three meshes of tests/shadow_raster_cases.py (box, uv_sphere, torus:
 1496 triangles) instanced K times (default 202: about 100 k triangles) over the view frustum in front of bench.py's camera, rasterised into the 3840 x 2160
@@ -9,6 +9,8 @@ counters and, from a host-side projection of the triangles the clip leaves uncha
 bounds the tile kernel). The same with every instance shrunk to 1 / 20, where the tile kernel's time is its scan of the rectangle list and its resolve.
 --textured: the same two scenes with material textures (plrf_set_scene_textures): every draw samples a 256 x 256 albedo and a 256 x 256 specular texture
 with full chains (two textures, shared by the draws) by the mesh generators' UVs; compare its tile times with a run without the option.
+--alpha: the --textured scenes with the alpha test (plrf_set_scene_alpha_cutoffs): every draw has cutoff 128 and the albedo texture's alpha is a 0 / 255
+checker in cells of 32 texels, so about half of each draw's fragments are discarded; compare its tile times with --textured of the same build.
 It also reports that a frame WITHOUT scene meshes records the passes and runs the general kernels it did before a scene was ever set.
 The report goes to stdout and to --out.
 """
@@ -47,11 +49,14 @@ def tile_hits(matrices, meshes, draws):
     return float(hits.mean()), int(hits.max()), int((hits > 0).sum())
 
 
-def scene_textures(draw_count):
-    """(textures, mesh_uvs, materials) for the three meshes of the instance set: a 256 x 256 albedo and a 256 x 256 specular texture, the host builds the chains"""
+def scene_textures(draw_count, alpha_checker=False):
+    """(textures, mesh_uvs, materials) for the three meshes of the instance set: a 256 x 256 albedo and a 256 x 256 specular texture, the host builds the chains.
+    alpha_checker: the albedo's alpha is 0 / 255 in cells of 32 x 32 texels instead of 255"""
     from plainrenderer_amd import meshes
     y, x = np.mgrid[0:256, 0:256].astype(np.uint32)
     albedo = ((x * 7 + y * 3) & 255) | (((x ^ y) & 255) << 8) | (((x * 5 + y * 11) & 255) << 16) | np.uint32(0xFF000000)
+    if alpha_checker:
+        albedo = (albedo & np.uint32(0x00FFFFFF)) | (np.where(((x >> 5) + (y >> 5)) & 1, 255, 0).astype(np.uint32) << np.uint32(24))
     specular = ((x + y) & 255) | (((x * 13) & 255) << 8) | (((y * 9) & 255) << 16) | np.uint32(0xFF000000)
     # the generators' UVs for the scene's meshes (tests/shadow_raster_cases.py mesh_scene: the same arguments, so the same vertices)
     uvs = [meshes.box((1.0, 1.5, 0.75), subdiv=4, with_uvs=True)[2], meshes.uv_sphere(1.25, segments=28, rings=14, with_uvs=True)[2],
@@ -82,6 +87,7 @@ def main():
     ap.add_argument("--frames", type=int, default=40)
     ap.add_argument("--instances", type=int, default=202)
     ap.add_argument("--textured", action="store_true")
+    ap.add_argument("--alpha", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
     import torch  # noqa: F401  (first: it brings its own HIP runtime)
@@ -95,7 +101,7 @@ def main():
     fp = FramePipeline(be, W, H, shadow_map_res=2048)
     _, cams, inputs = bench.build_scene(args, "cuda:0", W, H, None)
     inputs.upload(fp)
-    lines = ["# python tools/prepass_raster_cost.py%s: bench.py's scene at %d x %d, fast kernel set, %d frames per figure" % (" --textured" if a.textured else "", W, H, a.frames)]
+    lines = ["# python tools/prepass_raster_cost.py%s: bench.py's scene at %d x %d, fast kernel set, %d frames per figure" % (" --alpha" if a.alpha else " --textured" if a.textured else "", W, H, a.frames)]
     cursor = 1
     for i in range(args.warmup):
         fp.frame(cams[cursor + i], 1.0 / 60.0, 0.5)
@@ -110,8 +116,10 @@ def main():
         meshes = [pc.mesh_arrays(m, k != 0) for k, m in enumerate(raw)]
         scene_draws = [(m, t, *pc.material(d)) for d, (m, t) in enumerate(draws)]
         fp.set_scene_meshes(meshes, scene_draws)
-        if a.textured:
-            fp.set_scene_textures(*scene_textures(len(draws)))
+        if a.textured or a.alpha:
+            fp.set_scene_textures(*scene_textures(len(draws), alpha_checker=a.alpha))
+        if a.alpha:
+            fp.set_scene_alpha_cutoffs([128] * len(draws))
         times, _ = pass_times(be, fp, cams, cursor, a.frames)
         cursor += a.frames + 1
         submitted, clipped, drawn, rejects = fp.prepass_raster_stats()
