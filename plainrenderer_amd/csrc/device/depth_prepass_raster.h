@@ -4,7 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "sun_shadow_raster.h"
+#include "raster_record.h"
 
 namespace plr {
 namespace prepass {
@@ -38,8 +38,8 @@ constexpr uint32_t fullMipCount(uint32_t width, uint32_t height) {
 }
 static_assert(sizeof(Draw) == 24 && sizeof(MainPassMatrices) == 192, "pass buffer layouts");
 
-constexpr int kTileSize = sunraster::kTileSize;          // 64 x 64 64-bit keys: 32 KB of LDS per workgroup
-constexpr int kMaxResolution = sunraster::kMaxResolution;
+using rastercov::kTileSize;                              // 64 x 64 64-bit keys: 32 KB of LDS per workgroup
+using rastercov::kMaxResolution;
 constexpr uint32_t kMaxTriangles = 1u << 28;             // 6 sub-triangles each still count in 32 bits
 constexpr uint32_t kMaxSubTriangles = 6;                 // a triangle clipped by five planes has at most 8 vertices
 constexpr float kGuardNdc = 32.f;                        // the four side planes of the clip volume: |x|, |y| <= 32 w
@@ -58,7 +58,7 @@ static_assert(sizeof(ScratchHeader) == 64, "ScratchHeader layout");
 
 struct TriangleOrigin { uint32_t draw, local; };
 struct alignas(16) Record {
-    sunraster::SetupRecord s; // the sub-triangle with vertices 1 and 2 exchanged: A > 0, the shadow contract's record
+    rastercov::SetupRecord s; // the sub-triangle with vertices 1 and 2 exchanged: A > 0, the shadow contract's record
     uint32_t t;               // the triangle's number in submission order
     uint32_t pad[3];
 };

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "raster_record.h"
+
 namespace plr {
 namespace sunraster {
 
@@ -14,12 +16,14 @@ constexpr uint32_t kCascadeIndexConstant = 0;
 struct PushConstants { uint32_t drawCount, triangleCount; };
 struct Draw { uint32_t firstIndex, indexCount, vertexOffset, transformIndex; };
 
-constexpr int kTileSize = 64;          // pixels per tile edge: one workgroup, 4096 words of LDS
-constexpr int kMaxResolution = 16384;  // 256 tiles per axis: a tile rectangle is four bytes
-constexpr int kSubPixelBits = 8;
-constexpr float kGuardBandPixels = 1048576.f; // 2^20
-constexpr int32_t kNarrowSpan = 32768;        // a triangle whose snapped vertices span less than this on both axes: its edge functions and its area fit int32
-constexpr uint32_t kNarrowFlag = 8u;          // ... flagged in SetupRecord::topLeft
+// the contract's limits and the set-up record are the two rasterisers' (device/raster_record.h); this pass keeps its tile as 4096 words of LDS
+using rastercov::kGuardBandPixels;
+using rastercov::kMaxResolution;
+using rastercov::kNarrowFlag;
+using rastercov::kNarrowSpan;
+using rastercov::kSubPixelBits;
+using rastercov::kTileSize;
+using rastercov::SetupRecord;
 
 // scratch: header, then one 4-byte tile rectangle per surviving triangle (dense, for the tile kernel's scan), then one set-up record per surviving triangle
 struct alignas(8) ScratchHeader {
@@ -30,16 +34,6 @@ struct alignas(8) ScratchHeader {
     uint32_t pad[12];
 };
 static_assert(sizeof(ScratchHeader) == 64, "ScratchHeader layout");
-
-struct alignas(16) SetupRecord {
-    int32_t x0, y0, x1, y1, x2, y2;  // snapped vertices, 8 sub-pixel bits
-    uint32_t boxMin, boxMax;         // pixel box clipped to the map: x | y << 16, inclusive
-    int64_t e01, e12, e20;           // edge functions at the centre of pixel (0, 0)
-    int64_t area;                    // A > 0
-    float z0, dz1, dz2;              // z0, z1 - z0, z2 - z0
-    uint32_t topLeft;                // bit e: edge e (0 -> 1, 1 -> 2, 2 -> 0) is a top or a left edge; kNarrowFlag
-};
-static_assert(sizeof(SetupRecord) == 80, "SetupRecord layout");
 
 constexpr size_t rectOffset() { return sizeof(ScratchHeader); }
 constexpr size_t recordOffset(uint32_t triangleCount) { return sizeof(ScratchHeader) + (((size_t)triangleCount * 4u + 15u) & ~(size_t)15u); }

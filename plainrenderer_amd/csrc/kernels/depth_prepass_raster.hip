@@ -91,28 +91,29 @@
 // 8 x 8 stamps, in int32 where the triangle is narrow; LDS 64-bit atomic max. RESOLVE: behind the barrier a lane per pixel finds the winner's draw, fetches its
 // three vertices, evaluates the fp64 attributes and stores the five images, a wave per row segment of 64 four-byte texels (256 contiguous bytes per image).
 // Every tile scans every rectangle: no bins in this version. No global atomics on the targets. The tile kernel is a template over kTextured: the launcher picks
-// the instantiation by textureCount, and only the textured one holds the sampling code (the other is the kernel it was before textures, instruction for
-// instruction). Its resolve fetches the winner's vertices once for the three barycentric evaluations, samples nothing for a draw without a usable texture, and
-// computes every texel, UV and table address in 64 bits and checks it against its buffer before the load. A third instantiation (kTextured && kAlphaTest, picked by
-// alphaTest) holds the alpha test: per step of 64 records every lane finds its record's draw, cutoff, texture, V_k and UVs - once per record, all 64 chains of
-// loads at once - and leaves them in LDS; a record of an opaque draw takes the path it takes in the other two; the lane path and the wave path of a tested record
-// queue the fragments whose key is above their cell (the early out), and the wave samples 64 queued fragments at a time, one per lane. That kernel takes all its
-// arguments from LDS. The other two instantiations and the set-up kernel are the kernels they were, instruction for instruction.
+// the instantiation by textureCount, and only the textured one holds the sampling code. Its resolve fetches the winner's vertices once for the three barycentric
+// evaluations, samples nothing for a draw without a usable texture, and computes every texel, UV and table address in 64 bits and checks it against its buffer
+// before the load. A third instantiation (kTextured && kAlphaTest, picked by alphaTest) holds the alpha test: per step of 64 records every lane finds its
+// record's draw, cutoff, texture, V_k and UVs - once per record, all 64 chains of loads at once - and leaves them in LDS; a record of an opaque draw takes the path
+// it takes in the other two; the lane path and the wave path of a tested record queue the fragments whose key is above their cell (the early out), and the wave
+// samples 64 queued fragments at a time, one per lane. That kernel takes all its arguments from LDS.
+// The draw lookup and the step from three snapped vertices to a record are device/raster_setup.h's, the scan, the walk and a fragment's coverage and depth
+// device/raster_tile_walk.h's, both shared with "sunShadowRaster.comp"; this file holds the clip, the block's append, what becomes of a fragment (the key, the
+// alpha test's queue), the resolve and the launcher.
 #include <algorithm>
 
 #include "../backend.h"
 #include "../device/depth_prepass_raster.h"
 #include "../device/detmath.h"
-#include "../device/raster_coverage.h"
+#include "../device/raster_setup.h"
+#include "../device/raster_tile_walk.h"
 
 namespace plr {
 namespace prepass {
 
-using rastercov::edgeAt00;
-using rastercov::topOrLeft;
-using sunraster::kNarrowFlag;
-using sunraster::kNarrowSpan;
-using sunraster::SetupRecord;
+using rastercov::EdgeSteps;
+using rastercov::kNarrowFlag;
+using rastercov::SetupRecord;
 
 struct SetupParams {
     const float* transforms; const float* positions; const uint32_t* indices; const Draw* draws;
@@ -173,77 +174,23 @@ PLR_DI int setupSubTriangle(const float (*poly)[256], int k, uint32_t tid, int32
         ok = ok && f2u(poly[slot[v] * 4 + 3][tid]) != 0u;
     }
     if (!ok) return 1;
-    const int64_t area = (int64_t)(X[1] - X[0]) * (int64_t)(Y[2] - Y[0]) - (int64_t)(X[2] - X[0]) * (int64_t)(Y[1] - Y[0]);
-    if (area <= 0) return 0;
-    const int32_t xmin = min(X[0], min(X[1], X[2])), xmax = max(X[0], max(X[1], X[2]));
-    const int32_t ymin = min(Y[0], min(Y[1], Y[2])), ymax = max(Y[0], max(Y[1], Y[2]));
-    const int32_t ix0 = max(0, (xmin + 127) >> 8), ix1 = min(width - 1, (xmax - 128) >> 8);
-    const int32_t iy0 = max(0, (ymin + 127) >> 8), iy1 = min(height - 1, (ymax - 128) >> 8);
-    if (ix0 > ix1 || iy0 > iy1) return 0;
-    if (rec) {
-        SetupRecord& r = *rec;
-        r.x0 = X[0]; r.y0 = Y[0]; r.x1 = X[1]; r.y1 = Y[1]; r.x2 = X[2]; r.y2 = Y[2];
-        r.boxMin = (uint32_t)ix0 | ((uint32_t)iy0 << 16); r.boxMax = (uint32_t)ix1 | ((uint32_t)iy1 << 16);
-        r.e01 = edgeAt00(X[0], Y[0], X[1], Y[1]); r.e12 = edgeAt00(X[1], Y[1], X[2], Y[2]); r.e20 = edgeAt00(X[2], Y[2], X[0], Y[0]);
-        r.area = area;
-        r.z0 = z[0]; r.dz1 = z[1] - z[0]; r.dz2 = z[2] - z[0];
-        r.topLeft = (topOrLeft(X[1] - X[0], Y[1] - Y[0]) ? 1u : 0u) | (topOrLeft(X[2] - X[1], Y[2] - Y[1]) ? 2u : 0u) | (topOrLeft(X[0] - X[2], Y[0] - Y[2]) ? 4u : 0u);
-        if (xmax - xmin < kNarrowSpan && ymax - ymin < kNarrowSpan) r.topLeft |= kNarrowFlag;
-        *rect = (uint32_t)(ix0 >> 6) | ((uint32_t)(iy0 >> 6) << 8) | ((uint32_t)(ix1 >> 6) << 16) | ((uint32_t)(iy1 >> 6) << 24);
-    }
-    return 2;
+    return rastercov::setupTriangle(X, Y, z, width, height, rec, rect) ? 2 : 0;
 }
 
 __global__ __launch_bounds__(256) void depthPrepassSetupKernel(SetupParams p) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u, tid = threadIdx.x;
-    // the draw that holds triangle t, as in the shadow pass: the block walks the draws 256 at a time, a block-wide prefix sum of their triangle counts gives
-    // the chunk's boundaries in LDS and each lane bisects them
-    __shared__ uint32_t chunkEnd[256];
-    __shared__ uint32_t waveTotal[4];
     // the lane's polygon, [slot * 4 + component][thread]: planes 0, 2 and 4 write polyA (at most 4, 6, 8 vertices), the input and planes 1 and 3 polyB (3, 5, 7)
     __shared__ float polyA[32][256];
     __shared__ float polyB[28][256];
     const uint32_t wave = threadIdx.x >> 6;
-    const uint32_t lastOfBlock = min(blockIdx.x * 256u + 255u, p.triangleCount - 1u);
-    bool found = false;
-    uint32_t drawIndex = 0, local = 0, running = 0;
-    for (uint32_t chunk = 0; chunk < p.drawCount; chunk += 256u) {
-        const uint32_t d = chunk + threadIdx.x;
-        uint32_t sum = d < p.drawCount ? p.draws[d].indexCount / 3u : 0u;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)sum, off);
-            if ((int)lane >= off) sum += up;
-        }
-        if (lane == 63u) waveTotal[wave] = sum;
-        __syncthreads();
-        for (uint32_t w = 0; w < wave; w++) sum += waveTotal[w];
-        chunkEnd[threadIdx.x] = running + sum;
-        __syncthreads();
-        const uint32_t end = chunkEnd[255];
-        if (!found && t < p.triangleCount && t < end) {
-            uint32_t lo = 0, hi = 255; // the first k with t < chunkEnd[k]
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (t < chunkEnd[mid]) hi = mid; else lo = mid + 1u;
-            }
-            // (a raw record whose draws' triangle counts wrap 32 bits makes the boundaries non-monotone: a slot at or past drawCount is never loaded from)
-            if (chunk + lo < p.drawCount) {
-                found = true;
-                drawIndex = chunk + lo;
-                local = t - (lo ? chunkEnd[lo - 1u] : running);
-            }
-        }
-        running = end;
-        __syncthreads();
-        if (running > lastOfBlock) break; // (block-uniform) every triangle of the block has its draw
-    }
+    const rastercov::TriangleSlot found = rastercov::drawOfTriangle(p.draws, p.drawCount, p.triangleCount, t);
     uint32_t rejects = 0;
     bool clipped = false;
     int n = 0; // vertices of the clipped and projected polygon in polyA
-    if (found) {
-        p.origins[t] = TriangleOrigin{drawIndex, local};
-        const Draw draw = p.draws[drawIndex];
-        const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)local * 3u;
+    if (found.found) {
+        p.origins[t] = TriangleOrigin{found.draw, found.local};
+        const Draw draw = p.draws[found.draw];
+        const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)found.local * 3u;
         bool inBuffers = at + 3u <= (uint64_t)p.indexCount && draw.transformIndex < p.transformCount;
         uint64_t v[3] = {0, 0, 0};
         if (inBuffers)
@@ -277,7 +224,7 @@ __global__ __launch_bounds__(256) void depthPrepassSetupKernel(SetupParams p) {
                     const float x = polyA[i * 4 + 0][tid], y = polyA[i * 4 + 1][tid], z = polyA[i * 4 + 2][tid], w = polyA[i * 4 + 3][tid];
                     const float nx = x / w, ny = y / w, nz = z / w;
                     const float xf = (nx * 0.5f + 0.5f) * wf, yf = (ny * 0.5f + 0.5f) * hf;
-                    const bool ok = w > 0.f && fabsf(xf) < sunraster::kGuardBandPixels && fabsf(yf) < sunraster::kGuardBandPixels && fabsf(nz) < __builtin_inff();
+                    const bool ok = w > 0.f && fabsf(xf) < rastercov::kGuardBandPixels && fabsf(yf) < rastercov::kGuardBandPixels && fabsf(nz) < __builtin_inff();
                     polyA[i * 4 + 0][tid] = u2f(ok ? (uint32_t)(int32_t)__builtin_rintf(xf * 256.f) : 0u);
                     polyA[i * 4 + 1][tid] = u2f(ok ? (uint32_t)(int32_t)__builtin_rintf(yf * 256.f) : 0u);
                     polyA[i * 4 + 2][tid] = nz;
@@ -295,7 +242,7 @@ __global__ __launch_bounds__(256) void depthPrepassSetupKernel(SetupParams p) {
     }
     const uint32_t mine = (uint32_t)__popc(surviveMask);
     // one 64-bit atomic per block hands it a run of slots (the low word is the cursor) and counts its triangles (the high word); a lane appends 0 .. 6
-    // records, so the block's prefix sum is over counts
+    // records, so the block's prefix sum is over counts (the shadow pass appends one survivor per lane by ballot; neither form serves the other)
     __shared__ uint32_t waveSurvivors[4], blockFound, blockRejects, blockClipped, blockBase;
     if (threadIdx.x == 0) blockFound = blockRejects = blockClipped = 0u;
     uint32_t incl = mine;
@@ -305,7 +252,7 @@ __global__ __launch_bounds__(256) void depthPrepassSetupKernel(SetupParams p) {
     }
     if (lane == 63u) waveSurvivors[wave] = incl;
     __syncthreads();
-    const unsigned long long foundMask = __ballot(found), clippedMask = __ballot(clipped);
+    const unsigned long long foundMask = __ballot(found.found), clippedMask = __ballot(clipped);
     if (lane == 0) { atomicAdd(&blockFound, (uint32_t)__popcll(foundMask)); atomicAdd(&blockClipped, (uint32_t)__popcll(clippedMask)); }
     if (rejects) atomicAdd(&blockRejects, rejects);
     __syncthreads();
@@ -357,58 +304,6 @@ PLR_DI void keepFragment(float zf, uint32_t t, Key* cell) {
     atomicMax(cell, ((Key)f2u(zf) << 32) | (Key)t);
 }
 
-// coverage and depth of sub-triangle r at pixel (px, py): false where the pixel centre is not covered
-PLR_DI bool fragmentDepth(const SetupRecord& r, int64_t sx01, int64_t sy01, int64_t sx12, int64_t sy12, int64_t sx20, int64_t sy20, float fa, int px, int py, float* zf) {
-    const int64_t e01 = r.e01 + (int64_t)px * sx01 + (int64_t)py * sy01;
-    const int64_t e12 = r.e12 + (int64_t)px * sx12 + (int64_t)py * sy12;
-    const int64_t e20 = r.e20 + (int64_t)px * sx20 + (int64_t)py * sy20;
-    if (!rastercov::covered(e01, e12, e20, r.topLeft)) return false;
-    const float l1 = (float)e20 / fa, l2 = (float)e01 / fa;
-    *zf = (r.z0 + l1 * r.dz1) + l2 * r.dz2;
-    return true;
-}
-
-// one fragment of sub-triangle r at pixel (px, py); tile: the block's 64 x 64 keys, (ox, oy) its first pixel
-PLR_DI void prepassFragment(const SetupRecord& r, uint32_t t, int64_t sx01, int64_t sy01, int64_t sx12, int64_t sy12, int64_t sx20, int64_t sy20, float fa, int px, int py, Key* tile, int ox, int oy) {
-    float zf;
-    if (!fragmentDepth(r, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, &zf)) return;
-    keepFragment(zf, t, &tile[(py - oy) * kTileSize + (px - ox)]);
-}
-
-// the same fragment for a sub-triangle whose snapped vertices span less than 2^15 sub-pixel units on both axes (kNarrowFlag): the contract's int64 values fit
-// int32 and 24-bit multiplies (sun_shadow_raster.hip)
-PLR_DI bool fragmentDepthNarrow(const SetupRecord& r, float fa, int px, int py, float* zf) {
-    const int32_t Px = px * 256 + 128, Py = py * 256 + 128;
-    const int32_t e01 = __mul24(r.x1 - r.x0, Py - r.y0) - __mul24(r.y1 - r.y0, Px - r.x0);
-    const int32_t e12 = __mul24(r.x2 - r.x1, Py - r.y1) - __mul24(r.y2 - r.y1, Px - r.x1);
-    const int32_t e20 = __mul24(r.x0 - r.x2, Py - r.y2) - __mul24(r.y0 - r.y2, Px - r.x2);
-    if (!rastercov::covered(e01, e12, e20, r.topLeft)) return false;
-    const float l1 = (float)e20 / fa, l2 = (float)e01 / fa;
-    *zf = (r.z0 + l1 * r.dz1) + l2 * r.dz2;
-    return true;
-}
-PLR_DI void prepassFragmentNarrow(const SetupRecord& r, uint32_t t, float fa, int px, int py, Key* tile, int ox, int oy) {
-    float zf;
-    if (!fragmentDepthNarrow(r, fa, px, py, &zf)) return;
-    keepFragment(zf, t, &tile[(py - oy) * kTileSize + (px - ox)]);
-}
-
-// E(i, j) = E(0, 0) + i (-256 dy) + j (256 dx) for the pixel centre (256 i + 128, 256 j + 128)
-#define PLR_PREPASS_STEPS(r)                                                                                                                            \
-    const int64_t sx01 = -256ll * (int64_t)((r).y1 - (r).y0), sy01 = 256ll * (int64_t)((r).x1 - (r).x0);                                                \
-    const int64_t sx12 = -256ll * (int64_t)((r).y2 - (r).y1), sy12 = 256ll * (int64_t)((r).x2 - (r).x1);                                                \
-    const int64_t sx20 = -256ll * (int64_t)((r).y0 - (r).y2), sy20 = 256ll * (int64_t)((r).x0 - (r).x2);                                                \
-    const float fa = (float)(r).area
-
-// the record lane `src` holds, in every lane (src is wave-uniform)
-PLR_DI Record broadcastRecord(const Record& r, int src) {
-    union Words { Record rec; int w[sizeof(Record) / 4]; };
-    Words in, out;
-    in.rec = r;
-    for (size_t k = 0; k < sizeof(Record) / 4; k++) out.w[k] = __builtin_amdgcn_readlane(in.w[k], src);
-    return out.rec;
-}
-
 struct D3 { double x, y, z; };
 PLR_DI double det3(D3 a, D3 b, D3 c) { return (a.x * (b.y * c.z - b.z * c.y) - a.y * (b.x * c.z - b.z * c.x)) + a.z * (b.x * c.y - b.y * c.x); }
 PLR_DI double weighted(const double b[3], double a0, double a1, double a2) { return (b[0] * a0 + b[1] * a1) + b[2] * a2; }
@@ -428,7 +323,7 @@ PLR_DI uint32_t unorm8Half(float n) { // n * 0.5 + 0.5 under the image contract'
 }
 
 // ---- material textures (the sampling contract)
-// b of the same triangle at another point, by resolvePixel's formula
+// b of a triangle with the clip (x, y, w) V_k at the point P; s zero or non-finite: (1, 0, 0)
 PLR_DI void barycentricsAt(D3 P, const D3 V[3], double b[3]) {
     const double e0 = det3(P, V[1], V[2]), e1 = det3(P, V[2], V[0]), e2 = det3(P, V[0], V[1]);
     const double s = (e0 + e1) + e2;
@@ -507,9 +402,7 @@ PLR_DI bool usableTexture(const TextureInputs& tex, uint32_t index, Texture* out
     return true;
 }
 
-// the alpha test's V_k, UV fetch and sample point: resolvePixel<true>'s expressions, operation for operation, built from the same barycentricsAt, weighted and
-// clipComponent. (resolvePixel keeps its own text: with these three helpers factored out of it the compiler allocated the textured instantiation's registers
-// differently, and that kernel's instruction stream is held to its previous one. The tests compare the two paths bit for bit.)
+// V_k, the UV fetch and the sample point of the resolve and of the alpha test: one text, so a fragment's alpha is the alpha the resolve stores
 PLR_DI D3 clipXYW(const float* M, const float* q) {
     return D3{(double)clipComponent(M, 0, q[0], q[1], q[2]), (double)clipComponent(M, 1, q[0], q[1], q[2]), (double)clipComponent(M, 3, q[0], q[1], q[2])};
 }
@@ -546,16 +439,12 @@ PLR_DI void resolvePixel(const TileParams& p, const TextureInputs& tex, uint32_t
         const uint64_t v = (uint64_t)p.indices[at + k] + (uint64_t)draw.vertexOffset;
         vertex[k] = v;
         for (int c = 0; c < 3; c++) { pos[k][c] = p.positions[v * 3u + c]; nrm[k][c] = p.normals[v * 3u + c]; }
-        V[k] = D3{(double)clipComponent(mvp, 0, pos[k][0], pos[k][1], pos[k][2]), (double)clipComponent(mvp, 1, pos[k][0], pos[k][1], pos[k][2]),
-                  (double)clipComponent(mvp, 3, pos[k][0], pos[k][1], pos[k][2])};
-        prev[k] = D3{(double)clipComponent(mvpPrevious, 0, pos[k][0], pos[k][1], pos[k][2]), (double)clipComponent(mvpPrevious, 1, pos[k][0], pos[k][1], pos[k][2]),
-                     (double)clipComponent(mvpPrevious, 3, pos[k][0], pos[k][1], pos[k][2])};
+        V[k] = clipXYW(mvp, pos[k]);
+        prev[k] = clipXYW(mvpPrevious, pos[k]);
     }
     const D3 P{(double)(2 * x + 1) / (double)p.width - 1.0, (double)(2 * y + 1) / (double)p.height - 1.0, 1.0};
-    const double e0 = det3(P, V[1], V[2]), e1 = det3(P, V[2], V[0]), e2 = det3(P, V[0], V[1]);
-    const double s = (e0 + e1) + e2;
-    double b[3] = {1.0, 0.0, 0.0};
-    if (s != 0.0 && __builtin_fabs(s) < __builtin_inf()) { b[0] = e0 / s; b[1] = e1 / s; b[2] = e2 / s; }
+    double b[3];
+    barycentricsAt(P, V, b);
     // normal
     D3 face{0.0, 0.0, 0.0};
     {
@@ -591,21 +480,11 @@ PLR_DI void resolvePixel(const TileParams& p, const TextureInputs& tex, uint32_t
         const bool sampleAlbedo = usableTexture(tex, material.albedoTexture, &albedoTexture), sampleSpecular = usableTexture(tex, material.specularTexture, &specularTexture);
         if (!sampleAlbedo && !sampleSpecular) return;
         double tu[3], tv[3];
-        for (int k = 0; k < 3; k++) {
-            const bool inside = vertex[k] < tex.uvVertexCount;
-            tu[k] = inside ? (double)tex.uvs[vertex[k] * 2u] : 0.0;
-            tv[k] = inside ? (double)tex.uvs[vertex[k] * 2u + 1u] : 0.0;
-        }
-        double bx[3], by[3];
-        barycentricsAt(D3{(double)(2 * (x + 1) + 1) / (double)p.width - 1.0, P.y, 1.0}, V, bx);
-        barycentricsAt(D3{P.x, (double)(2 * (y + 1) + 1) / (double)p.height - 1.0, 1.0}, V, by);
-        double u = weighted(b, tu[0], tu[1], tu[2]), v = weighted(b, tv[0], tv[1], tv[2]);
-        const double dudx = weighted(bx, tu[0], tu[1], tu[2]) - u, dvdx = weighted(bx, tv[0], tv[1], tv[2]) - v;
-        const double dudy = weighted(by, tu[0], tu[1], tu[2]) - u, dvdy = weighted(by, tv[0], tv[1], tv[2]) - v;
-        if (!(__builtin_fabs(u) < 1048576.0 && __builtin_fabs(v) < 1048576.0)) u = v = 0.0; // (a NaN fails the comparison)
+        for (int k = 0; k < 3; k++) fetchUv(tex, vertex[k], &tu[k], &tv[k]);
+        const UvSample uv = uvSampleAt(P, b, V, tu, tv, x, y, p.width, p.height);
         const float mipBias = p.global->mipBias;
-        if (sampleAlbedo) *albedo = sampleTexture(tex, albedoTexture, u, v, dudx, dvdx, dudy, dvdy, mipBias);
-        if (sampleSpecular) *specular = sampleTexture(tex, specularTexture, u, v, dudx, dvdx, dudy, dvdy, mipBias);
+        if (sampleAlbedo) *albedo = sampleTexture(tex, albedoTexture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias);
+        if (sampleSpecular) *specular = sampleTexture(tex, specularTexture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias);
     }
 }
 
@@ -723,11 +602,70 @@ struct AlphaScan {
         pending = 0u;
         __builtin_amdgcn_wave_barrier();
     }
-    // is the fragment of sub-triangle r (of triangle t) at (px, py) a candidate?
-    PLR_DI bool candidateAt(const SetupRecord& r, uint32_t t, int64_t sx01, int64_t sy01, int64_t sx12, int64_t sy12, int64_t sx20, int64_t sy20, float fa, int px, int py, float* zf) const {
-        const bool covered = (r.topLeft & kNarrowFlag) ? fragmentDepthNarrow(r, fa, px, py, zf) : fragmentDepth(r, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, zf);
-        return covered && *zf > 0.f && (((Key)f2u(*zf) << 32) | (Key)t) > tile[(py - oy) * kTileSize + (px - ox)];
+    // is a covered fragment of triangle t with depth zf at (px, py) a candidate: kept by the zf > 0 rule and above its cell (the early out)?
+    PLR_DI bool above(uint32_t t, int px, int py, float zf) const { return zf > 0.f && (((Key)f2u(zf) << 32) | (Key)t) > tile[(py - oy) * kTileSize + (px - ox)]; }
+};
+
+// what becomes of a fragment without the alpha test: the pixel's key, by 64-bit maximum. tile: the block's 64 x 64 keys, (ox, oy) its first pixel
+struct KeyWalk : rastercov::PlainWalk {
+    Key* tile;
+    int ox, oy;
+    static PLR_DI const SetupRecord& setup(const Record& r) { return r.s; }
+    template <class D> PLR_DI void fragment(const Record& r, int, int px, int py, D&& depthAt) {
+        float zf;
+        if (depthAt(&zf)) keepFragment(zf, r.t, &tile[(py - oy) * kTileSize + (px - ox)]);
     }
+};
+
+// ... and with the alpha test, through all the hooks of rastercov::rasteriseTile: a fragment of an opaque draw's record goes KeyWalk's way, one of a discarded
+// draw's nowhere, and the candidates of a sampled record go into AlphaScan's queue
+struct AlphaWalk {
+    AlphaScan scan;
+    const TileParams* q;
+    const AlphaInputs* inputs;
+    uint32_t myCutoff;    // of this lane's record
+    uint32_t stampCutoff; // (wave-uniform) of the record the wave stamps; opaque outside the stamp path
+
+    static PLR_DI const SetupRecord& setup(const Record& r) { return r.s; }
+    // every lane's record at once: its draw's cutoff and, where the sample decides, its texture, V_k and UVs. Then the lane path of the sampled records: the <= 16
+    // pixels of every lane's box in step, so that the candidates can be queued
+    PLR_DI void beginStep(const Record& rr, bool hit, bool small, int bx0, int by0, int bx1, int by1) {
+        scan.mipBias = inputs->mipBias; scan.width = q->width; scan.height = q->height;
+        myCutoff = stampCutoff = kAlphaCutoffOpaque;
+        if (hit) {
+            AlphaRecord a;
+            alphaOfRecord(*q, *scan.tex, inputs->cutoffs, rr.t, a);
+            myCutoff = a.cutoff;
+            if (alphaSampled(a.cutoff)) scan.store(a);
+        }
+        __builtin_amdgcn_wave_barrier();
+        const bool laneTested = small && alphaSampled(myCutoff);
+        if (__ballot(laneTested)) {
+            const EdgeSteps steps(rr.s); // (fa: a narrow record's area fits int32, so the int64 conversion gives the int32 one's value)
+            for (int o = 0; o < 16; o++) {
+                const int px = bx0 + (o & 3), py = by0 + (o >> 2);
+                float zf = 0.f;
+                const bool candidate = laneTested && px <= bx1 && py <= by1 &&
+                                       ((rr.s.topLeft & kNarrowFlag) ? rastercov::fragmentDepthNarrow(rr.s, steps.fa, px, py, &zf) : rastercov::fragmentDepth(rr.s, steps, px, py, &zf)) &&
+                                       scan.above(rr.t, px, py, zf);
+                scan.push(candidate, px, py, zf, scan.lane);
+            }
+        }
+    }
+    PLR_DI bool lanePath() const { return myCutoff == kAlphaCutoffOpaque; }
+    PLR_DI bool beginStamps(int src) {
+        stampCutoff = (uint32_t)__builtin_amdgcn_readlane((int)myCutoff, src);
+        return stampCutoff != kAlphaCutoffDiscardAll;
+    }
+    // the stamps of a sampled record queue their candidates with the slot of the record's lane (the whole wave calls)
+    template <class D> PLR_DI void fragment(const Record& r, int slot, int px, int py, D&& depthAt) {
+        float zf = 0.f;
+        if (stampCutoff == kAlphaCutoffOpaque) {
+            if (depthAt(&zf)) keepFragment(zf, r.t, &scan.tile[(py - scan.oy) * kTileSize + (px - scan.ox)]);
+        } else
+            scan.push(depthAt(&zf) && scan.above(r.t, px, py, zf), px, py, zf, (uint32_t)slot);
+    }
+    PLR_DI void endStep() { scan.flush(); } // before the next step's records replace these
 };
 
 template <bool kTextured, bool kAlphaTest = false>
@@ -756,115 +694,14 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
     __syncthreads();
     const TileParams& q = *(kAlphaTest ? &sharedParams : &p);
     const uint32_t n = min(q.header->cursor, q.capacity);
-    const int tx1 = min(ox + kTileSize - 1, q.width - 1), ty1 = min(oy + kTileSize - 1, q.height - 1); // the tile's pixels inside the image
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) q.header->drawn = n;
-    // the scan of the shadow pass: a wave reads 256 rectangles per step (four per lane, one 16-byte load: the array is padded to that), queues the indices of
-    // those that touch its tile in LDS and takes the queue 64 at a time, a record per lane
-    uint32_t* queue = hitQueue[wave];
-    const unsigned long long lanesBelow = (1ull << lane) - 1ull;
-    auto touches = [&](uint32_t rc) { return (int)(rc & 255u) <= tx && tx <= (int)((rc >> 16) & 255u) && (int)((rc >> 8) & 255u) <= ty && ty <= (int)(rc >> 24); };
-    for (uint32_t base = wave * 256u; base < n; base += 1024u) {
-        const uint32_t i0 = base + lane * 4u;
-        uint4 rc = make_uint4(0u, 0u, 0u, 0u);
-        if (i0 < n) rc = *(const uint4*)(q.rects + i0);
-        const bool h0 = i0 < n && touches(rc.x), h1 = i0 + 1u < n && touches(rc.y), h2 = i0 + 2u < n && touches(rc.z), h3 = i0 + 3u < n && touches(rc.w);
-        const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1), m2 = __ballot(h2), m3 = __ballot(h3);
-        const uint32_t c0 = (uint32_t)__popcll(m0), c1 = c0 + (uint32_t)__popcll(m1), c2 = c1 + (uint32_t)__popcll(m2), total = c2 + (uint32_t)__popcll(m3);
-        if (total == 0u) continue;
-        if (h0) queue[(uint32_t)__popcll(m0 & lanesBelow)] = i0;
-        if (h1) queue[c0 + (uint32_t)__popcll(m1 & lanesBelow)] = i0 + 1u;
-        if (h2) queue[c1 + (uint32_t)__popcll(m2 & lanesBelow)] = i0 + 2u;
-        if (h3) queue[c2 + (uint32_t)__popcll(m3 & lanesBelow)] = i0 + 3u;
-        __builtin_amdgcn_wave_barrier(); // (one wave: its LDS operations execute in order)
-        for (uint32_t k = 0; k < total; k += 64u) {
-            bool hit = k + lane < total;
-            int bx0 = 0, by0 = 0, bx1 = -1, by1 = -1;
-            Record rr{};
-            if (hit) {
-                rr = q.records[queue[k + lane]];
-                bx0 = max((int)(rr.s.boxMin & 0xffffu), ox); by0 = max((int)(rr.s.boxMin >> 16), oy);
-                bx1 = min((int)(rr.s.boxMax & 0xffffu), tx1); by1 = min((int)(rr.s.boxMax >> 16), ty1);
-                hit = bx0 <= bx1 && by0 <= by1;
-            }
-            const bool small = hit && bx1 - bx0 < 4 && by1 - by0 < 4;
-            uint32_t myCutoff = kAlphaCutoffOpaque; // (kAlphaTest: of this lane's record; opaque: the record takes the paths below as they are)
-            AlphaScan scan{candidates[wave], alphaRecords[wave], &sharedTex, 0.f, 0, 0, tile, ox, oy, lane, 0u};
-            if constexpr (kAlphaTest) {
-                scan.mipBias = sharedAlpha.mipBias; scan.width = q.width; scan.height = q.height;
-                if (hit) { // every lane's record at once: its draw's cutoff and, where the sample decides, its texture, V_k and UVs
-                    AlphaRecord a;
-                    alphaOfRecord(q, sharedTex, sharedAlpha.cutoffs, rr.t, a);
-                    myCutoff = a.cutoff;
-                    if (alphaSampled(a.cutoff)) scan.store(a);
-                }
-                __builtin_amdgcn_wave_barrier();
-                const bool laneTested = small && alphaSampled(myCutoff);
-                if (__ballot(laneTested)) { // the lane path of the sampled records: the <= 16 pixels of every lane's box in step, so that the candidates can be queued
-                    PLR_PREPASS_STEPS(rr.s); // (fa: a narrow record's area fits int32, so the int64 conversion gives prepassFragmentNarrow's value)
-                    for (int o = 0; o < 16; o++) {
-                        const int px = bx0 + (o & 3), py = by0 + (o >> 2);
-                        float zf = 0.f;
-                        const bool candidate = laneTested && px <= bx1 && py <= by1 && scan.candidateAt(rr.s, rr.t, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, &zf);
-                        scan.push(candidate, px, py, zf, lane);
-                    }
-                }
-            }
-            const bool untested = myCutoff == kAlphaCutoffOpaque;
-            if (small && untested) { // its lane walks the <= 16 pixels
-                const SetupRecord& r = rr.s;
-                if (r.topLeft & kNarrowFlag) {
-                    const float fa = (float)(int32_t)r.area;
-                    for (int py = by0; py <= by1; py++)
-                        for (int px = bx0; px <= bx1; px++) prepassFragmentNarrow(r, rr.t, fa, px, py, tile, ox, oy);
-                } else {
-                    PLR_PREPASS_STEPS(r);
-                    for (int py = by0; py <= by1; py++)
-                        for (int px = bx0; px <= bx1; px++) prepassFragment(r, rr.t, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, tile, ox, oy);
-                }
-            }
-            unsigned long long large = __ballot(hit && !small);
-            while (large) { // the whole wave walks the box in 8 x 8 stamps, with the record broadcast from the lane that holds it
-                const int src = __ffsll((long long)large) - 1;
-                large &= large - 1ull;
-                const Record ur = broadcastRecord(rr, src);
-                const SetupRecord& u = ur.s;
-                const int lx0 = __builtin_amdgcn_readlane(bx0, src), ly0 = __builtin_amdgcn_readlane(by0, src);
-                const int lx1 = __builtin_amdgcn_readlane(bx1, src), ly1 = __builtin_amdgcn_readlane(by1, src);
-                if constexpr (kAlphaTest) {
-                    const uint32_t cutoff = (uint32_t)__builtin_amdgcn_readlane((int)myCutoff, src); // (wave-uniform)
-                    if (cutoff != kAlphaCutoffOpaque) {
-                        if (cutoff != kAlphaCutoffDiscardAll) { // the stamps queue their candidates with the slot of the record's lane
-                            PLR_PREPASS_STEPS(u);
-                            for (int sy = ly0; sy <= ly1; sy += 8)
-                                for (int sx = lx0; sx <= lx1; sx += 8) {
-                                    const int px = sx + (int)(lane & 7u), py = sy + (int)(lane >> 3);
-                                    float zf = 0.f;
-                                    const bool candidate = px <= lx1 && py <= ly1 && scan.candidateAt(u, ur.t, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, &zf);
-                                    scan.push(candidate, px, py, zf, (uint32_t)src);
-                                }
-                        }
-                        continue;
-                    }
-                }
-                if (u.topLeft & kNarrowFlag) { // (wave-uniform)
-                    const float fa = (float)(int32_t)u.area;
-                    for (int sy = ly0; sy <= ly1; sy += 8)
-                        for (int sx = lx0; sx <= lx1; sx += 8) {
-                            const int px = sx + (int)(lane & 7u), py = sy + (int)(lane >> 3);
-                            if (px <= lx1 && py <= ly1) prepassFragmentNarrow(u, ur.t, fa, px, py, tile, ox, oy);
-                        }
-                } else {
-                    PLR_PREPASS_STEPS(u);
-                    for (int sy = ly0; sy <= ly1; sy += 8)
-                        for (int sx = lx0; sx <= lx1; sx += 8) {
-                            const int px = sx + (int)(lane & 7u), py = sy + (int)(lane >> 3);
-                            if (px <= lx1 && py <= ly1) prepassFragment(u, ur.t, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, tile, ox, oy);
-                        }
-                }
-            }
-            if constexpr (kAlphaTest) scan.flush(); // before the next step's records replace these
-        }
-        __builtin_amdgcn_wave_barrier();
+    const rastercov::TileWindow window{tx, ty, ox, oy, min(ox + kTileSize - 1, q.width - 1), min(oy + kTileSize - 1, q.height - 1)};
+    if constexpr (kAlphaTest) {
+        AlphaWalk walk{AlphaScan{candidates[wave], alphaRecords[wave], &sharedTex, 0.f, 0, 0, tile, ox, oy, lane, 0u}, &q, &sharedAlpha, kAlphaCutoffOpaque, kAlphaCutoffOpaque};
+        rastercov::rasteriseTile(q.rects, q.records, n, window, hitQueue[wave], walk);
+    } else {
+        KeyWalk walk{{}, tile, ox, oy};
+        rastercov::rasteriseTile(q.rects, q.records, n, window, hitQueue[wave], walk);
     }
     __syncthreads();
     // resolve: a lane per pixel, a wave per tile row - 64 four-byte texels, 256 contiguous bytes of every image per store instruction

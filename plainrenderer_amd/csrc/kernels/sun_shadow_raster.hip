@@ -28,15 +28,18 @@
 //     written by every execution: the clear is part of the pass.
 //   sunShadow.frag's alpha test is left out - casters are opaque: its anisotropic repeat sampler is implementation-defined and material textures are no input here.
 //
-// Two kernels. SET-UP: a lane per triangle transforms, snaps, culls and clips; survivors are appended through a cursor (one atomic per block) to a dense array of 4-byte tile rectangles
-// and an array of set-up records (order free: the result is a maximum). TILES: a 256-thread block per 64 x 64 tile keeps the tile as 4096 words of LDS; each wave
-// reads 256 rectangles per step and queues those that touch its tile; a hit whose box inside the tile is at most 4 x 4 pixels is rasterised by its lane, larger ones by the whole wave in 8 x 8 stamps;
-// LDS atomic max; the block then stores its tile as Depth16 rows. Every tile scans every rectangle: no bins in this version.
+// Two kernels. SET-UP: a lane per triangle finds its draw, transforms, snaps, culls and boxes; survivors are appended through a cursor (one atomic per block) to a dense
+// array of 4-byte tile rectangles and an array of set-up records (order free: the result is a maximum). TILES: a 256-thread block per 64 x 64 tile keeps the tile as
+// 4096 words of LDS; each wave scans the rectangles and walks those that touch its tile; LDS atomic max; the block then stores its tile as Depth16 rows. Every tile
+// scans every rectangle: no bins in this version. The draw lookup and the record are device/raster_setup.h's, the scan, the walk and a fragment's coverage and
+// depth device/raster_tile_walk.h's, both shared with "depthPrepassRaster.comp"; this file holds the transform, the block's append, what becomes of a fragment
+// (clamp, encode, maximum), the tile's store and the launcher.
 #include <algorithm>
 
 #include "../backend.h"
 #include "../device/detmath.h"
-#include "../device/raster_coverage.h"
+#include "../device/raster_setup.h"
+#include "../device/raster_tile_walk.h"
 #include "../device/sun_shadow_raster.h"
 
 namespace plr {
@@ -49,53 +52,17 @@ struct SetupParams {
     int32_t res;
 };
 
-using rastercov::edgeAt00; // the coverage rules are shared with "depthPrepassRaster.comp" (device/raster_coverage.h)
-using rastercov::topOrLeft;
-
 __global__ __launch_bounds__(256) void sunShadowSetupKernel(SetupParams p) {
     const uint32_t t = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
-    // the draw that holds triangle t. The block walks the draws 256 at a time: every thread loads one draw's triangle count, a block-wide prefix sum gives
-    // the chunk's first-triangle boundaries in LDS, and each lane bisects them (instead of every lane walking the draws one dependent load after the other)
-    __shared__ uint32_t chunkEnd[256];
-    __shared__ uint32_t waveTotal[4];
     const uint32_t wave = threadIdx.x >> 6;
-    const uint32_t lastOfBlock = min(blockIdx.x * 256u + 255u, p.triangleCount - 1u);
-    bool found = false;
-    uint32_t drawIndex = 0, local = 0, running = 0;
-    for (uint32_t chunk = 0; chunk < p.drawCount; chunk += 256u) {
-        const uint32_t d = chunk + threadIdx.x;
-        uint32_t sum = d < p.drawCount ? p.draws[d].indexCount / 3u : 0u;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)sum, off);
-            if ((int)lane >= off) sum += up;
-        }
-        if (lane == 63u) waveTotal[wave] = sum;
-        __syncthreads();
-        for (uint32_t w = 0; w < wave; w++) sum += waveTotal[w];
-        chunkEnd[threadIdx.x] = running + sum;
-        __syncthreads();
-        const uint32_t end = chunkEnd[255];
-        if (!found && t < p.triangleCount && t < end) {
-            uint32_t lo = 0, hi = 255; // the first k with t < chunkEnd[k]
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (t < chunkEnd[mid]) hi = mid; else lo = mid + 1u;
-            }
-            found = true;
-            drawIndex = chunk + lo;
-            local = t - (lo ? chunkEnd[lo - 1u] : running);
-        }
-        running = end;
-        __syncthreads();
-        if (running > lastOfBlock) break; // (block-uniform) every triangle of the block has its draw
-    }
+    const rastercov::TriangleSlot found = rastercov::drawOfTriangle(p.draws, p.drawCount, p.triangleCount, t);
     Draw draw{};
-    if (found) draw = p.draws[drawIndex];
+    if (found.found) draw = p.draws[found.draw];
     bool reject = false, survivor = false;
     SetupRecord rec{};
     uint32_t rect = 0;
-    if (found) {
-        const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)local * 3u;
+    if (found.found) {
+        const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)found.local * 3u;
         bool inBuffers = at + 3u <= (uint64_t)p.indexCount && draw.transformIndex < p.transformCount;
         uint64_t v[3] = {0, 0, 0};
         if (inBuffers)
@@ -129,32 +96,14 @@ __global__ __launch_bounds__(256) void sunShadowSetupKernel(SetupParams p) {
                 z[k] = cz;
             }
             if (!inside) reject = true;
-            else {
-                const int64_t area = (int64_t)(X[1] - X[0]) * (int64_t)(Y[2] - Y[0]) - (int64_t)(X[2] - X[0]) * (int64_t)(Y[1] - Y[0]);
-                if (area > 0) {
-                    const int32_t xmin = min(X[0], min(X[1], X[2])), xmax = max(X[0], max(X[1], X[2]));
-                    const int32_t ymin = min(Y[0], min(Y[1], Y[2])), ymax = max(Y[0], max(Y[1], Y[2]));
-                    const int32_t ix0 = max(0, (xmin + 127) >> 8), ix1 = min(p.res - 1, (xmax - 128) >> 8);
-                    const int32_t iy0 = max(0, (ymin + 127) >> 8), iy1 = min(p.res - 1, (ymax - 128) >> 8);
-                    if (ix0 <= ix1 && iy0 <= iy1) {
-                        survivor = true;
-                        rec.x0 = X[0]; rec.y0 = Y[0]; rec.x1 = X[1]; rec.y1 = Y[1]; rec.x2 = X[2]; rec.y2 = Y[2];
-                        rec.boxMin = (uint32_t)ix0 | ((uint32_t)iy0 << 16); rec.boxMax = (uint32_t)ix1 | ((uint32_t)iy1 << 16);
-                        rec.e01 = edgeAt00(X[0], Y[0], X[1], Y[1]); rec.e12 = edgeAt00(X[1], Y[1], X[2], Y[2]); rec.e20 = edgeAt00(X[2], Y[2], X[0], Y[0]);
-                        rec.area = area;
-                        rec.z0 = z[0]; rec.dz1 = z[1] - z[0]; rec.dz2 = z[2] - z[0];
-                        rec.topLeft = (topOrLeft(X[1] - X[0], Y[1] - Y[0]) ? 1u : 0u) | (topOrLeft(X[2] - X[1], Y[2] - Y[1]) ? 2u : 0u) | (topOrLeft(X[0] - X[2], Y[0] - Y[2]) ? 4u : 0u);
-                        if (xmax - xmin < kNarrowSpan && ymax - ymin < kNarrowSpan) rec.topLeft |= kNarrowFlag;
-                        rect = (uint32_t)(ix0 >> 6) | ((uint32_t)(iy0 >> 6) << 8) | ((uint32_t)(ix1 >> 6) << 16) | ((uint32_t)(iy1 >> 6) << 24);
-                    }
-                }
-            }
+            else survivor = rastercov::setupTriangle(X, Y, z, p.res, p.res, &rec, &rect);
         }
     }
     // one 64-bit atomic per block hands it a run of slots (the low word is the cursor) and counts its triangles (the high word): a frame's waves adding to
     // the header one by one were most of this kernel's time (measured for 100 k triangles: 1569 waves x 4 atomics on one cache line, 62 us against 18)
+    // (the prepass appends 0 .. 6 records per lane through a prefix sum of counts; this is one survivor per lane by ballot, and neither form serves the other)
     __shared__ uint32_t waveSurvivors[4], waveFound[4], waveRejects[4], blockBase;
-    const unsigned long long foundMask = __ballot(found), rejectMask = __ballot(reject), survivorMask = __ballot(survivor);
+    const unsigned long long foundMask = __ballot(found.found), rejectMask = __ballot(reject), survivorMask = __ballot(survivor);
     if (lane == 0) { waveSurvivors[wave] = (uint32_t)__popcll(survivorMask); waveFound[wave] = (uint32_t)__popcll(foundMask); waveRejects[wave] = (uint32_t)__popcll(rejectMask); }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -183,53 +132,19 @@ struct TileParams {
     int32_t res;
 };
 
-// one fragment of triangle r at pixel (px, py) of the map; tile: the block's 64 x 64 words, (ox, oy) its first pixel
-PLR_DI void shadowFragment(const SetupRecord& r, int64_t sx01, int64_t sy01, int64_t sx12, int64_t sy12, int64_t sx20, int64_t sy20, float fa, int px, int py, uint32_t* tile, int ox, int oy) {
-    const int64_t e01 = r.e01 + (int64_t)px * sx01 + (int64_t)py * sy01;
-    const int64_t e12 = r.e12 + (int64_t)px * sx12 + (int64_t)py * sy12;
-    const int64_t e20 = r.e20 + (int64_t)px * sx20 + (int64_t)py * sy20;
-    const bool covered = (e01 > 0 || (e01 == 0 && (r.topLeft & 1u))) && (e12 > 0 || (e12 == 0 && (r.topLeft & 2u))) && (e20 > 0 || (e20 == 0 && (r.topLeft & 4u)));
-    if (!covered) return;
-    const float l1 = (float)e20 / fa, l2 = (float)e01 / fa;
-    float zf = (r.z0 + l1 * r.dz1) + l2 * r.dz2;
-    zf = fminf(fmaxf(zf, 0.f), 1.f);
-    const uint32_t code = (uint32_t)__builtin_rintf(zf * 65535.f);
-    atomicMax(&tile[(py - oy) * kTileSize + (px - ox)], code);
-}
-
-// The same fragment for a triangle whose snapped vertices span less than 2^15 sub-pixel units (128 pixels) on both axes (kNarrowFlag) - nearly every shadow-map
-// triangle. Every pixel of its box lies within that span of every vertex, so the factors of E = dx (Py - Ya) - dy (Px - Xa) are below 2^15, the products below
-// 2^30 and E and A below 2^31: the contract's int64 values, computed in 24-bit multiplies, and their conversion to fp32 is one instruction instead of the
-// int64 sequence (measured: the tile kernel of a 2048 x 2048 cascade with 49 k drawn triangles 443 -> 367 us).
-PLR_DI void shadowFragmentNarrow(const SetupRecord& r, float fa, int px, int py, uint32_t* tile, int ox, int oy) {
-    const int32_t Px = px * 256 + 128, Py = py * 256 + 128;
-    const int32_t e01 = __mul24(r.x1 - r.x0, Py - r.y0) - __mul24(r.y1 - r.y0, Px - r.x0);
-    const int32_t e12 = __mul24(r.x2 - r.x1, Py - r.y1) - __mul24(r.y2 - r.y1, Px - r.x1);
-    const int32_t e20 = __mul24(r.x0 - r.x2, Py - r.y2) - __mul24(r.y0 - r.y2, Px - r.x2);
-    const bool covered = (e01 > 0 || (e01 == 0 && (r.topLeft & 1u))) && (e12 > 0 || (e12 == 0 && (r.topLeft & 2u))) && (e20 > 0 || (e20 == 0 && (r.topLeft & 4u)));
-    if (!covered) return;
-    const float l1 = (float)e20 / fa, l2 = (float)e01 / fa;
-    float zf = (r.z0 + l1 * r.dz1) + l2 * r.dz2;
-    zf = fminf(fmaxf(zf, 0.f), 1.f);
-    const uint32_t code = (uint32_t)__builtin_rintf(zf * 65535.f);
-    atomicMax(&tile[(py - oy) * kTileSize + (px - ox)], code);
-}
-
-// E(i, j) = E(0, 0) + i (-256 dy) + j (256 dx) for the pixel centre (256 i + 128, 256 j + 128)
-#define PLR_SUN_RASTER_STEPS(r)                                                                                                                         \
-    const int64_t sx01 = -256ll * (int64_t)((r).y1 - (r).y0), sy01 = 256ll * (int64_t)((r).x1 - (r).x0);                                                \
-    const int64_t sx12 = -256ll * (int64_t)((r).y2 - (r).y1), sy12 = 256ll * (int64_t)((r).x2 - (r).x1);                                                \
-    const int64_t sx20 = -256ll * (int64_t)((r).y0 - (r).y2), sy20 = 256ll * (int64_t)((r).x0 - (r).x2);                                                \
-    const float fa = (float)(r).area
-
-// the record lane `src` holds, in every lane (src is wave-uniform)
-PLR_DI SetupRecord broadcastRecord(const SetupRecord& r, int src) {
-    union Words { SetupRecord rec; int w[sizeof(SetupRecord) / 4]; };
-    Words in, out;
-    in.rec = r;
-    for (size_t k = 0; k < sizeof(SetupRecord) / 4; k++) out.w[k] = __builtin_amdgcn_readlane(in.w[k], src);
-    return out.rec;
-}
+// what becomes of a fragment: depth clamp, Depth16 code, maximum. tile: the block's 64 x 64 words
+struct ShadowWalk : rastercov::PlainWalk {
+    uint32_t* tile;
+    int ox, oy;
+    static PLR_DI const SetupRecord& setup(const SetupRecord& r) { return r; }
+    template <class D> PLR_DI void fragment(const SetupRecord&, int, int px, int py, D&& depthAt) {
+        float zf;
+        if (!depthAt(&zf)) return;
+        zf = fminf(fmaxf(zf, 0.f), 1.f);
+        const uint32_t code = (uint32_t)__builtin_rintf(zf * 65535.f);
+        atomicMax(&tile[(py - oy) * kTileSize + (px - ox)], code);
+    }
+};
 
 __global__ __launch_bounds__(256) void sunShadowTileKernel(TileParams p) {
     __shared__ uint32_t tile[kTileSize * kTileSize];
@@ -240,77 +155,11 @@ __global__ __launch_bounds__(256) void sunShadowTileKernel(TileParams p) {
     for (uint32_t i = threadIdx.x; i < (uint32_t)(kTileSize * kTileSize); i += 256u) tile[i] = 0u;
     __syncthreads();
     const uint32_t n = min(p.header->cursor, p.capacity);
-    // the tile's pixels inside the map
-    const int tx1 = min(ox + kTileSize - 1, p.res - 1), ty1 = min(oy + kTileSize - 1, p.res - 1);
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.header->drawn = n;
-    // A wave reads 256 rectangles per step (four per lane, one 16-byte load: the array is padded to that), queues the indices of those that touch its tile in
-    // LDS and then takes the queue 64 at a time, a record per lane: one memory latency per 256 entries scanned plus one per 64 hits. Measured against 64
-    // entries per step with the record fetched behind the rectangle test (tools/shadow_raster_cost.py): the scan went from 1.5 to 0.85 us per thousand
-    // entries; the kernel's time in a busy tile is the hits' arithmetic, which this does not change.
-    uint32_t* queue = hitQueue[wave];
-    const unsigned long long lanesBelow = (1ull << lane) - 1ull;
-    auto touches = [&](uint32_t rc) { return (int)(rc & 255u) <= tx && tx <= (int)((rc >> 16) & 255u) && (int)((rc >> 8) & 255u) <= ty && ty <= (int)(rc >> 24); };
-    for (uint32_t base = wave * 256u; base < n; base += 1024u) {
-        const uint32_t i0 = base + lane * 4u;
-        uint4 rc = make_uint4(0u, 0u, 0u, 0u);
-        if (i0 < n) rc = *(const uint4*)(p.rects + i0);
-        const bool h0 = i0 < n && touches(rc.x), h1 = i0 + 1u < n && touches(rc.y), h2 = i0 + 2u < n && touches(rc.z), h3 = i0 + 3u < n && touches(rc.w);
-        const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1), m2 = __ballot(h2), m3 = __ballot(h3);
-        const uint32_t c0 = (uint32_t)__popcll(m0), c1 = c0 + (uint32_t)__popcll(m1), c2 = c1 + (uint32_t)__popcll(m2), total = c2 + (uint32_t)__popcll(m3);
-        if (total == 0u) continue;
-        if (h0) queue[(uint32_t)__popcll(m0 & lanesBelow)] = i0;
-        if (h1) queue[c0 + (uint32_t)__popcll(m1 & lanesBelow)] = i0 + 1u;
-        if (h2) queue[c1 + (uint32_t)__popcll(m2 & lanesBelow)] = i0 + 2u;
-        if (h3) queue[c2 + (uint32_t)__popcll(m3 & lanesBelow)] = i0 + 3u;
-        __builtin_amdgcn_wave_barrier(); // (one wave: its LDS operations execute in order)
-        for (uint32_t k = 0; k < total; k += 64u) {
-            bool hit = k + lane < total;
-            int bx0 = 0, by0 = 0, bx1 = -1, by1 = -1;
-            SetupRecord r{};
-            if (hit) {
-                r = p.records[queue[k + lane]];
-                bx0 = max((int)(r.boxMin & 0xffffu), ox); by0 = max((int)(r.boxMin >> 16), oy);
-                bx1 = min((int)(r.boxMax & 0xffffu), tx1); by1 = min((int)(r.boxMax >> 16), ty1);
-                hit = bx0 <= bx1 && by0 <= by1;
-            }
-            const bool small = hit && bx1 - bx0 < 4 && by1 - by0 < 4;
-            if (small) { // the usual shadow-map triangle: its lane walks the <= 16 pixels
-                if (r.topLeft & kNarrowFlag) {
-                    const float fa = (float)(int32_t)r.area;
-                    for (int py = by0; py <= by1; py++)
-                        for (int px = bx0; px <= bx1; px++) shadowFragmentNarrow(r, fa, px, py, tile, ox, oy);
-                } else {
-                    PLR_SUN_RASTER_STEPS(r);
-                    for (int py = by0; py <= by1; py++)
-                        for (int px = bx0; px <= bx1; px++) shadowFragment(r, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, tile, ox, oy);
-                }
-            }
-            unsigned long long large = __ballot(hit && !small);
-            while (large) { // the whole wave walks the box in 8 x 8 stamps, with the record broadcast from the lane that holds it
-                const int src = __ffsll((long long)large) - 1;
-                large &= large - 1ull;
-                const SetupRecord u = broadcastRecord(r, src);
-                const int lx0 = __builtin_amdgcn_readlane(bx0, src), ly0 = __builtin_amdgcn_readlane(by0, src);
-                const int lx1 = __builtin_amdgcn_readlane(bx1, src), ly1 = __builtin_amdgcn_readlane(by1, src);
-                if (u.topLeft & kNarrowFlag) { // (wave-uniform)
-                    const float fa = (float)(int32_t)u.area;
-                    for (int sy = ly0; sy <= ly1; sy += 8)
-                        for (int sx = lx0; sx <= lx1; sx += 8) {
-                            const int px = sx + (int)(lane & 7u), py = sy + (int)(lane >> 3);
-                            if (px <= lx1 && py <= ly1) shadowFragmentNarrow(u, fa, px, py, tile, ox, oy);
-                        }
-                } else {
-                    PLR_SUN_RASTER_STEPS(u);
-                    for (int sy = ly0; sy <= ly1; sy += 8)
-                        for (int sx = lx0; sx <= lx1; sx += 8) {
-                            const int px = sx + (int)(lane & 7u), py = sy + (int)(lane >> 3);
-                            if (px <= lx1 && py <= ly1) shadowFragment(u, sx01, sy01, sx12, sy12, sx20, sy20, fa, px, py, tile, ox, oy);
-                        }
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
+    // the kernel's time in a busy tile is the hits' arithmetic
+    const rastercov::TileWindow window{tx, ty, ox, oy, min(ox + kTileSize - 1, p.res - 1), min(oy + kTileSize - 1, p.res - 1)};
+    ShadowWalk walk{{}, tile, ox, oy};
+    rastercov::rasteriseTile(p.rects, p.records, n, window, hitQueue[wave], walk);
     __syncthreads();
     // the tile as Depth16 rows: eight texels per 16-byte store where the eight lie inside the map and the address allows, texel by texel at ragged edges
     const bool rowsAligned = (p.res & 7) == 0;
