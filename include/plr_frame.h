@@ -252,8 +252,8 @@ int plrf_apply_changes(void* pipeline); /* apply what was recorded now: a caller
  * While a pipeline has casters, every plrf_frame records sun_shadow_cascade_count executions of the pass behind the light matrices (also under sdf_debug_mode);
  * they rasterise the draws into shadow0 .. shadow<count - 1> with whatever sunShadowInfo holds, uploaded or computed (run_light_matrix). Maps at and above the
  * cascade count are not touched. Without casters nothing is recorded and the uploaded maps are used. The rasterisation contract - 8 sub-pixel bits, top-left
- * rule, front faces culled, depth clamp, round-to-nearest-even Depth16, a 2^20-pixel guard band with a counted reject instead of clipping, opaque casters - is
- * DESIGN.md "Sun shadow cascades as a compute pass".
+ * rule, front faces culled, depth clamp, round-to-nearest-even Depth16, a 2^20-pixel guard band with a counted reject instead of clipping, casters opaque unless
+ * plrf_set_shadow_caster_cutouts (below) gives them an alpha test - is DESIGN.md "Sun shadow cascades as a compute pass".
  * plrf_set_shadow_casters copies the meshes (positions and a uint32 triangle list each) and the draws; draw_count 0 removes the casters. PLR_ERR_INVALID_ARGUMENT,
  * with a message that names the cause: a mesh index or a vertex index out of range, an index count that is no multiple of 3, a model matrix whose last row is not
  * exactly (0, 0, 0, 1) (the pass does not divide by w). PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing.
@@ -319,10 +319,28 @@ int plrf_set_scene_textures(void* pipeline, const plrf_scene_texture* textures, 
  * call order. draw_count 0 removes them, and so does every plrf_set_scene_meshes and every plrf_set_scene_textures; they survive
  * plrf_set_scene_mesh_transforms, plrf_set_resolution and plrf_update_settings. While all cutoffs are 0, or none are set, every frame is what it is without this
  * call. PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: no scene set, no textures set, a count mismatch, NULL cutoffs with a non-zero count, a
- * value above 255. PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing. The sun shadow pass has no alpha test: a cutout casts its
- * quad's shadow. */
+ * value above 255. PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing. The sun shadow pass has an alpha test of its own, for its own
+ * meshes: plrf_set_shadow_caster_cutouts below. */
 #define PLRF_ALPHA_CUTOFF_REFERENCE 128u
 int plrf_set_scene_alpha_cutoffs(void* pipeline, const uint32_t* cutoffs, uint32_t draw_count);
+/* ---- alpha-tested cutout casters: sunShadow.frag:17-21 (sample the albedo texture's alpha, discard below 0.5) for the mesh shadow casters (DESIGN.md
+ * "Alpha-tested cutout casters in the sun shadow raster"). Casters are another mesh set than the scene's and keep their own copy of the textures:
+ * plrf_scene_texture as above (mip_count 0: the host builds the chain), mesh_uvs[k]: 2 floats per vertex of caster mesh k, NULL (the array or an entry): all
+ * (0, 0), and one plrf_shadow_cutout per caster draw: the texture whose alpha is tested, or PLRF_NO_TEXTURE (alpha 255 everywhere: the draw stays opaque), and a
+ * cutoff code 0 .. 255, 0 = opaque, PLRF_ALPHA_CUTOFF_REFERENCE = the reference's test. A fragment whose alpha code (isotropic trilinear, one level per triangle, no
+ * mip bias, UV interpolated with the depth's weights) is below its draw's cutoff casts no shadow; the counters of plrf_get_shadow_raster_stats do not depend on
+ * alpha. The pass culls FRONT faces: a single-sided card that faces the light is culled before it is tested, as in the reference - a card that is to cast a
+ * shadow from both sides needs both windings.
+ * plrf_set_shadow_caster_cutouts needs casters set; mesh_count and draw_count must be the casters'. Everything is copied and takes effect with the next frame, in
+ * call order. texture_count 0 removes the cutouts (the other arguments are not looked at), and so does every plrf_set_shadow_casters; they survive
+ * plrf_set_shadow_caster_transforms, plrf_set_resolution and plrf_update_settings. While none are set, or all cutoffs are 0, every frame is what it is without
+ * this call. PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: no casters set, a count mismatch, a texture size of 0 or above 16384, too many mips
+ * for the size, NULL texels, a texture index that is neither PLRF_NO_TEXTURE nor < texture_count, a cutoff above 255, more than 2^28 texels in total, a non-finite
+ * UV. PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing. */
+typedef struct plrf_shadow_cutout { uint32_t albedo_texture, alpha_cutoff; } plrf_shadow_cutout; /* PLRF_NO_TEXTURE; 0 .. 255, 0 = opaque */
+int plrf_set_shadow_caster_cutouts(void* pipeline, const plrf_scene_texture* textures, uint32_t texture_count,
+                                   const float* const* mesh_uvs, uint32_t mesh_count,
+                                   const plrf_shadow_cutout* cutouts, uint32_t draw_count);
 typedef struct plrf_prepass_raster_stats { uint64_t triangles_submitted, triangles_clipped, subtriangles_drawn, rejects; } plrf_prepass_raster_stats;
 int plrf_get_prepass_raster_stats(void* pipeline, plrf_prepass_raster_stats* out);
 /* one iteration of the reference's main loop: record the frame, update camera/UBOs, submit (does not wait for the GPU) */

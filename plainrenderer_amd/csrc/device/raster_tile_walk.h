@@ -16,14 +16,16 @@ struct EdgeSteps {
           sx20(-256ll * (int64_t)(r.y0 - r.y2)), sy20(256ll * (int64_t)(r.x0 - r.x2)), fa((float)r.area) {}
 };
 
-// coverage and depth of triangle r at pixel (px, py): false where the pixel centre is not covered, else the contract's zf
-PLR_DI bool fragmentDepth(const SetupRecord& r, const EdgeSteps& s, int px, int py, float* zf) {
+// coverage and depth of triangle r at pixel (px, py): false where the pixel centre is not covered, else the contract's zf and, where `weights` is given, the
+// fp32 weights l1, l2 it was formed from (a pass that interpolates more than depth; a null `weights` is a compile-time one and leaves no trace)
+PLR_DI bool fragmentDepth(const SetupRecord& r, const EdgeSteps& s, int px, int py, float* zf, float* weights = nullptr) {
     const int64_t e01 = r.e01 + (int64_t)px * s.sx01 + (int64_t)py * s.sy01;
     const int64_t e12 = r.e12 + (int64_t)px * s.sx12 + (int64_t)py * s.sy12;
     const int64_t e20 = r.e20 + (int64_t)px * s.sx20 + (int64_t)py * s.sy20;
     if (!covered(e01, e12, e20, r.topLeft)) return false;
     const float l1 = (float)e20 / s.fa, l2 = (float)e01 / s.fa;
     *zf = (r.z0 + l1 * r.dz1) + l2 * r.dz2;
+    if (weights) { weights[0] = l1; weights[1] = l2; }
     return true;
 }
 
@@ -31,7 +33,7 @@ PLR_DI bool fragmentDepth(const SetupRecord& r, const EdgeSteps& s, int px, int 
 // pixel of its box lies within that span of every vertex, so the factors of E = dx (Py - Ya) - dy (Px - Xa) are below 2^15, the products below 2^30 and E and A
 // below 2^31: the contract's int64 values, computed in 24-bit multiplies, and their conversion to fp32 is one instruction instead of the int64 sequence
 // (measured: the shadow tile kernel of a 2048 x 2048 cascade with 49 k drawn triangles 443 -> 367 us). fa: (float)(int32_t)r.area, which is (float)r.area.
-PLR_DI bool fragmentDepthNarrow(const SetupRecord& r, float fa, int px, int py, float* zf) {
+PLR_DI bool fragmentDepthNarrow(const SetupRecord& r, float fa, int px, int py, float* zf, float* weights = nullptr) {
     const int32_t Px = px * 256 + 128, Py = py * 256 + 128;
     const int32_t e01 = __mul24(r.x1 - r.x0, Py - r.y0) - __mul24(r.y1 - r.y0, Px - r.x0);
     const int32_t e12 = __mul24(r.x2 - r.x1, Py - r.y1) - __mul24(r.y2 - r.y1, Px - r.x1);
@@ -39,6 +41,7 @@ PLR_DI bool fragmentDepthNarrow(const SetupRecord& r, float fa, int px, int py, 
     if (!covered(e01, e12, e20, r.topLeft)) return false;
     const float l1 = (float)e20 / fa, l2 = (float)e01 / fa;
     *zf = (r.z0 + l1 * r.dz1) + l2 * r.dz2;
+    if (weights) { weights[0] = l1; weights[1] = l2; }
     return true;
 }
 
@@ -53,22 +56,23 @@ template <class T> PLR_DI T broadcastLane(const T& v, int src) {
 }
 
 // The pixels x0 .. x1, y0 .. y1 of triangle r, kStride x kStride at a time with this lane at (offx, offy) of each: fragment(px, py, depthAt) for every pixel of
-// the lane, inside the box or not; depthAt(&zf) is false outside the box and where the pixel centre is not covered, else it gives the depth. kStride 1: a lane
-// walks a box of its own; 8: the wave walks one box in 8 x 8 stamps, and all lanes arrive at every call together.
+// the lane, inside the box or not; depthAt(&zf) is false outside the box and where the pixel centre is not covered, else it gives the depth, and
+// depthAt(&zf, weights) the depth's two fp32 weights l1, l2 with it. kStride 1: a lane walks a box of its own; 8: the wave walks one box in 8 x 8 stamps, and
+// all lanes arrive at every call together.
 template <int kStride, class F> PLR_DI void walkBox(const SetupRecord& r, int x0, int y0, int x1, int y1, int offx, int offy, F&& fragment) {
     auto walk = [&](auto&& depthOf) {
         for (int sy = y0; sy <= y1; sy += kStride)
             for (int sx = x0; sx <= x1; sx += kStride) {
                 const int px = sx + offx, py = sy + offy;
-                fragment(px, py, [&](float* zf) { return px <= x1 && py <= y1 && depthOf(px, py, zf); });
+                fragment(px, py, [&](float* zf, float* weights = nullptr) { return px <= x1 && py <= y1 && depthOf(px, py, zf, weights); });
             }
     };
     if (r.topLeft & kNarrowFlag) {
         const float fa = (float)(int32_t)r.area;
-        walk([&](int px, int py, float* zf) { return fragmentDepthNarrow(r, fa, px, py, zf); });
+        walk([&](int px, int py, float* zf, float* weights) { return fragmentDepthNarrow(r, fa, px, py, zf, weights); });
     } else {
         const EdgeSteps steps(r);
-        walk([&](int px, int py, float* zf) { return fragmentDepth(r, steps, px, py, zf); });
+        walk([&](int px, int py, float* zf, float* weights) { return fragmentDepth(r, steps, px, py, zf, weights); });
     }
 }
 

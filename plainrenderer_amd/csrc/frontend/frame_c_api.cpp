@@ -106,6 +106,17 @@ int plrf_set_shadow_caster_transforms(void* p, const float* matrices16, uint32_t
     if (!p) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY_REFUSAL(((FramePipeline*)p)->setShadowCasterTransforms(matrices16, drawCount))
 }
+int plrf_set_shadow_caster_cutouts(void* p, const plrf_scene_texture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount,
+                                   const plrf_shadow_cutout* cutouts, uint32_t drawCount) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        std::vector<SceneTexture> t(textures ? textureCount : 0u);
+        for (size_t i = 0; i < t.size(); i++) t[i] = {textures[i].texels, textures[i].width, textures[i].height, textures[i].mip_count};
+        std::vector<ShadowCutout> m(cutouts ? drawCount : 0u);
+        for (size_t i = 0; i < m.size(); i++) m[i] = {cutouts[i].albedo_texture, cutouts[i].alpha_cutoff};
+        ((FramePipeline*)p)->setShadowCasterCutouts(t.empty() ? nullptr : t.data(), textureCount, meshUvs, meshCount, m.empty() ? nullptr : m.data(), drawCount);
+    })
+}
 int plrf_get_shadow_raster_stats(void* p, uint32_t cascade, plrf_shadow_raster_stats* out) {
     if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY_REFUSAL({

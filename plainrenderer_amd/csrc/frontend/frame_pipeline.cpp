@@ -1253,8 +1253,17 @@ void FramePipeline::renderSunShadowCascades() {
                                                     StorageBufferResource(m_casterIndices, true, plr::sunraster::kIndexBinding),
                                                     StorageBufferResource(m_casterDraws, true, plr::sunraster::kDrawBinding),
                                                     StorageBufferResource(m_casterScratch[c], false, plr::sunraster::kScratchBinding)};
-        const plr::sunraster::PushConstants pc{m_casterDrawCount, m_casterTriangleCount};
-        exe.pushConstants = dataToCharArray(&pc, sizeof(pc));
+        // without cutouts, or while every cutoff is 0: the 8-byte record
+        const bool tested = m_casterAlphaTested && m_casterTextureCount;
+        const plr::sunraster::CutoutPushConstants pc{m_casterDrawCount, m_casterTriangleCount, tested ? m_casterTextureCount : 0u};
+        exe.pushConstants = dataToCharArray(&pc, tested ? sizeof(pc) : sizeof(plr::sunraster::PushConstants));
+        if (tested) {
+            auto& buffers = exe.genericInfo.resources.storageBuffers;
+            buffers.push_back(StorageBufferResource(m_casterUvs, true, plr::sunraster::kUvBinding));
+            buffers.push_back(StorageBufferResource(m_casterMaterials, true, plr::sunraster::kCasterMaterialBinding));
+            buffers.push_back(StorageBufferResource(m_casterTextures, true, plr::sunraster::kTextureBinding));
+            buffers.push_back(StorageBufferResource(m_casterTexels, true, plr::sunraster::kTexelBinding));
+        }
         m_be.setComputePassExecution(exe);
     }
 }
@@ -1280,7 +1289,12 @@ static void refuseUnlessAffine(const float* m, uint32_t draw, const char* call) 
 void FramePipeline::setShadowCasters(const ShadowCasterMesh* meshes, uint32_t meshCount, const ShadowCasterDraw* draws, uint32_t drawCount) {
     if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setShadowCasters: a band / tile pipeline cannot rasterise shadow casters (every partition would draw every cascade)");
-    if (drawCount == 0) { m_casterDrawCount = m_casterTriangleCount = 0; return; }
+    if (drawCount == 0) {
+        m_casterDrawCount = m_casterTriangleCount = m_casterTextureCount = 0;
+        m_casterAlphaTested = false;
+        m_casterMeshVertexCounts.clear();
+        return;
+    }
     if (!meshes || !draws || meshCount == 0) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: draws without meshes");
     // everything is validated before anything is changed
     std::vector<uint32_t> firstIndex(meshCount), vertexOffset(meshCount);
@@ -1334,6 +1348,26 @@ void FramePipeline::setShadowCasters(const ShadowCasterMesh* meshes, uint32_t me
     for (int c = 0; c < settings.shading.sunShadowCascadeCount; c++)
         fillCasterBuffer(m_casterScratch[c], m_casterScratchBytes[c], nullptr, plr::sunraster::scratchBytes((uint32_t)triangles));
     m_casterDrawCount = drawCount; m_casterTriangleCount = (uint32_t)triangles;
+    m_casterMeshVertexCounts.resize(meshCount);
+    for (uint32_t m = 0; m < meshCount; m++) m_casterMeshVertexCounts[m] = meshes[m].vertexCount;
+    m_casterTextureCount = 0; // the cutouts belonged to the casters that were replaced
+    m_casterAlphaTested = false;
+}
+
+void FramePipeline::setShadowCasterCutouts(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts, uint32_t drawCount) {
+    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setShadowCasterCutouts: a band / tile pipeline cannot rasterise shadow casters");
+    if (textureCount == 0) { m_casterTextureCount = 0; m_casterAlphaTested = false; return; }
+    const PackedShadowCutouts packed = packShadowCasterCutouts(textures, textureCount, meshUvs, meshCount, cutouts, drawCount, m_casterMeshVertexCounts.data(),
+                                                               (uint32_t)m_casterMeshVertexCounts.size(), m_casterDrawCount); // validates everything before anything is changed
+    fillCasterBuffer(m_casterUvs, m_casterUvBytes, packed.uvs.data(), packed.uvs.size() * sizeof(float));
+    fillCasterBuffer(m_casterMaterials, m_casterMaterialBytes, packed.materials.data(), packed.materials.size() * sizeof(uint32_t));
+    fillCasterBuffer(m_casterTextures, m_casterTextureBytes, packed.textures.data(), packed.textures.size() * sizeof(uint32_t));
+    fillCasterBuffer(m_casterTexels, m_casterTexelBytes, packed.texels.data(), packed.texels.size() * sizeof(uint32_t));
+    for (int c = 0; c < settings.shading.sunShadowCascadeCount; c++) // a tested execution's records are larger
+        fillCasterBuffer(m_casterScratch[c], m_casterScratchBytes[c], nullptr, plr::sunraster::cutoutScratchBytes(m_casterTriangleCount));
+    m_casterTextureCount = textureCount;
+    m_casterAlphaTested = packed.tested;
 }
 
 void FramePipeline::setShadowCasterTransforms(const float* matrices16, uint32_t drawCount) {

@@ -355,6 +355,20 @@ struct PackedAlphaCutoffs {
 };
 // sceneDrawCount / sceneTextureCount: of the scene and the textures the pipeline holds. Throws FramePipelineRefusal.
 PackedAlphaCutoffs packSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawCount, uint32_t sceneDrawCount, uint32_t sceneTextureCount);
+// alpha-tested cutouts of the shadow casters (plr_frame.h plrf_set_shadow_caster_cutouts): per caster draw the texture whose alpha is tested (kNoSceneTexture:
+// alpha 255 everywhere) and the cutoff code 0 .. 255, 0 = opaque
+struct ShadowCutout { uint32_t albedoTexture = kNoSceneTexture, alphaCutoff = 0; };
+// what setShadowCasterCutouts validates and packs, without a backend: bindings 6 - 9 of a "sunShadowRaster.comp" record with textureCount > 0
+struct PackedShadowCutouts {
+    std::vector<float> uvs;          // 2 floats per vertex of the packed casters, zeros for a mesh given without
+    std::vector<uint32_t> materials; // 2 words per draw: {albedoTexture, cutoff}
+    std::vector<uint32_t> textures;  // 4 words per texture: {texelOffset, width, height, mipCount}
+    std::vector<uint32_t> texels;
+    bool tested = false; // a cutoff other than 0: only then the frames record the third push-constant word
+};
+// casterMeshVertexCounts / casterDrawCount: of the casters the pipeline holds (casterDrawCount 0: none). Throws FramePipelineRefusal.
+PackedShadowCutouts packShadowCasterCutouts(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts,
+                                            uint32_t drawCount, const uint32_t* casterMeshVertexCounts, uint32_t casterMeshCount, uint32_t casterDrawCount);
 // appends levels 1 .. of the full chain of a width x height level 0 (already the last `width * height` texels of `texels`): level l + 1 texel (x, y) per channel
 // is (a + b + c + d + 2) >> 2 of the level-l texels at (min(2x, W - 1) | min(2x + 1, W - 1), min(2y, H - 1) | min(2y + 1, H - 1))
 void appendMipChain(std::vector<uint32_t>& texels, uint32_t width, uint32_t height);
@@ -370,6 +384,16 @@ public:
     void setShadowCasters(const ShadowCasterMesh* meshes, uint32_t meshCount, const ShadowCasterDraw* draws, uint32_t drawCount);
     // the draws' model matrices for the next frame (setStorageBufferData: applied in call order at the next frame); drawCount must be the casters' draw count
     void setShadowCasterTransforms(const float* matrices16, uint32_t drawCount);
+    // alpha-tested cutouts for the casters now set (DESIGN.md "Alpha-tested cutout casters in the sun shadow raster"): textures as for setSceneTextures (the
+    // casters keep their own copy: they are another mesh set than the scene's), meshUvs[k]: 2 floats per vertex of caster mesh k, null: all (0, 0), and per draw
+    // the texture whose alpha is tested and a cutoff code 0 .. 255, 0 = opaque, 128 = the reference's alpha < 0.5 -> discard. From the next frame on, while a
+    // cutoff is not 0, the cascades are recorded with the third push-constant word and bindings 6 - 9, and a fragment whose alpha code is below its draw's cutoff
+    // is no fragment. The pass culls front faces, so a single-sided card that faces the light is culled before it is tested, as in the reference: a cutout that
+    // is to cast needs both windings. Everything is copied. textureCount 0 removes the cutouts; every setShadowCasters drops them too; they survive
+    // setShadowCasterTransforms, setResolution and updateSettings. Refusals: no casters, a mesh or draw count other than the casters', a texture size of 0 or above
+    // 16384, too many mips, null texels, a texture index out of range, a cutoff above 255, more than 2^28 texels, a non-finite UV are PLR_ERR_INVALID_ARGUMENT; a
+    // band / tile pipeline is PLR_ERR_UNSUPPORTED. A refused call changes nothing.
+    void setShadowCasterCutouts(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts, uint32_t drawCount);
     // counters of the last frame's execution for `cascade`; waits for the GPU. Zero before the first frame with casters.
     ShadowRasterStats shadowRasterStats(uint32_t cascade);
     // RenderFrontend::renderDepthPrepass (RenderFrontend.cpp:351, 792-802) as "depthPrepassRaster.comp" (kernels/depth_prepass_raster.hip): while a scene is set every
@@ -502,6 +526,12 @@ private:
     RenderPassHandle m_sunShadowRasterPass[4];
     StorageBufferHandle m_casterTransforms, m_casterPositions, m_casterIndices, m_casterDraws, m_casterScratch[4];
     size_t m_casterTransformBytes = 0, m_casterPositionBytes = 0, m_casterIndexBytes = 0, m_casterDrawBytes = 0, m_casterScratchBytes[4] = {0, 0, 0, 0};
+    // cutouts: created by the first setShadowCasterCutouts; 0 textures, or no cutoff other than 0 = the 8-byte pass record
+    uint32_t m_casterTextureCount = 0;
+    bool m_casterAlphaTested = false;
+    std::vector<uint32_t> m_casterMeshVertexCounts;
+    StorageBufferHandle m_casterUvs, m_casterMaterials, m_casterTextures, m_casterTexels;
+    size_t m_casterUvBytes = 0, m_casterMaterialBytes = 0, m_casterTextureBytes = 0, m_casterTexelBytes = 0;
     // scene meshes: created by the first setSceneMeshes (a pipeline without a scene allocates and records nothing for them). A buffer and the capacity that
     // describes it are one object
     struct SceneBuffer { StorageBufferHandle handle; size_t bytes = 0; };

@@ -1,6 +1,7 @@
 // Validation and packing of scene meshes, their material textures and their alpha cutoffs for "depthPrepassRaster.comp" (FramePipeline::setSceneMeshes,
-// setSceneTextures, setSceneAlphaCutoffs): host code without a backend call, so that a stand-alone program can run it under a sanitizer
-// (tools/scene_packing_check.cpp, tools/scene_texture_check.cpp, tools/scene_alpha_check.cpp).
+// setSceneTextures, setSceneAlphaCutoffs) and of the shadow casters' cutouts for "sunShadowRaster.comp" (setShadowCasterCutouts): host code without a backend
+// call, so that a stand-alone program can run it under a sanitizer (tools/scene_packing_check.cpp, tools/scene_texture_check.cpp, tools/scene_alpha_check.cpp,
+// tools/shadow_cutout_check.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -92,16 +93,9 @@ void appendMipChain(std::vector<uint32_t>& texels, uint32_t width, uint32_t heig
     }
 }
 
-// everything is validated before anything is built
-PackedTextures packSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials,
-                                 uint32_t drawCount, const uint32_t* sceneMeshVertexCounts, uint32_t sceneMeshCount, uint32_t sceneDrawCount) {
+// ---- the texture store and the UVs, shared by the scene's textures and the shadow casters' cutouts: `refuse` throws with the call's name in front
+template <class Refuse> static uint64_t validateTextures(const SceneTexture* textures, uint32_t textureCount, Refuse&& refuse) {
     namespace pp = plr::prepass;
-    const std::string call = "setSceneTextures";
-    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
-    if (sceneDrawCount == 0) refuse("no scene set (plrf_set_scene_meshes comes first)");
-    if (meshCount != sceneMeshCount) refuse("mesh count " + std::to_string(meshCount) + " differs from the mesh count " + std::to_string(sceneMeshCount) + " of the scene");
-    if (drawCount != sceneDrawCount) refuse("draw count " + std::to_string(drawCount) + " differs from the draw count " + std::to_string(sceneDrawCount) + " of the scene");
-    if (!textures || !materials) refuse("textures or materials are null");
     uint64_t total = 0;
     for (uint32_t t = 0; t < textureCount; t++) {
         const SceneTexture& tex = textures[t];
@@ -114,39 +108,92 @@ PackedTextures packSceneTextures(const SceneTexture* textures, uint32_t textureC
         const uint32_t levels = tex.mipCount ? tex.mipCount : full;
         for (uint32_t l = 0; l < levels; l++) total += (uint64_t)std::max(1u, tex.width >> l) * std::max(1u, tex.height >> l);
     }
+    return total;
+}
+
+// the UVs of the meshes back to back, zeros for a mesh given without; refuses a non-finite one
+template <class Refuse> static std::vector<float> packUvs(const float* const* meshUvs, uint32_t meshCount, const uint32_t* meshVertexCounts, Refuse&& refuse) {
+    uint64_t vertices = 0;
+    for (uint32_t m = 0; m < meshCount; m++) {
+        if (meshUvs && meshUvs[m])
+            for (size_t i = 0; i < (size_t)meshVertexCounts[m] * 2u; i++)
+                if (!std::isfinite(meshUvs[m][i]))
+                    refuse("non-finite UV: vertex " + std::to_string(i / 2u) + " of mesh " + std::to_string(m));
+        vertices += meshVertexCounts[m];
+    }
+    std::vector<float> uvs((size_t)vertices * 2u, 0.f);
+    size_t at = 0;
+    for (uint32_t m = 0; m < meshCount; m++) {
+        if (meshUvs && meshUvs[m] && meshVertexCounts[m]) std::memcpy(uvs.data() + at, meshUvs[m], (size_t)meshVertexCounts[m] * 8u);
+        at += (size_t)meshVertexCounts[m] * 2u;
+    }
+    return uvs;
+}
+
+// the table {texelOffset, width, height, mipCount} and the texels of validated textures, a chain built where mipCount is 0
+static void packTextureStore(const SceneTexture* textures, uint32_t textureCount, uint64_t total, std::vector<uint32_t>& table, std::vector<uint32_t>& texels) {
+    namespace pp = plr::prepass;
+    table.resize((size_t)textureCount * 4u);
+    texels.reserve((size_t)total);
+    for (uint32_t t = 0; t < textureCount; t++) {
+        const SceneTexture& tex = textures[t];
+        const pp::Texture entry{(uint32_t)texels.size(), tex.width, tex.height, tex.mipCount ? tex.mipCount : pp::fullMipCount(tex.width, tex.height)};
+        std::memcpy(table.data() + (size_t)t * 4u, &entry, sizeof(entry));
+        size_t given = 0;
+        for (uint32_t l = 0; l < std::max(1u, tex.mipCount); l++) given += (size_t)std::max(1u, tex.width >> l) * std::max(1u, tex.height >> l);
+        texels.insert(texels.end(), tex.texels, tex.texels + given);
+        if (tex.mipCount == 0) appendMipChain(texels, tex.width, tex.height);
+    }
+}
+
+// everything is validated before anything is built
+PackedTextures packSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials,
+                                 uint32_t drawCount, const uint32_t* sceneMeshVertexCounts, uint32_t sceneMeshCount, uint32_t sceneDrawCount) {
+    namespace pp = plr::prepass;
+    const std::string call = "setSceneTextures";
+    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
+    if (sceneDrawCount == 0) refuse("no scene set (plrf_set_scene_meshes comes first)");
+    if (meshCount != sceneMeshCount) refuse("mesh count " + std::to_string(meshCount) + " differs from the mesh count " + std::to_string(sceneMeshCount) + " of the scene");
+    if (drawCount != sceneDrawCount) refuse("draw count " + std::to_string(drawCount) + " differs from the draw count " + std::to_string(sceneDrawCount) + " of the scene");
+    if (!textures || !materials) refuse("textures or materials are null");
+    const uint64_t total = validateTextures(textures, textureCount, refuse);
     for (uint32_t d = 0; d < drawCount; d++)
         for (uint32_t index : {materials[d].albedoTexture, materials[d].specularTexture})
             if (index != kNoSceneTexture && index >= textureCount)
                 refuse("material texture index out of range: draw " + std::to_string(d) + " names texture " + std::to_string(index) + " of " + std::to_string(textureCount));
     if (total > pp::kMaxTexels) refuse("too many texels: " + std::to_string(total) + " in all levels of all textures, at most 2^28");
-    uint64_t vertices = 0;
-    for (uint32_t m = 0; m < meshCount; m++) {
-        if (meshUvs && meshUvs[m])
-            for (size_t i = 0; i < (size_t)sceneMeshVertexCounts[m] * 2u; i++)
-                if (!std::isfinite(meshUvs[m][i]))
-                    refuse("non-finite UV: vertex " + std::to_string(i / 2u) + " of mesh " + std::to_string(m));
-        vertices += sceneMeshVertexCounts[m];
-    }
     PackedTextures out;
-    out.uvs.assign((size_t)vertices * 2u, 0.f);
-    size_t at = 0;
-    for (uint32_t m = 0; m < meshCount; m++) {
-        if (meshUvs && meshUvs[m] && sceneMeshVertexCounts[m]) std::memcpy(out.uvs.data() + at, meshUvs[m], (size_t)sceneMeshVertexCounts[m] * 8u);
-        at += (size_t)sceneMeshVertexCounts[m] * 2u;
-    }
+    out.uvs = packUvs(meshUvs, meshCount, sceneMeshVertexCounts, refuse);
     out.materials.resize((size_t)drawCount * 2u);
     for (uint32_t d = 0; d < drawCount; d++) { out.materials[2u * d] = materials[d].albedoTexture; out.materials[2u * d + 1u] = materials[d].specularTexture; }
-    out.textures.resize((size_t)textureCount * 4u);
-    out.texels.reserve((size_t)total);
-    for (uint32_t t = 0; t < textureCount; t++) {
-        const SceneTexture& tex = textures[t];
-        const pp::Texture entry{(uint32_t)out.texels.size(), tex.width, tex.height, tex.mipCount ? tex.mipCount : pp::fullMipCount(tex.width, tex.height)};
-        std::memcpy(out.textures.data() + (size_t)t * 4u, &entry, sizeof(entry));
-        size_t given = 0;
-        for (uint32_t l = 0; l < std::max(1u, tex.mipCount); l++) given += (size_t)std::max(1u, tex.width >> l) * std::max(1u, tex.height >> l);
-        out.texels.insert(out.texels.end(), tex.texels, tex.texels + given);
-        if (tex.mipCount == 0) appendMipChain(out.texels, tex.width, tex.height);
+    packTextureStore(textures, textureCount, total, out.textures, out.texels);
+    return out;
+}
+
+// everything is validated before anything is built
+PackedShadowCutouts packShadowCasterCutouts(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts,
+                                            uint32_t drawCount, const uint32_t* casterMeshVertexCounts, uint32_t casterMeshCount, uint32_t casterDrawCount) {
+    namespace pp = plr::prepass;
+    const std::string call = "setShadowCasterCutouts";
+    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
+    if (casterDrawCount == 0) refuse("no casters set (plrf_set_shadow_casters comes first)");
+    if (meshCount != casterMeshCount) refuse("mesh count " + std::to_string(meshCount) + " differs from the mesh count " + std::to_string(casterMeshCount) + " of the casters");
+    if (drawCount != casterDrawCount) refuse("draw count " + std::to_string(drawCount) + " differs from the draw count " + std::to_string(casterDrawCount) + " of the casters");
+    if (!textures || !cutouts) refuse("textures or cutouts are null");
+    const uint64_t total = validateTextures(textures, textureCount, refuse);
+    PackedShadowCutouts out;
+    for (uint32_t d = 0; d < drawCount; d++) {
+        if (cutouts[d].albedoTexture != kNoSceneTexture && cutouts[d].albedoTexture >= textureCount)
+            refuse("texture index out of range: draw " + std::to_string(d) + " names texture " + std::to_string(cutouts[d].albedoTexture) + " of " + std::to_string(textureCount));
+        if (cutouts[d].alphaCutoff > 255u)
+            refuse("cutoff out of range: draw " + std::to_string(d) + " has " + std::to_string(cutouts[d].alphaCutoff) + ", a cutoff code is 0 (opaque) .. 255");
+        out.tested = out.tested || cutouts[d].alphaCutoff != pp::kAlphaCutoffOpaque;
     }
+    if (total > pp::kMaxTexels) refuse("too many texels: " + std::to_string(total) + " in all levels of all textures, at most 2^28");
+    out.uvs = packUvs(meshUvs, meshCount, casterMeshVertexCounts, refuse);
+    out.materials.resize((size_t)drawCount * 2u);
+    for (uint32_t d = 0; d < drawCount; d++) { out.materials[2u * d] = cutouts[d].albedoTexture; out.materials[2u * d + 1u] = cutouts[d].alphaCutoff; }
+    packTextureStore(textures, textureCount, total, out.textures, out.texels);
     return out;
 }
 

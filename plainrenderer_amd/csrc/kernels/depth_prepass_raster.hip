@@ -82,7 +82,8 @@
 //     counts sub-triangles with a non-empty box.
 //   freedom for the kernel: the result is a maximum, so a kernel may skip the alpha evaluation of a fragment whose key is not above the cell's current value; the
 //     image does not change. (There is no counter of discarded fragments: it would forbid exactly that.)
-//   sunShadow.frag's alpha test is not part of this pass: shadow casters have no UVs or materials, and a cutout casts its quad's shadow.
+//   sunShadow.frag's alpha test is not part of this pass: the shadow casters are another mesh set with UVs, textures and cutoffs of their own
+//   (kernels/sun_shadow_raster.hip, THE CUTOUT CONTRACT; plrf_set_shadow_caster_cutouts).
 //
 // Two kernels. SET-UP: a lane per triangle finds its draw (block-wide prefix sum, LDS bisection), transforms, clips (the polygon lives in LDS, a column per lane),
 // projects, snaps, culls and boxes; the block's sub-triangles are appended through one 64-bit atomic per block to a dense array of 4-byte tile rectangles and an

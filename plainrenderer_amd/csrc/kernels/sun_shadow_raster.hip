@@ -1,6 +1,7 @@
 // "sunShadowRaster.comp": the sun shadow cascades as a compute pass - RenderFrontend::renderSunShadowCascades (RenderFrontend.cpp:354, 760-774; pass description
-// :1565-1590; sunShadow.vert / sunShadow.frag) for opaque casters: depth only, orthographic, one Depth16 target per execution. One kernel family serves both math
-// modes: every decision is an integer one and the float part is a dozen IEEE operations per fragment.
+// :1565-1590; sunShadow.vert / sunShadow.frag): depth only, orthographic, one Depth16 target per execution, opaque casters and alpha-tested cutouts. One kernel
+// family serves both math modes: every decision is an integer one and the float part is a dozen IEEE operations per fragment (and, for a cutout's fragment, fp64
+// operations in a fixed order).
 // PLR_BUILD_FLAGS: -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt
 //
 // THE RASTERISATION CONTRACT (DESIGN.md "Sun shadow cascades as a compute pass"; tests/shadow_raster_reference.py implements it independently and every texel
@@ -26,15 +27,43 @@
 //     vertex depths whose difference overflows, times a zero weight - stores code 0, +inf stores 65535; code = rint(zf * 65535) as uint16
 //   cleared to 0, depth test GreaterEqual (RenderPass.cpp:105, :1574): a texel is the MAXIMUM code of its fragments, 0 without any. Every texel of the map is
 //     written by every execution: the clear is part of the pass.
-//   sunShadow.frag's alpha test is left out - casters are opaque: its anisotropic repeat sampler is implementation-defined and material textures are no input here.
+//   sunShadow.frag's alpha test (:17-21) is the clause below, of an execution with textureCount > 0; without it casters are opaque.
+//
+// THE CUTOUT CONTRACT (DESIGN.md "Alpha-tested cutout casters in the sun shadow raster"; tests/shadow_alpha_reference.py implements it independently, bit for
+// bit). Everything above stands; one clause is added. fp64 IEEE without contraction where fp64 is named.
+//   texture store: the prepass's (DESIGN.md "The sampling contract", Texture store): `texels` RGBA8 words, R in the low byte, levels back to back and unpadded;
+//     `textures` {texelOffset, width, height, mipCount}; an entry is usable when 1 <= width, height <= 16384 and 1 <= mipCount <= floor(log2(max(width,
+//     height))) + 1; a texel whose 64-bit address is outside `texels` reads 0
+//   uvs: 2 floats per vertex, indexed like positions (index + vertexOffset); a vertex outside `uvs` has (0, 0)
+//   casterMaterials: {albedoTexture, cutoff} per draw; c = min(cutoff, 256). c = 0: the draw is opaque and never sampled. A draw whose albedoTexture is
+//     0xffffffff, is >= textureCount or names an unusable entry has the alpha code 255 everywhere (shadow draws have no constant albedo word): opaque for
+//     c <= 255, nothing for c = 256
+//   UV of a fragment (no perspective: the pass is affine): with l1, l2 exactly the fp32 weights of the depth clause, u = (u0 + (double)l1 (u1 - u0)) +
+//     (double)l2 (u2 - u0) in fp64, the differences taken in fp64 from the widened floats; v likewise. If u or v is not finite, or |.| >= 2^20, both are 0 for
+//     the taps
+//   level: one per (triangle, texture). With the walk's integer steps sx20 = -256 (Y0 - Y2), sx01 = -256 (Y1 - Y0), sy20 = 256 (X0 - X2), sy01 = 256 (X1 - X0)
+//     and A, each converted to fp64 (nearest even): dudx = ((double)sx20 / (double)A) (u1 - u0) + ((double)sx01 / (double)A) (u2 - u0), dvdx with v, dudy and
+//     dvdy with sy. ax = (dudx W_0, dvdx H_0), ay likewise, rx = ax.x^2 + ax.y^2, ry likewise, rho2 = rx > ry ? rx : ry; r = (float)rho2; lod = 0.5f
+//     det_log2f(r) - the bias is 0: sunShadow.frag:18 calls texture() without g_mipBias -; !(lod > 0) -> 0; lod > mipCount - 1 -> that; q = (int)floorf(lod 256
+//     + 0.5f), L0 = q >> 8, fw = q & 255, L1 = min(L0 + 1, mipCount - 1). The gradient is taken from the raw UVs, before the validity rule
+//   alpha of a fragment: bits 24 - 31 of what the sampling contract's Taps clause yields for (u, v) at L0, L1, fw: per level Tu = (int64)floor((u W - 0.5) 256 +
+//     0.5) in fp64, x0 = Tu >> 8, fx = Tu & 255, x1 = x0 + 1, both wrapped to [0, W) by a non-negative modulo, y likewise; S_l = (256 - fx)(256 - fy) a00 +
+//     fx (256 - fy) a10 + (256 - fx) fy a01 + fx fy a11; S = (256 - fw) S_L0 + fw S_L1; alpha = (S + 2^23 - 1 + ((S >> 24) & 1)) >> 24
+//   visibility: a texel is the maximum code over its fragments that pass coverage AND alpha >= c, 0 without any: still an order-independent maximum. submitted,
+//     drawn and guardBandRejects do not depend on alpha, and there is no counter of discarded fragments: a fragment whose code is not above its cell's
+//     current value need not be sampled
+//   deviations from the reference: isotropic trilinear filtering for g_sampler_anisotropicRepeat; l is the depth's fp32 weight, not an exact plane
 //
 // Two kernels. SET-UP: a lane per triangle finds its draw, transforms, snaps, culls and boxes; survivors are appended through a cursor (one atomic per block) to a dense
 // array of 4-byte tile rectangles and an array of set-up records (order free: the result is a maximum). TILES: a 256-thread block per 64 x 64 tile keeps the tile as
 // 4096 words of LDS; each wave scans the rectangles and walks those that touch its tile; LDS atomic max; the block then stores its tile as Depth16 rows. Every tile
 // scans every rectangle: no bins in this version. The draw lookup and the record are device/raster_setup.h's, the scan, the walk and a fragment's coverage and
 // depth device/raster_tile_walk.h's, both shared with "depthPrepassRaster.comp"; this file holds the transform, the block's append, what becomes of a fragment
-// (clamp, encode, maximum), the tile's store and the launcher.
+// (clamp, encode, alpha test, maximum), the tile's store and the launcher. Both kernels are templates over kAlphaTest, picked by textureCount; the `false`
+// instantiations hold none of the cutout code. The tested set-up stores everything that depends on the triangle alone (cutoff, level sizes, first texel,
+// fw, the three UVs) behind the set-up record (128 bytes per record instead of 80); only u, v and the taps are per fragment.
 #include <algorithm>
+#include <type_traits>
 
 #include "../backend.h"
 #include "../device/detmath.h"
@@ -51,15 +80,82 @@ struct SetupParams {
     uint32_t cascade, drawCount, triangleCount, capacity, transformCount, vertexCount, indexCount;
     int32_t res;
 };
+// a tested execution's set-up: `s.records` is null, the 128-byte records go to `records`
+struct CutoutSetupParams {
+    SetupParams s;
+    const float* uvs; const CasterMaterial* materials; const Texture* textures; CutoutRecord* records;
+    uint64_t uvVertexCount;
+    uint32_t textureCount;
+};
+PLR_DI const SetupParams& plainParams(const SetupParams& a) { return a; }
+PLR_DI const SetupParams& plainParams(const CutoutSetupParams& a) { return a.s; }
+PLR_DI SetupRecord& setupOf(SetupRecord& r) { return r; }
+PLR_DI SetupRecord& setupOf(CutoutRecord& r) { return r.s; }
 
-__global__ __launch_bounds__(256) void sunShadowSetupKernel(SetupParams p) {
+// the table entry `index` names when it is usable: inside the table, 1 <= width, height <= 16384, 1 <= mipCount <= floor(log2(max(width, height))) + 1
+PLR_DI bool usableTexture(const Texture* textures, uint32_t textureCount, uint32_t index, Texture* out) {
+    if (index == kNoTexture || index >= textureCount) return false;
+    const Texture t = textures[index];
+    if (t.width < 1u || t.height < 1u || t.width > kMaxTextureSize || t.height > kMaxTextureSize) return false;
+    if (t.mipCount < 1u || t.mipCount > 32u - (uint32_t)__clz(max(t.width, t.height))) return false;
+    *out = t;
+    return true;
+}
+
+// what the alpha of a fragment of this triangle needs beyond its weights (the cutout contract: material, UVs, level): once per record. v: the three vertices
+PLR_DI void cutoutOfTriangle(const CutoutSetupParams& p, uint32_t draw, const uint64_t v[3], CutoutRecord& r) {
+    r.test = kAlphaCutoffOpaque;
+    r.size0 = r.size1 = r.base0Low = r.base0High = r.pad = 0u;
+    r.u0 = r.v0 = r.u1 = r.v1 = r.u2 = r.v2 = 0.f;
+    const CasterMaterial m = p.materials[draw]; // (draw < drawCount, and the launcher checked drawCount entries)
+    const uint32_t c = min(m.cutoff, kAlphaCutoffDiscardAll);
+    if (c == kAlphaCutoffOpaque) return;
+    if (c == kAlphaCutoffDiscardAll) { r.test = kAlphaCutoffDiscardAll; return; } // no alpha code reaches 256, sampled or constant
+    Texture tex;
+    if (!usableTexture(p.textures, p.textureCount, m.albedoTexture, &tex)) return; // alpha 255 everywhere: opaque for c <= 255
+    float uv[6];
+    for (int k = 0; k < 3; k++) { // a vertex outside `uvs` has (0, 0)
+        const bool inside = v[k] < p.uvVertexCount;
+        uv[2 * k] = inside ? p.uvs[v[k] * 2u] : 0.f;
+        uv[2 * k + 1] = inside ? p.uvs[v[k] * 2u + 1u] : 0.f;
+    }
+    const SetupRecord& s = r.s;
+    const double A = (double)s.area;
+    const double sx20 = (double)(-256ll * (int64_t)(s.y0 - s.y2)), sx01 = (double)(-256ll * (int64_t)(s.y1 - s.y0));
+    const double sy20 = (double)(256ll * (int64_t)(s.x0 - s.x2)), sy01 = (double)(256ll * (int64_t)(s.x1 - s.x0));
+    const double du1 = (double)uv[2] - (double)uv[0], du2 = (double)uv[4] - (double)uv[0];
+    const double dv1 = (double)uv[3] - (double)uv[1], dv2 = (double)uv[5] - (double)uv[1];
+    const double dudx = (sx20 / A) * du1 + (sx01 / A) * du2, dvdx = (sx20 / A) * dv1 + (sx01 / A) * dv2;
+    const double dudy = (sy20 / A) * du1 + (sy01 / A) * du2, dvdy = (sy20 / A) * dv1 + (sy01 / A) * dv2;
+    const double w0 = (double)tex.width, h0 = (double)tex.height;
+    const double axx = dudx * w0, axy = dvdx * h0, ayx = dudy * w0, ayy = dvdy * h0;
+    const double rx = axx * axx + axy * axy, ry = ayx * ayx + ayy * ayy;
+    const double rho2 = rx > ry ? rx : ry;
+    float lod = 0.5f * det_log2f((float)rho2); // bias 0
+    if (!(lod > 0.f)) lod = 0.f;
+    const float top = (float)(tex.mipCount - 1u);
+    if (lod > top) lod = top;
+    const int q = (int)__builtin_floorf(lod * 256.f + 0.5f);
+    const int L0 = q >> 8, L1 = min(L0 + 1, (int)tex.mipCount - 1);
+    uint64_t base = tex.texelOffset;
+    for (int l = 0; l < L0; l++) base += (uint64_t)max(1u, tex.width >> l) * (uint64_t)max(1u, tex.height >> l);
+    r.test = c | ((uint32_t)(q & 255) << 16) | (L1 != L0 ? 1u << 24 : 0u);
+    r.size0 = max(1u, tex.width >> L0) | (max(1u, tex.height >> L0) << 16); // (a level is at most 16384 wide and high: 15 bits)
+    r.size1 = max(1u, tex.width >> L1) | (max(1u, tex.height >> L1) << 16);
+    r.base0Low = (uint32_t)base; r.base0High = (uint32_t)(base >> 32);
+    r.u0 = uv[0]; r.v0 = uv[1]; r.u1 = uv[2]; r.v1 = uv[3]; r.u2 = uv[4]; r.v2 = uv[5];
+}
+
+template <bool kAlphaTest>
+__global__ __launch_bounds__(256) void sunShadowSetupKernel(std::conditional_t<kAlphaTest, CutoutSetupParams, SetupParams> args) {
+    const SetupParams& p = plainParams(args);
     const uint32_t t = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
     const rastercov::TriangleSlot found = rastercov::drawOfTriangle(p.draws, p.drawCount, p.triangleCount, t);
     Draw draw{};
     if (found.found) draw = p.draws[found.draw];
     bool reject = false, survivor = false;
-    SetupRecord rec{};
+    std::conditional_t<kAlphaTest, CutoutRecord, SetupRecord> rec{};
     uint32_t rect = 0;
     if (found.found) {
         const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)found.local * 3u;
@@ -96,7 +192,9 @@ __global__ __launch_bounds__(256) void sunShadowSetupKernel(SetupParams p) {
                 z[k] = cz;
             }
             if (!inside) reject = true;
-            else survivor = rastercov::setupTriangle(X, Y, z, p.res, p.res, &rec, &rect);
+            else survivor = rastercov::setupTriangle(X, Y, z, p.res, p.res, &setupOf(rec), &rect);
+            if constexpr (kAlphaTest)
+                if (survivor) cutoutOfTriangle(args, found.draw, v, rec);
         }
     }
     // one 64-bit atomic per block hands it a run of slots (the low word is the cursor) and counts its triangles (the high word): a frame's waves adding to
@@ -120,7 +218,8 @@ __global__ __launch_bounds__(256) void sunShadowSetupKernel(SetupParams p) {
         const uint32_t slot = base + (uint32_t)__popcll(survivorMask & ((1ull << lane) - 1ull));
         if (slot < p.capacity) { // (always: the cursor counts at most triangleCount survivors and the launcher sized the arrays for that many)
             p.rects[slot] = rect;
-            p.records[slot] = rec;
+            if constexpr (kAlphaTest) args.records[slot] = rec;
+            else p.records[slot] = rec;
         }
     }
 }
@@ -131,6 +230,16 @@ struct TileParams {
     uint32_t capacity;
     int32_t res;
 };
+// a tested execution's tiles: `t.records` is null
+struct CutoutTileParams {
+    TileParams t;
+    const CutoutRecord* records; const uint32_t* texels;
+    uint64_t texelCount;
+};
+PLR_DI const TileParams& plainParams(const TileParams& a) { return a; }
+PLR_DI const TileParams& plainParams(const CutoutTileParams& a) { return a.t; }
+PLR_DI const SetupRecord* recordsOf(const TileParams& a) { return a.records; }
+PLR_DI const CutoutRecord* recordsOf(const CutoutTileParams& a) { return a.records; }
 
 // what becomes of a fragment: depth clamp, Depth16 code, maximum. tile: the block's 64 x 64 words
 struct ShadowWalk : rastercov::PlainWalk {
@@ -146,7 +255,72 @@ struct ShadowWalk : rastercov::PlainWalk {
     }
 };
 
-__global__ __launch_bounds__(256) void sunShadowTileKernel(TileParams p) {
+// t mod n in [0, n) for |t| < 2^35 and 1 <= n <= 2^14: t / n is an integer or at least 2^-14 away from one, 16 times the spacing of fp64 at 2^34, so the floor
+// of the fp64 quotient is the exact one (|u| < 2^20 and W <= 2^14 bound Tu >> 8 by 2^34)
+PLR_DI int wrapRepeat(int64_t t, int n) {
+    const double q = __builtin_floor((double)t / (double)n);
+    return (int)(t - (int64_t)q * (int64_t)n);
+}
+
+// the alpha channel's weighted sum over the four taps of one level (w x h texels, the first at `base`); every address in 64 bits and checked before its load
+PLR_DI uint32_t alphaTaps(const uint32_t* texels, uint64_t texelCount, uint64_t base, int w, int h, double u, double v) {
+    const int64_t Tu = (int64_t)__builtin_floor((u * (double)w - 0.5) * 256.0 + 0.5), Tv = (int64_t)__builtin_floor((v * (double)h - 0.5) * 256.0 + 0.5);
+    const uint32_t fx = (uint32_t)(Tu & 255), fy = (uint32_t)(Tv & 255);
+    const int x0 = wrapRepeat(Tu >> 8, w), y0 = wrapRepeat(Tv >> 8, h);
+    const int x1 = x0 + 1 == w ? 0 : x0 + 1, y1 = y0 + 1 == h ? 0 : y0 + 1;
+    auto fetch = [&](int x, int y) {
+        const uint64_t at = base + (uint64_t)y * (uint64_t)w + (uint64_t)x;
+        return (at < texelCount ? texels[at] : 0u) >> 24;
+    };
+    return ((256u - fx) * (256u - fy) * fetch(x0, y0) + fx * (256u - fy) * fetch(x1, y0)) + ((256u - fx) * fy * fetch(x0, y1) + fx * fy * fetch(x1, y1));
+}
+
+// the alpha code of the fragment of record r with the depth's weights l1, l2 (the cutout contract)
+PLR_DI uint32_t fragmentAlpha(const CutoutRecord& r, const uint32_t* texels, uint64_t texelCount, float l1, float l2) {
+    const double u0 = (double)r.u0, v0 = (double)r.v0;
+    double u = (u0 + (double)l1 * ((double)r.u1 - u0)) + (double)l2 * ((double)r.u2 - u0);
+    double v = (v0 + (double)l1 * ((double)r.v1 - v0)) + (double)l2 * ((double)r.v2 - v0);
+    if (!(__builtin_fabs(u) < 1048576.0 && __builtin_fabs(v) < 1048576.0)) u = v = 0.0; // (a NaN fails the comparison)
+    const uint32_t fw = (r.test >> 16) & 255u;
+    const uint64_t base = (uint64_t)r.base0Low | ((uint64_t)r.base0High << 32);
+    const int w = (int)(r.size0 & 0xffffu), h = (int)(r.size0 >> 16);
+    const uint32_t s0 = alphaTaps(texels, texelCount, base, w, h, u, v);
+    uint32_t s1 = 0u;
+    if (fw != 0u) // (with fw == 0 the upper level has no weight; with L1 == L0 it is the same level again)
+        s1 = alphaTaps(texels, texelCount, (r.test >> 24) & 1u ? base + (uint64_t)w * (uint64_t)h : base, (int)(r.size1 & 0xffffu), (int)(r.size1 >> 16), u, v);
+    const uint32_t S = (256u - fw) * s0 + fw * s1;
+    return (S + 0x7fffffu + ((S >> 24) & 1u)) >> 24;
+}
+
+// a tested execution's fragment: the same, and a record with a cutoff samples its alpha before the maximum
+struct CutoutWalk : rastercov::PlainWalk {
+    uint32_t* tile;
+    int ox, oy;
+    const uint32_t* texels;
+    uint64_t texelCount;
+    uint32_t myCutoff; // of this lane's record of the step
+    static PLR_DI const SetupRecord& setup(const CutoutRecord& r) { return r.s; }
+    PLR_DI void beginStep(const CutoutRecord& rr, bool hit, bool, int, int, int, int) { myCutoff = hit ? rr.test & 0x1ffu : kAlphaCutoffOpaque; }
+    PLR_DI bool lanePath() const { return myCutoff != kAlphaCutoffDiscardAll; } // a record with c = 256 is dropped whole
+    PLR_DI bool beginStamps(int src) { return (uint32_t)__builtin_amdgcn_readlane((int)myCutoff, src) != kAlphaCutoffDiscardAll; }
+    template <class D> PLR_DI void fragment(const CutoutRecord& r, int, int px, int py, D&& depthAt) {
+        float zf, weights[2];
+        if (!depthAt(&zf, weights)) return;
+        zf = fminf(fmaxf(zf, 0.f), 1.f);
+        const uint32_t code = (uint32_t)__builtin_rintf(zf * 65535.f);
+        uint32_t* cell = &tile[(py - oy) * kTileSize + (px - ox)];
+        const uint32_t c = r.test & 0x1ffu;
+        if (c != kAlphaCutoffOpaque) { // the one branch: every other record's fragment goes the opaque way
+            if (code <= *cell) return; // a filter only: the atomic below decides
+            if (fragmentAlpha(r, texels, texelCount, weights[0], weights[1]) < c) return;
+        }
+        atomicMax(cell, code);
+    }
+};
+
+template <bool kAlphaTest>
+__global__ __launch_bounds__(256) void sunShadowTileKernel(std::conditional_t<kAlphaTest, CutoutTileParams, TileParams> args) {
+    const TileParams& p = plainParams(args);
     __shared__ uint32_t tile[kTileSize * kTileSize];
     __shared__ uint32_t hitQueue[4][256]; // per wave: the entries of the current step that touch the tile
     const int tx = (int)blockIdx.x, ty = (int)blockIdx.y;
@@ -158,8 +332,13 @@ __global__ __launch_bounds__(256) void sunShadowTileKernel(TileParams p) {
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.header->drawn = n;
     // the kernel's time in a busy tile is the hits' arithmetic
     const rastercov::TileWindow window{tx, ty, ox, oy, min(ox + kTileSize - 1, p.res - 1), min(oy + kTileSize - 1, p.res - 1)};
-    ShadowWalk walk{{}, tile, ox, oy};
-    rastercov::rasteriseTile(p.rects, p.records, n, window, hitQueue[wave], walk);
+    if constexpr (kAlphaTest) {
+        CutoutWalk walk{{}, tile, ox, oy, args.texels, args.texelCount, kAlphaCutoffOpaque};
+        rastercov::rasteriseTile(p.rects, args.records, n, window, hitQueue[wave], walk);
+    } else {
+        ShadowWalk walk{{}, tile, ox, oy};
+        rastercov::rasteriseTile(p.rects, p.records, n, window, hitQueue[wave], walk);
+    }
     __syncthreads();
     // the tile as Depth16 rows: eight texels per 16-byte store where the eight lie inside the map and the address allows, texel by texel at ragged edges
     const bool rowsAligned = (p.res & 7) == 0;
@@ -183,8 +362,9 @@ static int launchSunShadowRaster(const PassCtx& c) {
     const uint32_t cascade = c.specUint(kCascadeIndexConstant, 0u);
     if (cascade >= 4u) return c.fail(-1, "sunShadowRaster: cascadeIndex (specialisation constant 0) is " + std::to_string(cascade) + ", a sunShadowInfo block holds 4 light matrices");
     if (c.push.size() < sizeof(PushConstants)) return c.fail(-1, "sunShadowRaster: push constants {drawCount, triangleCount} missing");
-    PushConstants pc;
-    std::memcpy(&pc, c.push.data(), sizeof(pc));
+    CutoutPushConstants pc{};
+    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0
+    const bool tested = pc.textureCount != 0u;
     if (c.dispatch[0] != 1u || c.dispatch[1] != 1u || c.dispatch[2] != 1u || c.base[0] != 0u || c.base[1] != 0u)
         return c.fail(-1, "sunShadowRaster: the dispatch is {1, 1, 1} (the launcher derives its grids from the push constants and the map)");
     if (int rc = c.needSbuf(kSunShadowInfoBinding, sizeof(ShadowCascadeInfo), "sunShadowRaster sunShadowInfo")) return rc;
@@ -192,7 +372,17 @@ static int launchSunShadowRaster(const PassCtx& c) {
     if (int rc = c.needSbuf(kPositionBinding, 0, "sunShadowRaster positions (3 floats per vertex)")) return rc;
     if (int rc = c.needSbuf(kIndexBinding, 0, "sunShadowRaster indices (uint32 triangle list)")) return rc;
     if (int rc = c.needSbuf(kDrawBinding, (size_t)pc.drawCount * sizeof(Draw), "sunShadowRaster draws {firstIndex, indexCount, vertexOffset, transformIndex}")) return rc;
-    if (int rc = c.needSbuf(kScratchBinding, scratchBytes(pc.triangleCount), "sunShadowRaster scratch (64 + 16 ceil(triangleCount / 4) + 80 triangleCount bytes)")) return rc;
+    if (!tested) {
+        if (int rc = c.needSbuf(kScratchBinding, scratchBytes(pc.triangleCount), "sunShadowRaster scratch (64 + 16 ceil(triangleCount / 4) + 80 triangleCount bytes)")) return rc;
+    } else {
+        if (int rc = c.needSbuf(kScratchBinding, cutoutScratchBytes(pc.triangleCount),
+                                "sunShadowRaster scratch of an execution with textureCount > 0 (64 + 16 ceil(triangleCount / 4) + 128 triangleCount bytes)"))
+            return rc;
+        if (int rc = c.needSbuf(kUvBinding, 0, "sunShadowRaster uvs (binding 6: 2 floats per vertex)")) return rc;
+        if (int rc = c.needSbuf(kCasterMaterialBinding, (size_t)pc.drawCount * sizeof(CasterMaterial), "sunShadowRaster casterMaterials (binding 7: {albedoTexture, cutoff} per draw)")) return rc;
+        if (int rc = c.needSbuf(kTextureBinding, (size_t)pc.textureCount * sizeof(Texture), "sunShadowRaster textures (binding 8: {texelOffset, width, height, mipCount})")) return rc;
+        if (int rc = c.needSbuf(kTexelBinding, 0, "sunShadowRaster texels (binding 9: RGBA8, every texture's levels back to back)")) return rc;
+    }
     if (c.sbuf[kScratchBinding].readOnly) return c.fail(-4, "sunShadowRaster: the scratch buffer (binding 5) is bound read-only");
     if (int rc = c.needStorage(kMapBinding, F_D16, "sunShadowRaster shadow map")) return rc;
     const ImgView map = c.storage[kMapBinding];
@@ -201,28 +391,49 @@ static int launchSunShadowRaster(const PassCtx& c) {
     if ((pc.drawCount == 0u) != (pc.triangleCount == 0u)) return c.fail(-1, "sunShadowRaster: drawCount and triangleCount must both be zero or both be non-zero");
     for (int b : {kTransformBinding, kPositionBinding, kIndexBinding, kDrawBinding, kSunShadowInfoBinding})
         if (c.sbuf[b].ptr == c.sbuf[kScratchBinding].ptr) return c.fail(-4, "sunShadowRaster: the scratch buffer is also bound as an input");
+    if (tested)
+        for (int b : {kUvBinding, kCasterMaterialBinding, kTextureBinding, kTexelBinding})
+            if (c.sbuf[b].ptr == c.sbuf[kScratchBinding].ptr)
+                return c.fail(-4, "sunShadowRaster: the scratch buffer is also bound as an input (binding " + std::to_string(b) + ")");
 
     uint8_t* scratch = (uint8_t*)c.sbuf[kScratchBinding].ptr;
     if (hipMemsetAsync(scratch, 0, sizeof(ScratchHeader), c.stream) != hipSuccess) return c.fail(-2, "sunShadowRaster: clearing the scratch header failed");
     if (pc.triangleCount) {
-        SetupParams s{};
+        CutoutSetupParams cs{};
+        SetupParams& s = cs.s;
         s.info = (const ShadowCascadeInfo*)c.sbuf[kSunShadowInfoBinding].ptr; s.transforms = (const float*)c.sbuf[kTransformBinding].ptr;
         s.positions = (const float*)c.sbuf[kPositionBinding].ptr; s.indices = (const uint32_t*)c.sbuf[kIndexBinding].ptr; s.draws = (const Draw*)c.sbuf[kDrawBinding].ptr;
-        s.header = (ScratchHeader*)scratch; s.rects = (uint32_t*)(scratch + rectOffset()); s.records = (SetupRecord*)(scratch + recordOffset(pc.triangleCount));
+        s.header = (ScratchHeader*)scratch; s.rects = (uint32_t*)(scratch + rectOffset());
         s.cascade = cascade; s.drawCount = pc.drawCount; s.triangleCount = pc.triangleCount; s.capacity = pc.triangleCount;
         s.transformCount = (uint32_t)std::min<size_t>(c.sbuf[kTransformBinding].size / 64u, 0xffffffffu);
         s.vertexCount = (uint32_t)std::min<size_t>(c.sbuf[kPositionBinding].size / 12u, 0xffffffffu);
         s.indexCount = (uint32_t)std::min<size_t>(c.sbuf[kIndexBinding].size / 4u, 0xffffffffu);
         s.res = map.w;
-        sunShadowSetupKernel<<<divUp(pc.triangleCount, 256u), 256, 0, c.stream>>>(s);
+        if (tested) {
+            cs.uvs = (const float*)c.sbuf[kUvBinding].ptr; cs.materials = (const CasterMaterial*)c.sbuf[kCasterMaterialBinding].ptr;
+            cs.textures = (const Texture*)c.sbuf[kTextureBinding].ptr; cs.records = (CutoutRecord*)(scratch + recordOffset(pc.triangleCount));
+            cs.uvVertexCount = c.sbuf[kUvBinding].size / 8u; cs.textureCount = pc.textureCount;
+            sunShadowSetupKernel<true><<<divUp(pc.triangleCount, 256u), 256, 0, c.stream>>>(cs);
+        } else {
+            s.records = (SetupRecord*)(scratch + recordOffset(pc.triangleCount));
+            sunShadowSetupKernel<false><<<divUp(pc.triangleCount, 256u), 256, 0, c.stream>>>(s);
+        }
         PLR_CHECK_LAUNCH(c);
         c.splitTiming("set-up");
     }
-    TileParams t{};
-    t.header = (ScratchHeader*)scratch; t.rects = (const uint32_t*)(scratch + rectOffset()); t.records = (const SetupRecord*)(scratch + recordOffset(pc.triangleCount));
+    CutoutTileParams ct{};
+    TileParams& t = ct.t;
+    t.header = (ScratchHeader*)scratch; t.rects = (const uint32_t*)(scratch + rectOffset());
     t.map = (uint16_t*)map.ptr; t.capacity = pc.triangleCount; t.res = map.w;
     const unsigned tiles = divUp((unsigned)map.w, (unsigned)kTileSize);
-    sunShadowTileKernel<<<dim3(tiles, tiles), 256, 0, c.stream>>>(t);
+    if (tested) {
+        ct.records = (const CutoutRecord*)(scratch + recordOffset(pc.triangleCount)); ct.texels = (const uint32_t*)c.sbuf[kTexelBinding].ptr;
+        ct.texelCount = c.sbuf[kTexelBinding].size / 4u;
+        sunShadowTileKernel<true><<<dim3(tiles, tiles), 256, 0, c.stream>>>(ct);
+    } else {
+        t.records = (const SetupRecord*)(scratch + recordOffset(pc.triangleCount));
+        sunShadowTileKernel<false><<<dim3(tiles, tiles), 256, 0, c.stream>>>(t);
+    }
     PLR_CHECK_LAUNCH(c);
     return 0;
 }

@@ -77,6 +77,10 @@ class PlrfSceneMaterial(C.Structure):
     _fields_ = [("albedo_texture", C.c_uint32), ("specular_texture", C.c_uint32)]
 
 
+class PlrfShadowCutout(C.Structure):
+    _fields_ = [("albedo_texture", C.c_uint32), ("alpha_cutoff", C.c_uint32)]
+
+
 class PlrfPrepassRasterStats(C.Structure):
     _fields_ = [("triangles_submitted", C.c_uint64), ("triangles_clipped", C.c_uint64), ("subtriangles_drawn", C.c_uint64), ("rejects", C.c_uint64)]
 
@@ -298,6 +302,17 @@ class FramePipeline:
         a = np.ascontiguousarray(matrices, np.float32).reshape(-1, 16)
         self._check(self.lib.plrf_set_shadow_caster_transforms(self.handle, a.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(a.shape[0])))
 
+    def set_shadow_caster_cutouts(self, textures, mesh_uvs, cutouts):
+        """alpha-tested cutouts for the casters now set. textures: as for set_scene_textures (the casters keep their own copy); mesh_uvs: one n x 2 float32 array
+        or None per caster mesh; cutouts: one (albedo texture or NO_TEXTURE, alpha cutoff code 0 .. 255) per caster draw, 0: opaque, ALPHA_CUTOFF_REFERENCE = 128:
+        the reference's alpha < 0.5 -> discard. Copied; from the next frame on. No textures: the cutouts are removed. The pass culls front faces: a single-sided
+        card that faces the light is culled before it is tested"""
+        t, u, keep = self._texture_arguments(textures, mesh_uvs)
+        m = (PlrfShadowCutout * max(len(cutouts), 1))()
+        for k, (albedo, cutoff) in enumerate(cutouts):
+            m[k] = PlrfShadowCutout(int(albedo), int(cutoff))
+        self._check(self.lib.plrf_set_shadow_caster_cutouts(self.handle, t, C.c_uint32(len(textures)), u, C.c_uint32(len(mesh_uvs)), m, C.c_uint32(len(cutouts))))
+
     def shadow_raster_stats(self, cascade):
         """(triangles submitted, triangles drawn, guard-band rejects) of the last frame's execution for the cascade; waits for the GPU"""
         s = PlrfShadowRasterStats()
@@ -329,10 +344,9 @@ class FramePipeline:
         a = np.ascontiguousarray(matrices, np.float32).reshape(-1, 16)
         self._check(self.lib.plrf_set_scene_mesh_transforms(self.handle, a.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(a.shape[0])))
 
-    def set_scene_textures(self, textures, mesh_uvs, materials):
-        """textures: [(texels uint32 RGBA8 with R in the low byte, width, height, mip_count)] - mip_count levels back to back, or 0: level 0 only and the host builds
-        the full chain; mesh_uvs: one n x 2 float32 array or None per mesh of the scene; materials: one (albedo texture, specular texture) per draw, NO_TEXTURE for
-        the draw's constant word. Copied; from the next frame on. No textures: they are removed"""
+    @staticmethod
+    def _texture_arguments(textures, mesh_uvs):
+        """the plrf_scene_texture array and the UV pointer array of set_scene_textures / set_shadow_caster_cutouts, and the arrays they point into"""
         tex = [np.ascontiguousarray(t[0], np.uint32).reshape(-1) for t in textures]
         uvs = [None if u is None else np.ascontiguousarray(u, np.float32).reshape(-1, 2) for u in mesh_uvs]
         t = (PlrfSceneTexture * max(len(textures), 1))()
@@ -345,10 +359,17 @@ class FramePipeline:
         u = (C.POINTER(C.c_float) * max(len(uvs), 1))()
         for k, a in enumerate(uvs):
             u[k] = None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+        return t, u, (tex, uvs)
+
+    def set_scene_textures(self, textures, mesh_uvs, materials):
+        """textures: [(texels uint32 RGBA8 with R in the low byte, width, height, mip_count)] - mip_count levels back to back, or 0: level 0 only and the host builds
+        the full chain; mesh_uvs: one n x 2 float32 array or None per mesh of the scene; materials: one (albedo texture, specular texture) per draw, NO_TEXTURE for
+        the draw's constant word. Copied; from the next frame on. No textures: they are removed"""
+        t, u, keep = self._texture_arguments(textures, mesh_uvs)
         m = (PlrfSceneMaterial * max(len(materials), 1))()
         for k, (albedo, specular) in enumerate(materials):
             m[k] = PlrfSceneMaterial(int(albedo), int(specular))
-        self._check(self.lib.plrf_set_scene_textures(self.handle, t, C.c_uint32(len(textures)), u, C.c_uint32(len(uvs)), m, C.c_uint32(len(materials))))
+        self._check(self.lib.plrf_set_scene_textures(self.handle, t, C.c_uint32(len(textures)), u, C.c_uint32(len(mesh_uvs)), m, C.c_uint32(len(materials))))
 
     def set_scene_alpha_cutoffs(self, cutoffs):
         """one alpha cutoff code 0 .. 255 per draw of the scene (0: opaque, ALPHA_CUTOFF_REFERENCE = 128: the reference's alpha < 0.5 -> discard); needs textures.

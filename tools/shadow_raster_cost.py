@@ -1,6 +1,6 @@
 """What the sun shadow cascades cost as a compute pass ("sunShadowRaster.comp", plrf_set_shadow_casters) in bench.py's 4K frame.
 
-    python tools/shadow_raster_cost.py [--out FILE] [--frames N] [--rounds R] [--instances K]
+    python tools/shadow_raster_cost.py [--out FILE] [--frames N] [--rounds R] [--instances K] [--alpha]
 
 One process, one build. The casters are the three meshes of tests/shadow_raster_cases.py (box, uv_sphere, torus: 1496 triangles) instanced K times (default 202:
 about 100 k triangles) over the view frustum in front of bench.py's camera, rasterised into the frame's three 2048 x 2048 cascades with the uploaded light matrices.
@@ -11,6 +11,9 @@ about 100 k triangles) over the view frustum in front of bench.py's camera, rast
     rectangle list (entries x tiles) and its clear, not fragment work - the two runs together say which of the two bounds the kernel;
   * the frame with and without casters, alternately (--rounds blocks of --frames frames each, host clock around the submits and one wait; the uploaded shadow
     maps are restored in front of every block without casters, so both kinds of block shade the same maps each time).
+--alpha: every draw is an alpha-tested cutout (plrf_set_shadow_caster_cutouts): the meshes' own UVs, one 256 x 256 texture whose alpha is a 0 / 255 checker in
+cells of 32 texels with its full chain, cutoff 128 - the pass' tested instantiation, against the same scene without the switch.
+--rounds 0 leaves out the frame with and without casters.
 The report goes to stdout and to --out.
 """
 import argparse
@@ -38,6 +41,17 @@ def instances(cam, count, shrink=1.0):
         scale = rng.uniform(0.5, 2.0, 3) * (0.25 + d / 30.0) * shrink
         draws.append((k % 3, sc.affine(scale, rng.uniform(0, 6.28), rng.uniform(-1.0, 1.0), at)))
     return s["meshes"], draws
+
+
+def checker_cutouts(draw_count):
+    """the arguments of set_shadow_caster_cutouts under --alpha: (textures, mesh_uvs, cutouts)"""
+    from plainrenderer_amd import meshes
+    uvs = [meshes.box((1.0, 1.5, 0.75), subdiv=4, with_uvs=True)[2], meshes.uv_sphere(1.25, segments=28, rings=14, with_uvs=True)[2],
+           meshes.torus(1.5, 0.5, segments=24, sides=12, with_uvs=True)[2]]  # (the meshes of tests/shadow_raster_cases.py's mesh scene)
+    y, x = np.mgrid[0:256, 0:256]
+    alpha = np.where(((x // 32) + (y // 32)) % 2 == 0, 255, 0).astype(np.uint32)
+    texels = ((alpha << np.uint32(24)) | np.uint32(0x00808080)).reshape(-1)
+    return [(texels, 256, 256, 0)], uvs, [(0, 128)] * draw_count  # mip_count 0: the host builds the full chain
 
 
 def tile_hits(light, meshes, draws, res):
@@ -91,6 +105,7 @@ def main():
     ap.add_argument("--frames", type=int, default=40)
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--instances", type=int, default=202)
+    ap.add_argument("--alpha", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
     sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle")]
@@ -103,7 +118,8 @@ def main():
     fp = FramePipeline(be, W, H, shadow_map_res=RES)
     _, cams, inputs = bench.build_scene(args, "cuda:0", W, H, None)
     inputs.upload(fp)
-    lines = ["# python tools/shadow_raster_cost.py: bench.py's scene at %d x %d, cascades %d x %d, fast kernel set, %d frames per block" % (W, H, RES, RES, a.frames)]
+    lines = ["# python tools/shadow_raster_cost.py%s: bench.py's scene at %d x %d, cascades %d x %d, fast kernel set, %d frames per block"
+             % (" --alpha" if a.alpha else "", W, H, RES, RES, a.frames)]
     cursor = 1
     for i in range(args.warmup):
         fp.frame(cams[cursor + i], 1.0 / 60.0, 0.5)
@@ -115,6 +131,8 @@ def main():
     for label, shrink in (("meshes at scale", 1.0), ("meshes shrunk to 1 / 20", 0.05)):
         meshes, draws = instances(cams[1], a.instances, shrink)
         fp.set_shadow_casters(meshes, draws)
+        if a.alpha:
+            fp.set_shadow_caster_cutouts(*checker_cutouts(len(draws)))
         times = pass_times(be, fp, cams, cursor, a.frames)
         cursor += a.frames + 1
         lines.append("%s: %d draws" % (label, len(draws)))
@@ -139,12 +157,15 @@ def main():
         without_ms.append(timed_block(be, fp, cams, cursor + 1, a.frames))
         cursor += a.frames + 1
         fp.set_shadow_casters(meshes, draws)
+        if a.alpha:
+            fp.set_shadow_caster_cutouts(*checker_cutouts(len(draws)))
         fp.frame(cams[cursor], 1.0 / 60.0, 0.5)
         with_ms.append(timed_block(be, fp, cams, cursor + 1, a.frames))
         cursor += a.frames + 1
-    lines.append("frame without casters: " + ", ".join("%.4f" % v for v in without_ms) + " ms per frame (median %.4f)" % float(np.median(without_ms)))
-    lines.append("frame with casters:    " + ", ".join("%.4f" % v for v in with_ms) + " ms per frame (median %.4f)" % float(np.median(with_ms)))
-    lines.append("difference of the medians: %.1f us per frame for three cascades" % ((float(np.median(with_ms)) - float(np.median(without_ms))) * 1e3))
+    if a.rounds:
+        lines.append("frame without casters: " + ", ".join("%.4f" % v for v in without_ms) + " ms per frame (median %.4f)" % float(np.median(without_ms)))
+        lines.append("frame with casters:    " + ", ".join("%.4f" % v for v in with_ms) + " ms per frame (median %.4f)" % float(np.median(with_ms)))
+        lines.append("difference of the medians: %.1f us per frame for three cascades" % ((float(np.median(with_ms)) - float(np.median(without_ms))) * 1e3))
     text = "\n".join(lines) + "\n"
     sys.stdout.write(text)
     if a.out:
