@@ -294,7 +294,7 @@ int plrf_set_scene_meshes(void* pipeline, const plrf_scene_mesh* meshes, uint32_
 int plrf_set_scene_mesh_transforms(void* pipeline, const float* matrices16, uint32_t draw_count);
 /* ---- material textures of the scene meshes: depthPrepass.frag / triangle.frag's albedoTexture and specularTexture sampled per pixel with the interpolated UV and
  * g_mipBias (DESIGN.md "Material textures in the depth prepass": the sampling contract in integers and IEEE operations - repeat addressing, isotropic trilinear
- * filtering with 8 sub-texel and 8 level-fraction bits, forward-difference derivatives of the triangle's own plane, round half even; no normal map; the alpha test: plrf_set_scene_alpha_cutoffs below).
+ * filtering with 8 sub-texel and 8 level-fraction bits, forward-difference derivatives of the triangle's own plane, round half even; the alpha test: plrf_set_scene_alpha_cutoffs below; the normal map: plrf_set_scene_normal_maps below).
  * plrf_scene_texture: RGBA8 texels, R in the low byte, row-major; mip_count >= 1: that many levels back to back, level l being max(1, width >> l) x
  * max(1, height >> l); mip_count 0: level 0 only and the host builds the full chain, each texel the rounded mean (a + b + c + d + 2) >> 2 of the level below at
  * (min(2x, W - 1) | min(2x + 1, W - 1), min(2y, H - 1) | min(2y + 1, H - 1)). plrf_scene_material, one per draw: the texture an output samples, or PLRF_NO_TEXTURE
@@ -323,6 +323,28 @@ int plrf_set_scene_textures(void* pipeline, const plrf_scene_texture* textures, 
  * meshes: plrf_set_shadow_caster_cutouts below. */
 #define PLRF_ALPHA_CUTOFF_REFERENCE 128u
 int plrf_set_scene_alpha_cutoffs(void* pipeline, const uint32_t* cutoffs, uint32_t draw_count);
+/* ---- normal maps: triangle.frag:180-196 (shade with normalize(passTBN * normalTexelReconstructed)) as a sixth image of the depth prepass, "shadingNormal" (RGBA8,
+ * frame size; DESIGN.md "Normal maps in the depth prepass": the contract in fp64 IEEE operations). normal_textures[d]: PLRF_NO_TEXTURE or an index into the textures
+ * given to plrf_set_scene_textures; the texel is the sampling contract's word (same UV, level with g_mipBias, taps, round half even), R and G are x and y.
+ * decode PLRF_NORMAL_DECODE_REFERENCE: the reference's reconstruction as written, z = sqrt(1 - x x + 2 y) on the [0, 1] codes, n_t = 2 (x, y, z) - 1;
+ * PLRF_NORMAL_DECODE_UNIT: n_t = (2 x - 1, 2 y - 1, sqrt(max(0, 1 - n_t.x^2 - n_t.y^2))). The shading normal is normalize(T n_t.x + B n_t.y + N n_t.z) with the
+ * interpolated, not renormalised, per-vertex basis (each vector normalize(mat3(model) v)); where that is zero, and for a draw without a normal texture, it is the
+ * vertex normal of the "normal" image. mesh_tangents[k]: 3 floats per vertex of mesh k, NULL (the array or an entry): all (0, 0, 0). mesh_bitangents[k] likewise;
+ * NULL (the array or an entry): the host derives normalize(cross(tangent, normal)) per vertex in fp64 (ModelImport.cpp:184), (0, 0, 0) where the length is not a
+ * finite number > 0 - which needs a mesh that was given with normals.
+ * While normal maps are set the deferred shade reads "shadingNormal" where it read "normal"; the SDF trace and the GI filters keep "normal" (the reference's split:
+ * depthPrepass.frag:48 stores the vertex normal). Depth, motion, normal, albedo, specular and the counters never depend on normal maps. The image is created by
+ * the first successful call (plrf_get_image(.., "shadingNormal") fails before) and re-created by a resize.
+ * plrf_set_scene_normal_maps needs a scene with textures set; mesh_count and draw_count must be the scene's. Everything is copied and takes effect with the next
+ * frame, in call order. draw_count 0 removes them, and so does every plrf_set_scene_meshes and every plrf_set_scene_textures; they survive
+ * plrf_set_scene_mesh_transforms, plrf_set_scene_alpha_cutoffs, plrf_set_resolution and plrf_update_settings. PLR_ERR_INVALID_ARGUMENT, with a message that names
+ * the cause: no scene set, no textures set, a count mismatch, NULL normal_textures with a non-zero count, an index that is neither PLRF_NO_TEXTURE nor <
+ * texture_count, a non-finite tangent or bitangent (vertex and mesh are named), a decode other than 1 or 2, NULL bitangents with non-NULL tangents for a mesh
+ * given without normals. PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing. */
+#define PLRF_NORMAL_DECODE_REFERENCE 1u
+#define PLRF_NORMAL_DECODE_UNIT 2u
+int plrf_set_scene_normal_maps(void* pipeline, const float* const* mesh_tangents, const float* const* mesh_bitangents, uint32_t mesh_count,
+                               const uint32_t* normal_textures, uint32_t draw_count, uint32_t decode);
 /* ---- alpha-tested cutout casters: sunShadow.frag:17-21 (sample the albedo texture's alpha, discard below 0.5) for the mesh shadow casters (DESIGN.md
  * "Alpha-tested cutout casters in the sun shadow raster"). Casters are another mesh set than the scene's and keep their own copy of the textures:
  * plrf_scene_texture as above (mip_count 0: the host builds the chain), mesh_uvs[k]: 2 floats per vertex of caster mesh k, NULL (the array or an entry): all

@@ -13,10 +13,13 @@ namespace prepass {
 constexpr int kTransformBinding = 0, kPositionBinding = 1, kNormalBinding = 2, kIndexBinding = 3, kDrawBinding = 4, kScratchBinding = 5;                  // storage buffers
 constexpr int kUvBinding = 6, kMaterialBinding = 7, kTextureBinding = 8, kTexelBinding = 9; // storage buffers of a textured execution (textureCount > 0)
 constexpr int kAlphaCutoffBinding = 10; // storage buffer of an alpha-tested execution (alphaTest != 0): one uint32 cutoff code per draw
+constexpr int kTangentBinding = 11, kBitangentBinding = 12, kNormalMaterialBinding = 13; // storage buffers of a normal-mapped execution (normalMap != 0)
 constexpr int kDepthBinding = 0, kMotionBinding = 1, kNormalImageBinding = 2, kAlbedoBinding = 3, kSpecularBinding = 4;                                   // storage images
+constexpr int kShadingNormalBinding = 5; // storage image of a normal-mapped execution: the per-pixel shading normal (RGBA8)
 struct PushConstants { uint32_t drawCount, triangleCount; };
 struct TexturedPushConstants { uint32_t drawCount, triangleCount, textureCount; }; // the optional third word: 0, or absent, is the untextured pass
 struct AlphaPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest; }; // the optional fourth word: 0, or absent, is the pass without the alpha test
+struct NormalPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest, normalMap; }; // the optional fifth word: 0, or absent, is the pass without normal maps
 struct Draw { uint32_t firstIndex, indexCount, vertexOffset, transformIndex, albedo, specular; }; // albedo, specular: RGBA8 texels as they are stored
 struct MainPassMatrices { float model[16], mvp[16], mvpPrevious[16]; };                            // glm column-major (RenderFrontend.cpp:581-585)
 // material textures ("The sampling contract"): `texels` holds RGBA8 texels, R in the low byte, every texture's levels back to back and unpadded; level l is
@@ -29,6 +32,10 @@ constexpr uint64_t kMaxTexels = 1ull << 28;                         // what plrf
 // the alpha test ("The alpha test contract"): a draw's cutoff code c, 0 = opaque; a fragment passes when its alpha code is >= c. The kernel uses min(word, 256):
 // a word above 255 discards every fragment of the draw
 constexpr uint32_t kAlphaCutoffOpaque = 0, kAlphaCutoffReference = 128, kAlphaCutoffDiscardAll = 256;
+// normal maps ("Normal maps in the depth prepass"): the fifth push-constant word selects the decode of the sampled texel; `tangents` and `bitangents` hold 3 floats
+// per vertex, `normalMaterials` one texture index (or kNoTexture) per draw into the same textures / texels store
+constexpr uint32_t kNormalDecodeReference = 1, kNormalDecodeUnit = 2;
+constexpr uint32_t kNoWinner = 0xffffffffu; // what the tile kernel leaves in a shadingNormal texel without a winner, for the shading-normal kernel behind it
 static_assert(sizeof(Texture) == 16 && sizeof(Material) == 8, "texture buffer layouts");
 // the levels a width x height texture can have: floor(log2(max(width, height))) + 1
 constexpr uint32_t fullMipCount(uint32_t width, uint32_t height) {

@@ -159,6 +159,11 @@ int plrf_set_scene_alpha_cutoffs(void* p, const uint32_t* cutoffs, uint32_t draw
     if (!p) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY_REFUSAL(((FramePipeline*)p)->setSceneAlphaCutoffs(cutoffs, drawCount))
 }
+int plrf_set_scene_normal_maps(void* p, const float* const* meshTangents, const float* const* meshBitangents, uint32_t meshCount, const uint32_t* normalTextures,
+                               uint32_t drawCount, uint32_t decode) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL(((FramePipeline*)p)->setSceneNormalMaps(meshTangents, meshBitangents, meshCount, normalTextures, drawCount, decode))
+}
 int plrf_get_prepass_raster_stats(void* p, plrf_prepass_raster_stats* out) {
     if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY_REFUSAL({
@@ -171,6 +176,10 @@ int plrf_destroy(void* p) { delete (FramePipeline*)p; return PLR_OK; }
 
 int plrf_get_image(void* p, const char* name, plr_image_handle* out) {
     const ImageHandle h = ((FramePipeline*)p)->image(name);
+    if (h.index == invalidIndex && std::string(name) == "shadingNormal") {
+        g_ferr = "image 'shadingNormal' does not exist yet: the first successful plrf_set_scene_normal_maps creates it";
+        return PLR_ERR_INVALID_ARGUMENT;
+    }
     if (h.index == invalidIndex) { g_ferr = std::string("unknown image '") + name + "'"; return PLR_ERR_INVALID_ARGUMENT; }
     *out = RenderBackend::toC(h);
     return PLR_OK;

@@ -960,6 +960,7 @@ ImageHandle FramePipeline::image(const std::string& n) const {
     if (n == "post0") return m_postProcessBuffers[0];
     if (n == "post1") return m_postProcessBuffers[1];
     if (n == "normal") return m_worldSpaceNormalImage;
+    if (n == "shadingNormal") return m_shadingNormalCreated ? m_shadingNormalImage : ImageHandle{}; // (exists once normal maps were set)
     if (n == "albedo") return m_albedoImage;
     if (n == "specular") return m_specularImage;
     if (n == "pyramid") return m_minMaxDepthPyramid;
@@ -1157,7 +1158,8 @@ void FramePipeline::computeDeferredShading(ImageHandle colorTarget, const FrameR
     exe.genericInfo.resources.storageImages = {ImageResource(colorTarget, 0, 0)};
     exe.genericInfo.resources.sampledImages = {ImageResource(m_brdfLut, 0, 3), ImageResource(indirectLight.Y_SH, 0, 15), ImageResource(indirectLight.CoCg, 0, 16),
                                                ImageResource(m_volumetricIntegrationVolume, 0, 18),
-                                               ImageResource(current.depthBuffer, 0, 20), ImageResource(m_worldSpaceNormalImage, 0, 21),
+                                               // (triangle.frag:180-196 lights with the normal-mapped normal; the trace and the GI filters keep the vertex normal)
+                                               ImageResource(current.depthBuffer, 0, 20), ImageResource(normalMapped() ? m_shadingNormalImage : m_worldSpaceNormalImage, 0, 21),
                                                ImageResource(m_albedoImage, 0, 22), ImageResource(m_specularImage, 0, 23), ImageResource(m_skyLut, 0, 24)};
     for (uint32_t i = 0; i < (uint32_t)maxSunShadowCascadeCount; i++) exe.genericInfo.resources.sampledImages.push_back(ImageResource(m_shadowMaps[i], 0, 9 + i));
     exe.genericInfo.resources.uniformBuffers = {UniformBufferResource(m_volumetricsInfoBuffer, 19)};
@@ -1406,14 +1408,19 @@ void FramePipeline::renderDepthPrepass(const FrameRenderTargets& current) {
                                                 StorageBufferResource(m_sceneNormals.handle, true, pp::kNormalBinding), StorageBufferResource(m_sceneIndices.handle, true, pp::kIndexBinding),
                                                 StorageBufferResource(m_sceneDraws.handle, true, pp::kDrawBinding), StorageBufferResource(m_sceneScratch.handle, false, pp::kScratchBinding)};
     const bool alphaTested = m_sceneAlphaTested && m_sceneTextureCount;
-    const pp::AlphaPushConstants pc{m_sceneDrawCount, m_sceneTriangleCount, m_sceneTextureCount, alphaTested ? 1u : 0u};
-    // without textures: the 8-byte record; without a cutoff other than 0: the 12-byte one
-    exe.pushConstants = dataToCharArray(&pc, alphaTested ? sizeof(pc) : m_sceneTextureCount ? sizeof(pp::TexturedPushConstants) : sizeof(pp::PushConstants));
+    const pp::NormalPushConstants pc{m_sceneDrawCount, m_sceneTriangleCount, m_sceneTextureCount, alphaTested ? 1u : 0u, normalMapped() ? m_sceneNormalDecode : 0u};
+    // without textures: the 8-byte record; without a cutoff other than 0: the 12-byte one; without normal maps: the 16-byte one
+    exe.pushConstants = dataToCharArray(&pc, normalMapped() ? sizeof(pc) : alphaTested ? sizeof(pp::AlphaPushConstants) : m_sceneTextureCount ? sizeof(pp::TexturedPushConstants) : sizeof(pp::PushConstants));
     if (m_sceneTextureCount) {
         auto& buffers = exe.genericInfo.resources.storageBuffers;
         buffers.push_back(StorageBufferResource(m_sceneUvs.handle, true, pp::kUvBinding)); buffers.push_back(StorageBufferResource(m_sceneMaterials.handle, true, pp::kMaterialBinding));
         buffers.push_back(StorageBufferResource(m_sceneTextures.handle, true, pp::kTextureBinding)); buffers.push_back(StorageBufferResource(m_sceneTexels.handle, true, pp::kTexelBinding));
         if (alphaTested) buffers.push_back(StorageBufferResource(m_sceneAlphaCutoffs.handle, true, pp::kAlphaCutoffBinding));
+        if (normalMapped()) {
+            buffers.push_back(StorageBufferResource(m_sceneTangents.handle, true, pp::kTangentBinding)); buffers.push_back(StorageBufferResource(m_sceneBitangents.handle, true, pp::kBitangentBinding));
+            buffers.push_back(StorageBufferResource(m_sceneNormalMaterials.handle, true, pp::kNormalMaterialBinding));
+            exe.genericInfo.resources.storageImages.push_back(ImageResource(m_shadingNormalImage, 0, pp::kShadingNormalBinding));
+        }
     }
     m_be.setComputePassExecution(exe);
     m_sceneRecorded = true;
@@ -1443,7 +1450,8 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
     if (drawCount == 0) {
         m_sceneDrawCount = m_sceneTriangleCount = m_sceneTextureCount = 0;
         m_scenePreviousValid = m_sceneRecorded = m_sceneAlphaTested = false;
-        m_sceneMeshVertexCounts.clear();
+        m_sceneNormalDecode = 0;
+        m_sceneMeshVertexCounts.clear(); m_sceneMeshHasNormals.clear(); m_sceneNormalsHost.clear();
         return;
     }
     const PackedScene packed = packSceneMeshes(meshes, meshCount, draws, drawCount); // validates everything before anything is changed
@@ -1467,12 +1475,15 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
     m_sceneMeshVertexCounts = packed.meshVertexCounts;
     m_sceneTextureCount = 0; // the textures belonged to the scene that was replaced
     m_sceneAlphaTested = false; // and so did the cutoffs
+    m_sceneNormalDecode = 0;    // and the normal maps
+    m_sceneMeshHasNormals = packed.meshHasNormals;
+    m_sceneNormalsHost = packed.normals;
 }
 
 void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {
     if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneTextures: a band / tile pipeline cannot rasterise scene meshes");
-    if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = false; return; }
+    if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = false; m_sceneNormalDecode = 0; return; }
     const PackedTextures packed = packSceneTextures(textures, textureCount, meshUvs, meshCount, materials, drawCount, m_sceneMeshVertexCounts.data(),
                                                     (uint32_t)m_sceneMeshVertexCounts.size(), m_sceneDrawCount); // validates everything before anything is changed
     auto fill = [&](SceneBuffer& b, const std::vector<uint32_t>& data) { fillCasterBuffer(b.handle, b.bytes, data.data(), data.size() * sizeof(uint32_t)); };
@@ -1482,6 +1493,26 @@ void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t text
     fill(m_sceneTexels, packed.texels);
     m_sceneTextureCount = textureCount;
     m_sceneAlphaTested = false; // the cutoffs belonged to the materials that were replaced
+    m_sceneNormalDecode = 0;    // and the normal maps named textures that were replaced
+}
+
+void FramePipeline::setSceneNormalMaps(const float* const* meshTangents, const float* const* meshBitangents, uint32_t meshCount, const uint32_t* normalTextures, uint32_t drawCount,
+                                       uint32_t decode) {
+    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneNormalMaps: a band / tile pipeline cannot rasterise scene meshes");
+    if (drawCount == 0) { m_sceneNormalDecode = 0; return; }
+    SceneNormalMapContext scene;
+    scene.meshVertexCounts = m_sceneMeshVertexCounts.data(); scene.meshHasNormals = m_sceneMeshHasNormals.data(); scene.normals = m_sceneNormalsHost.data();
+    scene.meshCount = (uint32_t)m_sceneMeshVertexCounts.size(); scene.drawCount = m_sceneDrawCount; scene.textureCount = m_sceneTextureCount;
+    const PackedNormalMaps packed = packSceneNormalMaps(meshTangents, meshBitangents, meshCount, normalTextures, drawCount, decode, scene); // validates everything before anything is changed
+    fillCasterBuffer(m_sceneTangents.handle, m_sceneTangents.bytes, packed.tangents.data(), packed.tangents.size() * sizeof(float));
+    fillCasterBuffer(m_sceneBitangents.handle, m_sceneBitangents.bytes, packed.bitangents.data(), packed.bitangents.size() * sizeof(float));
+    fillCasterBuffer(m_sceneNormalMaterials.handle, m_sceneNormalMaterials.bytes, packed.normalMaterials.data(), packed.normalMaterials.size() * sizeof(uint32_t));
+    if (!m_shadingNormalCreated) { // at the size the other G-buffer images have now: a pending resize re-creates it with them
+        m_shadingNormalImage = m_be.createImage(desc2D(settings.width, settings.height, ImageFormat::RGBA8), nullptr, 0);
+        m_shadingNormalCreated = true;
+    }
+    m_sceneNormalDecode = packed.decode;
 }
 
 void FramePipeline::setSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawCount) {
@@ -1975,6 +2006,7 @@ void FramePipeline::applyResolution(uint32_t W, uint32_t H) {
                        m_frameRenderTargets[1].colorBuffer, m_frameRenderTargets[1].depthBuffer, m_postProcessBuffers[0], m_postProcessBuffers[1], m_worldSpaceNormalImage,
                        m_albedoImage, m_specularImage},
                       W, H);
+    if (m_shadingNormalCreated) m_be.resizeImages({m_shadingNormalImage}, W, H);
     m_be.resizeImages({m_depthHalfRes}, W / 2, H / 2);
     m_be.recreateImage(m_minMaxDepthPyramid, depthPyramidDescription(settings)); // (its mip layout follows the size: full chain or per tile)
     m_be.updateComputePassShaderDescription(m_depthPyramidPass, depthPyramidShaderDescription());

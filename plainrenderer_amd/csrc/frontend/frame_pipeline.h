@@ -330,6 +330,7 @@ struct PackedScene {
     std::vector<uint32_t> draws;                   // 6 words per draw: {firstIndex, indexCount, vertexOffset, transformIndex, albedo, specular}
     uint32_t triangleCount = 0;
     std::vector<uint32_t> meshVertexCounts;        // per mesh, in the order the positions are packed: what packSceneTextures lays the UVs out by
+    std::vector<uint8_t> meshHasNormals;           // per mesh: given with vertex normals (packSceneNormalMaps derives bitangents from them)
 };
 PackedScene packSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const SceneDraw* draws, uint32_t drawCount);
 void refuseNonFiniteMatrices(const float* matrices16, uint32_t drawCount, const char* call);
@@ -355,6 +356,22 @@ struct PackedAlphaCutoffs {
 };
 // sceneDrawCount / sceneTextureCount: of the scene and the textures the pipeline holds. Throws FramePipelineRefusal.
 PackedAlphaCutoffs packSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawCount, uint32_t sceneDrawCount, uint32_t sceneTextureCount);
+// what setSceneNormalMaps validates, derives and packs, without a backend: bindings 11 - 13 of a normal-mapped "depthPrepassRaster.comp" and its fifth push-constant word
+struct PackedNormalMaps {
+    std::vector<float> tangents, bitangents; // 3 floats per vertex of the packed scene, zeros for a mesh given without tangents
+    std::vector<uint32_t> normalMaterials;   // one texture index, or kNoSceneTexture, per draw
+    uint32_t decode = 0;
+};
+// of the scene and the textures the pipeline holds: per mesh its vertex count and whether it came with normals, the packed normals (3 floats per vertex)
+struct SceneNormalMapContext {
+    const uint32_t* meshVertexCounts = nullptr; const uint8_t* meshHasNormals = nullptr; const float* normals = nullptr;
+    uint32_t meshCount = 0, drawCount = 0, textureCount = 0;
+};
+// bitangent = normalize(cross(tangent, normal)) in fp64 from the promoted floats, each component (float)(c_r / len); (0, 0, 0) where len is not a finite number > 0
+void deriveBitangent(const float tangent[3], const float normal[3], float out[3]);
+// Throws FramePipelineRefusal.
+PackedNormalMaps packSceneNormalMaps(const float* const* meshTangents, const float* const* meshBitangents, uint32_t meshCount, const uint32_t* normalTextures, uint32_t drawCount,
+                                     uint32_t decode, const SceneNormalMapContext& scene);
 // alpha-tested cutouts of the shadow casters (plr_frame.h plrf_set_shadow_caster_cutouts): per caster draw the texture whose alpha is tested (kNoSceneTexture:
 // alpha 255 everywhere) and the cutoff code 0 .. 255, 0 = opaque
 struct ShadowCutout { uint32_t albedoTexture = kNoSceneTexture, alphaCutoff = 0; };
@@ -417,6 +434,17 @@ public:
     // and setSceneTextures drop them too. Refusals: no scene, no textures, a count other than the scene's, null cutoffs, a value above 255 are
     // PLR_ERR_INVALID_ARGUMENT; a band / tile pipeline is PLR_ERR_UNSUPPORTED. A refused call changes nothing.
     void setSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawCount);
+    // normal maps for the scene and textures now set (DESIGN.md "Normal maps in the depth prepass"): per draw an index into the scene's textures or kNoSceneTexture,
+    // per mesh 3 floats per vertex of tangents (null: all (0, 0, 0)) and of bitangents (null: derived on the host as normalize(cross(tangent, normal)),
+    // deriveBitangent), and the decode (1: the reference's, 2: unit). From the next frame on the pass is recorded with the fifth push-constant word, bindings
+    // 11 - 13 and storage image 5 - the shadingNormal image, created by the first successful call and re-created by a resize -, and the deferred shade reads
+    // shadingNormal where it read normal; the SDF trace and the GI filters keep normal. Everything is copied. drawCount 0 removes them and the shade reads normal
+    // again; setSceneMeshes and setSceneTextures drop them too; they survive setSceneMeshTransforms, setSceneAlphaCutoffs, setResolution and updateSettings.
+    // Refusals: no scene, no textures, a mesh or draw count other than the scene's, null normalTextures, an index that names no texture, a non-finite tangent or
+    // bitangent, a decode other than 1 or 2, null bitangents with tangents for a mesh given without normals are PLR_ERR_INVALID_ARGUMENT; a band / tile pipeline
+    // is PLR_ERR_UNSUPPORTED. A refused call changes nothing.
+    void setSceneNormalMaps(const float* const* meshTangents, const float* const* meshBitangents, uint32_t meshCount, const uint32_t* normalTextures, uint32_t drawCount,
+                            uint32_t decode);
     // counters of the last frame's execution for the scene now set; waits for the GPU. Zero while no scene is set and before the first frame of a newly set scene.
     PrepassRasterStats prepassRasterStats();
     // RenderFrontend::setResolution (RenderFrontend.cpp:408-421): recorded, applied at the start of the next frame() (prepareNewFrame, :199-222). Every image and
@@ -546,6 +574,14 @@ private:
     // alpha cutoffs: created by the first setSceneAlphaCutoffs; not tested = the pass record without the fourth push-constant word
     bool m_sceneAlphaTested = false;
     SceneBuffer m_sceneAlphaCutoffs;
+    // normal maps: buffers and the shadingNormal image created by the first setSceneNormalMaps; decode 0 = the pass record without the fifth push-constant word
+    uint32_t m_sceneNormalDecode = 0;
+    std::vector<uint8_t> m_sceneMeshHasNormals;
+    std::vector<float> m_sceneNormalsHost; // the packed normals: what absent bitangents are derived from
+    SceneBuffer m_sceneTangents, m_sceneBitangents, m_sceneNormalMaterials;
+    ImageHandle m_shadingNormalImage;
+    bool m_shadingNormalCreated = false;
+    bool normalMapped() const { return m_sceneNormalDecode != 0 && m_sceneTextureCount != 0 && m_sceneDrawCount != 0; }
     std::vector<float> m_sceneModel, m_scenePreviousModel; // 16 floats per draw: what the next frame uses, what the last recorded frame used
 public:
     AtmosphereSettings atmosphereSettings;

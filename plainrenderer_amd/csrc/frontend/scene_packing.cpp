@@ -1,7 +1,7 @@
-// Validation and packing of scene meshes, their material textures and their alpha cutoffs for "depthPrepassRaster.comp" (FramePipeline::setSceneMeshes,
-// setSceneTextures, setSceneAlphaCutoffs) and of the shadow casters' cutouts for "sunShadowRaster.comp" (setShadowCasterCutouts): host code without a backend
-// call, so that a stand-alone program can run it under a sanitizer (tools/scene_packing_check.cpp, tools/scene_texture_check.cpp, tools/scene_alpha_check.cpp,
-// tools/shadow_cutout_check.cpp).
+// Validation and packing of scene meshes, their material textures, their alpha cutoffs and their normal maps for "depthPrepassRaster.comp"
+// (FramePipeline::setSceneMeshes, setSceneTextures, setSceneAlphaCutoffs, setSceneNormalMaps) and of the shadow casters' cutouts for "sunShadowRaster.comp"
+// (setShadowCasterCutouts): host code without a backend call, so that a stand-alone program can run it under a sanitizer (tools/scene_packing_check.cpp,
+// tools/scene_texture_check.cpp, tools/scene_alpha_check.cpp, tools/scene_normal_check.cpp, tools/shadow_cutout_check.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -69,7 +69,8 @@ PackedScene packSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const S
     }
     out.triangleCount = (uint32_t)triangles;
     out.meshVertexCounts.resize(meshCount);
-    for (uint32_t m = 0; m < meshCount; m++) out.meshVertexCounts[m] = meshes[m].vertexCount;
+    out.meshHasNormals.resize(meshCount);
+    for (uint32_t m = 0; m < meshCount; m++) { out.meshVertexCounts[m] = meshes[m].vertexCount; out.meshHasNormals[m] = meshes[m].normals ? 1 : 0; }
     return out;
 }
 
@@ -211,6 +212,64 @@ PackedAlphaCutoffs packSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawC
         out.tested = out.tested || cutoffs[d] != plr::prepass::kAlphaCutoffOpaque;
     }
     out.cutoffs.assign(cutoffs, cutoffs + drawCount);
+    return out;
+}
+
+// normalize(cross(tangent, normal)) in fp64 from the promoted floats (ModelImport.cpp:184), (0, 0, 0) where the length is not a finite number > 0. The build is
+// -ffp-contract=off: every operation below is one IEEE operation, in this order
+void deriveBitangent(const float t[3], const float n[3], float out[3]) {
+    const double tx = t[0], ty = t[1], tz = t[2], nx = n[0], ny = n[1], nz = n[2];
+    const double cx = ty * nz - tz * ny, cy = tz * nx - tx * nz, cz = tx * ny - ty * nx;
+    const double len = std::sqrt((cx * cx + cy * cy) + cz * cz);
+    const bool good = len > 0.0 && std::isfinite(len);
+    out[0] = good ? (float)(cx / len) : 0.f; out[1] = good ? (float)(cy / len) : 0.f; out[2] = good ? (float)(cz / len) : 0.f;
+}
+
+// everything is validated before anything is built
+PackedNormalMaps packSceneNormalMaps(const float* const* meshTangents, const float* const* meshBitangents, uint32_t meshCount, const uint32_t* normalTextures, uint32_t drawCount,
+                                     uint32_t decode, const SceneNormalMapContext& scene) {
+    namespace pp = plr::prepass;
+    const std::string call = "setSceneNormalMaps";
+    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
+    if (scene.drawCount == 0) refuse("no scene set (plrf_set_scene_meshes comes first)");
+    if (scene.textureCount == 0) refuse("no textures set (plrf_set_scene_textures comes first: a normal map is one of the scene's textures)");
+    if (meshCount != scene.meshCount) refuse("mesh count " + std::to_string(meshCount) + " differs from the mesh count " + std::to_string(scene.meshCount) + " of the scene");
+    if (drawCount != scene.drawCount) refuse("draw count " + std::to_string(drawCount) + " differs from the draw count " + std::to_string(scene.drawCount) + " of the scene");
+    if (!normalTextures) refuse("normal_textures are null");
+    if (decode != pp::kNormalDecodeReference && decode != pp::kNormalDecodeUnit)
+        refuse("decode is " + std::to_string(decode) + ", it must be 1 (PLRF_NORMAL_DECODE_REFERENCE) or 2 (PLRF_NORMAL_DECODE_UNIT)");
+    for (uint32_t d = 0; d < drawCount; d++)
+        if (normalTextures[d] != kNoSceneTexture && normalTextures[d] >= scene.textureCount)
+            refuse("normal texture index out of range: draw " + std::to_string(d) + " names texture " + std::to_string(normalTextures[d]) + " of " + std::to_string(scene.textureCount));
+    uint64_t vertices = 0;
+    for (uint32_t m = 0; m < meshCount; m++) {
+        const float* tangents = meshTangents ? meshTangents[m] : nullptr;
+        const float* bitangents = meshBitangents ? meshBitangents[m] : nullptr;
+        if (tangents && !bitangents && !scene.meshHasNormals[m])
+            refuse("mesh " + std::to_string(m) + " was given without normals: its bitangents cannot be derived from cross(tangent, normal), give them");
+        for (const float* v : {tangents, bitangents})
+            if (v)
+                for (size_t i = 0; i < (size_t)scene.meshVertexCounts[m] * 3u; i++)
+                    if (!std::isfinite(v[i]))
+                        refuse(std::string("non-finite ") + (v == tangents ? "tangent" : "bitangent") + ": vertex " + std::to_string(i / 3u) + " of mesh " + std::to_string(m));
+        vertices += scene.meshVertexCounts[m];
+    }
+    PackedNormalMaps out;
+    out.tangents.assign((size_t)vertices * 3u, 0.f);
+    out.bitangents.assign((size_t)vertices * 3u, 0.f);
+    size_t at = 0;
+    for (uint32_t m = 0; m < meshCount; m++) {
+        const float* tangents = meshTangents ? meshTangents[m] : nullptr;
+        const float* bitangents = meshBitangents ? meshBitangents[m] : nullptr;
+        const size_t floats = (size_t)scene.meshVertexCounts[m] * 3u;
+        if (tangents && floats) std::memcpy(out.tangents.data() + at, tangents, floats * sizeof(float));
+        if (bitangents && floats) std::memcpy(out.bitangents.data() + at, bitangents, floats * sizeof(float));
+        else if (tangents) // derived; without tangents they stay (0, 0, 0)
+            for (size_t v = 0; v < floats; v += 3u) deriveBitangent(tangents + v, scene.normals + at + v, out.bitangents.data() + at + v);
+        at += floats;
+    }
+    out.normalMaterials.assign(normalTextures, normalTextures + drawCount);
+    out.decode = decode;
     return out;
 }
 

@@ -66,7 +66,7 @@
 //     fx = Tu & 255, x1 = x0 + 1, both wrapped to [0, W) by a non-negative modulo (repeat); y0, fy, y1 likewise with v and H. Per channel
 //     S_l = (256 - fx)(256 - fy) c00 + fx (256 - fy) c10 + (256 - fx) fy c01 + fx fy c11; S = (256 - fw) S_L0 + fw S_L1 (<= 255 * 2^24: fits uint32); the stored
 //     code is (S + 2^23 - 1 + ((S >> 24) & 1)) >> 24, round half even. All four channels, alpha included; albedo is filtered in code space.
-//   Isotropic trilinear filtering stands in for the implementation-defined anisotropic sampler; there is no normal map.
+//   Isotropic trilinear filtering stands in for the implementation-defined anisotropic sampler; the normal map: THE NORMAL MAP CONTRACT below.
 //
 // THE ALPHA TEST CONTRACT (DESIGN.md "Alpha-tested cutouts in the depth prepass"; tests/prepass_alpha_reference.py implements it independently, bit for bit). Only an
 // execution whose fourth push-constant word alphaTest is != 0 tests (it needs textureCount > 0 and storage buffer 10 `alphaCutoffs`, one uint32 per draw).
@@ -84,6 +84,32 @@
 //     image does not change. (There is no counter of discarded fragments: it would forbid exactly that.)
 //   sunShadow.frag's alpha test is not part of this pass: the shadow casters are another mesh set with UVs, textures and cutoffs of their own
 //   (kernels/sun_shadow_raster.hip, THE CUTOUT CONTRACT; plrf_set_shadow_caster_cutouts).
+//
+// THE NORMAL MAP CONTRACT (DESIGN.md "Normal maps in the depth prepass"; tests/prepass_normal_reference.py implements it independently, bit for bit on every texel
+// of shadingNormal). Only an execution whose fifth push-constant word normalMap is 1 or 2 writes storage image 5, shadingNormal (it needs textureCount > 0 and
+// storage buffers 11 - 13); visibility, depth, motion, normal, albedo, specular and the counters do not depend on it. fp64 IEEE without contraction, correctly
+// rounded divide and sqrt, unless stated otherwise.
+//   inputs: `tangents` and `bitangents` hold 3 floats per vertex, indexed like positions; a vertex outside `tangents` has the tangent (0, 0, 0), one outside
+//     `bitangents` the bitangent (0, 0, 0). `normalMaterials` holds one uint32 per draw: an index into the SAME textures / texels store as albedo and specular, or
+//     0xffffffff; usable by the sampling contract's rule. `materials` keeps its 8-byte stride.
+//   per winner pixel of triangle t at P, with the b of the ORIGINAL triangle:
+//     per-vertex basis: T_k = normalize(mat3(model) * tangent_k), B_k likewise, by the normal rule's arithmetic word for word (component r = (m[0][r] x +
+//       m[1][r] y) + m[2][r] z; normalize gives (0, 0, 0) where the length is not a finite number > 0); N_k is exactly the normal rule's, face normal included.
+//     interpolated basis: T = sum b_k T_k, B = sum b_k B_k, Nv = sum b_k N_k, each (b0 a0 + b1 a1) + b2 a2; NOT renormalised (passTBN is interpolated raw).
+//     texel: the sampling contract's RGBA8 word for the draw's normal texture at this pixel (same UV, validity rule, derivatives, level with g_mipBias, taps, round
+//       half even: uvSampleAt, sampleTexture); cx = bits 0 - 7, cy = bits 8 - 15; x = cx / 255.0, y = cy / 255.0.
+//     decode 1, reference (triangle.frag:181-182, as written): z = sqrt(((1 - x x) + y) + y), n_t = (2 x - 1, 2 y - 1, 2 z - 1); the radicand is never negative.
+//     decode 2, unit: nx = 2 x - 1, ny = 2 y - 1, q = (1 - nx nx) - ny ny, nz = q > 0 ? sqrt(q) : 0, n_t = (nx, ny, nz).
+//     shading normal: M_r = (T_r n_t.x + B_r n_t.y) + Nv_r n_t.z, n_s = normalize(M) with the zero rule; where n_s is zero it is the normal rule's n (the word of
+//       `normal`; the reference's NaN fallback N = passTBN[2], :194-196, normalised). n_s is rounded once to fp32 and stored as n_s * 0.5 + 0.5 by the UNORM8 rule,
+//       alpha 255.
+//     no normal map: the pixel stores exactly the word the pass stores to `normal` - a draw whose normalMaterials word names no usable texture, a draw at or past
+//       drawCount, a draw past the end of normalMaterials.
+//   a pixel without a winner stores 0; every texel of shadingNormal is written by every normal-mapped execution.
+//   deviations: the filtered texel is quantised to 8 bits before the decode; isotropic trilinear filtering; fp32 tangents for the A2R10G10B10 SNORM vertex format;
+//     the normalised fallback; decode 1 is the reference's expression, not a unit-length one.
+// The tile kernel of such an execution (kNormalMap) leaves the winner's t, or kNoWinner, in the shadingNormal texel, and depthPrepassShadingNormalKernel behind it,
+// a lane per pixel, turns that texel into the shading normal in place.
 //
 // Two kernels. SET-UP: a lane per triangle finds its draw (block-wide prefix sum, LDS bisection), transforms, clips (the polygon lives in LDS, a column per lane),
 // projects, snaps, culls and boxes; the block's sub-triangles are appended through one 64-bit atomic per block to a dense array of 4-byte tile rectangles and an
@@ -297,6 +323,10 @@ struct TileParams {
     TextureInputs tex; // a textured execution only (behind everything else: the untextured kernel's argument offsets stay)
     const uint32_t* alphaCutoffs; // an alpha-tested execution only: tex.drawCount words
 };
+// a normal-mapped execution's tile kernel leaves the winner's t in the shadingNormal texel (the other instantiations keep their argument block)
+struct NormalTileParams : TileParams { uint32_t* shadingNormal; };
+template <bool kNormalMap> struct TileParamsOf { typedef TileParams type; };
+template <> struct TileParamsOf<true> { typedef NormalTileParams type; };
 
 typedef unsigned long long Key;
 
@@ -425,6 +455,34 @@ PLR_DI UvSample uvSampleAt(D3 P, const double b[3], const D3 V[3], const double 
     return s;
 }
 
+// the winner's vertex fetch, mat3(model) * v and N_k: one text for the resolve and for the shading-normal kernel, so the vertex normal the latter interpolates is
+// the one behind `normal`. The vertices are inside `positions` and `normals`: the set-up kernel made a record of this triangle
+PLR_DI void fetchWinnerVertices(const uint32_t* indices, const float* positions, const float* normals, uint64_t at, uint32_t vertexOffset, uint64_t vertex[3], float pos[3][3],
+                                float nrm[3][3]) {
+    for (int k = 0; k < 3; k++) {
+        const uint64_t v = (uint64_t)indices[at + k] + (uint64_t)vertexOffset;
+        vertex[k] = v;
+        for (int c = 0; c < 3; c++) { pos[k][c] = positions[v * 3u + c]; nrm[k][c] = normals[v * 3u + c]; }
+    }
+}
+PLR_DI D3 rotated(const float* model, D3 in) { // mat3(model) * in: component r = (m[0][r] x + m[1][r] y) + m[2][r] z
+    return D3{((double)model[0] * in.x + (double)model[4] * in.y) + (double)model[8] * in.z, ((double)model[1] * in.x + (double)model[5] * in.y) + (double)model[9] * in.z,
+              ((double)model[2] * in.x + (double)model[6] * in.y) + (double)model[10] * in.z};
+}
+PLR_DI void vertexNormals(const float pos[3][3], const float nrm[3][3], const float* model, D3 N[3]) {
+    D3 face{0.0, 0.0, 0.0};
+    {
+        const D3 a{(double)pos[0][0] - (double)pos[2][0], (double)pos[0][1] - (double)pos[2][1], (double)pos[0][2] - (double)pos[2][2]};
+        const D3 c{(double)pos[0][0] - (double)pos[1][0], (double)pos[0][1] - (double)pos[1][1], (double)pos[0][2] - (double)pos[1][2]};
+        face = normalized(D3{a.y * c.z - a.z * c.y, a.z * c.x - a.x * c.z, a.x * c.y - a.y * c.x});
+    }
+    for (int k = 0; k < 3; k++) {
+        D3 in{(double)nrm[k][0], (double)nrm[k][1], (double)nrm[k][2]};
+        if (nrm[k][0] == 0.f && nrm[k][1] == 0.f && nrm[k][2] == 0.f) in = face;
+        N[k] = normalized(rotated(model, in));
+    }
+}
+
 // the winner's attributes at pixel (x, y): motion, normal and the draw's two material words (kTextured: the sampled texel where its material names a texture)
 template <bool kTextured>
 PLR_DI void resolvePixel(const TileParams& p, const TextureInputs& tex, uint32_t t, int x, int y, uint32_t* motion, uint32_t* normal, uint32_t* albedo, uint32_t* specular) {
@@ -436,10 +494,8 @@ PLR_DI void resolvePixel(const TileParams& p, const TextureInputs& tex, uint32_t
     float pos[3][3], nrm[3][3];
     D3 V[3], prev[3];
     uint64_t vertex[3];
+    fetchWinnerVertices(p.indices, p.positions, p.normals, at, draw.vertexOffset, vertex, pos, nrm);
     for (int k = 0; k < 3; k++) {
-        const uint64_t v = (uint64_t)p.indices[at + k] + (uint64_t)draw.vertexOffset;
-        vertex[k] = v;
-        for (int c = 0; c < 3; c++) { pos[k][c] = p.positions[v * 3u + c]; nrm[k][c] = p.normals[v * 3u + c]; }
         V[k] = clipXYW(mvp, pos[k]);
         prev[k] = clipXYW(mvpPrevious, pos[k]);
     }
@@ -447,19 +503,8 @@ PLR_DI void resolvePixel(const TileParams& p, const TextureInputs& tex, uint32_t
     double b[3];
     barycentricsAt(P, V, b);
     // normal
-    D3 face{0.0, 0.0, 0.0};
-    {
-        const D3 a{(double)pos[0][0] - (double)pos[2][0], (double)pos[0][1] - (double)pos[2][1], (double)pos[0][2] - (double)pos[2][2]};
-        const D3 c{(double)pos[0][0] - (double)pos[1][0], (double)pos[0][1] - (double)pos[1][1], (double)pos[0][2] - (double)pos[1][2]};
-        face = normalized(D3{a.y * c.z - a.z * c.y, a.z * c.x - a.x * c.z, a.x * c.y - a.y * c.x});
-    }
     D3 N[3];
-    for (int k = 0; k < 3; k++) {
-        D3 in{(double)nrm[k][0], (double)nrm[k][1], (double)nrm[k][2]};
-        if (nrm[k][0] == 0.f && nrm[k][1] == 0.f && nrm[k][2] == 0.f) in = face;
-        N[k] = normalized(D3{((double)model[0] * in.x + (double)model[4] * in.y) + (double)model[8] * in.z, ((double)model[1] * in.x + (double)model[5] * in.y) + (double)model[9] * in.z,
-                             ((double)model[2] * in.x + (double)model[6] * in.y) + (double)model[10] * in.z});
-    }
+    vertexNormals(pos, nrm, model, N);
     const D3 nn = normalized(D3{weighted(b, N[0].x, N[1].x, N[2].x), weighted(b, N[0].y, N[1].y, N[2].y), weighted(b, N[0].z, N[1].z, N[2].z)});
     *normal = unorm8Half((float)nn.x) | (unorm8Half((float)nn.y) << 8) | (unorm8Half((float)nn.z) << 16) | (255u << 24);
     // motion
@@ -669,9 +714,12 @@ struct AlphaWalk {
     PLR_DI void endStep() { scan.flush(); } // before the next step's records replace these
 };
 
-template <bool kTextured, bool kAlphaTest = false>
-__global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
+// kNormalMap: the resolve also leaves the winner's t (kNoWinner: none) in the shadingNormal texel, for depthPrepassShadingNormalKernel behind this kernel
+template <bool kTextured, bool kAlphaTest = false, bool kNormalMap = false>
+__global__ __launch_bounds__(256) void depthPrepassTileKernel(typename TileParamsOf<kNormalMap>::type p) {
+    typedef typename TileParamsOf<kNormalMap>::type Params;
     static_assert(kTextured || !kAlphaTest, "the alpha of a fragment is a texture sample");
+    static_assert(kTextured || !kNormalMap, "the shading normal is a texture sample");
     __shared__ Key tile[kTileSize * kTileSize];
     __shared__ uint32_t hitQueue[4][256]; // per wave: the entries of the current step that touch the tile
     const int tx = (int)blockIdx.x, ty = (int)blockIdx.y;
@@ -688,12 +736,12 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
     }
     // the alpha-tested kernel takes ALL its arguments from LDS: its scan needs the resolve's buffers too, and held in scalar registers from the kernel's entry
     // thirty of them were spilled
-    __shared__ TileParams sharedParams;
+    __shared__ Params sharedParams;
     if constexpr (kAlphaTest) {
         if (threadIdx.x == 0) { sharedAlpha = AlphaInputs{p.alphaCutoffs, p.global->mipBias}; sharedParams = p; }
     }
     __syncthreads();
-    const TileParams& q = *(kAlphaTest ? &sharedParams : &p);
+    const Params& q = *(kAlphaTest ? &sharedParams : &p);
     const uint32_t n = min(q.header->cursor, q.capacity);
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) q.header->drawn = n;
     const rastercov::TileWindow window{tx, ty, ox, oy, min(ox + kTileSize - 1, q.width - 1), min(oy + kTileSize - 1, q.height - 1)};
@@ -714,17 +762,110 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(TileParams p) {
         const Key key = tile[i];
         uint32_t motion = 0u, normal = 0u, albedo = 0u, specular = 0u;
         const uint32_t t = (uint32_t)key;
-        if (key != 0ull && t < q.triangleCount) resolvePixel<kTextured>(q, tex, t, x, y, &motion, &normal, &albedo, &specular);
+        const bool winner = key != 0ull && t < q.triangleCount;
+        if (winner) resolvePixel<kTextured>(q, tex, t, x, y, &motion, &normal, &albedo, &specular);
         const size_t at = (size_t)y * (size_t)q.width + (size_t)x;
         q.depth[at] = u2f((uint32_t)(key >> 32));
         q.motion[at] = motion; q.normal[at] = normal; q.albedo[at] = albedo; q.specular[at] = specular;
+        if constexpr (kNormalMap) q.shadingNormal[at] = winner ? t : kNoWinner;
     }
+}
+
+// ---- normal maps (the normal map contract)
+struct ShadingNormalParams {
+    const TriangleOrigin* origins; const float* transforms; const float* positions; const float* normals; const uint32_t* indices; const Draw* draws;
+    const GlobalUbo* global;
+    const uint32_t* normal;  // what the tile kernel stored: a pixel without a normal map, and one whose M does not normalise, takes this word
+    uint32_t* shadingNormal; // in: the winner's t or kNoWinner; out: the shading normal
+    const float* tangents; const float* bitangents; const uint32_t* normalMaterials;
+    uint64_t tangentVertexCount, bitangentVertexCount;
+    uint32_t triangleCount, normalMaterialCount, decode;
+    int32_t width, height;
+    TextureInputs tex;
+};
+
+PLR_DI D3 fetchBasisVector(const float* buffer, uint64_t vertexCount, uint64_t vertex) { // a vertex outside the buffer has (0, 0, 0)
+    if (vertex >= vertexCount) return D3{0.0, 0.0, 0.0};
+    return D3{(double)buffer[vertex * 3u], (double)buffer[vertex * 3u + 1u], (double)buffer[vertex * 3u + 2u]};
+}
+
+// n_s of triangle origins[t] = o at pixel (x, y) with the usable normal texture `texture`, as the stored word; `fallback` where M does not normalise
+PLR_DI uint32_t shadingNormalAt(const ShadingNormalParams& p, TriangleOrigin o, Texture texture, int x, int y, uint32_t fallback) {
+    const Draw draw = p.draws[o.draw];
+    const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)o.local * 3u;
+    const float* model = p.transforms + (size_t)draw.transformIndex * 48u;
+    const float* mvp = model + 16;
+    float pos[3][3], nrm[3][3];
+    uint64_t vertex[3];
+    fetchWinnerVertices(p.indices, p.positions, p.normals, at, draw.vertexOffset, vertex, pos, nrm);
+    D3 V[3];
+    for (int k = 0; k < 3; k++) V[k] = clipXYW(mvp, pos[k]);
+    const D3 P{(double)(2 * x + 1) / (double)p.width - 1.0, (double)(2 * y + 1) / (double)p.height - 1.0, 1.0};
+    double b[3];
+    barycentricsAt(P, V, b);
+    // the texel: the sampling contract's word, through the albedo sampler's own functions
+    double tu[3], tv[3];
+    for (int k = 0; k < 3; k++) fetchUv(p.tex, vertex[k], &tu[k], &tv[k]);
+    const UvSample uv = uvSampleAt(P, b, V, tu, tv, x, y, p.width, p.height);
+    const uint32_t texel = sampleTexture(p.tex, texture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, p.global->mipBias);
+    const double cx = (double)(texel & 255u) / 255.0, cy = (double)((texel >> 8) & 255u) / 255.0;
+    D3 nt;
+    if (p.decode == kNormalDecodeReference) {
+        const double z = __builtin_sqrt(((1.0 - cx * cx) + cy) + cy); // (the reference's expression as written)
+        nt = D3{2.0 * cx - 1.0, 2.0 * cy - 1.0, 2.0 * z - 1.0};
+    } else {
+        const double nx = 2.0 * cx - 1.0, ny = 2.0 * cy - 1.0;
+        const double q = (1.0 - nx * nx) - ny * ny;
+        nt = D3{nx, ny, q > 0.0 ? __builtin_sqrt(q) : 0.0};
+    }
+    // the interpolated basis, not renormalised
+    D3 N[3];
+    vertexNormals(pos, nrm, model, N);
+    D3 M{0.0, 0.0, 0.0};
+    {
+        D3 T[3], B[3];
+        for (int k = 0; k < 3; k++) {
+            T[k] = normalized(rotated(model, fetchBasisVector(p.tangents, p.tangentVertexCount, vertex[k])));
+            B[k] = normalized(rotated(model, fetchBasisVector(p.bitangents, p.bitangentVertexCount, vertex[k])));
+        }
+        const D3 Ti{weighted(b, T[0].x, T[1].x, T[2].x), weighted(b, T[0].y, T[1].y, T[2].y), weighted(b, T[0].z, T[1].z, T[2].z)};
+        const D3 Bi{weighted(b, B[0].x, B[1].x, B[2].x), weighted(b, B[0].y, B[1].y, B[2].y), weighted(b, B[0].z, B[1].z, B[2].z)};
+        const D3 Nv{weighted(b, N[0].x, N[1].x, N[2].x), weighted(b, N[0].y, N[1].y, N[2].y), weighted(b, N[0].z, N[1].z, N[2].z)};
+        M = D3{(Ti.x * nt.x + Bi.x * nt.y) + Nv.x * nt.z, (Ti.y * nt.x + Bi.y * nt.y) + Nv.y * nt.z, (Ti.z * nt.x + Bi.z * nt.y) + Nv.z * nt.z};
+    }
+    const D3 ns = normalized(M);
+    if (ns.x == 0.0 && ns.y == 0.0 && ns.z == 0.0) return fallback; // the Normal rule's n: the word behind `normal`
+    return unorm8Half((float)ns.x) | (unorm8Half((float)ns.y) << 8) | (unorm8Half((float)ns.z) << 16) | (255u << 24);
+}
+
+// A lane per pixel, a wave per 64 consecutive pixels of one row (256 contiguous bytes read and stored), in place: a lane reads the t the tile kernel left in its
+// texel and overwrites that texel. No LDS, no atomics. A wave of sky only, and a wave none of whose draws has a usable normal texture, leave by a ballot.
+__global__ __launch_bounds__(256) void depthPrepassShadingNormalKernel(ShadingNormalParams p) {
+    const int x = (int)(blockIdx.x * 64u + (threadIdx.x & 63u)), y = (int)(blockIdx.y * 4u + (threadIdx.x >> 6));
+    if (y >= p.height) return; // (wave-uniform)
+    const bool inside = x < p.width;
+    const size_t at = (size_t)y * (size_t)p.width + (size_t)(inside ? x : 0);
+    const uint32_t t = inside ? p.shadingNormal[at] : kNoWinner;
+    const bool winner = t < p.triangleCount;
+    uint32_t word = 0u;
+    if (__ballot(winner) != 0ull) {
+        TriangleOrigin o{0u, 0u};
+        Texture texture{};
+        bool mapped = false;
+        if (winner) {
+            word = p.normal[at];
+            o = p.origins[t];
+            if (o.draw < p.tex.drawCount && o.draw < p.normalMaterialCount) mapped = usableTexture(p.tex, p.normalMaterials[o.draw], &texture);
+        }
+        if (__ballot(mapped) != 0ull && mapped) word = shadingNormalAt(p, o, texture, x, y, word);
+    }
+    if (inside) p.shadingNormal[at] = word;
 }
 
 static int launchDepthPrepassRaster(const PassCtx& c) {
     if (c.push.size() < sizeof(PushConstants)) return c.fail(-1, "depthPrepassRaster: push constants {drawCount, triangleCount} missing");
-    AlphaPushConstants pc{};
-    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0; 12: alphaTest 0
+    NormalPushConstants pc{};
+    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0; 12: alphaTest 0; 16: normalMap 0
     if (c.dispatch[0] != 1u || c.dispatch[1] != 1u || c.dispatch[2] != 1u || c.base[0] != 0u || c.base[1] != 0u)
         return c.fail(-1, "depthPrepassRaster: the dispatch is {1, 1, 1} (the launcher derives its grids from the push constants and the images)");
     if (pc.triangleCount > kMaxTriangles) return c.fail(-1, "depthPrepassRaster: triangleCount " + std::to_string(pc.triangleCount) + " exceeds 2^28");
@@ -747,6 +888,14 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
     if (pc.alphaTest) {
         if (pc.textureCount == 0u) return c.fail(-1, "depthPrepassRaster: alphaTest is set and textureCount is 0 (the alpha of a fragment is its albedo sample: the alpha test needs textures)");
         if (int rc = c.needSbuf(kAlphaCutoffBinding, (size_t)pc.drawCount * 4u, "depthPrepassRaster alphaCutoffs (one uint32 cutoff code per draw)")) return rc;
+    }
+    if (pc.normalMap) {
+        if (pc.normalMap != kNormalDecodeReference && pc.normalMap != kNormalDecodeUnit)
+            return c.fail(-1, "depthPrepassRaster: normalMap is " + std::to_string(pc.normalMap) + ", it must be 0 (none), 1 (the reference's decode) or 2 (the unit decode)");
+        if (pc.textureCount == 0u) return c.fail(-1, "depthPrepassRaster: normalMap is set and textureCount is 0 (a normal map is a texture of the texture store: normal maps need textures)");
+        if (int rc = c.needSbuf(kTangentBinding, 0, "depthPrepassRaster tangents (3 floats per vertex)")) return rc;
+        if (int rc = c.needSbuf(kBitangentBinding, 0, "depthPrepassRaster bitangents (3 floats per vertex)")) return rc;
+        if (int rc = c.needSbuf(kNormalMaterialBinding, (size_t)pc.drawCount * 4u, "depthPrepassRaster normalMaterials (one uint32 texture index per draw)")) return rc;
     }
     if (c.sbuf[kScratchBinding].readOnly) return c.fail(-4, "depthPrepassRaster: the scratch buffer (binding 5) is bound read-only");
     if (int rc = c.needStorage(kDepthBinding, F_D32, "depthPrepassRaster depth")) return rc;
@@ -771,6 +920,18 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
             if (c.sbuf[b].ptr == c.sbuf[kScratchBinding].ptr) return c.fail(-4, "depthPrepassRaster: the scratch buffer is also bound as an input");
     if (pc.alphaTest && c.sbuf[kAlphaCutoffBinding].ptr == c.sbuf[kScratchBinding].ptr)
         return c.fail(-4, "depthPrepassRaster: the scratch buffer is also bound as an input (binding 10, alphaCutoffs)");
+    if (pc.normalMap) {
+        if (int rc = c.needStorage(kShadingNormalBinding, F_RGBA8, "depthPrepassRaster shadingNormal")) return rc;
+        const ImgView sn = c.storage[kShadingNormalBinding];
+        if (sn.w != depth.w || sn.h != depth.h || sn.d > 1)
+            return c.fail(-4, "depthPrepassRaster: shadingNormal (storage binding 5) is " + std::to_string(sn.w) + " x " + std::to_string(sn.h) + ", it must have the size of the other five: depth is " +
+                                  std::to_string(depth.w) + " x " + std::to_string(depth.h));
+        for (int o = 0; o < kShadingNormalBinding; o++)
+            if (c.storage[o].ptr == sn.ptr) return c.fail(-4, "depthPrepassRaster: one image is bound at two storage bindings (shadingNormal, binding 5)");
+        for (int b : {kTangentBinding, kBitangentBinding, kNormalMaterialBinding})
+            if (c.sbuf[b].ptr == c.sbuf[kScratchBinding].ptr)
+                return c.fail(-4, "depthPrepassRaster: the scratch buffer is also bound as an input (binding " + std::to_string(b) + ", a normal map input)");
+    }
 
     uint8_t* scratch = (uint8_t*)c.sbuf[kScratchBinding].ptr;
     if (hipMemsetAsync(scratch, 0, sizeof(ScratchHeader), c.stream) != hipSuccess) return c.fail(-2, "depthPrepassRaster: clearing the scratch header failed");
@@ -805,7 +966,27 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
         t.tex.textures = (const Texture*)c.sbuf[kTextureBinding].ptr; t.tex.texels = (const uint32_t*)c.sbuf[kTexelBinding].ptr;
         t.tex.uvVertexCount = c.sbuf[kUvBinding].size / 8u; t.tex.texelCount = c.sbuf[kTexelBinding].size / 4u;
         t.tex.drawCount = pc.drawCount; t.tex.textureCount = pc.textureCount;
-        if (pc.alphaTest) {
+        if (pc.normalMap) {
+            NormalTileParams n{};
+            static_cast<TileParams&>(n) = t;
+            n.shadingNormal = (uint32_t*)c.storage[kShadingNormalBinding].ptr;
+            if (pc.alphaTest) {
+                n.alphaCutoffs = (const uint32_t*)c.sbuf[kAlphaCutoffBinding].ptr;
+                depthPrepassTileKernel<true, true, true><<<tiles, 256, 0, c.stream>>>(n);
+            } else
+                depthPrepassTileKernel<true, false, true><<<tiles, 256, 0, c.stream>>>(n);
+            PLR_CHECK_LAUNCH(c);
+            c.splitTiming("tiles");
+            ShadingNormalParams s{};
+            s.origins = t.origins; s.transforms = t.transforms; s.positions = t.positions; s.normals = t.normals; s.indices = t.indices; s.draws = t.draws;
+            s.global = c.global; s.normal = t.normal; s.shadingNormal = n.shadingNormal;
+            s.tangents = (const float*)c.sbuf[kTangentBinding].ptr; s.bitangents = (const float*)c.sbuf[kBitangentBinding].ptr;
+            s.normalMaterials = (const uint32_t*)c.sbuf[kNormalMaterialBinding].ptr;
+            s.tangentVertexCount = c.sbuf[kTangentBinding].size / 12u; s.bitangentVertexCount = c.sbuf[kBitangentBinding].size / 12u;
+            s.triangleCount = pc.triangleCount; s.normalMaterialCount = (uint32_t)std::min<size_t>(c.sbuf[kNormalMaterialBinding].size / 4u, 0xffffffffu);
+            s.decode = pc.normalMap; s.width = depth.w; s.height = depth.h; s.tex = t.tex;
+            depthPrepassShadingNormalKernel<<<dim3(divUp((unsigned)depth.w, 64u), divUp((unsigned)depth.h, 4u)), 256, 0, c.stream>>>(s);
+        } else if (pc.alphaTest) {
             t.alphaCutoffs = (const uint32_t*)c.sbuf[kAlphaCutoffBinding].ptr;
             depthPrepassTileKernel<true, true><<<tiles, 256, 0, c.stream>>>(t);
         } else

@@ -67,6 +67,7 @@ class PlrfSceneDraw(C.Structure):
 
 NO_TEXTURE = 0xFFFFFFFF  # PLRF_NO_TEXTURE
 ALPHA_CUTOFF_REFERENCE = 128  # PLRF_ALPHA_CUTOFF_REFERENCE
+NORMAL_DECODE_REFERENCE, NORMAL_DECODE_UNIT = 1, 2  # PLRF_NORMAL_DECODE_REFERENCE, PLRF_NORMAL_DECODE_UNIT
 
 
 class PlrfSceneTexture(C.Structure):
@@ -338,6 +339,7 @@ class FramePipeline:
             d[k].model_matrix = (C.c_float * 16)(*[float(v) for v in np.asarray(matrix, np.float32).reshape(16)])
             d[k].albedo_rgba8, d[k].specular_rgba8 = int(albedo), int(specular)
         self._check(self.lib.plrf_set_scene_meshes(self.handle, m, C.c_uint32(len(meshes)), d, C.c_uint32(len(draws))))
+        self._scene_mesh_count = len(meshes)  # (what set_scene_normal_maps passes when it is given neither tangents nor bitangents)
 
     def set_scene_mesh_transforms(self, matrices):
         """one 16-float model matrix per draw, from the next frame on"""
@@ -377,6 +379,27 @@ class FramePipeline:
         a = np.ascontiguousarray(cutoffs, np.uint32).reshape(-1)
         self.lib.plrf_set_scene_alpha_cutoffs.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]
         self._check(self.lib.plrf_set_scene_alpha_cutoffs(self.handle, a.ctypes.data_as(C.POINTER(C.c_uint32)) if a.size else None, C.c_uint32(a.size)))
+
+    def set_scene_normal_maps(self, mesh_tangents, mesh_bitangents, normal_textures, decode=NORMAL_DECODE_REFERENCE):
+        """normal maps for the scene and textures now set: mesh_tangents, mesh_bitangents: one n x 3 float32 array or None per mesh of the scene (the list itself
+        may be None: every mesh without) - no tangents: all (0, 0, 0); no bitangents: the host derives normalize(cross(tangent, normal)); normal_textures: one
+        texture index or NO_TEXTURE per draw; decode: NORMAL_DECODE_REFERENCE (the reference's reconstruction as written) or NORMAL_DECODE_UNIT. Copied; from the
+        next frame on the prepass writes the "shadingNormal" image and the deferred shade reads it. No normal_textures: they are removed"""
+        def pointers(arrays):
+            if arrays is None:
+                return None, 0, []
+            keep = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in arrays]
+            p = (C.POINTER(C.c_float) * max(len(keep), 1))()
+            for k, a in enumerate(keep):
+                p[k] = None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+            return p, len(keep), keep
+        t, tn, keep_t = pointers(mesh_tangents)
+        b, bn, keep_b = pointers(mesh_bitangents)
+        n = np.ascontiguousarray(normal_textures, np.uint32).reshape(-1)
+        self.lib.plrf_set_scene_normal_maps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32]
+        self._check(self.lib.plrf_set_scene_normal_maps(self.handle, None if t is None else C.cast(t, C.c_void_p), None if b is None else C.cast(b, C.c_void_p),
+                                                        C.c_uint32(max(tn, bn) if t is not None or b is not None else getattr(self, "_scene_mesh_count", 0)), n.ctypes.data_as(C.POINTER(C.c_uint32)) if n.size else None, C.c_uint32(n.size),
+                                                        C.c_uint32(int(decode))))
 
     def prepass_raster_stats(self):
         """(triangles submitted, triangles clipped, sub-triangles drawn, rejects) of the last frame's execution; waits for the GPU"""

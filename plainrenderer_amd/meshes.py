@@ -6,6 +6,10 @@ the negative of the counter-clockwise normal, so triangles are emitted clockwise
 with_uvs=True makes uv_sphere, box and torus return a third array, n x 2 float32 texture coordinates per vertex, in [0, 1]: (segment / segments, ring / rings) on the
 sphere, the face grid's (i / subdiv, j / subdiv) on every box face, (segment / segments, side / sides) on the torus. Vertices are not duplicated for them: the sphere's and
 the torus' last column of quads shares its far vertices with the first column, so the coordinate runs back to 0 across that one column (a seam).
+
+with_tangents=True makes them return one more array behind everything else, n x 3 float32 unit tangents per vertex along increasing u: the direction of growing
+longitude on the sphere (also at the poles) and around the torus' major circle, the face grid's i axis on every box face. Without the flag the return shapes are
+what they were.
 """
 import numpy as np
 
@@ -23,11 +27,12 @@ def _finish(positions, tris, outward_ref=None):
     return positions, tris[keep].reshape(-1)
 
 
-def _with_uvs(mesh, uvs, with_uvs):
-    return mesh + (np.asarray(uvs, np.float32).reshape(-1, 2),) if with_uvs else mesh
+def _with_uvs(mesh, uvs, with_uvs, tangents=None):
+    mesh = mesh + (np.asarray(uvs, np.float32).reshape(-1, 2),) if with_uvs else mesh
+    return mesh if tangents is None else mesh + (np.asarray(tangents, np.float32).reshape(-1, 3),)
 
 
-def uv_sphere(radius=1.0, segments=24, rings=12, centre=(0.0, 0.0, 0.0), with_uvs=False):
+def uv_sphere(radius=1.0, segments=24, rings=12, centre=(0.0, 0.0, 0.0), with_uvs=False, with_tangents=False):
     pos = []
     for r in range(rings + 1):
         th = np.pi * r / rings
@@ -41,10 +46,11 @@ def uv_sphere(radius=1.0, segments=24, rings=12, centre=(0.0, 0.0, 0.0), with_uv
             c = (r + 1) * segments + s; d = (r + 1) * segments + (s + 1) % segments
             tris += [(a, b, c), (b, d, c)]
     p = np.asarray(pos, np.float32) + np.asarray(centre, np.float32)
-    return _with_uvs(_finish(p, tris), [(s / segments, r / rings) for r in range(rings + 1) for s in range(segments)], with_uvs)
+    tangents = [(-np.sin(2.0 * np.pi * s / segments), 0.0, np.cos(2.0 * np.pi * s / segments)) for r in range(rings + 1) for s in range(segments)] if with_tangents else None
+    return _with_uvs(_finish(p, tris), [(s / segments, r / rings) for r in range(rings + 1) for s in range(segments)], with_uvs, tangents)
 
 
-def box(half=(1.0, 1.0, 1.0), centre=(0.0, 0.0, 0.0), subdiv=2, with_uvs=False):
+def box(half=(1.0, 1.0, 1.0), centre=(0.0, 0.0, 0.0), subdiv=2, with_uvs=False, with_tangents=False):
     """Axis-aligned box, each face a subdiv x subdiv grid of quads."""
     half = np.asarray(half, np.float32)
     pos, tris = [], []
@@ -64,10 +70,11 @@ def box(half=(1.0, 1.0, 1.0), centre=(0.0, 0.0, 0.0), subdiv=2, with_uvs=False):
                     a = base + i * (subdiv + 1) + j; b = a + 1; c = a + subdiv + 1; d = c + 1
                     tris += [(a, b, c), (b, d, c)]
     p = np.asarray(pos, np.float32) + np.asarray(centre, np.float32)
-    return _with_uvs(_finish(p, tris), [(i / subdiv, j / subdiv) for _ in range(6) for i in range(subdiv + 1) for j in range(subdiv + 1)], with_uvs)
+    tangents = [np.eye(3)[(axis + 1) % 3] for axis in range(3) for _ in range(2 * (subdiv + 1) ** 2)] if with_tangents else None
+    return _with_uvs(_finish(p, tris), [(i / subdiv, j / subdiv) for _ in range(6) for i in range(subdiv + 1) for j in range(subdiv + 1)], with_uvs, tangents)
 
 
-def torus(major=1.5, minor=0.5, segments=24, sides=12, centre=(0.0, 0.0, 0.0), with_uvs=False):
+def torus(major=1.5, minor=0.5, segments=24, sides=12, centre=(0.0, 0.0, 0.0), with_uvs=False, with_tangents=False):
     pos, tris = [], []
     for i in range(segments):
         a = 2.0 * np.pi * i / segments
@@ -91,7 +98,8 @@ def torus(major=1.5, minor=0.5, segments=24, sides=12, centre=(0.0, 0.0, 0.0), w
         out[:, [0, 2]] = xz / np.maximum(n, 1e-9) * major
         return out
     positions, idx = _finish(p, tris, outward_ref=ring_centre)
-    return _with_uvs((positions + c3, idx), [(i / segments, j / sides) for i in range(segments) for j in range(sides)], with_uvs)
+    tangents = [(-np.sin(2.0 * np.pi * i / segments), 0.0, np.cos(2.0 * np.pi * i / segments)) for i in range(segments) for j in range(sides)] if with_tangents else None
+    return _with_uvs((positions + c3, idx), [(i / segments, j / sides) for i in range(segments) for j in range(sides)], with_uvs, tangents)
 
 
 def bounds(positions):

@@ -1,6 +1,6 @@
 """What the depth prepass costs as a compute pass ("depthPrepassRaster.comp", plrf_set_scene_meshes) in bench.py's 4K frame.
 
-    python tools/prepass_raster_cost.py [--out FILE] [--frames N] [--instances K] [--textured | --alpha]
+    python tools/prepass_raster_cost.py [--out FILE] [--frames N] [--instances K] [--textured | --alpha | --normal-mapped]
 
 One process, one build. The scene is the instance set of tools/shadow_raster_cost.py: the three meshes of tests/shadow_raster_cases.py (box, uv_sphere, torus:
 1496 triangles) instanced K times (default 202: about 100 k triangles) over the view frustum in front of bench.py's camera, rasterised into the 3840 x 2160
@@ -11,6 +11,8 @@ bounds the tile kernel). The same with every instance shrunk to 1 / 20, where th
 with full chains (two textures, shared by the draws) by the mesh generators' UVs; compare its tile times with a run without the option.
 --alpha: the --textured scenes with the alpha test (plrf_set_scene_alpha_cutoffs): every draw has cutoff 128 and the albedo texture's alpha is a 0 / 255
 checker in cells of 32 texels, so about half of each draw's fragments are discarded; compare its tile times with --textured of the same build.
+--normal-mapped: the --textured scenes with normal maps (plrf_set_scene_normal_maps): every draw names a 256 x 256 normal texture with a full chain; the tile
+kernel and the shading-normal kernel behind it are reported separately; compare with --textured of the same build.
 It also reports that a frame WITHOUT scene meshes records the passes and runs the general kernels it did before a scene was ever set.
 The report goes to stdout and to --out.
 """
@@ -64,6 +66,22 @@ def scene_textures(draw_count, alpha_checker=False):
     return [(albedo.reshape(-1), 256, 256, 0), (specular.reshape(-1), 256, 256, 0)], uvs, [(0, 1)] * draw_count
 
 
+def scene_normal_maps(draw_count):
+    """(one more texture, mesh_tangents, mesh_bitangents, normal_textures): a 256 x 256 normal texture (the host builds the chain) named by every draw, the
+    generators' tangents; the box came without normals, so its bitangents are given (cross(tangent, area-weighted vertex normal)), the others the host derives"""
+    import prepass_raster_cases as pc
+    from plainrenderer_amd import meshes
+    y, x = np.mgrid[0:256, 0:256].astype(np.float64)
+    nx, ny = 0.5 + 0.35 * np.sin(x * (2.0 * np.pi / 32.0)), 0.5 + 0.35 * np.cos(y * (2.0 * np.pi / 16.0))
+    texels = np.rint(nx * 255.0).astype(np.uint32) | (np.rint(ny * 255.0).astype(np.uint32) << 8) | np.uint32(0xFFFF0000)
+    raw = [meshes.box((1.0, 1.5, 0.75), subdiv=4, with_tangents=True), meshes.uv_sphere(1.25, segments=28, rings=14, with_tangents=True),
+           meshes.torus(1.5, 0.5, segments=24, sides=12, with_tangents=True)]
+    tangents = [np.asarray(m[-1], np.float32) for m in raw]
+    c = np.cross(tangents[0].astype(np.float64), pc.vertex_normals(raw[0][0], raw[0][1]).astype(np.float64))
+    box_bitangents = (c / np.maximum(np.linalg.norm(c, axis=1, keepdims=True), 1e-30)).astype(np.float32)
+    return (texels.reshape(-1), 256, 256, 0), tangents, [box_bitangents, None, None], [2] * draw_count
+
+
 def pass_times(be, fp, cams, first, frames):
     """-> ({pass name: mean us} of the prepass, number of timed entries of the last frame)"""
     be.setPassTiming(True)
@@ -88,6 +106,7 @@ def main():
     ap.add_argument("--instances", type=int, default=202)
     ap.add_argument("--textured", action="store_true")
     ap.add_argument("--alpha", action="store_true")
+    ap.add_argument("--normal-mapped", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
     import torch  # noqa: F401  (first: it brings its own HIP runtime)
@@ -101,7 +120,7 @@ def main():
     fp = FramePipeline(be, W, H, shadow_map_res=2048)
     _, cams, inputs = bench.build_scene(args, "cuda:0", W, H, None)
     inputs.upload(fp)
-    lines = ["# python tools/prepass_raster_cost.py%s: bench.py's scene at %d x %d, fast kernel set, %d frames per figure" % (" --alpha" if a.alpha else " --textured" if a.textured else "", W, H, a.frames)]
+    lines = ["# python tools/prepass_raster_cost.py%s: bench.py's scene at %d x %d, fast kernel set, %d frames per figure" % (" --normal-mapped" if a.normal_mapped else " --alpha" if a.alpha else " --textured" if a.textured else "", W, H, a.frames)]
     cursor = 1
     for i in range(args.warmup):
         fp.frame(cams[cursor + i], 1.0 / 60.0, 0.5)
@@ -116,7 +135,12 @@ def main():
         meshes = [pc.mesh_arrays(m, k != 0) for k, m in enumerate(raw)]
         scene_draws = [(m, t, *pc.material(d)) for d, (m, t) in enumerate(draws)]
         fp.set_scene_meshes(meshes, scene_draws)
-        if a.textured or a.alpha:
+        if a.normal_mapped:
+            textures, uvs, materials = scene_textures(len(draws))
+            normal_texture, tangents, bitangents, normal_textures = scene_normal_maps(len(draws))
+            fp.set_scene_textures(textures + [normal_texture], uvs, materials)
+            fp.set_scene_normal_maps(tangents, bitangents, normal_textures)
+        elif a.textured or a.alpha:
             fp.set_scene_textures(*scene_textures(len(draws), alpha_checker=a.alpha))
         if a.alpha:
             fp.set_scene_alpha_cutoffs([128] * len(draws))
@@ -126,8 +150,11 @@ def main():
         matrices = be.downloadStorageBuffer(fp.storage_buffer("mainPassMatrices"), 192 * len(draws), dtype=np.float32).reshape(-1, 48)
         covered = max(int((be.downloadImage(fp.image("depth%d" % t), 0, np.float32) > 0).sum()) for t in (0, 1))
         mean_hits, max_hits, touched = tile_hits(matrices, meshes, scene_draws)
+        # a normal-mapped execution reports the tile kernel as "(tiles)" and the shading-normal kernel behind it under the pass' name
         lines.append("%-26s %9d %9d %9d %8d %8d %13d %11.2f %10.2f" % (label, submitted, drawn, clipped, rejects, covered, max_hits, times.get("Depth prepass (set-up)", float("nan")),
-                                                                 times.get("Depth prepass", float("nan"))))
+                                                                 times.get("Depth prepass (tiles)", times.get("Depth prepass", float("nan")))))
+        if a.normal_mapped:
+            lines.append("  shading-normal kernel: %.2f us" % times.get("Depth prepass", float("nan")))
         lines.append("  %d draws; %d of %d tiles touched, %.1f rectangles per tile on average" % (len(draws), touched, tiles, mean_hits))
     general_with = be.getGeneralKernelExecutions()
     fp.set_scene_meshes([], [])
