@@ -310,6 +310,24 @@ typedef struct plrf_scene_texture { const uint32_t* texels; uint32_t width, heig
 typedef struct plrf_scene_material { uint32_t albedo_texture, specular_texture; } plrf_scene_material;
 int plrf_set_scene_textures(void* pipeline, const plrf_scene_texture* textures, uint32_t texture_count, const float* const* mesh_uvs, uint32_t mesh_count,
                             const plrf_scene_material* materials, uint32_t draw_count);
+/* ---- block-compressed material textures (DESIGN.md "Block-compressed textures in the depth prepass"): plrf_set_scene_textures for textures that carry a format.
+ * plrf_scene_texture_data: `data` holds `bytes` bytes. format PLR_FORMAT_RGBA8: the texels of a plrf_scene_texture, and the entry behaves exactly as one
+ * (mip_count 0: the host builds the chain). format PLR_FORMAT_BC1, PLR_FORMAT_BC3 or PLR_FORMAT_BC5: the blocks of mip_count >= 1 levels back to back, level l being
+ * ceil(W_l / 4) x ceil(H_l / 4) blocks (8 bytes for BC1, 16 for BC3 and BC5), row-major, with W_l = max(1, width >> l) - the payload of a DXT1 / DXT5 / ATI2 DDS
+ * file as plr_load_dds_file returns it. The pass decodes the four taps of every footprint in integers (BC1: (r, g, b, 255), the BC1_RGB variant; BC3: (r, g, b, a),
+ * the colour block always in four-colour mode; BC5: (R, G, 0, 255)) and then filters them as the sampling contract filters RGBA8 words; plr_decode_bc_to_rgba8
+ * (plr_image_io.h) is the same decode on the host. `bytes` must be the exact size of the entry's levels. Semantics, lifetime and removal are
+ * plrf_set_scene_textures': the stores replace one another, texture_count 0 removes, and alpha cutoffs and normal maps set afterwards index this store. A call whose
+ * entries are all RGBA8 records exactly the pass plrf_set_scene_textures records. PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: what
+ * plrf_set_scene_textures refuses, an unknown format, mip_count 0 on a compressed entry, a bytes mismatch, more than 2^28 words in total (a compressed entry starts
+ * at a multiple of 16 bytes). PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing. */
+typedef struct plrf_scene_texture_data {
+    const void* data;
+    uint64_t bytes;
+    uint32_t width, height, mip_count, format; /* PLR_FORMAT_RGBA8 | BC1 | BC3 | BC5 */
+} plrf_scene_texture_data;
+int plrf_set_scene_textures_formatted(void* pipeline, const plrf_scene_texture_data* textures, uint32_t texture_count, const float* const* mesh_uvs, uint32_t mesh_count,
+                                      const plrf_scene_material* materials, uint32_t draw_count);
 /* ---- alpha-tested cutouts: depthPrepass.frag:27-30 (sample the albedo texture's alpha with g_mipBias, discard below 0.5) as a per-draw cutoff code 0 .. 255
  * (DESIGN.md "Alpha-tested cutouts in the depth prepass"). 0 is opaque; PLRF_ALPHA_CUTOFF_REFERENCE (128) is the reference's test, a / 255 < 0.5 <=> a <= 127.
  * The alpha code of a fragment is bits 24 - 31 of the albedo word the sampling contract yields for its triangle at that pixel (the draw's constant albedo_rgba8

@@ -5,6 +5,7 @@
  * File layout: magic 0x20534444 ("DDS "), the 124-byte DDS_header, for fourCC "DX10" the 20-byte DDS_headerDX10, then the raw texels
  * (x fastest, then y, then z; all mips consecutively). The writer always emits a DX10 header (formats RGBA8 and R16_sFloat, as the
  * reference); the reader understands DX10/R16_FLOAT and the legacy fourCCs DXT1 (BC1), DXT5 (BC3), ATI2 (BC5), as the reference.
+ * plr_decode_bc_to_rgba8 decodes the blocks of such a file's BC1 / BC3 / BC5 levels on the host.
  * All functions return PLR_OK (0) or a negative code; plr_last_error() (plr.h) explains. No GPU is involved. */
 #ifndef PLR_IMAGE_IO_H
 #define PLR_IMAGE_IO_H
@@ -25,6 +26,15 @@ int plr_load_dds_file(const char* path, plr_image_desc* out_desc, void* out_data
 /* in-memory forms of the same (used by the file functions): serialise to / parse from a byte buffer */
 int plr_encode_dds(const plr_image_desc* desc, const void* data, size_t data_size, void* out_file, size_t capacity, size_t* out_file_size);
 int plr_decode_dds(const void* file, size_t file_size, plr_image_desc* out_desc, size_t* out_data_offset, size_t* out_data_size);
+
+/* One level of a block-compressed image to RGBA8 words, R in the low byte, in plain integer arithmetic: the decode "depthPrepassRaster.comp" applies to the taps of a
+ * compressed scene texture (DESIGN.md "Block-compressed textures in the depth prepass"), so a caller can hand the same codes to an entry point that takes RGBA8
+ * only (plrf_set_shadow_caster_cutouts). format: PLR_FORMAT_BC1 (8-byte blocks: (r, g, b, 255), three-colour mode with an opaque black index 3 where c0 <= c1),
+ * PLR_FORMAT_BC3 (16-byte blocks: alpha block, then a colour block that is always in four-colour mode) or PLR_FORMAT_BC5 (16-byte blocks: (R, G, 0, 255)). The
+ * level is ceil(width / 4) x ceil(height / 4) blocks, row-major; texel (x, y) is position 4 (y & 3) + (x & 3) of block (x >> 2, y >> 2). bytes must be exactly
+ * the level's size; out_words receives width * height words. PLR_ERR_INVALID_ARGUMENT: another format, a side of 0 or above 16384, a NULL pointer, a byte count
+ * other than the level's. */
+int plr_decode_bc_to_rgba8(int format, uint32_t width, uint32_t height, const void* blocks, uint64_t bytes, uint32_t* out_words);
 
 #ifdef __cplusplus
 }

@@ -14,12 +14,14 @@ constexpr int kTransformBinding = 0, kPositionBinding = 1, kNormalBinding = 2, k
 constexpr int kUvBinding = 6, kMaterialBinding = 7, kTextureBinding = 8, kTexelBinding = 9; // storage buffers of a textured execution (textureCount > 0)
 constexpr int kAlphaCutoffBinding = 10; // storage buffer of an alpha-tested execution (alphaTest != 0): one uint32 cutoff code per draw
 constexpr int kTangentBinding = 11, kBitangentBinding = 12, kNormalMaterialBinding = 13; // storage buffers of a normal-mapped execution (normalMap != 0)
+constexpr int kTextureFormatBinding = 14; // storage buffer of a format-aware execution (textureFormats = 1): one uint32 format code per texture
 constexpr int kDepthBinding = 0, kMotionBinding = 1, kNormalImageBinding = 2, kAlbedoBinding = 3, kSpecularBinding = 4;                                   // storage images
 constexpr int kShadingNormalBinding = 5; // storage image of a normal-mapped execution: the per-pixel shading normal (RGBA8)
 struct PushConstants { uint32_t drawCount, triangleCount; };
 struct TexturedPushConstants { uint32_t drawCount, triangleCount, textureCount; }; // the optional third word: 0, or absent, is the untextured pass
 struct AlphaPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest; }; // the optional fourth word: 0, or absent, is the pass without the alpha test
 struct NormalPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest, normalMap; }; // the optional fifth word: 0, or absent, is the pass without normal maps
+struct FormatPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest, normalMap, textureFormats; }; // the optional sixth word: 0, or absent, is the pass whose textures are all RGBA8
 struct Draw { uint32_t firstIndex, indexCount, vertexOffset, transformIndex, albedo, specular; }; // albedo, specular: RGBA8 texels as they are stored
 struct MainPassMatrices { float model[16], mvp[16], mvpPrevious[16]; };                            // glm column-major (RenderFrontend.cpp:581-585)
 // material textures ("The sampling contract"): `texels` holds RGBA8 texels, R in the low byte, every texture's levels back to back and unpadded; level l is
@@ -27,6 +29,20 @@ struct MainPassMatrices { float model[16], mvp[16], mvpPrevious[16]; };         
 struct Texture { uint32_t texelOffset, width, height, mipCount; };  // texelOffset in texels
 struct Material { uint32_t albedoTexture, specularTexture; };       // per draw; kNoTexture: the draw's constant word
 constexpr uint32_t kNoTexture = 0xffffffffu;
+// block-compressed textures ("Block-compressed textures in the depth prepass"): a format-aware execution's `textureFormats` holds one of these codes per texture.
+// A compressed texture's levels are ceil(W_l / 4) x ceil(H_l / 4) blocks, row-major, back to back in `texels`; its texelOffset counts uint32 words and is a
+// multiple of its block's words. A code above kTextureFormatBc5 makes the entry unusable
+constexpr uint32_t kTextureFormatRgba8 = 0, kTextureFormatBc1 = 1, kTextureFormatBc3 = 2, kTextureFormatBc5 = 3;
+constexpr uint32_t blockWords(uint32_t format) { return format == kTextureFormatBc1 ? 2u : 4u; } // of a compressed format: 8-byte and 16-byte blocks
+// the uint32 words of all `mipCount` levels of a width x height texture of `format`
+constexpr uint64_t textureWords(uint32_t format, uint32_t width, uint32_t height, uint32_t mipCount) {
+    uint64_t words = 0;
+    for (uint32_t l = 0; l < mipCount; l++) {
+        const uint64_t w = (width >> l) ? (width >> l) : 1u, h = (height >> l) ? (height >> l) : 1u;
+        words += format == kTextureFormatRgba8 ? w * h : ((w + 3u) / 4u) * ((h + 3u) / 4u) * blockWords(format);
+    }
+    return words;
+}
 constexpr uint32_t kMaxTextureSize = 16384;
 constexpr uint64_t kMaxTexels = 1ull << 28;                         // what plrf_set_scene_textures accepts in total
 // the alpha test ("The alpha test contract"): a draw's cutoff code c, 0 = opaque; a fragment passes when its alpha code is >= c. The kernel uses min(word, 256):

@@ -9,6 +9,7 @@
 
 #include "../../../include/plr_image_io.h"
 #include "../backend.h"
+#include "frame_pipeline.h"
 
 namespace {
 
@@ -117,6 +118,16 @@ extern "C" int plr_encode_dds(const plr_image_desc* desc, const void* data, size
 
 extern "C" int plr_decode_dds(const void* file, size_t fileSize, plr_image_desc* desc, size_t* dataOffset, size_t* dataSize) {
     return decode((const uint8_t*)file, fileSize, desc, dataOffset, dataSize);
+}
+
+// the block decode contract on the host (frontend/scene_packing.cpp decodeBlockCompressedLevel)
+extern "C" int plr_decode_bc_to_rgba8(int format, uint32_t width, uint32_t height, const void* blocks, uint64_t bytes, uint32_t* outWords) {
+    try {
+        plrhost::decodeBlockCompressedLevel((uint32_t)format, width, height, blocks, bytes, outWords);
+    } catch (const plrhost::FramePipelineRefusal& e) {
+        return setLastError(e.code, e.what());
+    }
+    return PLR_OK;
 }
 
 extern "C" int plr_write_dds_file(const char* path, const plr_image_desc* desc, const void* data, size_t dataSize) {

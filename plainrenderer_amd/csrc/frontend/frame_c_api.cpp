@@ -155,6 +155,17 @@ int plrf_set_scene_textures(void* p, const plrf_scene_texture* textures, uint32_
         ((FramePipeline*)p)->setSceneTextures(t.empty() ? nullptr : t.data(), textureCount, meshUvs, meshCount, m.empty() ? nullptr : m.data(), drawCount);
     })
 }
+int plrf_set_scene_textures_formatted(void* p, const plrf_scene_texture_data* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount,
+                                      const plrf_scene_material* materials, uint32_t drawCount) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        std::vector<SceneTextureData> t(textures ? textureCount : 0u);
+        for (size_t i = 0; i < t.size(); i++) t[i] = {textures[i].data, textures[i].bytes, textures[i].width, textures[i].height, textures[i].mip_count, textures[i].format};
+        std::vector<SceneMaterial> m(materials ? drawCount : 0u);
+        for (size_t i = 0; i < m.size(); i++) m[i] = {materials[i].albedo_texture, materials[i].specular_texture};
+        ((FramePipeline*)p)->setSceneTexturesFormatted(t.empty() ? nullptr : t.data(), textureCount, meshUvs, meshCount, m.empty() ? nullptr : m.data(), drawCount);
+    })
+}
 int plrf_set_scene_alpha_cutoffs(void* p, const uint32_t* cutoffs, uint32_t drawCount) {
     if (!p) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY_REFUSAL(((FramePipeline*)p)->setSceneAlphaCutoffs(cutoffs, drawCount))

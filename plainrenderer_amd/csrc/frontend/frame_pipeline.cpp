@@ -1408,14 +1408,16 @@ void FramePipeline::renderDepthPrepass(const FrameRenderTargets& current) {
                                                 StorageBufferResource(m_sceneNormals.handle, true, pp::kNormalBinding), StorageBufferResource(m_sceneIndices.handle, true, pp::kIndexBinding),
                                                 StorageBufferResource(m_sceneDraws.handle, true, pp::kDrawBinding), StorageBufferResource(m_sceneScratch.handle, false, pp::kScratchBinding)};
     const bool alphaTested = m_sceneAlphaTested && m_sceneTextureCount;
-    const pp::NormalPushConstants pc{m_sceneDrawCount, m_sceneTriangleCount, m_sceneTextureCount, alphaTested ? 1u : 0u, normalMapped() ? m_sceneNormalDecode : 0u};
-    // without textures: the 8-byte record; without a cutoff other than 0: the 12-byte one; without normal maps: the 16-byte one
-    exe.pushConstants = dataToCharArray(&pc, normalMapped() ? sizeof(pc) : alphaTested ? sizeof(pp::AlphaPushConstants) : m_sceneTextureCount ? sizeof(pp::TexturedPushConstants) : sizeof(pp::PushConstants));
+    const bool compressed = m_sceneTexturesCompressed && m_sceneTextureCount;
+    const pp::FormatPushConstants pc{m_sceneDrawCount, m_sceneTriangleCount, m_sceneTextureCount, alphaTested ? 1u : 0u, normalMapped() ? m_sceneNormalDecode : 0u, compressed ? 1u : 0u};
+    // without textures: the 8-byte record; without a cutoff other than 0: the 12-byte one; without normal maps: the 16-byte one; without a compressed texture: the 20-byte one
+    exe.pushConstants = dataToCharArray(&pc, compressed ? sizeof(pc) : normalMapped() ? sizeof(pp::NormalPushConstants) : alphaTested ? sizeof(pp::AlphaPushConstants) : m_sceneTextureCount ? sizeof(pp::TexturedPushConstants) : sizeof(pp::PushConstants));
     if (m_sceneTextureCount) {
         auto& buffers = exe.genericInfo.resources.storageBuffers;
         buffers.push_back(StorageBufferResource(m_sceneUvs.handle, true, pp::kUvBinding)); buffers.push_back(StorageBufferResource(m_sceneMaterials.handle, true, pp::kMaterialBinding));
         buffers.push_back(StorageBufferResource(m_sceneTextures.handle, true, pp::kTextureBinding)); buffers.push_back(StorageBufferResource(m_sceneTexels.handle, true, pp::kTexelBinding));
         if (alphaTested) buffers.push_back(StorageBufferResource(m_sceneAlphaCutoffs.handle, true, pp::kAlphaCutoffBinding));
+        if (compressed) buffers.push_back(StorageBufferResource(m_sceneTextureFormats.handle, true, pp::kTextureFormatBinding));
         if (normalMapped()) {
             buffers.push_back(StorageBufferResource(m_sceneTangents.handle, true, pp::kTangentBinding)); buffers.push_back(StorageBufferResource(m_sceneBitangents.handle, true, pp::kBitangentBinding));
             buffers.push_back(StorageBufferResource(m_sceneNormalMaterials.handle, true, pp::kNormalMaterialBinding));
@@ -1449,7 +1451,7 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneMeshes: a band / tile pipeline cannot rasterise scene meshes (a partition would have to rasterise only its own rectangle)");
     if (drawCount == 0) {
         m_sceneDrawCount = m_sceneTriangleCount = m_sceneTextureCount = 0;
-        m_scenePreviousValid = m_sceneRecorded = m_sceneAlphaTested = false;
+        m_scenePreviousValid = m_sceneRecorded = m_sceneAlphaTested = m_sceneTexturesCompressed = false;
         m_sceneNormalDecode = 0;
         m_sceneMeshVertexCounts.clear(); m_sceneMeshHasNormals.clear(); m_sceneNormalsHost.clear();
         return;
@@ -1474,6 +1476,7 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
     m_sceneDrawCount = drawCount; m_sceneTriangleCount = packed.triangleCount;
     m_sceneMeshVertexCounts = packed.meshVertexCounts;
     m_sceneTextureCount = 0; // the textures belonged to the scene that was replaced
+    m_sceneTexturesCompressed = false;
     m_sceneAlphaTested = false; // and so did the cutoffs
     m_sceneNormalDecode = 0;    // and the normal maps
     m_sceneMeshHasNormals = packed.meshHasNormals;
@@ -1483,7 +1486,7 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
 void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {
     if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneTextures: a band / tile pipeline cannot rasterise scene meshes");
-    if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = false; m_sceneNormalDecode = 0; return; }
+    if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = m_sceneTexturesCompressed = false; m_sceneNormalDecode = 0; return; }
     const PackedTextures packed = packSceneTextures(textures, textureCount, meshUvs, meshCount, materials, drawCount, m_sceneMeshVertexCounts.data(),
                                                     (uint32_t)m_sceneMeshVertexCounts.size(), m_sceneDrawCount); // validates everything before anything is changed
     auto fill = [&](SceneBuffer& b, const std::vector<uint32_t>& data) { fillCasterBuffer(b.handle, b.bytes, data.data(), data.size() * sizeof(uint32_t)); };
@@ -1492,6 +1495,25 @@ void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t text
     fill(m_sceneTextures, packed.textures);
     fill(m_sceneTexels, packed.texels);
     m_sceneTextureCount = textureCount;
+    m_sceneTexturesCompressed = false;
+    m_sceneAlphaTested = false; // the cutoffs belonged to the materials that were replaced
+    m_sceneNormalDecode = 0;    // and the normal maps named textures that were replaced
+}
+
+void FramePipeline::setSceneTexturesFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {
+    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneTexturesFormatted: a band / tile pipeline cannot rasterise scene meshes");
+    if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = m_sceneTexturesCompressed = false; m_sceneNormalDecode = 0; return; }
+    const PackedFormattedTextures packed = packSceneTexturesFormatted(textures, textureCount, meshUvs, meshCount, materials, drawCount, m_sceneMeshVertexCounts.data(),
+                                                                      (uint32_t)m_sceneMeshVertexCounts.size(), m_sceneDrawCount); // validates everything before anything is changed
+    auto fill = [&](SceneBuffer& b, const std::vector<uint32_t>& data) { fillCasterBuffer(b.handle, b.bytes, data.data(), data.size() * sizeof(uint32_t)); };
+    fillCasterBuffer(m_sceneUvs.handle, m_sceneUvs.bytes, packed.uvs.data(), packed.uvs.size() * sizeof(float));
+    fill(m_sceneMaterials, packed.materials);
+    fill(m_sceneTextures, packed.textures);
+    fill(m_sceneTexels, packed.texels);
+    if (packed.compressed) fill(m_sceneTextureFormats, packed.formats);
+    m_sceneTextureCount = textureCount;
+    m_sceneTexturesCompressed = packed.compressed;
     m_sceneAlphaTested = false; // the cutoffs belonged to the materials that were replaced
     m_sceneNormalDecode = 0;    // and the normal maps named textures that were replaced
 }

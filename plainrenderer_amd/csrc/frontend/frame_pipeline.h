@@ -349,6 +349,22 @@ struct PackedTextures {
 // sceneMeshVertexCounts / sceneDrawCount: of the scene the pipeline holds (sceneMeshCount 0: none). Throws FramePipelineRefusal.
 PackedTextures packSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials,
                                  uint32_t drawCount, const uint32_t* sceneMeshVertexCounts, uint32_t sceneMeshCount, uint32_t sceneDrawCount);
+// material textures with a format (plr_frame.h plrf_set_scene_textures_formatted): `data` holds `bytes` bytes - RGBA8 texels as for SceneTexture, or the BC1 / BC3 /
+// BC5 blocks of mipCount >= 1 levels back to back, level l being ceil(W_l / 4) x ceil(H_l / 4) blocks, row-major. format: PLR_FORMAT_RGBA8 | BC1 | BC3 | BC5
+struct SceneTextureData { const void* data = nullptr; uint64_t bytes = 0; uint32_t width = 0, height = 0, mipCount = 0, format = 0; };
+// what setSceneTexturesFormatted validates and packs, without a backend: PackedTextures - `textures` with word offsets, `texels` with the blocks of a compressed
+// texture at a multiple of 4 words - and binding 14 of a format-aware "depthPrepassRaster.comp", one format code per texture
+struct PackedFormattedTextures : PackedTextures {
+    std::vector<uint32_t> formats;
+    bool compressed = false; // an entry that is not RGBA8: only then the frame records the sixth push-constant word
+};
+// Throws FramePipelineRefusal.
+PackedFormattedTextures packSceneTexturesFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials,
+                                                   uint32_t drawCount, const uint32_t* sceneMeshVertexCounts, uint32_t sceneMeshCount, uint32_t sceneDrawCount);
+// the block decode contract on the host (plr_image_io.h plr_decode_bc_to_rgba8): one width x height level of `format` (PLR_FORMAT_BC1 | BC3 | BC5), `bytes` bytes of
+// blocks, into width * height RGBA8 words, R in the low byte. Throws FramePipelineRefusal: another format, a size of 0 or above 16384, null pointers, a byte count
+// other than the level's
+void decodeBlockCompressedLevel(uint32_t format, uint32_t width, uint32_t height, const void* blocks, uint64_t bytes, uint32_t* outWords);
 // what setSceneAlphaCutoffs validates and packs, without a backend: binding 10 of an alpha-tested "depthPrepassRaster.comp", one cutoff code per draw
 struct PackedAlphaCutoffs {
     std::vector<uint32_t> cutoffs;
@@ -428,6 +444,12 @@ public:
     // too. Refusals: no scene, a mesh or draw count other than the scene's, a texture size of 0 or above 16384, too many mips, null texels, a material index out
     // of range, more than 2^28 texels, a non-finite UV are PLR_ERR_INVALID_ARGUMENT; a band / tile pipeline is PLR_ERR_UNSUPPORTED. A refused call changes nothing.
     void setSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount);
+    // setSceneTextures for textures that carry a format (DESIGN.md "Block-compressed textures in the depth prepass"): RGBA8 entries behave as there (mipCount 0
+    // included); a BC1, BC3 or BC5 entry gives the blocks of its mipCount >= 1 levels and is sampled through the block decode contract. While an entry is
+    // compressed the pass is recorded with the sixth push-constant word and binding 14; a call whose entries are all RGBA8 records what setSceneTextures records.
+    // Lifetime, removal and what cutoffs and normal maps set afterwards index are setSceneTextures'. Further refusals (PLR_ERR_INVALID_ARGUMENT): an unknown
+    // format, mipCount 0 on a compressed entry, a byte count other than the exact size of the entry's levels, more than 2^28 words in total.
+    void setSceneTexturesFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount);
     // alpha-tested cutouts for the scene and textures now set (DESIGN.md "Alpha-tested cutouts in the depth prepass"): one cutoff code 0 .. 255 per draw, 0 =
     // opaque, 128 = the reference's alpha < 0.5 -> discard. From the next frame on, while a cutoff is not 0, the pass is recorded with the fourth push-constant word
     // and binding 10, and a fragment whose sampled albedo alpha code is below its draw's cutoff is no fragment. Copied. drawCount 0 removes them; setSceneMeshes
@@ -571,6 +593,8 @@ private:
     uint32_t m_sceneTextureCount = 0;
     std::vector<uint32_t> m_sceneMeshVertexCounts;
     SceneBuffer m_sceneUvs, m_sceneMaterials, m_sceneTextures, m_sceneTexels;
+    bool m_sceneTexturesCompressed = false; // setSceneTexturesFormatted with a BC1 / BC3 / BC5 entry: the sixth push-constant word and binding 14
+    SceneBuffer m_sceneTextureFormats;
     // alpha cutoffs: created by the first setSceneAlphaCutoffs; not tested = the pass record without the fourth push-constant word
     bool m_sceneAlphaTested = false;
     SceneBuffer m_sceneAlphaCutoffs;

@@ -1,7 +1,8 @@
 // Validation and packing of scene meshes, their material textures, their alpha cutoffs and their normal maps for "depthPrepassRaster.comp"
-// (FramePipeline::setSceneMeshes, setSceneTextures, setSceneAlphaCutoffs, setSceneNormalMaps) and of the shadow casters' cutouts for "sunShadowRaster.comp"
-// (setShadowCasterCutouts): host code without a backend call, so that a stand-alone program can run it under a sanitizer (tools/scene_packing_check.cpp,
-// tools/scene_texture_check.cpp, tools/scene_alpha_check.cpp, tools/scene_normal_check.cpp, tools/shadow_cutout_check.cpp).
+// (FramePipeline::setSceneMeshes, setSceneTextures, setSceneTexturesFormatted, setSceneAlphaCutoffs, setSceneNormalMaps) and of the shadow casters' cutouts for
+// "sunShadowRaster.comp" (setShadowCasterCutouts), and the host's decoder of BC1 / BC3 / BC5 blocks: host code without a backend call, so that a stand-alone
+// program can run it under a sanitizer (tools/scene_packing_check.cpp, tools/scene_texture_check.cpp, tools/scene_alpha_check.cpp, tools/scene_normal_check.cpp,
+// tools/shadow_cutout_check.cpp, tools/scene_bc_check.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -95,17 +96,23 @@ void appendMipChain(std::vector<uint32_t>& texels, uint32_t width, uint32_t heig
 }
 
 // ---- the texture store and the UVs, shared by the scene's textures and the shadow casters' cutouts: `refuse` throws with the call's name in front
-template <class Refuse> static uint64_t validateTextures(const SceneTexture* textures, uint32_t textureCount, Refuse&& refuse) {
+// size, mip count and data pointer of texture t, the rules every texture call shares; returns the levels of its full chain
+template <class Refuse> static uint32_t validateTextureShape(uint32_t t, uint32_t width, uint32_t height, uint32_t mipCount, const void* data, Refuse&& refuse) {
     namespace pp = plr::prepass;
+    if (width < 1u || height < 1u || width > pp::kMaxTextureSize || height > pp::kMaxTextureSize)
+        refuse("texture size out of range: texture " + std::to_string(t) + " is " + std::to_string(width) + " x " + std::to_string(height) + ", each side must be 1 .. 16384");
+    const uint32_t full = pp::fullMipCount(width, height);
+    if (mipCount > full)
+        refuse("too many mips: texture " + std::to_string(t) + " (" + std::to_string(width) + " x " + std::to_string(height) + ") has " + std::to_string(mipCount) + " levels, at most " + std::to_string(full));
+    if (!data) refuse("null texels: texture " + std::to_string(t));
+    return full;
+}
+
+template <class Refuse> static uint64_t validateTextures(const SceneTexture* textures, uint32_t textureCount, Refuse&& refuse) {
     uint64_t total = 0;
     for (uint32_t t = 0; t < textureCount; t++) {
         const SceneTexture& tex = textures[t];
-        if (tex.width < 1u || tex.height < 1u || tex.width > pp::kMaxTextureSize || tex.height > pp::kMaxTextureSize)
-            refuse("texture size out of range: texture " + std::to_string(t) + " is " + std::to_string(tex.width) + " x " + std::to_string(tex.height) + ", each side must be 1 .. 16384");
-        const uint32_t full = pp::fullMipCount(tex.width, tex.height);
-        if (tex.mipCount > full)
-            refuse("too many mips: texture " + std::to_string(t) + " (" + std::to_string(tex.width) + " x " + std::to_string(tex.height) + ") has " + std::to_string(tex.mipCount) + " levels, at most " + std::to_string(full));
-        if (!tex.texels) refuse("null texels: texture " + std::to_string(t));
+        const uint32_t full = validateTextureShape(t, tex.width, tex.height, tex.mipCount, tex.texels, refuse);
         const uint32_t levels = tex.mipCount ? tex.mipCount : full;
         for (uint32_t l = 0; l < levels; l++) total += (uint64_t)std::max(1u, tex.width >> l) * std::max(1u, tex.height >> l);
     }
@@ -169,6 +176,138 @@ PackedTextures packSceneTextures(const SceneTexture* textures, uint32_t textureC
     for (uint32_t d = 0; d < drawCount; d++) { out.materials[2u * d] = materials[d].albedoTexture; out.materials[2u * d + 1u] = materials[d].specularTexture; }
     packTextureStore(textures, textureCount, total, out.textures, out.texels);
     return out;
+}
+
+// ---- block-compressed textures (DESIGN.md "Block-compressed textures in the depth prepass")
+// the contract's format code of a PLR_FORMAT_* value, or -1
+static int textureFormatCode(uint32_t format) {
+    namespace pp = plr::prepass;
+    switch (format) {
+    case PLR_FORMAT_RGBA8: return (int)pp::kTextureFormatRgba8;
+    case PLR_FORMAT_BC1: return (int)pp::kTextureFormatBc1;
+    case PLR_FORMAT_BC3: return (int)pp::kTextureFormatBc3;
+    case PLR_FORMAT_BC5: return (int)pp::kTextureFormatBc5;
+    default: return -1;
+    }
+}
+
+// everything is validated before anything is built. An RGBA8 entry is packed as packSceneTextures packs it; a compressed one starts at a multiple of 4 words (16
+// bytes), zeros in front of it where needed. Without a compressed entry the result is packSceneTextures' own, and `compressed` stays false
+PackedFormattedTextures packSceneTexturesFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials,
+                                                   uint32_t drawCount, const uint32_t* sceneMeshVertexCounts, uint32_t sceneMeshCount, uint32_t sceneDrawCount) {
+    namespace pp = plr::prepass;
+    const std::string call = "setSceneTexturesFormatted";
+    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
+    if (sceneDrawCount == 0) refuse("no scene set (plrf_set_scene_meshes comes first)");
+    if (meshCount != sceneMeshCount) refuse("mesh count " + std::to_string(meshCount) + " differs from the mesh count " + std::to_string(sceneMeshCount) + " of the scene");
+    if (drawCount != sceneDrawCount) refuse("draw count " + std::to_string(drawCount) + " differs from the draw count " + std::to_string(sceneDrawCount) + " of the scene");
+    if (!textures || !materials) refuse("textures or materials are null");
+    uint64_t total = 0;
+    std::vector<uint32_t> codes(textureCount), offsets(textureCount);
+    for (uint32_t t = 0; t < textureCount; t++) {
+        const SceneTextureData& tex = textures[t];
+        const int code = textureFormatCode(tex.format);
+        if (code < 0)
+            refuse("unknown format: texture " + std::to_string(t) + " has format " + std::to_string(tex.format) + ", it must be PLR_FORMAT_RGBA8, PLR_FORMAT_BC1, PLR_FORMAT_BC3 or PLR_FORMAT_BC5");
+        const uint32_t full = validateTextureShape(t, tex.width, tex.height, tex.mipCount, tex.data, refuse);
+        const bool blocks = (uint32_t)code != pp::kTextureFormatRgba8;
+        if (blocks && tex.mipCount == 0)
+            refuse("mip_count 0 on a compressed texture: texture " + std::to_string(t) + " (the host has no encoder to build a chain with: give its levels)");
+        const uint64_t given = pp::textureWords((uint32_t)code, tex.width, tex.height, std::max(1u, tex.mipCount)) * 4u;
+        if (tex.bytes != given)
+            refuse("bytes mismatch: texture " + std::to_string(t) + " (" + std::to_string(tex.width) + " x " + std::to_string(tex.height) + ", " + std::to_string(std::max(1u, tex.mipCount)) +
+                   " level(s)) has " + std::to_string(tex.bytes) + " bytes, its levels hold " + std::to_string(given));
+        if (blocks) total = (total + 3u) & ~(uint64_t)3u;
+        offsets[t] = (uint32_t)std::min<uint64_t>(total, 0xffffffffu); // (a total that does not fit is refused below)
+        total += pp::textureWords((uint32_t)code, tex.width, tex.height, tex.mipCount ? tex.mipCount : full);
+        codes[t] = (uint32_t)code;
+    }
+    for (uint32_t d = 0; d < drawCount; d++)
+        for (uint32_t index : {materials[d].albedoTexture, materials[d].specularTexture})
+            if (index != kNoSceneTexture && index >= textureCount)
+                refuse("material texture index out of range: draw " + std::to_string(d) + " names texture " + std::to_string(index) + " of " + std::to_string(textureCount));
+    if (total > pp::kMaxTexels) refuse("too many texels: " + std::to_string(total) + " words in all levels of all textures, at most 2^28");
+    PackedFormattedTextures out;
+    out.uvs = packUvs(meshUvs, meshCount, sceneMeshVertexCounts, refuse);
+    out.materials.resize((size_t)drawCount * 2u);
+    for (uint32_t d = 0; d < drawCount; d++) { out.materials[2u * d] = materials[d].albedoTexture; out.materials[2u * d + 1u] = materials[d].specularTexture; }
+    out.textures.resize((size_t)textureCount * 4u);
+    out.texels.reserve((size_t)total);
+    for (uint32_t t = 0; t < textureCount; t++) {
+        const SceneTextureData& tex = textures[t];
+        out.texels.resize(offsets[t], 0u); // (the padding in front of a compressed texture)
+        const pp::Texture entry{offsets[t], tex.width, tex.height, tex.mipCount ? tex.mipCount : pp::fullMipCount(tex.width, tex.height)};
+        std::memcpy(out.textures.data() + (size_t)t * 4u, &entry, sizeof(entry));
+        const size_t words = (size_t)(tex.bytes / 4u);
+        out.texels.resize(out.texels.size() + words);
+        std::memcpy(out.texels.data() + offsets[t], tex.data, words * 4u); // (the caller's data may sit at any alignment)
+        if (tex.mipCount == 0) appendMipChain(out.texels, tex.width, tex.height);
+        out.compressed = out.compressed || codes[t] != pp::kTextureFormatRgba8;
+    }
+    out.formats = codes;
+    return out;
+}
+
+// the contract's colour block: texel i as r | g << 8 | b << 16
+static uint32_t colourBlockTexel(const uint8_t* b, uint32_t i, bool alwaysFour) {
+    const uint32_t c0 = (uint32_t)b[0] | ((uint32_t)b[1] << 8), c1 = (uint32_t)b[2] | ((uint32_t)b[3] << 8);
+    const uint32_t indices = (uint32_t)b[4] | ((uint32_t)b[5] << 8) | ((uint32_t)b[6] << 16) | ((uint32_t)b[7] << 24);
+    const uint32_t k = (indices >> (2u * i)) & 3u;
+    const bool four = alwaysFour || c0 > c1;
+    auto expand = [](uint32_t c, int channel) { // RGB565, red in the high bits
+        const uint32_t r5 = (c >> 11) & 31u, g6 = (c >> 5) & 63u, b5 = c & 31u;
+        return channel == 0 ? (r5 << 3) | (r5 >> 2) : channel == 1 ? (g6 << 2) | (g6 >> 4) : (b5 << 3) | (b5 >> 2);
+    };
+    uint32_t word = 0;
+    for (int channel = 0; channel < 3; channel++) {
+        const uint32_t e0 = expand(c0, channel), e1 = expand(c1, channel);
+        uint32_t c;
+        if (k == 0u) c = e0;
+        else if (k == 1u) c = e1;
+        else if (four) c = k == 2u ? (2u * e0 + e1 + 1u) / 3u : (e0 + 2u * e1 + 1u) / 3u;
+        else c = k == 2u ? (e0 + e1 + 1u) >> 1 : 0u;
+        word |= c << (8 * channel);
+    }
+    return word;
+}
+// the contract's alpha block: the code of texel i
+static uint32_t alphaBlockTexel(const uint8_t* b, uint32_t i) {
+    const uint32_t a0 = b[0], a1 = b[1];
+    uint64_t bits = 0;
+    for (int k = 0; k < 6; k++) bits |= (uint64_t)b[2 + k] << (8 * k);
+    const uint32_t k = (uint32_t)((bits >> (3u * i)) & 7u);
+    if (k == 0u) return a0;
+    if (k == 1u) return a1;
+    if (a0 > a1) return ((8u - k) * a0 + (k - 1u) * a1 + 3u) / 7u;
+    if (k == 6u) return 0u;
+    if (k == 7u) return 255u;
+    return ((6u - k) * a0 + (k - 1u) * a1 + 2u) / 5u;
+}
+
+void decodeBlockCompressedLevel(uint32_t format, uint32_t width, uint32_t height, const void* blocks, uint64_t bytes, uint32_t* outWords) {
+    namespace pp = plr::prepass;
+    const std::string call = "plr_decode_bc_to_rgba8";
+    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
+    const int code = textureFormatCode(format);
+    if (code <= 0) refuse("format " + std::to_string(format) + " is not PLR_FORMAT_BC1, PLR_FORMAT_BC3 or PLR_FORMAT_BC5");
+    if (width < 1u || height < 1u || width > pp::kMaxTextureSize || height > pp::kMaxTextureSize)
+        refuse("the level is " + std::to_string(width) + " x " + std::to_string(height) + ", each side must be 1 .. 16384");
+    if (!blocks || !outWords) refuse("blocks or out_words are null");
+    const uint64_t need = pp::textureWords((uint32_t)code, width, height, 1) * 4u;
+    if (bytes != need)
+        refuse("bytes mismatch: " + std::to_string(bytes) + " bytes for a " + std::to_string(width) + " x " + std::to_string(height) + " level that holds " + std::to_string(need));
+    const size_t blockBytes = (size_t)pp::blockWords((uint32_t)code) * 4u, blocksPerRow = ((size_t)width + 3u) / 4u;
+    const uint8_t* data = (const uint8_t*)blocks;
+    for (uint32_t y = 0; y < height; y++)
+        for (uint32_t x = 0; x < width; x++) {
+            const uint8_t* b = data + ((size_t)(y >> 2) * blocksPerRow + (x >> 2)) * blockBytes;
+            const uint32_t i = 4u * (y & 3u) + (x & 3u);
+            uint32_t word;
+            if ((uint32_t)code == pp::kTextureFormatBc1) word = colourBlockTexel(b, i, false) | (255u << 24);
+            else if ((uint32_t)code == pp::kTextureFormatBc3) word = colourBlockTexel(b + 8, i, true) | (alphaBlockTexel(b, i) << 24);
+            else word = alphaBlockTexel(b, i) | (alphaBlockTexel(b + 8, i) << 8) | (255u << 24);
+            outWords[(size_t)y * width + x] = word;
+        }
 }
 
 // everything is validated before anything is built

@@ -111,6 +111,32 @@
 // The tile kernel of such an execution (kNormalMap) leaves the winner's t, or kNoWinner, in the shadingNormal texel, and depthPrepassShadingNormalKernel behind it,
 // a lane per pixel, turns that texel into the shading normal in place.
 //
+// THE BLOCK DECODE CONTRACT (DESIGN.md "Block-compressed textures in the depth prepass"; tests/prepass_bc_reference.py implements it independently, bit for bit). Only
+// an execution whose sixth push-constant word textureFormats is 1 decodes (it needs textureCount > 0 and storage buffer 14 `textureFormats`, one uint32 per texture);
+// a push of 20 bytes or fewer, or the word at 0, is the pass above. Everything is in integers; / is floor division of non-negative integers.
+//   format codes: 0 RGBA8, as above; 1 BC1, 8-byte blocks; 2 BC3, 16-byte blocks; 3 BC5, 16-byte blocks.
+//   layout: level l of a compressed texture is ceil(W_l / 4) x ceil(H_l / 4) blocks, row-major, W_l = max(1, W_0 >> l) as before; levels lie back to back and
+//     unpadded, in the same `texels` buffer as the RGBA8 textures. texelOffset of a compressed entry counts uint32 words of `texels` (for RGBA8, words and texels are
+//     the same number). Texel (x, y) of a level lives in block (x >> 2, y >> 2) at position i = 4 (y & 3) + (x & 3). Levels smaller than 4 x 4 are one block; the
+//     positions outside the level are never addressed.
+//   colour block (8 bytes): c0, c1 little-endian uint16 RGB565, red in the high bits, then a little-endian uint32 of 2-bit indices, texel i at bits 2 i. Expansion:
+//     r8 = (r5 << 3) | (r5 >> 2), g8 = (g6 << 2) | (g6 >> 4), b8 like r8. Four-colour mode, per channel: index 0 is c0, 1 is c1, 2 is (2 c0 + c1 + 1) / 3, 3 is
+//     (c0 + 2 c1 + 1) / 3. Three-colour mode: 0 and 1 as before, 2 is (c0 + c1 + 1) >> 1, 3 is (0, 0, 0). BC1 uses four-colour mode when c0 > c1, compared as uint16,
+//     otherwise three-colour mode; BC1 alpha is always 255, index 3 of three-colour mode included (the reference's BC1_RGB variant). BC3's colour block is always
+//     four-colour mode, whatever the order of c0 and c1.
+//   alpha block (8 bytes: BC3's first half and both halves of BC5): bytes a0, a1, then a little-endian 48-bit integer of 3-bit indices, texel i at bits 3 i. Indices 0
+//     and 1 are a0 and a1. With a0 > a1, index k = 2 .. 7 is ((8 - k) a0 + (k - 1) a1 + 3) / 7; otherwise k = 2 .. 5 is ((6 - k) a0 + (k - 1) a1 + 2) / 5, 6 is 0
+//     and 7 is 255. Both divisions round to nearest and have no ties.
+//   words, R in the low byte: BC1 (r, g, b, 255); BC3: bytes 0 - 7 the alpha block, 8 - 15 the colour block: (r, g, b, a); BC5: bytes 0 - 7 the R block, 8 - 15 the G
+//     block: (R, G, 0, 255).
+//   usable entries: a compressed entry is usable under the sampling contract's rule on width, height and mipCount; in addition its texelOffset must be a multiple of 2
+//     words (BC1) or 4 words (BC3, BC5). An entry whose format code is above 3 is unusable. An unusable entry yields the draw's constant word, as before.
+//   out of range: a tap whose block does not lie wholly inside `texels` reads word 0, all four channels; the 64-bit address is checked before the load.
+//   everything else is the sampling contract, unchanged and applied to the decoded words: UV, the forward-difference derivatives, the level from W_0, H_0 in texels,
+//     the taps, repeat wrap and weights, the round-half-even code.
+// The format-aware instantiations (kFormats) decode per tap: blockTexel loads the tap's block with one plain vector load and extracts its texel; the alpha-only
+// path (kFirst == 3) loads BC3's alpha block alone and nothing for BC1 and BC5.
+//
 // Two kernels. SET-UP: a lane per triangle finds its draw (block-wide prefix sum, LDS bisection), transforms, clips (the polygon lives in LDS, a column per lane),
 // projects, snaps, culls and boxes; the block's sub-triangles are appended through one 64-bit atomic per block to a dense array of 4-byte tile rectangles and an
 // array of records that carry t. TILES: a 256-thread block per 64 x 64 tile keeps the tile's 64-bit keys in LDS (32 KB); each wave reads 256 rectangles per step
@@ -309,10 +335,19 @@ __global__ __launch_bounds__(256) void depthPrepassSetupKernel(SetupParams p) {
 }
 
 struct TextureInputs {
+    static constexpr bool kFormats = false;
     const float* uvs; const Material* materials; const Texture* textures; const uint32_t* texels;
     uint64_t uvVertexCount, texelCount;
     uint32_t drawCount, textureCount;
 };
+// a format-aware execution's (textureFormats = 1): one format code per texture; texelCount counts the uint32 words of `texels`. The other instantiations keep
+// TextureInputs, and with it their argument blocks and their LDS
+struct FormatTextureInputs : TextureInputs {
+    static constexpr bool kFormats = true;
+    const uint32_t* formats;
+};
+template <bool kFormats> struct TextureInputsOf { typedef TextureInputs type; };
+template <> struct TextureInputsOf<true> { typedef FormatTextureInputs type; };
 struct TileParams {
     ScratchHeader* header; const TriangleOrigin* origins; const uint32_t* rects; const Record* records;
     const float* transforms; const float* positions; const float* normals; const uint32_t* indices; const Draw* draws;
@@ -325,8 +360,13 @@ struct TileParams {
 };
 // a normal-mapped execution's tile kernel leaves the winner's t in the shadingNormal texel (the other instantiations keep their argument block)
 struct NormalTileParams : TileParams { uint32_t* shadingNormal; };
-template <bool kNormalMap> struct TileParamsOf { typedef TileParams type; };
-template <> struct TileParamsOf<true> { typedef NormalTileParams type; };
+template <bool kNormalMap, bool kFormats = false> struct TileParamsOf { typedef TileParams type; };
+template <> struct TileParamsOf<true, false> { typedef NormalTileParams type; };
+// a format-aware execution's: binding 14 behind everything else
+struct FormatTileParams : TileParams { const uint32_t* formats; };
+struct FormatNormalTileParams : NormalTileParams { const uint32_t* formats; };
+template <> struct TileParamsOf<false, true> { typedef FormatTileParams type; };
+template <> struct TileParamsOf<true, true> { typedef FormatNormalTileParams type; };
 
 typedef unsigned long long Key;
 
@@ -371,14 +411,82 @@ PLR_DI int wrapRepeat(int64_t t, int n) {
 
 struct TexelSums { uint32_t c[4]; }; // per channel: 16 bits of weight on 8 bits of code
 
+// ---- block-compressed textures (the block decode contract). A format-aware instantiation carries a usable texture's format code in bits 16 - 31 of the
+// Texture's mipCount (usableTexture puts it there; a usable mipCount is at most 15), so that an AlphaRecord keeps its 36 words
+template <bool kFormats> PLR_DI uint32_t mipCountOf(const Texture& t) { return kFormats ? t.mipCount & 0xffffu : t.mipCount; }
+template <bool kFormats> PLR_DI uint32_t formatOf(const Texture& t) { return kFormats ? t.mipCount >> 16 : kTextureFormatRgba8; }
+// the uint32 words of a w x h level of `format`
+PLR_DI uint64_t levelWords(uint32_t format, uint32_t w, uint32_t h) {
+    if (format != kTextureFormatRgba8) return (uint64_t)((w + 3u) >> 2) * (uint64_t)((h + 3u) >> 2) * (format == kTextureFormatBc1 ? 2u : 4u);
+    return (uint64_t)w * (uint64_t)h;
+}
+// texel i of a colour block {c0 | c1 << 16, indices} as r | g << 8 | b << 16
+PLR_DI uint32_t colourBlockTexel(uint32_t endpoints, uint32_t indices, uint32_t i, bool alwaysFour) {
+    const uint32_t c0 = endpoints & 0xffffu, c1 = endpoints >> 16, k = (indices >> (2u * i)) & 3u;
+    const bool four = alwaysFour || c0 > c1;
+    uint32_t word = 0u;
+    for (int ch = 0; ch < 3; ch++) { // red in the high bits of the RGB565 word
+        const uint32_t shift = ch == 0 ? 11u : ch == 1 ? 5u : 0u, bits = ch == 1 ? 6u : 5u;
+        const uint32_t q0 = (c0 >> shift) & ((1u << bits) - 1u), q1 = (c1 >> shift) & ((1u << bits) - 1u);
+        const uint32_t e0 = (q0 << (8u - bits)) | (q0 >> (2u * bits - 8u)), e1 = (q1 << (8u - bits)) | (q1 >> (2u * bits - 8u));
+        uint32_t c;
+        if (k == 0u) c = e0;
+        else if (k == 1u) c = e1;
+        else if (four) c = k == 2u ? (2u * e0 + e1 + 1u) / 3u : (e0 + 2u * e1 + 1u) / 3u;
+        else c = k == 2u ? (e0 + e1 + 1u) >> 1 : 0u;
+        word |= c << (8 * ch);
+    }
+    return word;
+}
+// texel i of an alpha block {a0 | a1 << 8 | the low 16 index bits << 16, the high 32 index bits}
+PLR_DI uint32_t alphaBlockTexel(uint32_t lo, uint32_t hi, uint32_t i) {
+    const uint32_t a0 = lo & 255u, a1 = (lo >> 8) & 255u;
+    const uint32_t k = (uint32_t)(((((uint64_t)hi << 16) | (uint64_t)(lo >> 16)) >> (3u * i)) & 7ull);
+    if (k == 0u) return a0;
+    if (k == 1u) return a1;
+    if (a0 > a1) return ((8u - k) * a0 + (k - 1u) * a1 + 3u) / 7u;
+    if (k == 6u) return 0u;
+    if (k == 7u) return 255u;
+    return ((6u - k) * a0 + (k - 1u) * a1 + 2u) / 5u;
+}
+// the word of texel (x, y) of a compressed level (w texels wide, first word at `base`): the block's 64-bit word address is checked against wordCount before
+// the load, a block that does not lie wholly inside reads 0. The loads are aligned: usableTexture refused an offset that is no multiple of the block size.
+// kFirst == 3 (the alpha only): BC3 loads its alpha block alone, BC1 and BC5 load nothing
+template <int kFirst>
+PLR_DI uint32_t blockTexel(const uint32_t* texels, uint64_t wordCount, uint64_t base, uint32_t format, int w, int x, int y) {
+    const uint32_t blockWords = format == kTextureFormatBc1 ? 2u : 4u;
+    const uint64_t at = base + ((uint64_t)(y >> 2) * (uint64_t)(((uint32_t)w + 3u) >> 2) + (uint64_t)(x >> 2)) * (uint64_t)blockWords;
+    if (at + (uint64_t)blockWords > wordCount) return 0u;
+    const uint32_t i = 4u * ((uint32_t)y & 3u) + ((uint32_t)x & 3u);
+    if (format == kTextureFormatBc1) {
+        if constexpr (kFirst == 3) return 255u << 24;
+        const uint2 b = *(const uint2*)(texels + at);
+        return colourBlockTexel(b.x, b.y, i, false) | (255u << 24);
+    }
+    if (format == kTextureFormatBc3) {
+        if constexpr (kFirst == 3) {
+            const uint2 b = *(const uint2*)(texels + at);
+            return alphaBlockTexel(b.x, b.y, i) << 24;
+        }
+        const uint4 b = *(const uint4*)(texels + at);
+        return colourBlockTexel(b.z, b.w, i, true) | (alphaBlockTexel(b.x, b.y, i) << 24);
+    }
+    if constexpr (kFirst == 3) return 255u << 24; // BC5
+    const uint4 b = *(const uint4*)(texels + at);
+    return alphaBlockTexel(b.x, b.y, i) | (alphaBlockTexel(b.z, b.w, i) << 8) | (255u << 24);
+}
+
 // the four taps of one level (dimensions w x h, first texel at `base`), weighted; every address in 64 bits and checked against texelCount before its load
-template <int kFirst = 0>
-PLR_DI TexelSums bilinearTaps(const uint32_t* texels, uint64_t texelCount, uint64_t base, int w, int h, double u, double v) {
+template <int kFirst = 0, bool kFormats = false>
+PLR_DI TexelSums bilinearTaps(const uint32_t* texels, uint64_t texelCount, uint64_t base, int w, int h, double u, double v, uint32_t format = kTextureFormatRgba8) {
     const int64_t Tu = (int64_t)__builtin_floor((u * (double)w - 0.5) * 256.0 + 0.5), Tv = (int64_t)__builtin_floor((v * (double)h - 0.5) * 256.0 + 0.5);
     const uint32_t fx = (uint32_t)(Tu & 255), fy = (uint32_t)(Tv & 255);
     const int x0 = wrapRepeat(Tu >> 8, w), y0 = wrapRepeat(Tv >> 8, h);
     const int x1 = x0 + 1 == w ? 0 : x0 + 1, y1 = y0 + 1 == h ? 0 : y0 + 1;
     auto fetch = [&](int x, int y) {
+        if constexpr (kFormats) {
+            if (format != kTextureFormatRgba8) return blockTexel<kFirst>(texels, texelCount, base, format, w, x, y);
+        }
         const uint64_t at = base + (uint64_t)y * (uint64_t)w + (uint64_t)x;
         return at < texelCount ? texels[at] : 0u;
     };
@@ -392,7 +500,7 @@ PLR_DI TexelSums bilinearTaps(const uint32_t* texels, uint64_t texelCount, uint6
 
 // one trilinear sample of `texture`: (u, v) for the taps, (dudx, dvdx) and (dudy, dvdy) the raw forward differences. kFirst: the first channel computed - 3 is
 // the alpha-only sample of the coverage path, whose bits 24 - 31 are those of the full word because every channel is filtered by itself
-template <int kFirst = 0>
+template <int kFirst = 0, bool kFormats = false>
 PLR_DI uint32_t sampleTexture(const TextureInputs& tex, Texture texture, double u, double v, double dudx, double dvdx, double dudy, double dvdy, float mipBias) {
     const double w0 = (double)texture.width, h0 = (double)texture.height;
     const double axx = dudx * w0, axy = dvdx * h0, ayx = dudy * w0, ayy = dvdy * h0;
@@ -401,19 +509,25 @@ PLR_DI uint32_t sampleTexture(const TextureInputs& tex, Texture texture, double 
     const float r = (float)rho2;
     float lod = 0.5f * det_log2f(r) + mipBias;
     if (!(lod > 0.f)) lod = 0.f;
-    const float top = (float)(texture.mipCount - 1u);
+    const uint32_t mipCount = mipCountOf<kFormats>(texture), format = formatOf<kFormats>(texture);
+    const float top = (float)(mipCount - 1u);
     if (lod > top) lod = top;
     const int q = (int)__builtin_floorf(lod * 256.f + 0.5f);
-    const int L0 = q >> 8, L1 = min(L0 + 1, (int)texture.mipCount - 1);
+    const int L0 = q >> 8, L1 = min(L0 + 1, (int)mipCount - 1);
     const uint32_t fw = (uint32_t)(q & 255);
     uint64_t base = texture.texelOffset;
-    for (int l = 0; l < L0; l++) base += (uint64_t)max(1u, texture.width >> l) * (uint64_t)max(1u, texture.height >> l);
+    for (int l = 0; l < L0; l++) {
+        if constexpr (kFormats) base += levelWords(format, max(1u, texture.width >> l), max(1u, texture.height >> l));
+        else base += (uint64_t)max(1u, texture.width >> l) * (uint64_t)max(1u, texture.height >> l);
+    }
     const int w = (int)max(1u, texture.width >> L0), h = (int)max(1u, texture.height >> L0);
-    const TexelSums s0 = bilinearTaps<kFirst>(tex.texels, tex.texelCount, base, w, h, u, v);
+    const TexelSums s0 = bilinearTaps<kFirst, kFormats>(tex.texels, tex.texelCount, base, w, h, u, v, format);
     TexelSums s1{{0u, 0u, 0u, 0u}};
     if (fw != 0u) { // (with fw == 0 the upper level has no weight; with L1 == L0 it is the same level again)
-        const uint64_t base1 = L1 == L0 ? base : base + (uint64_t)w * (uint64_t)h;
-        s1 = bilinearTaps<kFirst>(tex.texels, tex.texelCount, base1, (int)max(1u, texture.width >> L1), (int)max(1u, texture.height >> L1), u, v);
+        uint64_t base1 = base;
+        if constexpr (kFormats) base1 += L1 == L0 ? 0u : levelWords(format, (uint32_t)w, (uint32_t)h);
+        else base1 = L1 == L0 ? base : base + (uint64_t)w * (uint64_t)h;
+        s1 = bilinearTaps<kFirst, kFormats>(tex.texels, tex.texelCount, base1, (int)max(1u, texture.width >> L1), (int)max(1u, texture.height >> L1), u, v, format);
     }
     uint32_t word = 0u;
     for (int k = kFirst; k < 4; k++) {
@@ -424,12 +538,21 @@ PLR_DI uint32_t sampleTexture(const TextureInputs& tex, Texture texture, double 
 }
 
 // the table entry `index` names when it is usable: inside the table, 1 <= width, height <= 16384, 1 <= mipCount <= floor(log2(max(width, height))) + 1
-PLR_DI bool usableTexture(const TextureInputs& tex, uint32_t index, Texture* out) {
+// A format-aware execution (Tex::kFormats): also a format code of at most 3 and, for a compressed entry, a texelOffset that is a multiple of its block's words;
+// the format code goes into bits 16 - 31 of out->mipCount (mipCountOf, formatOf)
+template <class Tex>
+PLR_DI bool usableTexture(const Tex& tex, uint32_t index, Texture* out) {
     if (index == kNoTexture || index >= tex.textureCount) return false;
     const Texture t = tex.textures[index];
     if (t.width < 1u || t.height < 1u || t.width > kMaxTextureSize || t.height > kMaxTextureSize) return false;
     if (t.mipCount < 1u || t.mipCount > 32u - (uint32_t)__clz(max(t.width, t.height))) return false;
     *out = t;
+    if constexpr (Tex::kFormats) {
+        const uint32_t format = tex.formats[index];
+        if (format > kTextureFormatBc5) return false;
+        if (format != kTextureFormatRgba8 && (t.texelOffset & (format == kTextureFormatBc1 ? 1u : 3u)) != 0u) return false;
+        out->mipCount = t.mipCount | (format << 16);
+    }
     return true;
 }
 
@@ -484,8 +607,8 @@ PLR_DI void vertexNormals(const float pos[3][3], const float nrm[3][3], const fl
 }
 
 // the winner's attributes at pixel (x, y): motion, normal and the draw's two material words (kTextured: the sampled texel where its material names a texture)
-template <bool kTextured>
-PLR_DI void resolvePixel(const TileParams& p, const TextureInputs& tex, uint32_t t, int x, int y, uint32_t* motion, uint32_t* normal, uint32_t* albedo, uint32_t* specular) {
+template <bool kTextured, class Tex>
+PLR_DI void resolvePixel(const TileParams& p, const Tex& tex, uint32_t t, int x, int y, uint32_t* motion, uint32_t* normal, uint32_t* albedo, uint32_t* specular) {
     const TriangleOrigin o = p.origins[t];
     const Draw draw = p.draws[o.draw];
     const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)o.local * 3u;
@@ -529,8 +652,8 @@ PLR_DI void resolvePixel(const TileParams& p, const TextureInputs& tex, uint32_t
         for (int k = 0; k < 3; k++) fetchUv(tex, vertex[k], &tu[k], &tv[k]);
         const UvSample uv = uvSampleAt(P, b, V, tu, tv, x, y, p.width, p.height);
         const float mipBias = p.global->mipBias;
-        if (sampleAlbedo) *albedo = sampleTexture(tex, albedoTexture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias);
-        if (sampleSpecular) *specular = sampleTexture(tex, specularTexture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias);
+        if (sampleAlbedo) *albedo = sampleTexture<0, Tex::kFormats>(tex, albedoTexture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias);
+        if (sampleSpecular) *specular = sampleTexture<0, Tex::kFormats>(tex, specularTexture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias);
     }
 }
 
@@ -548,7 +671,8 @@ static_assert(sizeof(AlphaRecord) == kAlphaRecordWords * 4, "AlphaRecord is move
 PLR_DI bool alphaSampled(uint32_t cutoff) { return cutoff != kAlphaCutoffOpaque && cutoff != kAlphaCutoffDiscardAll; }
 struct AlphaInputs { const uint32_t* cutoffs; float mipBias; };
 
-PLR_DI void alphaOfRecord(const TileParams& p, const TextureInputs& tex, const uint32_t* cutoffs, uint32_t t, AlphaRecord& a) {
+template <class Tex>
+PLR_DI void alphaOfRecord(const TileParams& p, const Tex& tex, const uint32_t* cutoffs, uint32_t t, AlphaRecord& a) {
     a.cutoff = kAlphaCutoffOpaque;
     if (t >= p.triangleCount) return; // (never: the set-up kernel wrote t)
     const TriangleOrigin o = p.origins[t];
@@ -576,12 +700,13 @@ PLR_DI void alphaOfRecord(const TileParams& p, const TextureInputs& tex, const u
 }
 
 // a(t, i, j): bits 24 - 31 of the albedo word the resolve would store for this triangle at pixel (x, y) - the same functions in the same order
+template <bool kFormats>
 PLR_DI uint32_t fragmentAlpha(const TextureInputs& tex, const AlphaRecord& a, float mipBias, int x, int y, int width, int height) {
     const D3 P{(double)(2 * x + 1) / (double)width - 1.0, (double)(2 * y + 1) / (double)height - 1.0, 1.0};
     double b[3];
     barycentricsAt(P, a.V, b);
     const UvSample uv = uvSampleAt(P, b, a.V, a.tu, a.tv, x, y, width, height);
-    return sampleTexture<3>(tex, a.texture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias) >> 24;
+    return sampleTexture<3, kFormats>(tex, a.texture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias) >> 24;
 }
 
 // THE ALPHA-TESTED SCAN. A sample costs far more than coverage, a stamp of a triangle's box or a lane's 4 x 4 box is seldom full, and the loads that lead to a
@@ -592,10 +717,10 @@ PLR_DI uint32_t fragmentAlpha(const TextureInputs& tex, const AlphaRecord& a, fl
 struct Candidate { uint32_t xy; float zf; uint32_t slot; }; // x | y << 16 (the frame is at most 16384 wide and high); slot: the lane that holds the record
 constexpr uint32_t kCandidateSlots = 128;                   // fewer than 64 pending + at most 64 of one push
 
-struct AlphaScan {
+template <class Tex> struct AlphaScan {
     Candidate* queue;                 // this wave's kCandidateSlots entries
     uint32_t (*records)[64];          // this wave's kAlphaRecordWords x 64 words
-    const TextureInputs* tex;
+    const Tex* tex;
     float mipBias;
     int width, height;
     Key* tile;
@@ -619,7 +744,7 @@ struct AlphaScan {
             const int px = (int)(xy & 0xffffu), py = (int)(xy >> 16);
             Key* cell = &tile[(py - oy) * kTileSize + (px - ox)];
             const Key key = ((Key)f2u(zf) << 32) | (Key)u.r.t;
-            if (key > *cell && fragmentAlpha(*tex, u.r, mipBias, px, py, width, height) >= u.r.cutoff) atomicMax(cell, key);
+            if (key > *cell && fragmentAlpha<Tex::kFormats>(*tex, u.r, mipBias, px, py, width, height) >= u.r.cutoff) atomicMax(cell, key);
         }
     }
     // called by the whole wave: the lanes with `candidate` append theirs; a full wave of candidates is sampled at once
@@ -665,8 +790,8 @@ struct KeyWalk : rastercov::PlainWalk {
 
 // ... and with the alpha test, through all the hooks of rastercov::rasteriseTile: a fragment of an opaque draw's record goes KeyWalk's way, one of a discarded
 // draw's nowhere, and the candidates of a sampled record go into AlphaScan's queue
-struct AlphaWalk {
-    AlphaScan scan;
+template <class Tex> struct AlphaWalk {
+    AlphaScan<Tex> scan;
     const TileParams* q;
     const AlphaInputs* inputs;
     uint32_t myCutoff;    // of this lane's record
@@ -715,9 +840,12 @@ struct AlphaWalk {
 };
 
 // kNormalMap: the resolve also leaves the winner's t (kNoWinner: none) in the shadingNormal texel, for depthPrepassShadingNormalKernel behind this kernel
-template <bool kTextured, bool kAlphaTest = false, bool kNormalMap = false>
-__global__ __launch_bounds__(256) void depthPrepassTileKernel(typename TileParamsOf<kNormalMap>::type p) {
-    typedef typename TileParamsOf<kNormalMap>::type Params;
+// kFormats: the format-aware instantiations (textureFormats = 1) - the same text with the block decode behind every tap
+template <bool kTextured, bool kAlphaTest = false, bool kNormalMap = false, bool kFormats = false>
+__global__ __launch_bounds__(256) void depthPrepassTileKernel(typename TileParamsOf<kNormalMap, kFormats>::type p) {
+    typedef typename TileParamsOf<kNormalMap, kFormats>::type Params;
+    typedef typename TextureInputsOf<kFormats>::type Tex;
+    static_assert(kTextured || !kFormats, "a format belongs to a texture");
     static_assert(kTextured || !kAlphaTest, "the alpha of a fragment is a texture sample");
     static_assert(kTextured || !kNormalMap, "the shading normal is a texture sample");
     __shared__ Key tile[kTileSize * kTileSize];
@@ -727,12 +855,15 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(typename TileParam
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint32_t i = threadIdx.x; i < (uint32_t)(kTileSize * kTileSize); i += 256u) tile[i] = 0ull;
     // the textured resolve takes its inputs from LDS: held in scalar registers from the kernel's entry they would be spilled across the scan, which needs them all
-    __shared__ TextureInputs sharedTex;
+    __shared__ Tex sharedTex;
     __shared__ AlphaInputs sharedAlpha; // the alpha-tested scan's, for the same reason
     __shared__ Candidate candidates[4][kCandidateSlots];           // } per wave (the alpha-tested kernel only): AlphaScan
     __shared__ uint32_t alphaRecords[4][kAlphaRecordWords][64];    // }
     if constexpr (kTextured) {
-        if (threadIdx.x == 0) sharedTex = p.tex;
+        if (threadIdx.x == 0) {
+            static_cast<TextureInputs&>(sharedTex) = p.tex;
+            if constexpr (kFormats) sharedTex.formats = p.formats;
+        }
     }
     // the alpha-tested kernel takes ALL its arguments from LDS: its scan needs the resolve's buffers too, and held in scalar registers from the kernel's entry
     // thirty of them were spilled
@@ -746,7 +877,7 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(typename TileParam
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) q.header->drawn = n;
     const rastercov::TileWindow window{tx, ty, ox, oy, min(ox + kTileSize - 1, q.width - 1), min(oy + kTileSize - 1, q.height - 1)};
     if constexpr (kAlphaTest) {
-        AlphaWalk walk{AlphaScan{candidates[wave], alphaRecords[wave], &sharedTex, 0.f, 0, 0, tile, ox, oy, lane, 0u}, &q, &sharedAlpha, kAlphaCutoffOpaque, kAlphaCutoffOpaque};
+        AlphaWalk<Tex> walk{AlphaScan<Tex>{candidates[wave], alphaRecords[wave], &sharedTex, 0.f, 0, 0, tile, ox, oy, lane, 0u}, &q, &sharedAlpha, kAlphaCutoffOpaque, kAlphaCutoffOpaque};
         rastercov::rasteriseTile(q.rects, q.records, n, window, hitQueue[wave], walk);
     } else {
         KeyWalk walk{{}, tile, ox, oy};
@@ -754,7 +885,7 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(typename TileParam
     }
     __syncthreads();
     // resolve: a lane per pixel, a wave per tile row - 64 four-byte texels, 256 contiguous bytes of every image per store instruction
-    TextureInputs tex{};
+    Tex tex{};
     if constexpr (kTextured) tex = sharedTex;
     for (uint32_t i = threadIdx.x; i < (uint32_t)(kTileSize * kTileSize); i += 256u) {
         const int y = oy + (int)(i >> 6), x = ox + (int)(i & 63u);
@@ -763,7 +894,7 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(typename TileParam
         uint32_t motion = 0u, normal = 0u, albedo = 0u, specular = 0u;
         const uint32_t t = (uint32_t)key;
         const bool winner = key != 0ull && t < q.triangleCount;
-        if (winner) resolvePixel<kTextured>(q, tex, t, x, y, &motion, &normal, &albedo, &specular);
+        if (winner) resolvePixel<kTextured, Tex>(q, tex, t, x, y, &motion, &normal, &albedo, &specular);
         const size_t at = (size_t)y * (size_t)q.width + (size_t)x;
         q.depth[at] = u2f((uint32_t)(key >> 32));
         q.motion[at] = motion; q.normal[at] = normal; q.albedo[at] = albedo; q.specular[at] = specular;
@@ -790,6 +921,7 @@ PLR_DI D3 fetchBasisVector(const float* buffer, uint64_t vertexCount, uint64_t v
 }
 
 // n_s of triangle origins[t] = o at pixel (x, y) with the usable normal texture `texture`, as the stored word; `fallback` where M does not normalise
+template <bool kFormats>
 PLR_DI uint32_t shadingNormalAt(const ShadingNormalParams& p, TriangleOrigin o, Texture texture, int x, int y, uint32_t fallback) {
     const Draw draw = p.draws[o.draw];
     const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)o.local * 3u;
@@ -807,7 +939,7 @@ PLR_DI uint32_t shadingNormalAt(const ShadingNormalParams& p, TriangleOrigin o, 
     double tu[3], tv[3];
     for (int k = 0; k < 3; k++) fetchUv(p.tex, vertex[k], &tu[k], &tv[k]);
     const UvSample uv = uvSampleAt(P, b, V, tu, tv, x, y, p.width, p.height);
-    const uint32_t texel = sampleTexture(p.tex, texture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, p.global->mipBias);
+    const uint32_t texel = sampleTexture<0, kFormats>(p.tex, texture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, p.global->mipBias);
     const double cx = (double)(texel & 255u) / 255.0, cy = (double)((texel >> 8) & 255u) / 255.0;
     D3 nt;
     if (p.decode == kNormalDecodeReference) {
@@ -840,7 +972,12 @@ PLR_DI uint32_t shadingNormalAt(const ShadingNormalParams& p, TriangleOrigin o, 
 
 // A lane per pixel, a wave per 64 consecutive pixels of one row (256 contiguous bytes read and stored), in place: a lane reads the t the tile kernel left in its
 // texel and overwrites that texel. No LDS, no atomics. A wave of sky only, and a wave none of whose draws has a usable normal texture, leave by a ballot.
-__global__ __launch_bounds__(256) void depthPrepassShadingNormalKernel(ShadingNormalParams p) {
+struct FormatShadingNormalParams : ShadingNormalParams { const uint32_t* formats; };
+template <bool kFormats> struct ShadingNormalParamsOf { typedef ShadingNormalParams type; };
+template <> struct ShadingNormalParamsOf<true> { typedef FormatShadingNormalParams type; };
+
+template <bool kFormats = false>
+__global__ __launch_bounds__(256) void depthPrepassShadingNormalKernel(typename ShadingNormalParamsOf<kFormats>::type p) {
     const int x = (int)(blockIdx.x * 64u + (threadIdx.x & 63u)), y = (int)(blockIdx.y * 4u + (threadIdx.x >> 6));
     if (y >= p.height) return; // (wave-uniform)
     const bool inside = x < p.width;
@@ -855,17 +992,25 @@ __global__ __launch_bounds__(256) void depthPrepassShadingNormalKernel(ShadingNo
         if (winner) {
             word = p.normal[at];
             o = p.origins[t];
-            if (o.draw < p.tex.drawCount && o.draw < p.normalMaterialCount) mapped = usableTexture(p.tex, p.normalMaterials[o.draw], &texture);
+            if (o.draw < p.tex.drawCount && o.draw < p.normalMaterialCount) {
+                if constexpr (kFormats) {
+                    FormatTextureInputs tex;
+                    static_cast<TextureInputs&>(tex) = p.tex;
+                    tex.formats = p.formats;
+                    mapped = usableTexture(tex, p.normalMaterials[o.draw], &texture);
+                } else
+                    mapped = usableTexture(p.tex, p.normalMaterials[o.draw], &texture);
+            }
         }
-        if (__ballot(mapped) != 0ull && mapped) word = shadingNormalAt(p, o, texture, x, y, word);
+        if (__ballot(mapped) != 0ull && mapped) word = shadingNormalAt<kFormats>(p, o, texture, x, y, word);
     }
     if (inside) p.shadingNormal[at] = word;
 }
 
 static int launchDepthPrepassRaster(const PassCtx& c) {
     if (c.push.size() < sizeof(PushConstants)) return c.fail(-1, "depthPrepassRaster: push constants {drawCount, triangleCount} missing");
-    NormalPushConstants pc{};
-    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0; 12: alphaTest 0; 16: normalMap 0
+    FormatPushConstants pc{};
+    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0; 12: alphaTest 0; 16: normalMap 0; 20: textureFormats 0
     if (c.dispatch[0] != 1u || c.dispatch[1] != 1u || c.dispatch[2] != 1u || c.base[0] != 0u || c.base[1] != 0u)
         return c.fail(-1, "depthPrepassRaster: the dispatch is {1, 1, 1} (the launcher derives its grids from the push constants and the images)");
     if (pc.triangleCount > kMaxTriangles) return c.fail(-1, "depthPrepassRaster: triangleCount " + std::to_string(pc.triangleCount) + " exceeds 2^28");
@@ -896,6 +1041,14 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
         if (int rc = c.needSbuf(kTangentBinding, 0, "depthPrepassRaster tangents (3 floats per vertex)")) return rc;
         if (int rc = c.needSbuf(kBitangentBinding, 0, "depthPrepassRaster bitangents (3 floats per vertex)")) return rc;
         if (int rc = c.needSbuf(kNormalMaterialBinding, (size_t)pc.drawCount * 4u, "depthPrepassRaster normalMaterials (one uint32 texture index per draw)")) return rc;
+    }
+    if (pc.textureFormats) {
+        if (pc.textureFormats != 1u)
+            return c.fail(-1, "depthPrepassRaster: textureFormats is " + std::to_string(pc.textureFormats) + ", it must be 0 (every texture is RGBA8) or 1 (binding 14 holds a format code per texture)");
+        if (pc.textureCount == 0u) return c.fail(-1, "depthPrepassRaster: textureFormats is set and textureCount is 0 (a format belongs to a texture of the texture store)");
+        if (int rc = c.needSbuf(kTextureFormatBinding, (size_t)pc.textureCount * 4u, "depthPrepassRaster textureFormats (binding 14: one uint32 format code per texture)")) return rc;
+        if (c.sbuf[kTextureFormatBinding].ptr == c.sbuf[kScratchBinding].ptr)
+            return c.fail(-4, "depthPrepassRaster: the scratch buffer is also bound as an input (binding 14, textureFormats)");
     }
     if (c.sbuf[kScratchBinding].readOnly) return c.fail(-4, "depthPrepassRaster: the scratch buffer (binding 5) is bound read-only");
     if (int rc = c.needStorage(kDepthBinding, F_D32, "depthPrepassRaster depth")) return rc;
@@ -966,18 +1119,25 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
         t.tex.textures = (const Texture*)c.sbuf[kTextureBinding].ptr; t.tex.texels = (const uint32_t*)c.sbuf[kTexelBinding].ptr;
         t.tex.uvVertexCount = c.sbuf[kUvBinding].size / 8u; t.tex.texelCount = c.sbuf[kTexelBinding].size / 4u;
         t.tex.drawCount = pc.drawCount; t.tex.textureCount = pc.textureCount;
+        const uint32_t* formats = pc.textureFormats ? (const uint32_t*)c.sbuf[kTextureFormatBinding].ptr : nullptr; // only then the format-aware instantiations run
+        if (pc.alphaTest) t.alphaCutoffs = (const uint32_t*)c.sbuf[kAlphaCutoffBinding].ptr;
         if (pc.normalMap) {
             NormalTileParams n{};
             static_cast<TileParams&>(n) = t;
             n.shadingNormal = (uint32_t*)c.storage[kShadingNormalBinding].ptr;
-            if (pc.alphaTest) {
-                n.alphaCutoffs = (const uint32_t*)c.sbuf[kAlphaCutoffBinding].ptr;
+            if (formats) {
+                FormatNormalTileParams f{};
+                static_cast<NormalTileParams&>(f) = n;
+                f.formats = formats;
+                if (pc.alphaTest) depthPrepassTileKernel<true, true, true, true><<<tiles, 256, 0, c.stream>>>(f);
+                else depthPrepassTileKernel<true, false, true, true><<<tiles, 256, 0, c.stream>>>(f);
+            } else if (pc.alphaTest)
                 depthPrepassTileKernel<true, true, true><<<tiles, 256, 0, c.stream>>>(n);
-            } else
+            else
                 depthPrepassTileKernel<true, false, true><<<tiles, 256, 0, c.stream>>>(n);
             PLR_CHECK_LAUNCH(c);
             c.splitTiming("tiles");
-            ShadingNormalParams s{};
+            FormatShadingNormalParams s{};
             s.origins = t.origins; s.transforms = t.transforms; s.positions = t.positions; s.normals = t.normals; s.indices = t.indices; s.draws = t.draws;
             s.global = c.global; s.normal = t.normal; s.shadingNormal = n.shadingNormal;
             s.tangents = (const float*)c.sbuf[kTangentBinding].ptr; s.bitangents = (const float*)c.sbuf[kBitangentBinding].ptr;
@@ -985,11 +1145,19 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
             s.tangentVertexCount = c.sbuf[kTangentBinding].size / 12u; s.bitangentVertexCount = c.sbuf[kBitangentBinding].size / 12u;
             s.triangleCount = pc.triangleCount; s.normalMaterialCount = (uint32_t)std::min<size_t>(c.sbuf[kNormalMaterialBinding].size / 4u, 0xffffffffu);
             s.decode = pc.normalMap; s.width = depth.w; s.height = depth.h; s.tex = t.tex;
-            depthPrepassShadingNormalKernel<<<dim3(divUp((unsigned)depth.w, 64u), divUp((unsigned)depth.h, 4u)), 256, 0, c.stream>>>(s);
-        } else if (pc.alphaTest) {
-            t.alphaCutoffs = (const uint32_t*)c.sbuf[kAlphaCutoffBinding].ptr;
+            s.formats = formats;
+            const dim3 rows(divUp((unsigned)depth.w, 64u), divUp((unsigned)depth.h, 4u));
+            if (formats) depthPrepassShadingNormalKernel<true><<<rows, 256, 0, c.stream>>>(s);
+            else depthPrepassShadingNormalKernel<false><<<rows, 256, 0, c.stream>>>(static_cast<const ShadingNormalParams&>(s));
+        } else if (formats) {
+            FormatTileParams f{};
+            static_cast<TileParams&>(f) = t;
+            f.formats = formats;
+            if (pc.alphaTest) depthPrepassTileKernel<true, true, false, true><<<tiles, 256, 0, c.stream>>>(f);
+            else depthPrepassTileKernel<true, false, false, true><<<tiles, 256, 0, c.stream>>>(f);
+        } else if (pc.alphaTest)
             depthPrepassTileKernel<true, true><<<tiles, 256, 0, c.stream>>>(t);
-        } else
+        else
             depthPrepassTileKernel<true><<<tiles, 256, 0, c.stream>>>(t);
     } else
         depthPrepassTileKernel<false><<<tiles, 256, 0, c.stream>>>(t);

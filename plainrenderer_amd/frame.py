@@ -74,6 +74,10 @@ class PlrfSceneTexture(C.Structure):
     _fields_ = [("texels", C.POINTER(C.c_uint32)), ("width", C.c_uint32), ("height", C.c_uint32), ("mip_count", C.c_uint32)]
 
 
+class PlrfSceneTextureData(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("bytes", C.c_uint64), ("width", C.c_uint32), ("height", C.c_uint32), ("mip_count", C.c_uint32), ("format", C.c_uint32)]
+
+
 class PlrfSceneMaterial(C.Structure):
     _fields_ = [("albedo_texture", C.c_uint32), ("specular_texture", C.c_uint32)]
 
@@ -372,6 +376,30 @@ class FramePipeline:
         for k, (albedo, specular) in enumerate(materials):
             m[k] = PlrfSceneMaterial(int(albedo), int(specular))
         self._check(self.lib.plrf_set_scene_textures(self.handle, t, C.c_uint32(len(textures)), u, C.c_uint32(len(mesh_uvs)), m, C.c_uint32(len(materials))))
+
+    def set_scene_textures_formatted(self, textures, mesh_uvs, materials):
+        """set_scene_textures for textures that carry a format: textures: [(data, width, height, mip_count, format)] with format an ImageFormat - RGBA8: data are
+        uint32 texels as for set_scene_textures (mip_count 0: the host builds the chain); BC1, BC3, BC5: data are the bytes (any array, or bytes) of the blocks of
+        mip_count >= 1 levels back to back, as image_io.load_dds_file returns them for a DXT1 / DXT5 / ATI2 file. The byte count handed over is the array's: the
+        call refuses one that is not the exact size of the levels. mesh_uvs, materials, lifetime and removal as for set_scene_textures"""
+        def as_bytes(data, fmt):  # RGBA8 texels are uint32 words whatever integer type they come in; blocks are taken as the bytes they are
+            if isinstance(data, (bytes, bytearray)):
+                return np.frombuffer(data, np.uint8)
+            return (np.ascontiguousarray(data, np.uint32) if int(fmt) == 2 else np.ascontiguousarray(data)).reshape(-1).view(np.uint8)
+        data = [as_bytes(t[0], t[4]) for t in textures]
+        uvs = [None if u is None else np.ascontiguousarray(u, np.float32).reshape(-1, 2) for u in mesh_uvs]
+        t = (PlrfSceneTextureData * max(len(textures), 1))()
+        for k, (_, width, height, mips, fmt) in enumerate(textures):
+            t[k] = PlrfSceneTextureData(data[k].ctypes.data if data[k].size else None, data[k].size, int(width), int(height), int(mips), int(fmt))
+        u = (C.POINTER(C.c_float) * max(len(uvs), 1))()
+        for k, a in enumerate(uvs):
+            u[k] = None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+        m = (PlrfSceneMaterial * max(len(materials), 1))()
+        for k, (albedo, specular) in enumerate(materials):
+            m[k] = PlrfSceneMaterial(int(albedo), int(specular))
+        self.lib.plrf_set_scene_textures_formatted.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        self._check(self.lib.plrf_set_scene_textures_formatted(self.handle, C.cast(t, C.c_void_p), C.c_uint32(len(textures)), C.cast(u, C.c_void_p), C.c_uint32(len(mesh_uvs)),
+                                                               C.cast(m, C.c_void_p), C.c_uint32(len(materials))))
 
     def set_scene_alpha_cutoffs(self, cutoffs):
         """one alpha cutoff code 0 .. 255 per draw of the scene (0: opaque, ALPHA_CUTOFF_REFERENCE = 128: the reference's alpha < 0.5 -> discard); needs textures.

@@ -5,7 +5,7 @@ import numpy as np
 
 from .backend import ImageDescription, ImageFormat, ImageType, MipCount, PlrError, _ImageDesc, _load
 
-IMAGE_IO_SYMBOLS = ["plr_write_dds_file", "plr_load_dds_file", "plr_encode_dds", "plr_decode_dds"]
+IMAGE_IO_SYMBOLS = ["plr_write_dds_file", "plr_load_dds_file", "plr_encode_dds", "plr_decode_dds", "plr_decode_bc_to_rgba8"]
 
 
 def _check(lib, rc):
@@ -59,3 +59,18 @@ def load_dds_file(path):
     out = np.empty(size.value, np.uint8)
     _check(lib, lib.plr_load_dds_file(str(path).encode(), C.byref(cd), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size), C.byref(size)))
     return _pydesc(cd), out
+
+
+def bc_level_bytes(fmt: ImageFormat, width, height):
+    """the bytes of one width x height level of BC1 (8-byte blocks), BC3 or BC5 (16-byte blocks)"""
+    return ((int(width) + 3) // 4) * ((int(height) + 3) // 4) * (8 if fmt == ImageFormat.BC1 else 16)
+
+
+def decode_bc_to_rgba8(fmt: ImageFormat, width, height, blocks):
+    """one BC1 / BC3 / BC5 level -> height x width uint32 RGBA8 words, R in the low byte: the decode the depth prepass applies to a compressed scene texture"""
+    lib = _load()
+    src = np.frombuffer(blocks, np.uint8) if isinstance(blocks, (bytes, bytearray)) else np.ascontiguousarray(blocks).view(np.uint8).reshape(-1)
+    out = np.empty((max(int(height), 0), max(int(width), 0)), np.uint32)
+    lib.plr_decode_bc_to_rgba8.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    _check(lib, lib.plr_decode_bc_to_rgba8(int(fmt), int(width), int(height), src.ctypes.data if src.size else None, src.size, out.ctypes.data if out.size else None))
+    return out

@@ -1,6 +1,6 @@
 """What the depth prepass costs as a compute pass ("depthPrepassRaster.comp", plrf_set_scene_meshes) in bench.py's 4K frame.
 
-    python tools/prepass_raster_cost.py [--out FILE] [--frames N] [--instances K] [--textured | --alpha | --normal-mapped]
+    python tools/prepass_raster_cost.py [--out FILE] [--frames N] [--instances K] [--textured [--bc] | --alpha | --normal-mapped]
 
 One process, one build. The scene is the instance set of tools/shadow_raster_cost.py: the three meshes of tests/shadow_raster_cases.py (box, uv_sphere, torus:
 1496 triangles) instanced K times (default 202: about 100 k triangles) over the view frustum in front of bench.py's camera, rasterised into the 3840 x 2160
@@ -9,6 +9,8 @@ counters and, from a host-side projection of the triangles the clip leaves uncha
 bounds the tile kernel). The same with every instance shrunk to 1 / 20, where the tile kernel's time is its scan of the rectangle list and its resolve.
 --textured: the same two scenes with material textures (plrf_set_scene_textures): every draw samples a 256 x 256 albedo and a 256 x 256 specular texture
 with full chains (two textures, shared by the draws) by the mesh generators' UVs; compare its tile times with a run without the option.
+--textured --bc: the --textured scenes with both textures block-compressed (plrf_set_scene_textures_formatted): the albedo as BC1 and the specular as BC3, 256 x 256
+with full chains of random blocks; the store's bytes are reported; compare its tile times with --textured of the same build.
 --alpha: the --textured scenes with the alpha test (plrf_set_scene_alpha_cutoffs): every draw has cutoff 128 and the albedo texture's alpha is a 0 / 255
 checker in cells of 32 texels, so about half of each draw's fragments are discarded; compare its tile times with --textured of the same build.
 --normal-mapped: the --textured scenes with normal maps (plrf_set_scene_normal_maps): every draw names a 256 x 256 normal texture with a full chain; the tile
@@ -66,6 +68,15 @@ def scene_textures(draw_count, alpha_checker=False):
     return [(albedo.reshape(-1), 256, 256, 0), (specular.reshape(-1), 256, 256, 0)], uvs, [(0, 1)] * draw_count
 
 
+def scene_textures_bc(draw_count):
+    """(textures, mesh_uvs, materials) of scene_textures with the albedo as BC1 and the specular as BC3: random blocks, all nine levels given"""
+    from plainrenderer_amd import ImageFormat
+    _, uvs, materials = scene_textures(draw_count)
+    rng = np.random.default_rng(7)
+    blocks = sum(((max(1, 256 >> l) + 3) // 4) ** 2 for l in range(9))
+    return [(rng.integers(0, 256, blocks * 8, dtype=np.uint8), 256, 256, 9, ImageFormat.BC1), (rng.integers(0, 256, blocks * 16, dtype=np.uint8), 256, 256, 9, ImageFormat.BC3)], uvs, materials
+
+
 def scene_normal_maps(draw_count):
     """(one more texture, mesh_tangents, mesh_bitangents, normal_textures): a 256 x 256 normal texture (the host builds the chain) named by every draw, the
     generators' tangents; the box came without normals, so its bitangents are given (cross(tangent, area-weighted vertex normal)), the others the host derives"""
@@ -105,6 +116,7 @@ def main():
     ap.add_argument("--frames", type=int, default=40)
     ap.add_argument("--instances", type=int, default=202)
     ap.add_argument("--textured", action="store_true")
+    ap.add_argument("--bc", action="store_true")
     ap.add_argument("--alpha", action="store_true")
     ap.add_argument("--normal-mapped", action="store_true")
     ap.add_argument("--out")
@@ -120,7 +132,7 @@ def main():
     fp = FramePipeline(be, W, H, shadow_map_res=2048)
     _, cams, inputs = bench.build_scene(args, "cuda:0", W, H, None)
     inputs.upload(fp)
-    lines = ["# python tools/prepass_raster_cost.py%s: bench.py's scene at %d x %d, fast kernel set, %d frames per figure" % (" --normal-mapped" if a.normal_mapped else " --alpha" if a.alpha else " --textured" if a.textured else "", W, H, a.frames)]
+    lines = ["# python tools/prepass_raster_cost.py%s: bench.py's scene at %d x %d, fast kernel set, %d frames per figure" % (" --normal-mapped" if a.normal_mapped else " --alpha" if a.alpha else " --textured --bc" if a.textured and a.bc else " --textured" if a.textured else "", W, H, a.frames)]
     cursor = 1
     for i in range(args.warmup):
         fp.frame(cams[cursor + i], 1.0 / 60.0, 0.5)
@@ -140,6 +152,8 @@ def main():
             normal_texture, tangents, bitangents, normal_textures = scene_normal_maps(len(draws))
             fp.set_scene_textures(textures + [normal_texture], uvs, materials)
             fp.set_scene_normal_maps(tangents, bitangents, normal_textures)
+        elif a.textured and a.bc:
+            fp.set_scene_textures_formatted(*scene_textures_bc(len(draws)))
         elif a.textured or a.alpha:
             fp.set_scene_textures(*scene_textures(len(draws), alpha_checker=a.alpha))
         if a.alpha:
@@ -156,6 +170,9 @@ def main():
         if a.normal_mapped:
             lines.append("  shading-normal kernel: %.2f us" % times.get("Depth prepass", float("nan")))
         lines.append("  %d draws; %d of %d tiles touched, %.1f rectangles per tile on average" % (len(draws), touched, tiles, mean_hits))
+    if a.textured and not a.alpha and not a.normal_mapped:
+        chain = sum(max(1, 256 >> l) ** 2 for l in range(9))
+        lines.append("texture store: %d bytes" % (sum(t[0].size for t in scene_textures_bc(1)[0]) if a.bc else 2 * chain * 4))
     general_with = be.getGeneralKernelExecutions()
     fp.set_scene_meshes([], [])
     _, entries_after = pass_times(be, fp, cams, cursor, 2)
