@@ -1,5 +1,6 @@
 """The alpha test of the "depthPrepassRaster.comp" pass through the C-ABI against tests/prepass_alpha_reference.py, in both math modes: all five images and the
 four counters must be bit-identical to the reference, and no pixel is left out. The cases and what each is for: tests/prepass_alpha_cases.py.
+Tiles with hundreds of records (several steps, windows and waves of the scan): tests/prepass_crowd_cases.py, tests/test_prepass_crowd.py.
 
 A record with the 8- or 12-byte push constants, or with alphaTest 0, is the pass without the test whatever is bound at 10; with alphaTest != 0 the launcher
 refuses a missing or short binding 10, textureCount 0 and a scratch buffer that is also binding 10, by name.

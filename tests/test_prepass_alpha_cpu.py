@@ -1,5 +1,6 @@
 """The alpha test's reference (tests/prepass_alpha_reference.py) against the textured reference where nothing is tested, the input conditions of the GPU cases
-(tests/prepass_alpha_cases.py), the host's validation under a sanitizer, and the entry point at the C boundary; no GPU."""
+(tests/prepass_alpha_cases.py), the host's validation under a sanitizer, and the entry point at the C boundary; no GPU.
+The input conditions of the crowded-tile cases (tests/prepass_crowd_cases.py): tests/test_prepass_crowd_cpu.py."""
 import ctypes as C
 import os
 import shutil

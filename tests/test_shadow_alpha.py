@@ -1,5 +1,6 @@
 """Alpha-tested cutout casters of the "sunShadowRaster.comp" pass through the C-ABI against tests/shadow_alpha_reference.py, in both math modes: every texel of
 the Depth16 map and the three counters must be bit-identical. The cases and what each is for: tests/shadow_alpha_cases.py.
+A tile with 650 records from three set-up blocks: tests/shadow_crowd_cases.py, tests/test_prepass_crowd.py.
 
 A record with the 8-byte push constants, or with textureCount 0, is the opaque pass whatever is bound at 6 - 9; with textureCount > 0 the launcher refuses a
 missing or short binding 6 - 9, a scratch buffer of the opaque size and a scratch buffer that is also bound at 6 - 9, by name, and leaves the map as it was.
