@@ -294,7 +294,7 @@ int plrf_set_scene_meshes(void* pipeline, const plrf_scene_mesh* meshes, uint32_
 int plrf_set_scene_mesh_transforms(void* pipeline, const float* matrices16, uint32_t draw_count);
 /* ---- material textures of the scene meshes: depthPrepass.frag / triangle.frag's albedoTexture and specularTexture sampled per pixel with the interpolated UV and
  * g_mipBias (DESIGN.md "Material textures in the depth prepass": the sampling contract in integers and IEEE operations - repeat addressing, isotropic trilinear
- * filtering with 8 sub-texel and 8 level-fraction bits, forward-difference derivatives of the triangle's own plane, round half even; the alpha test: plrf_set_scene_alpha_cutoffs below; the normal map: plrf_set_scene_normal_maps below).
+ * filtering with 8 sub-texel and 8 level-fraction bits, forward-difference derivatives of the triangle's own plane, round half even; the alpha test: plrf_set_scene_alpha_cutoffs below; the normal map: plrf_set_scene_normal_maps below; anisotropic filtering in place of the isotropic: plrf_set_scene_anisotropy below).
  * plrf_scene_texture: RGBA8 texels, R in the low byte, row-major; mip_count >= 1: that many levels back to back, level l being max(1, width >> l) x
  * max(1, height >> l); mip_count 0: level 0 only and the host builds the full chain, each texel the rounded mean (a + b + c + d + 2) >> 2 of the level below at
  * (min(2x, W - 1) | min(2x + 1, W - 1), min(2y, H - 1) | min(2y + 1, H - 1)). plrf_scene_material, one per draw: the texture an output samples, or PLRF_NO_TEXTURE
@@ -363,6 +363,19 @@ int plrf_set_scene_alpha_cutoffs(void* pipeline, const uint32_t* cutoffs, uint32
 #define PLRF_NORMAL_DECODE_UNIT 2u
 int plrf_set_scene_normal_maps(void* pipeline, const float* const* mesh_tangents, const float* const* mesh_bitangents, uint32_t mesh_count,
                                const uint32_t* normal_textures, uint32_t draw_count, uint32_t decode);
+/* ---- anisotropic filtering of the scene's material textures: the reference samples them through g_sampler_anisotropicRepeat (RenderFrontend.cpp:1305-1314),
+ * a sampler with useAnisotropy = true and maxAnisotropy = 8 (ResourceDescriptions.h:169, VulkanSampler.cpp:23). DESIGN.md "Anisotropic filtering in the depth
+ * prepass": the contract - per sample N = 1 .. max_anisotropy probes along the major axis of the pixel's footprint, N the smallest integer with N^2 rmin >= rmax,
+ * at the mip level of rho2 / N^2, summed in integers and divided by N with round half even; probe count and placement are this contract's (Vulkan leaves them to
+ * the implementation). It applies to every sample of the prepass: albedo, specular, the tested alpha of the cutouts and the normal-map texel, RGBA8 and
+ * block-compressed alike. max_anisotropy 0 or 1: off, every frame is what it is without this call; 2 .. 16: on (PLRF_ANISOTROPY_REFERENCE, 8: the reference's
+ * sampler), from the next recorded frame, in call order. One scalar of pipeline state: it needs neither a scene nor textures (while the scene has none the pass
+ * record is what it was) and survives plrf_set_scene_meshes, plrf_set_scene_textures, plrf_set_scene_textures_formatted, plrf_set_scene_alpha_cutoffs,
+ * plrf_set_scene_normal_maps, plrf_set_scene_mesh_transforms, plrf_set_resolution and plrf_update_settings. The sun shadow raster's cutout sampling stays
+ * isotropic. PLR_ERR_INVALID_ARGUMENT, with a message that names the value: a value above 16. PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call
+ * changes nothing. */
+#define PLRF_ANISOTROPY_REFERENCE 8u
+int plrf_set_scene_anisotropy(void* pipeline, uint32_t max_anisotropy);
 /* ---- alpha-tested cutout casters: sunShadow.frag:17-21 (sample the albedo texture's alpha, discard below 0.5) for the mesh shadow casters (DESIGN.md
  * "Alpha-tested cutout casters in the sun shadow raster"). Casters are another mesh set than the scene's and keep their own copy of the textures:
  * plrf_scene_texture as above (mip_count 0: the host builds the chain), mesh_uvs[k]: 2 floats per vertex of caster mesh k, NULL (the array or an entry): all

@@ -22,6 +22,10 @@ struct TexturedPushConstants { uint32_t drawCount, triangleCount, textureCount; 
 struct AlphaPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest; }; // the optional fourth word: 0, or absent, is the pass without the alpha test
 struct NormalPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest, normalMap; }; // the optional fifth word: 0, or absent, is the pass without normal maps
 struct FormatPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest, normalMap, textureFormats; }; // the optional sixth word: 0, or absent, is the pass whose textures are all RGBA8
+struct AnisoPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest, normalMap, textureFormats, maxAnisotropy; }; // the optional seventh word: 0, 1, or absent, is the pass with isotropic trilinear filtering
+// anisotropic filtering ("Anisotropic filtering in the depth prepass"): maxAnisotropy 2 .. kMaxAnisotropy selects the anisotropic instantiations; the reference's
+// sampler has 8 (ResourceDescriptions.h:169, VulkanSampler.cpp:23)
+constexpr uint32_t kMaxAnisotropy = 16, kAnisotropyReference = 8;
 struct Draw { uint32_t firstIndex, indexCount, vertexOffset, transformIndex, albedo, specular; }; // albedo, specular: RGBA8 texels as they are stored
 struct MainPassMatrices { float model[16], mvp[16], mvpPrevious[16]; };                            // glm column-major (RenderFrontend.cpp:581-585)
 // material textures ("The sampling contract"): `texels` holds RGBA8 texels, R in the low byte, every texture's levels back to back and unpadded; level l is

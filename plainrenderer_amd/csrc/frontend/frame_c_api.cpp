@@ -175,6 +175,10 @@ int plrf_set_scene_normal_maps(void* p, const float* const* meshTangents, const 
     if (!p) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY_REFUSAL(((FramePipeline*)p)->setSceneNormalMaps(meshTangents, meshBitangents, meshCount, normalTextures, drawCount, decode))
 }
+int plrf_set_scene_anisotropy(void* p, uint32_t maxAnisotropy) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL(((FramePipeline*)p)->setSceneAnisotropy(maxAnisotropy))
+}
 int plrf_get_prepass_raster_stats(void* p, plrf_prepass_raster_stats* out) {
     if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY_REFUSAL({

@@ -1409,9 +1409,12 @@ void FramePipeline::renderDepthPrepass(const FrameRenderTargets& current) {
                                                 StorageBufferResource(m_sceneDraws.handle, true, pp::kDrawBinding), StorageBufferResource(m_sceneScratch.handle, false, pp::kScratchBinding)};
     const bool alphaTested = m_sceneAlphaTested && m_sceneTextureCount;
     const bool compressed = m_sceneTexturesCompressed && m_sceneTextureCount;
-    const pp::FormatPushConstants pc{m_sceneDrawCount, m_sceneTriangleCount, m_sceneTextureCount, alphaTested ? 1u : 0u, normalMapped() ? m_sceneNormalDecode : 0u, compressed ? 1u : 0u};
-    // without textures: the 8-byte record; without a cutoff other than 0: the 12-byte one; without normal maps: the 16-byte one; without a compressed texture: the 20-byte one
-    exe.pushConstants = dataToCharArray(&pc, compressed ? sizeof(pc) : normalMapped() ? sizeof(pp::NormalPushConstants) : alphaTested ? sizeof(pp::AlphaPushConstants) : m_sceneTextureCount ? sizeof(pp::TexturedPushConstants) : sizeof(pp::PushConstants));
+    const bool anisotropic = m_sceneMaxAnisotropy >= 2u && m_sceneTextureCount;
+    const pp::AnisoPushConstants pc{m_sceneDrawCount, m_sceneTriangleCount, m_sceneTextureCount, alphaTested ? 1u : 0u, normalMapped() ? m_sceneNormalDecode : 0u, compressed ? 1u : 0u,
+                                    anisotropic ? m_sceneMaxAnisotropy : 0u};
+    // without textures: the 8-byte record; without a cutoff other than 0: the 12-byte one; without normal maps: the 16-byte one; without a compressed texture: the 20-byte one;
+    // without anisotropic filtering: the 24-byte one (with it and an all-RGBA8 store: 28 bytes with word 6 at 0, and no binding 14)
+    exe.pushConstants = dataToCharArray(&pc, anisotropic ? sizeof(pc) : compressed ? sizeof(pp::FormatPushConstants) : normalMapped() ? sizeof(pp::NormalPushConstants) : alphaTested ? sizeof(pp::AlphaPushConstants) : m_sceneTextureCount ? sizeof(pp::TexturedPushConstants) : sizeof(pp::PushConstants));
     if (m_sceneTextureCount) {
         auto& buffers = exe.genericInfo.resources.storageBuffers;
         buffers.push_back(StorageBufferResource(m_sceneUvs.handle, true, pp::kUvBinding)); buffers.push_back(StorageBufferResource(m_sceneMaterials.handle, true, pp::kMaterialBinding));
@@ -1544,6 +1547,14 @@ void FramePipeline::setSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawC
     const PackedAlphaCutoffs packed = packSceneAlphaCutoffs(cutoffs, drawCount, m_sceneDrawCount, m_sceneTextureCount); // validates everything before anything is changed
     fillCasterBuffer(m_sceneAlphaCutoffs.handle, m_sceneAlphaCutoffs.bytes, packed.cutoffs.data(), packed.cutoffs.size() * sizeof(uint32_t));
     m_sceneAlphaTested = packed.tested;
+}
+
+void FramePipeline::setSceneAnisotropy(uint32_t maxAnisotropy) {
+    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneAnisotropy: a band / tile pipeline cannot rasterise scene meshes");
+    if (maxAnisotropy > plr::prepass::kMaxAnisotropy)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setSceneAnisotropy: max anisotropy " + std::to_string(maxAnisotropy) + " is above 16 (0 or 1: off, 2 .. 16: on)");
+    m_sceneMaxAnisotropy = maxAnisotropy;
 }
 
 void FramePipeline::setSceneMeshTransforms(const float* matrices16, uint32_t drawCount) {

@@ -467,6 +467,12 @@ public:
     // is PLR_ERR_UNSUPPORTED. A refused call changes nothing.
     void setSceneNormalMaps(const float* const* meshTangents, const float* const* meshBitangents, uint32_t meshCount, const uint32_t* normalTextures, uint32_t drawCount,
                             uint32_t decode);
+    // anisotropic filtering of every texture sample of the depth prepass (DESIGN.md "Anisotropic filtering in the depth prepass"): 0 or 1 is off - isotropic
+    // trilinear filtering, the pass record as it was -, 2 .. 16 is the contract's A (8: the reference's sampler). One scalar of pipeline state: it needs neither a
+    // scene nor textures, takes effect with the next recorded frame whose scene has textures (the seventh push-constant word), and survives every other scene call,
+    // setResolution and updateSettings. Refusals: a value above 16 is PLR_ERR_INVALID_ARGUMENT; a band / tile pipeline is PLR_ERR_UNSUPPORTED. A refused call
+    // changes nothing.
+    void setSceneAnisotropy(uint32_t maxAnisotropy);
     // counters of the last frame's execution for the scene now set; waits for the GPU. Zero while no scene is set and before the first frame of a newly set scene.
     PrepassRasterStats prepassRasterStats();
     // RenderFrontend::setResolution (RenderFrontend.cpp:408-421): recorded, applied at the start of the next frame() (prepareNewFrame, :199-222). Every image and
@@ -600,6 +606,7 @@ private:
     SceneBuffer m_sceneAlphaCutoffs;
     // normal maps: buffers and the shadingNormal image created by the first setSceneNormalMaps; decode 0 = the pass record without the fifth push-constant word
     uint32_t m_sceneNormalDecode = 0;
+    uint32_t m_sceneMaxAnisotropy = 0; // setSceneAnisotropy: >= 2 with textures set = the pass record with the seventh push-constant word; no scene call resets it
     std::vector<uint8_t> m_sceneMeshHasNormals;
     std::vector<float> m_sceneNormalsHost; // the packed normals: what absent bitangents are derived from
     SceneBuffer m_sceneTangents, m_sceneBitangents, m_sceneNormalMaterials;

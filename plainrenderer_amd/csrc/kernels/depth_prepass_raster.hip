@@ -66,7 +66,8 @@
 //     fx = Tu & 255, x1 = x0 + 1, both wrapped to [0, W) by a non-negative modulo (repeat); y0, fy, y1 likewise with v and H. Per channel
 //     S_l = (256 - fx)(256 - fy) c00 + fx (256 - fy) c10 + (256 - fx) fy c01 + fx fy c11; S = (256 - fw) S_L0 + fw S_L1 (<= 255 * 2^24: fits uint32); the stored
 //     code is (S + 2^23 - 1 + ((S >> 24) & 1)) >> 24, round half even. All four channels, alpha included; albedo is filtered in code space.
-//   Isotropic trilinear filtering stands in for the implementation-defined anisotropic sampler; the normal map: THE NORMAL MAP CONTRACT below.
+//   Without the seventh push-constant word isotropic trilinear filtering stands in for the reference's anisotropic sampler; with it: THE ANISOTROPIC CONTRACT
+//   below, whose probe placement and count are this project's (Vulkan leaves them to the implementation). The normal map: THE NORMAL MAP CONTRACT below.
 //
 // THE ALPHA TEST CONTRACT (DESIGN.md "Alpha-tested cutouts in the depth prepass"; tests/prepass_alpha_reference.py implements it independently, bit for bit). Only an
 // execution whose fourth push-constant word alphaTest is != 0 tests (it needs textureCount > 0 and storage buffer 10 `alphaCutoffs`, one uint32 per draw).
@@ -106,7 +107,7 @@
 //     no normal map: the pixel stores exactly the word the pass stores to `normal` - a draw whose normalMaterials word names no usable texture, a draw at or past
 //       drawCount, a draw past the end of normalMaterials.
 //   a pixel without a winner stores 0; every texel of shadingNormal is written by every normal-mapped execution.
-//   deviations: the filtered texel is quantised to 8 bits before the decode; isotropic trilinear filtering; fp32 tangents for the A2R10G10B10 SNORM vertex format;
+//   deviations: the filtered texel is quantised to 8 bits before the decode; isotropic trilinear filtering, or the anisotropic contract's probes; fp32 tangents for the A2R10G10B10 SNORM vertex format;
 //     the normalised fallback; decode 1 is the reference's expression, not a unit-length one.
 // The tile kernel of such an execution (kNormalMap) leaves the winner's t, or kNoWinner, in the shadingNormal texel, and depthPrepassShadingNormalKernel behind it,
 // a lane per pixel, turns that texel into the shading normal in place.
@@ -136,6 +137,25 @@
 //     the taps, repeat wrap and weights, the round-half-even code.
 // The format-aware instantiations (kFormats) decode per tap: blockTexel loads the tap's block with one plain vector load and extracts its texel; the alpha-only
 // path (kFirst == 3) loads BC3's alpha block alone and nothing for BC1 and BC5.
+//
+// THE ANISOTROPIC CONTRACT (DESIGN.md "Anisotropic filtering in the depth prepass"; tests/prepass_aniso_reference.py implements it independently, bit for bit). Only an
+// execution whose seventh push-constant word maxAnisotropy = A is 2 .. 16 runs it (it needs textureCount > 0; a push of 24 bytes or fewer, or the word at 0 or 1, is
+// the pass above; a value above 16 is refused). It applies to EVERY sample: albedo, specular, the alpha of the coverage path, the normal-map texel, RGBA8 and
+// block-compressed alike. Everything not named is the sampling contract. fp64 IEEE without contraction where values are fp64, integers elsewhere.
+//   major axis: per texture and pixel ax, ay, rx, ry as above. The major axis is x where rx > ry (the rho2 expression), otherwise y; rmax = rho2, rmin the other of
+//     rx, ry; (du, dv) are the raw forward differences of the major axis: (dudx, dvdx) or (dudy, dvdy).
+//   probe count: N = 1; while (N < A && (double)(N N) rmin < rmax) N++. No square root, no division. A NaN compares false: N = 1; rmin = 0 < rmax: N = A; rmax = 0: N = 1.
+//   level: r = (float)(rho2 / (double)(N N)), then lod, the clamps, q, L0, L1, fw as above (N = 1 divides by 1.0: the level is the isotropic one).
+//   probes: N = 1: the one probe is (u, v) as validated above, no arithmetic on it. N > 1, k = 0 .. N - 1: t_k = (double)(2 k + 1 - N) / (double)(2 N),
+//     u_k = u + t_k du, v_k = v + t_k dv - a multiply, then an add, from the RAW u, v - and the validity rule anew per probe: u_k or v_k not finite or |.| >= 2^20:
+//     that probe taps at (0, 0).
+//   sum: per probe the trilinear integer sum per channel S_k = (256 - fw) S_L0 + fw S_L1 <= 255 * 2^24 at the shared L0, L1, fw; T = sum S_k in 64 bits, T < 2^36.
+//   stored code: T / (N 2^24) rounded half to even: D = N 2^24, qd = T / D, rem = T - qd D, code = qd + (2 rem > D || (2 rem == D && (qd & 1))); all four channels.
+//     For N = 1 this is (S + 2^23 - 1 + ((S >> 24) & 1)) >> 24.
+// The anisotropic instantiations (kAniso) exist in the format-aware form only: four tile kernels and one shading-normal kernel; without binding 14 their `formats`
+// pointer is null and every texture has format code 0. The kernel counts N without the early exit (the test is monotone in n: sampleTexture), walks one rolled loop of
+// N or 2 N steps - a step is one (probe, level) pair, so one copy of the taps serves both levels and L1's steps do not exist where fw == 0 - to each lane's own
+// count, and divides by a truncated fp32 quotient that is exact for T >> 24 < 2^12 and N <= 16.
 //
 // Two kernels. SET-UP: a lane per triangle finds its draw (block-wide prefix sum, LDS bisection), transforms, clips (the polygon lives in LDS, a column per lane),
 // projects, snaps, culls and boxes; the block's sub-triangles are appended through one 64-bit atomic per block to a dense array of 4-byte tile rectangles and an
@@ -335,7 +355,7 @@ __global__ __launch_bounds__(256) void depthPrepassSetupKernel(SetupParams p) {
 }
 
 struct TextureInputs {
-    static constexpr bool kFormats = false;
+    static constexpr bool kFormats = false, kAniso = false;
     const float* uvs; const Material* materials; const Texture* textures; const uint32_t* texels;
     uint64_t uvVertexCount, texelCount;
     uint32_t drawCount, textureCount;
@@ -346,8 +366,19 @@ struct FormatTextureInputs : TextureInputs {
     static constexpr bool kFormats = true;
     const uint32_t* formats;
 };
-template <bool kFormats> struct TextureInputsOf { typedef TextureInputs type; };
-template <> struct TextureInputsOf<true> { typedef FormatTextureInputs type; };
+// an anisotropic execution's (maxAnisotropy 2 .. 16): always format-aware - `formats` is null where textureFormats is 0, and every texture is RGBA8 then
+struct AnisoTextureInputs : FormatTextureInputs {
+    static constexpr bool kAniso = true;
+    uint32_t maxAnisotropy;
+};
+template <bool kFormats, bool kAniso = false> struct TextureInputsOf { typedef TextureInputs type; };
+template <> struct TextureInputsOf<true, false> { typedef FormatTextureInputs type; };
+template <> struct TextureInputsOf<true, true> { typedef AnisoTextureInputs type; };
+// A of the anisotropic contract; 0 in every other instantiation, which never reads it
+template <class Tex> PLR_DI uint32_t maxAnisotropyOf(const Tex& tex) {
+    if constexpr (Tex::kAniso) return tex.maxAnisotropy;
+    else return 0u;
+}
 struct TileParams {
     ScratchHeader* header; const TriangleOrigin* origins; const uint32_t* rects; const Record* records;
     const float* transforms; const float* positions; const float* normals; const uint32_t* indices; const Draw* draws;
@@ -360,13 +391,18 @@ struct TileParams {
 };
 // a normal-mapped execution's tile kernel leaves the winner's t in the shadingNormal texel (the other instantiations keep their argument block)
 struct NormalTileParams : TileParams { uint32_t* shadingNormal; };
-template <bool kNormalMap, bool kFormats = false> struct TileParamsOf { typedef TileParams type; };
-template <> struct TileParamsOf<true, false> { typedef NormalTileParams type; };
+template <bool kNormalMap, bool kFormats = false, bool kAniso = false> struct TileParamsOf { typedef TileParams type; };
+template <> struct TileParamsOf<true, false, false> { typedef NormalTileParams type; };
 // a format-aware execution's: binding 14 behind everything else
 struct FormatTileParams : TileParams { const uint32_t* formats; };
 struct FormatNormalTileParams : NormalTileParams { const uint32_t* formats; };
-template <> struct TileParamsOf<false, true> { typedef FormatTileParams type; };
-template <> struct TileParamsOf<true, true> { typedef FormatNormalTileParams type; };
+template <> struct TileParamsOf<false, true, false> { typedef FormatTileParams type; };
+template <> struct TileParamsOf<true, true, false> { typedef FormatNormalTileParams type; };
+// an anisotropic execution's: the seventh push-constant word behind everything else
+struct AnisoTileParams : FormatTileParams { uint32_t maxAnisotropy; };
+struct AnisoNormalTileParams : FormatNormalTileParams { uint32_t maxAnisotropy; };
+template <> struct TileParamsOf<false, true, true> { typedef AnisoTileParams type; };
+template <> struct TileParamsOf<true, true, true> { typedef AnisoNormalTileParams type; };
 
 typedef unsigned long long Key;
 
@@ -500,13 +536,24 @@ PLR_DI TexelSums bilinearTaps(const uint32_t* texels, uint64_t texelCount, uint6
 
 // one trilinear sample of `texture`: (u, v) for the taps, (dudx, dvdx) and (dudy, dvdy) the raw forward differences. kFirst: the first channel computed - 3 is
 // the alpha-only sample of the coverage path, whose bits 24 - 31 are those of the full word because every channel is filtered by itself
-template <int kFirst = 0, bool kFormats = false>
-PLR_DI uint32_t sampleTexture(const TextureInputs& tex, Texture texture, double u, double v, double dudx, double dvdx, double dudy, double dvdy, float mipBias) {
+// kAniso (the anisotropic contract): (u, v) are the RAW ones, the validity rule is applied per probe here; maxAniso is A, 2 .. 16
+template <int kFirst = 0, bool kFormats = false, bool kAniso = false>
+PLR_DI uint32_t sampleTexture(const TextureInputs& tex, Texture texture, double u, double v, double dudx, double dvdx, double dudy, double dvdy, float mipBias,
+                              uint32_t maxAniso = 0u) {
     const double w0 = (double)texture.width, h0 = (double)texture.height;
     const double axx = dudx * w0, axy = dvdx * h0, ayx = dudy * w0, ayy = dvdy * h0;
     const double rx = axx * axx + axy * axy, ry = ayx * ayx + ayy * ayy;
     const double rho2 = rx > ry ? rx : ry;
-    const float r = (float)rho2;
+    float r = (float)rho2;
+    uint32_t probes = 1u; // N
+    if constexpr (kAniso) {
+        const double rmin = rx > ry ? ry : rx;
+        // the contract's loop stops at the first n with !(n n rmin < rmax); rmin >= 0 or a NaN, so n n rmin does not decrease with n and the test, once false, stays
+        // false: N = 1 + the number of n in [1, A) that pass. A is wave-uniform: this loop has a scalar trip count and no exec mask (a NaN passes none: N = 1)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+        for (uint32_t n = 1u; n < maxAniso; n++) probes += (double)(n * n) * rmin < rho2 ? 1u : 0u;
+        r = (float)(rho2 / (double)(probes * probes));
+    }
     float lod = 0.5f * det_log2f(r) + mipBias;
     if (!(lod > 0.f)) lod = 0.f;
     const uint32_t mipCount = mipCountOf<kFormats>(texture), format = formatOf<kFormats>(texture);
@@ -521,6 +568,47 @@ PLR_DI uint32_t sampleTexture(const TextureInputs& tex, Texture texture, double 
         else base += (uint64_t)max(1u, texture.width >> l) * (uint64_t)max(1u, texture.height >> l);
     }
     const int w = (int)max(1u, texture.width >> L0), h = (int)max(1u, texture.height >> L0);
+    if constexpr (kAniso) {
+        // N probes along the major axis at the shared L0, L1, fw; T = the sum of their trilinear integer sums, the code T / (N 2^24) rounded half to even. The
+        // loop stays rolled and runs to this lane's own N
+        const bool majorX = rx > ry;
+        // N = 1: the one probe is (u, v) with no arithmetic on it. Its t is 0, and with (du, dv) = (0, 0) for such a lane u + 0 * 0 is u, value for value (a NaN
+        // stays one, -0 becomes +0, which no tap tells apart) - without a per-lane condition held across the loop
+        const double du = probes == 1u ? 0.0 : majorX ? dudx : dudy, dv = probes == 1u ? 0.0 : majorX ? dvdx : dvdy;
+        uint64_t base1 = base;
+        if (L1 != L0) base1 += levelWords(format, (uint32_t)w, (uint32_t)h);
+        const int w1 = (int)max(1u, texture.width >> L1), h1 = (int)max(1u, texture.height >> L1);
+        uint64_t T[4] = {0ull, 0ull, 0ull, 0ull};
+        // one step per (probe, level): a single copy of the taps serves both levels, and L1's steps do not exist where fw == 0
+        const uint32_t twoLevels = fw != 0u ? 1u : 0u, steps = probes << twoLevels;
+        // a lane runs to its own N; the loop's exit is the wave's (a ballot and a scalar branch: one exec mask held, not a divergent loop's two), and the lane
+        // counts its own steps down, so that the step's small integers live in vector registers: the alpha-tested scan has no scalar register to spare
+#pragma unroll 1
+        for (uint32_t left = steps; __ballot(left != 0u) != 0ull;) {
+            if (left == 0u) continue;
+            const uint32_t i = steps - left;
+            left--;
+            const uint32_t k = i >> twoLevels;
+            const bool upper = (i & twoLevels) != 0u;
+            const double t = (double)(2 * (int)k + 1 - (int)probes) / (double)(2u * probes);
+            double pu = u + t * du, pv = v + t * dv;
+            if (!(__builtin_fabs(pu) < 1048576.0 && __builtin_fabs(pv) < 1048576.0)) pu = pv = 0.0; // the validity rule, per probe (a NaN fails the comparison)
+            const TexelSums s = bilinearTaps<kFirst, true>(tex.texels, tex.texelCount, upper ? base1 : base, upper ? w1 : w, upper ? h1 : h, pu, pv, format);
+            const uint32_t weight = upper ? fw : 256u - fw; // weight * s.c <= 256 * 255 * 2^16: fits uint32
+            for (int c = kFirst; c < 4; c++) T[c] += (uint64_t)(weight * s.c[c]);
+        }
+        // qd = floor(T / D), D = N 2^24: floor((T >> 24) / N) is the same integer; T >> 24 < 2^12 and N <= 16 are exact in fp32, and their quotient is an integer or
+        // at least 1 / 16 away from one, 2^7 times the spacing of fp32 below 2^12: the truncated, correctly rounded fp32 quotient is the exact one
+        const uint64_t D = (uint64_t)probes << 24;
+        const float fn = (float)probes;
+        uint32_t word = 0u;
+        for (int c = kFirst; c < 4; c++) {
+            const uint32_t qd = (uint32_t)((float)(uint32_t)(T[c] >> 24) / fn);
+            const uint64_t twice = 2ull * (T[c] - (uint64_t)qd * D);
+            word |= (qd + (uint32_t)(twice > D || (twice == D && (qd & 1u)))) << (8 * c);
+        }
+        return word;
+    }
     const TexelSums s0 = bilinearTaps<kFirst, kFormats>(tex.texels, tex.texelCount, base, w, h, u, v, format);
     TexelSums s1{{0u, 0u, 0u, 0u}};
     if (fw != 0u) { // (with fw == 0 the upper level has no weight; with L1 == L0 it is the same level again)
@@ -548,7 +636,9 @@ PLR_DI bool usableTexture(const Tex& tex, uint32_t index, Texture* out) {
     if (t.mipCount < 1u || t.mipCount > 32u - (uint32_t)__clz(max(t.width, t.height))) return false;
     *out = t;
     if constexpr (Tex::kFormats) {
-        const uint32_t format = tex.formats[index];
+        uint32_t format;
+        if constexpr (Tex::kAniso) format = tex.formats ? tex.formats[index] : kTextureFormatRgba8; // (wave-uniform: no binding 14, every texture is RGBA8)
+        else format = tex.formats[index];
         if (format > kTextureFormatBc5) return false;
         if (format != kTextureFormatRgba8 && (t.texelOffset & (format == kTextureFormatBc1 ? 1u : 3u)) != 0u) return false;
         out->mipCount = t.mipCount | (format << 16);
@@ -566,6 +656,8 @@ PLR_DI void fetchUv(const TextureInputs& tex, uint64_t vertex, double* u, double
     *v = inside ? (double)tex.uvs[vertex * 2u + 1u] : 0.0;
 }
 struct UvSample { double u, v, dudx, dvdx, dudy, dvdy; }; // (u, v) validated for the taps, the forward differences raw
+// kRaw (an anisotropic execution): (u, v) stay raw - sampleTexture<., ., true> validates every probe itself
+template <bool kRaw = false>
 PLR_DI UvSample uvSampleAt(D3 P, const double b[3], const D3 V[3], const double tu[3], const double tv[3], int x, int y, int width, int height) {
     double bx[3], by[3];
     barycentricsAt(D3{(double)(2 * (x + 1) + 1) / (double)width - 1.0, P.y, 1.0}, V, bx);
@@ -574,7 +666,9 @@ PLR_DI UvSample uvSampleAt(D3 P, const double b[3], const D3 V[3], const double 
     s.u = weighted(b, tu[0], tu[1], tu[2]); s.v = weighted(b, tv[0], tv[1], tv[2]);
     s.dudx = weighted(bx, tu[0], tu[1], tu[2]) - s.u; s.dvdx = weighted(bx, tv[0], tv[1], tv[2]) - s.v;
     s.dudy = weighted(by, tu[0], tu[1], tu[2]) - s.u; s.dvdy = weighted(by, tv[0], tv[1], tv[2]) - s.v;
-    if (!(__builtin_fabs(s.u) < 1048576.0 && __builtin_fabs(s.v) < 1048576.0)) s.u = s.v = 0.0; // (a NaN fails the comparison)
+    if constexpr (!kRaw) {
+        if (!(__builtin_fabs(s.u) < 1048576.0 && __builtin_fabs(s.v) < 1048576.0)) s.u = s.v = 0.0; // (a NaN fails the comparison)
+    }
     return s;
 }
 
@@ -650,10 +744,11 @@ PLR_DI void resolvePixel(const TileParams& p, const Tex& tex, uint32_t t, int x,
         if (!sampleAlbedo && !sampleSpecular) return;
         double tu[3], tv[3];
         for (int k = 0; k < 3; k++) fetchUv(tex, vertex[k], &tu[k], &tv[k]);
-        const UvSample uv = uvSampleAt(P, b, V, tu, tv, x, y, p.width, p.height);
+        const UvSample uv = uvSampleAt<Tex::kAniso>(P, b, V, tu, tv, x, y, p.width, p.height);
         const float mipBias = p.global->mipBias;
-        if (sampleAlbedo) *albedo = sampleTexture<0, Tex::kFormats>(tex, albedoTexture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias);
-        if (sampleSpecular) *specular = sampleTexture<0, Tex::kFormats>(tex, specularTexture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias);
+        const uint32_t maxAniso = maxAnisotropyOf(tex);
+        if (sampleAlbedo) *albedo = sampleTexture<0, Tex::kFormats, Tex::kAniso>(tex, albedoTexture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias, maxAniso);
+        if (sampleSpecular) *specular = sampleTexture<0, Tex::kFormats, Tex::kAniso>(tex, specularTexture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias, maxAniso);
     }
 }
 
@@ -700,13 +795,13 @@ PLR_DI void alphaOfRecord(const TileParams& p, const Tex& tex, const uint32_t* c
 }
 
 // a(t, i, j): bits 24 - 31 of the albedo word the resolve would store for this triangle at pixel (x, y) - the same functions in the same order
-template <bool kFormats>
-PLR_DI uint32_t fragmentAlpha(const TextureInputs& tex, const AlphaRecord& a, float mipBias, int x, int y, int width, int height) {
+template <bool kFormats, bool kAniso = false>
+PLR_DI uint32_t fragmentAlpha(const TextureInputs& tex, const AlphaRecord& a, float mipBias, int x, int y, int width, int height, uint32_t maxAniso = 0u) {
     const D3 P{(double)(2 * x + 1) / (double)width - 1.0, (double)(2 * y + 1) / (double)height - 1.0, 1.0};
     double b[3];
     barycentricsAt(P, a.V, b);
-    const UvSample uv = uvSampleAt(P, b, a.V, a.tu, a.tv, x, y, width, height);
-    return sampleTexture<3, kFormats>(tex, a.texture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias) >> 24;
+    const UvSample uv = uvSampleAt<kAniso>(P, b, a.V, a.tu, a.tv, x, y, width, height);
+    return sampleTexture<3, kFormats, kAniso>(tex, a.texture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, mipBias, maxAniso) >> 24;
 }
 
 // THE ALPHA-TESTED SCAN. A sample costs far more than coverage, a stamp of a triangle's box or a lane's 4 x 4 box is seldom full, and the loads that lead to a
@@ -744,7 +839,7 @@ template <class Tex> struct AlphaScan {
             const int px = (int)(xy & 0xffffu), py = (int)(xy >> 16);
             Key* cell = &tile[(py - oy) * kTileSize + (px - ox)];
             const Key key = ((Key)f2u(zf) << 32) | (Key)u.r.t;
-            if (key > *cell && fragmentAlpha<Tex::kFormats>(*tex, u.r, mipBias, px, py, width, height) >= u.r.cutoff) atomicMax(cell, key);
+            if (key > *cell && fragmentAlpha<Tex::kFormats, Tex::kAniso>(*tex, u.r, mipBias, px, py, width, height, maxAnisotropyOf(*tex)) >= u.r.cutoff) atomicMax(cell, key);
         }
     }
     // called by the whole wave: the lanes with `candidate` append theirs; a full wave of candidates is sampled at once
@@ -841,10 +936,12 @@ template <class Tex> struct AlphaWalk {
 
 // kNormalMap: the resolve also leaves the winner's t (kNoWinner: none) in the shadingNormal texel, for depthPrepassShadingNormalKernel behind this kernel
 // kFormats: the format-aware instantiations (textureFormats = 1) - the same text with the block decode behind every tap
-template <bool kTextured, bool kAlphaTest = false, bool kNormalMap = false, bool kFormats = false>
-__global__ __launch_bounds__(256) void depthPrepassTileKernel(typename TileParamsOf<kNormalMap, kFormats>::type p) {
-    typedef typename TileParamsOf<kNormalMap, kFormats>::type Params;
-    typedef typename TextureInputsOf<kFormats>::type Tex;
+// kAniso: the anisotropic instantiations (maxAnisotropy 2 .. 16) - format-aware all of them, with the probe loop behind every sample
+template <bool kTextured, bool kAlphaTest = false, bool kNormalMap = false, bool kFormats = false, bool kAniso = false>
+__global__ __launch_bounds__(256) void depthPrepassTileKernel(typename TileParamsOf<kNormalMap, kFormats, kAniso>::type p) {
+    typedef typename TileParamsOf<kNormalMap, kFormats, kAniso>::type Params;
+    typedef typename TextureInputsOf<kFormats, kAniso>::type Tex;
+    static_assert(kFormats || !kAniso, "the anisotropic instantiations exist in the format-aware form only");
     static_assert(kTextured || !kFormats, "a format belongs to a texture");
     static_assert(kTextured || !kAlphaTest, "the alpha of a fragment is a texture sample");
     static_assert(kTextured || !kNormalMap, "the shading normal is a texture sample");
@@ -863,6 +960,7 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(typename TileParam
         if (threadIdx.x == 0) {
             static_cast<TextureInputs&>(sharedTex) = p.tex;
             if constexpr (kFormats) sharedTex.formats = p.formats;
+            if constexpr (kAniso) sharedTex.maxAnisotropy = p.maxAnisotropy;
         }
     }
     // the alpha-tested kernel takes ALL its arguments from LDS: its scan needs the resolve's buffers too, and held in scalar registers from the kernel's entry
@@ -921,8 +1019,8 @@ PLR_DI D3 fetchBasisVector(const float* buffer, uint64_t vertexCount, uint64_t v
 }
 
 // n_s of triangle origins[t] = o at pixel (x, y) with the usable normal texture `texture`, as the stored word; `fallback` where M does not normalise
-template <bool kFormats>
-PLR_DI uint32_t shadingNormalAt(const ShadingNormalParams& p, TriangleOrigin o, Texture texture, int x, int y, uint32_t fallback) {
+template <bool kFormats, bool kAniso = false>
+PLR_DI uint32_t shadingNormalAt(const ShadingNormalParams& p, TriangleOrigin o, Texture texture, int x, int y, uint32_t fallback, uint32_t maxAniso = 0u) {
     const Draw draw = p.draws[o.draw];
     const uint64_t at = (uint64_t)draw.firstIndex + (uint64_t)o.local * 3u;
     const float* model = p.transforms + (size_t)draw.transformIndex * 48u;
@@ -938,8 +1036,8 @@ PLR_DI uint32_t shadingNormalAt(const ShadingNormalParams& p, TriangleOrigin o, 
     // the texel: the sampling contract's word, through the albedo sampler's own functions
     double tu[3], tv[3];
     for (int k = 0; k < 3; k++) fetchUv(p.tex, vertex[k], &tu[k], &tv[k]);
-    const UvSample uv = uvSampleAt(P, b, V, tu, tv, x, y, p.width, p.height);
-    const uint32_t texel = sampleTexture<0, kFormats>(p.tex, texture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, p.global->mipBias);
+    const UvSample uv = uvSampleAt<kAniso>(P, b, V, tu, tv, x, y, p.width, p.height);
+    const uint32_t texel = sampleTexture<0, kFormats, kAniso>(p.tex, texture, uv.u, uv.v, uv.dudx, uv.dvdx, uv.dudy, uv.dvdy, p.global->mipBias, maxAniso);
     const double cx = (double)(texel & 255u) / 255.0, cy = (double)((texel >> 8) & 255u) / 255.0;
     D3 nt;
     if (p.decode == kNormalDecodeReference) {
@@ -973,11 +1071,14 @@ PLR_DI uint32_t shadingNormalAt(const ShadingNormalParams& p, TriangleOrigin o, 
 // A lane per pixel, a wave per 64 consecutive pixels of one row (256 contiguous bytes read and stored), in place: a lane reads the t the tile kernel left in its
 // texel and overwrites that texel. No LDS, no atomics. A wave of sky only, and a wave none of whose draws has a usable normal texture, leave by a ballot.
 struct FormatShadingNormalParams : ShadingNormalParams { const uint32_t* formats; };
-template <bool kFormats> struct ShadingNormalParamsOf { typedef ShadingNormalParams type; };
-template <> struct ShadingNormalParamsOf<true> { typedef FormatShadingNormalParams type; };
+struct AnisoShadingNormalParams : FormatShadingNormalParams { uint32_t maxAnisotropy; };
+template <bool kFormats, bool kAniso = false> struct ShadingNormalParamsOf { typedef ShadingNormalParams type; };
+template <> struct ShadingNormalParamsOf<true, false> { typedef FormatShadingNormalParams type; };
+template <> struct ShadingNormalParamsOf<true, true> { typedef AnisoShadingNormalParams type; };
 
-template <bool kFormats = false>
-__global__ __launch_bounds__(256) void depthPrepassShadingNormalKernel(typename ShadingNormalParamsOf<kFormats>::type p) {
+template <bool kFormats = false, bool kAniso = false>
+__global__ __launch_bounds__(256) void depthPrepassShadingNormalKernel(typename ShadingNormalParamsOf<kFormats, kAniso>::type p) {
+    static_assert(kFormats || !kAniso, "the anisotropic instantiation exists in the format-aware form only");
     const int x = (int)(blockIdx.x * 64u + (threadIdx.x & 63u)), y = (int)(blockIdx.y * 4u + (threadIdx.x >> 6));
     if (y >= p.height) return; // (wave-uniform)
     const bool inside = x < p.width;
@@ -993,7 +1094,12 @@ __global__ __launch_bounds__(256) void depthPrepassShadingNormalKernel(typename 
             word = p.normal[at];
             o = p.origins[t];
             if (o.draw < p.tex.drawCount && o.draw < p.normalMaterialCount) {
-                if constexpr (kFormats) {
+                if constexpr (kAniso) {
+                    AnisoTextureInputs tex;
+                    static_cast<TextureInputs&>(tex) = p.tex;
+                    tex.formats = p.formats;
+                    mapped = usableTexture(tex, p.normalMaterials[o.draw], &texture);
+                } else if constexpr (kFormats) {
                     FormatTextureInputs tex;
                     static_cast<TextureInputs&>(tex) = p.tex;
                     tex.formats = p.formats;
@@ -1002,15 +1108,18 @@ __global__ __launch_bounds__(256) void depthPrepassShadingNormalKernel(typename 
                     mapped = usableTexture(p.tex, p.normalMaterials[o.draw], &texture);
             }
         }
-        if (__ballot(mapped) != 0ull && mapped) word = shadingNormalAt<kFormats>(p, o, texture, x, y, word);
+        if constexpr (kAniso) {
+            if (__ballot(mapped) != 0ull && mapped) word = shadingNormalAt<true, true>(p, o, texture, x, y, word, p.maxAnisotropy);
+        } else if (__ballot(mapped) != 0ull && mapped) word = shadingNormalAt<kFormats>(p, o, texture, x, y, word);
     }
     if (inside) p.shadingNormal[at] = word;
 }
 
 static int launchDepthPrepassRaster(const PassCtx& c) {
     if (c.push.size() < sizeof(PushConstants)) return c.fail(-1, "depthPrepassRaster: push constants {drawCount, triangleCount} missing");
-    FormatPushConstants pc{};
-    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0; 12: alphaTest 0; 16: normalMap 0; 20: textureFormats 0
+    AnisoPushConstants pc{};
+    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0; 12: alphaTest 0; 16: normalMap 0; 20: textureFormats 0; 24: maxAnisotropy 0
+    const bool aniso = pc.maxAnisotropy >= 2u; // 0 and 1: the isotropic pass, word for word
     if (c.dispatch[0] != 1u || c.dispatch[1] != 1u || c.dispatch[2] != 1u || c.base[0] != 0u || c.base[1] != 0u)
         return c.fail(-1, "depthPrepassRaster: the dispatch is {1, 1, 1} (the launcher derives its grids from the push constants and the images)");
     if (pc.triangleCount > kMaxTriangles) return c.fail(-1, "depthPrepassRaster: triangleCount " + std::to_string(pc.triangleCount) + " exceeds 2^28");
@@ -1049,6 +1158,11 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
         if (int rc = c.needSbuf(kTextureFormatBinding, (size_t)pc.textureCount * 4u, "depthPrepassRaster textureFormats (binding 14: one uint32 format code per texture)")) return rc;
         if (c.sbuf[kTextureFormatBinding].ptr == c.sbuf[kScratchBinding].ptr)
             return c.fail(-4, "depthPrepassRaster: the scratch buffer is also bound as an input (binding 14, textureFormats)");
+    }
+    if (aniso) {
+        if (pc.maxAnisotropy > kMaxAnisotropy)
+            return c.fail(-1, "depthPrepassRaster: maxAnisotropy is " + std::to_string(pc.maxAnisotropy) + ", it must be 0 or 1 (isotropic trilinear filtering) or 2 .. 16 (the probe count's upper bound)");
+        if (pc.textureCount == 0u) return c.fail(-1, "depthPrepassRaster: maxAnisotropy is set and textureCount is 0 (anisotropic filtering is a property of the texture samples: it needs textures)");
     }
     if (c.sbuf[kScratchBinding].readOnly) return c.fail(-4, "depthPrepassRaster: the scratch buffer (binding 5) is bound read-only");
     if (int rc = c.needStorage(kDepthBinding, F_D32, "depthPrepassRaster depth")) return rc;
@@ -1125,7 +1239,13 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
             NormalTileParams n{};
             static_cast<TileParams&>(n) = t;
             n.shadingNormal = (uint32_t*)c.storage[kShadingNormalBinding].ptr;
-            if (formats) {
+            if (aniso) { // format-aware whatever textureFormats says: a null `formats` makes every texture RGBA8
+                AnisoNormalTileParams a{};
+                static_cast<NormalTileParams&>(a) = n;
+                a.formats = formats; a.maxAnisotropy = pc.maxAnisotropy;
+                if (pc.alphaTest) depthPrepassTileKernel<true, true, true, true, true><<<tiles, 256, 0, c.stream>>>(a);
+                else depthPrepassTileKernel<true, false, true, true, true><<<tiles, 256, 0, c.stream>>>(a);
+            } else if (formats) {
                 FormatNormalTileParams f{};
                 static_cast<NormalTileParams&>(f) = n;
                 f.formats = formats;
@@ -1137,7 +1257,7 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
                 depthPrepassTileKernel<true, false, true><<<tiles, 256, 0, c.stream>>>(n);
             PLR_CHECK_LAUNCH(c);
             c.splitTiming("tiles");
-            FormatShadingNormalParams s{};
+            AnisoShadingNormalParams s{};
             s.origins = t.origins; s.transforms = t.transforms; s.positions = t.positions; s.normals = t.normals; s.indices = t.indices; s.draws = t.draws;
             s.global = c.global; s.normal = t.normal; s.shadingNormal = n.shadingNormal;
             s.tangents = (const float*)c.sbuf[kTangentBinding].ptr; s.bitangents = (const float*)c.sbuf[kBitangentBinding].ptr;
@@ -1145,10 +1265,17 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
             s.tangentVertexCount = c.sbuf[kTangentBinding].size / 12u; s.bitangentVertexCount = c.sbuf[kBitangentBinding].size / 12u;
             s.triangleCount = pc.triangleCount; s.normalMaterialCount = (uint32_t)std::min<size_t>(c.sbuf[kNormalMaterialBinding].size / 4u, 0xffffffffu);
             s.decode = pc.normalMap; s.width = depth.w; s.height = depth.h; s.tex = t.tex;
-            s.formats = formats;
+            s.formats = formats; s.maxAnisotropy = pc.maxAnisotropy;
             const dim3 rows(divUp((unsigned)depth.w, 64u), divUp((unsigned)depth.h, 4u));
-            if (formats) depthPrepassShadingNormalKernel<true><<<rows, 256, 0, c.stream>>>(s);
+            if (aniso) depthPrepassShadingNormalKernel<true, true><<<rows, 256, 0, c.stream>>>(s);
+            else if (formats) depthPrepassShadingNormalKernel<true><<<rows, 256, 0, c.stream>>>(static_cast<const FormatShadingNormalParams&>(s));
             else depthPrepassShadingNormalKernel<false><<<rows, 256, 0, c.stream>>>(static_cast<const ShadingNormalParams&>(s));
+        } else if (aniso) {
+            AnisoTileParams a{};
+            static_cast<TileParams&>(a) = t;
+            a.formats = formats; a.maxAnisotropy = pc.maxAnisotropy;
+            if (pc.alphaTest) depthPrepassTileKernel<true, true, false, true, true><<<tiles, 256, 0, c.stream>>>(a);
+            else depthPrepassTileKernel<true, false, false, true, true><<<tiles, 256, 0, c.stream>>>(a);
         } else if (formats) {
             FormatTileParams f{};
             static_cast<TileParams&>(f) = t;

@@ -68,6 +68,7 @@ class PlrfSceneDraw(C.Structure):
 NO_TEXTURE = 0xFFFFFFFF  # PLRF_NO_TEXTURE
 ALPHA_CUTOFF_REFERENCE = 128  # PLRF_ALPHA_CUTOFF_REFERENCE
 NORMAL_DECODE_REFERENCE, NORMAL_DECODE_UNIT = 1, 2  # PLRF_NORMAL_DECODE_REFERENCE, PLRF_NORMAL_DECODE_UNIT
+ANISOTROPY_REFERENCE = 8  # PLRF_ANISOTROPY_REFERENCE
 
 
 class PlrfSceneTexture(C.Structure):
@@ -428,6 +429,12 @@ class FramePipeline:
         self._check(self.lib.plrf_set_scene_normal_maps(self.handle, None if t is None else C.cast(t, C.c_void_p), None if b is None else C.cast(b, C.c_void_p),
                                                         C.c_uint32(max(tn, bn) if t is not None or b is not None else getattr(self, "_scene_mesh_count", 0)), n.ctypes.data_as(C.POINTER(C.c_uint32)) if n.size else None, C.c_uint32(n.size),
                                                         C.c_uint32(int(decode))))
+
+    def set_scene_anisotropy(self, max_anisotropy):
+        """anisotropic filtering of every texture sample of the depth prepass: 0 or 1 off, 2 .. 16 on (ANISOTROPY_REFERENCE = 8: the reference's sampler), from the
+        next recorded frame; needs neither a scene nor textures and survives every other scene call, set_resolution and update_settings"""
+        self.lib.plrf_set_scene_anisotropy.argtypes = [C.c_void_p, C.c_uint32]
+        self._check(self.lib.plrf_set_scene_anisotropy(self.handle, C.c_uint32(int(max_anisotropy))))
 
     def prepass_raster_stats(self):
         """(triangles submitted, triangles clipped, sub-triangles drawn, rejects) of the last frame's execution; waits for the GPU"""

@@ -1,6 +1,6 @@
 """What the depth prepass costs as a compute pass ("depthPrepassRaster.comp", plrf_set_scene_meshes) in bench.py's 4K frame.
 
-    python tools/prepass_raster_cost.py [--out FILE] [--frames N] [--instances K] [--textured [--bc] | --alpha | --normal-mapped]
+    python tools/prepass_raster_cost.py [--out FILE] [--frames N] [--instances K] [--textured [--bc] | --alpha | --normal-mapped] [--aniso N] [--floor]
 
 One process, one build. The scene is the instance set of tools/shadow_raster_cost.py: the three meshes of tests/shadow_raster_cases.py (box, uv_sphere, torus:
 1496 triangles) instanced K times (default 202: about 100 k triangles) over the view frustum in front of bench.py's camera, rasterised into the 3840 x 2160
@@ -15,6 +15,11 @@ with full chains of random blocks; the store's bytes are reported; compare its t
 checker in cells of 32 texels, so about half of each draw's fragments are discarded; compare its tile times with --textured of the same build.
 --normal-mapped: the --textured scenes with normal maps (plrf_set_scene_normal_maps): every draw names a 256 x 256 normal texture with a full chain; the tile
 kernel and the shading-normal kernel behind it are reported separately; compare with --textured of the same build.
+--aniso N: on top of any of the textured options, anisotropic filtering with maxAnisotropy N (plrf_set_scene_anisotropy); compare with the same options without it.
+--floor: a third scene beside the two - one large ground quad 1.5 units below the camera, spanned by the camera's right and forward vectors, seen at a grazing
+angle, with the textures of the option at 2 UV units per world unit. The instance scenes' footprints are mostly near-isotropic; this one's are not. With --aniso its
+line is followed by the distribution of N over the covered pixels, from tests/prepass_aniso_reference.py on the same view at 480 x 270 (the ratio of a
+footprint's axes, and with it N, does not depend on the resolution).
 It also reports that a frame WITHOUT scene meshes records the passes and runs the general kernels it did before a scene was ever set.
 The report goes to stdout and to --out.
 """
@@ -93,6 +98,32 @@ def scene_normal_maps(draw_count):
     return (texels.reshape(-1), 256, 256, 0), tangents, [box_bitangents, None, None], [2] * draw_count
 
 
+def floor_scene(cam):
+    """(meshes, draws, mesh_uvs): one quad in the plane 1.5 units below the camera (along -up), 120 units wide and from 5 units behind the camera to 300 ahead,
+    both windings, UV = 2 (distance along right, distance along forward)"""
+    import prepass_raster_cases as pc
+    p, f, u, r = (np.asarray(v, np.float64) for v in (cam.position, cam.forward, cam.up, cam.right))
+    corners = [(-60.0, -5.0), (60.0, -5.0), (60.0, 300.0), (-60.0, 300.0)]
+    positions = np.array([p - 1.5 * u + a * r + b * f for a, b in corners], np.float32)
+    normals = np.tile(u.astype(np.float32), (4, 1))
+    indices = np.array([0, 2, 1, 0, 3, 2, 0, 1, 2, 0, 2, 3], np.uint32)
+    return [(positions, normals, indices)], [(0, pc.IDENTITY)], [np.array(corners, np.float32) * np.float32(2.0)]
+
+
+def probe_count_histogram(matrices, positions, indices, uvs, textures, mip_bias, max_anisotropy):
+    """N over the covered pixels of the floor at 480 x 270, from the tests' reference: {N: share}"""
+    import prepass_aniso_reference as aniso
+    import prepass_raster_cases as pc
+    import prepass_texture_cases as tc
+    import prepass_texture_reference as tref
+    case = pc.make_case(480, 270, matrices, positions, indices, [[0, indices.size, 0, 0]])
+    chains = [(tref.build_chain(t[0], t[1], t[2]), t[1], t[2], tref.full_mip_count(t[1], t[2])) for t in textures]
+    tex = tc.textured(case, uvs, [(0, 1)], chains, mip_bias=mip_bias)[1]
+    N = aniso.base_images(case, tex, None, max_anisotropy, diagnostics=True)["diagnostics"]["albedo"]["N"]
+    values, counts = np.unique(N[N > 0], return_counts=True)
+    return {int(v): float(c) / float(counts.sum()) for v, c in zip(values, counts)}
+
+
 def pass_times(be, fp, cams, first, frames):
     """-> ({pass name: mean us} of the prepass, number of timed entries of the last frame)"""
     be.setPassTiming(True)
@@ -119,8 +150,12 @@ def main():
     ap.add_argument("--bc", action="store_true")
     ap.add_argument("--alpha", action="store_true")
     ap.add_argument("--normal-mapped", action="store_true")
+    ap.add_argument("--aniso", type=int, default=0)
+    ap.add_argument("--floor", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.aniso >= 2 and not (a.textured or a.alpha or a.normal_mapped):
+        ap.error("--aniso needs one of --textured, --alpha, --normal-mapped: it is a property of the texture samples")
     import torch  # noqa: F401  (first: it brings its own HIP runtime)
     import bench
     import prepass_raster_cases as pc
@@ -132,7 +167,7 @@ def main():
     fp = FramePipeline(be, W, H, shadow_map_res=2048)
     _, cams, inputs = bench.build_scene(args, "cuda:0", W, H, None)
     inputs.upload(fp)
-    lines = ["# python tools/prepass_raster_cost.py%s: bench.py's scene at %d x %d, fast kernel set, %d frames per figure" % (" --normal-mapped" if a.normal_mapped else " --alpha" if a.alpha else " --textured --bc" if a.textured and a.bc else " --textured" if a.textured else "", W, H, a.frames)]
+    lines = ["# python tools/prepass_raster_cost.py%s: bench.py's scene at %d x %d, fast kernel set, %d frames per figure" % ((" --normal-mapped" if a.normal_mapped else " --alpha" if a.alpha else " --textured --bc" if a.textured and a.bc else " --textured" if a.textured else "") + (" --aniso %d" % a.aniso if a.aniso else "") + (" --floor" if a.floor else ""), W, H, a.frames)]
     cursor = 1
     for i in range(args.warmup):
         fp.frame(cams[cursor + i], 1.0 / 60.0, 0.5)
@@ -142,20 +177,29 @@ def main():
     cursor += 3
     tiles = ((W + 63) // 64) * ((H + 63) // 64)
     lines.append("%-26s %9s %9s %9s %8s %8s %13s %11s %10s" % ("scene", "submitted", "drawn", "clipped", "rejects", "covered", "busiest tile", "set-up us", "tiles us"))
-    for label, shrink in (("meshes at scale", 1.0), ("meshes shrunk to 1 / 20", 0.05)):
-        raw, draws = shadow_raster_cost.instances(cams[1], a.instances, shrink)
-        meshes = [pc.mesh_arrays(m, k != 0) for k, m in enumerate(raw)]
+    fp.set_scene_anisotropy(a.aniso)
+    for label, shrink in (("meshes at scale", 1.0), ("meshes shrunk to 1 / 20", 0.05)) + ((("floor", None),) if a.floor else ()):
+        floor_uvs = None
+        if shrink is None:
+            meshes, draws, floor_uvs = floor_scene(cams[1])
+        else:
+            raw, draws = shadow_raster_cost.instances(cams[1], a.instances, shrink)
+            meshes = [pc.mesh_arrays(m, k != 0) for k, m in enumerate(raw)]
         scene_draws = [(m, t, *pc.material(d)) for d, (m, t) in enumerate(draws)]
         fp.set_scene_meshes(meshes, scene_draws)
+        on_floor = lambda t: (t[0], floor_uvs, t[2]) if floor_uvs is not None else t  # the floor is one mesh with UVs of its own
         if a.normal_mapped:
-            textures, uvs, materials = scene_textures(len(draws))
+            textures, uvs, materials = on_floor(scene_textures(len(draws)))
             normal_texture, tangents, bitangents, normal_textures = scene_normal_maps(len(draws))
             fp.set_scene_textures(textures + [normal_texture], uvs, materials)
+            if floor_uvs is not None:  # tangent along the camera's right, bitangent along its forward
+                tangents = [np.tile(np.asarray(cams[1].right, np.float32), (4, 1))]
+                bitangents = [np.tile(np.asarray(cams[1].forward, np.float32), (4, 1))]
             fp.set_scene_normal_maps(tangents, bitangents, normal_textures)
         elif a.textured and a.bc:
-            fp.set_scene_textures_formatted(*scene_textures_bc(len(draws)))
+            fp.set_scene_textures_formatted(*on_floor(scene_textures_bc(len(draws))))
         elif a.textured or a.alpha:
-            fp.set_scene_textures(*scene_textures(len(draws), alpha_checker=a.alpha))
+            fp.set_scene_textures(*on_floor(scene_textures(len(draws), alpha_checker=a.alpha)))
         if a.alpha:
             fp.set_scene_alpha_cutoffs([128] * len(draws))
         times, _ = pass_times(be, fp, cams, cursor, a.frames)
@@ -170,6 +214,10 @@ def main():
         if a.normal_mapped:
             lines.append("  shading-normal kernel: %.2f us" % times.get("Depth prepass", float("nan")))
         lines.append("  %d draws; %d of %d tiles touched, %.1f rectangles per tile on average" % (len(draws), touched, tiles, mean_hits))
+        if floor_uvs is not None and a.aniso >= 2 and a.textured and not a.bc:
+            g = np.frombuffer(fp.submitted_globals(), np.float32)
+            shares = probe_count_histogram(matrices, meshes[0][0], meshes[0][2], floor_uvs[0], scene_textures(1)[0], float(g[79]), a.aniso)
+            lines.append("  N over the covered pixels (reference, 480 x 270): " + ", ".join("%d: %.1f %%" % (n, 100.0 * share) for n, share in sorted(shares.items())))
     if a.textured and not a.alpha and not a.normal_mapped:
         chain = sum(max(1, 256 >> l) ** 2 for l in range(9))
         lines.append("texture store: %d bytes" % (sum(t[0].size for t in scene_textures_bc(1)[0]) if a.bc else 2 * chain * 4))
