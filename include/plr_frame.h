@@ -65,12 +65,33 @@ typedef struct plrf_settings {
      * carry a column range and the transfers are rectangles (plrf_exchange_plan_rects). With band_overlap_exchange 1 a tile behaves as with 0 (its producers
      * are never split); 2 produces the FRAME of the tile first (plr.h first_rows + first_cols). */
     uint32_t band_col_begin, band_col_end;
+    /* 1: a partitioned pipeline (band_row_end or band_col_end non-zero) rasterises scene meshes and shadow casters: the eight scene / caster calls below behave
+     * as on an unpartitioned pipeline (same validation, lifetime and removal rules). The depth prepass is recorded with the 44-byte pass record, restricted to this
+     * rank's raster window (plrf_raster_window_for): the tiles of the owned rectangle and of everything a pass of this pipeline reads around it. G-buffer texels
+     * outside the window and its wrap strips (plrf_raster_wrap_strips_for) are never written and never read. Every rank rasterises every shadow cascade in full: the maps are not screen-partitioned (the redundancy
+     * is inherent, like the bloom chain's), and with run_light_matrix their matrices come from the all-reduced depth range, so all ranks draw the same maps.
+     * plrf_get_prepass_raster_stats does not depend on the window. 0 (the default): those calls are refused with PLR_ERR_UNSUPPORTED on a partitioned pipeline and the
+     * G-buffer is uploaded. No effect on an unpartitioned pipeline. Fixed for the pipeline's lifetime, like the other band fields. (It stands with the band fields, in
+     * front of run_sky, which stays the struct's last field.) */
+    uint32_t band_raster;
     /* 1: "skyAndSunSprite.comp" right after the deferred shade (Sky::renderSky, Techniques/Sky.cpp:318-353, as one compute pass over the depth == 0 pixels of
      * the colour buffer: the banding dither, the froxel in-scattering on the sky and the sun disc with limb darkening; geometry pixels are not touched). Off by
      * default. Needs run_shading (plrf_create: PLR_ERR_INVALID_ARGUMENT otherwise), is not recorded while sdf_debug_mode != 0 and is fixed for the pipeline's
      * lifetime like the other run_* flags. */
     uint32_t run_sky;
 } plrf_settings;
+
+/* The raster window of a pipeline with these settings, in 64 x 64 tiles of the frame, half-open: out_tiles = {x0, y0, x1, y1}. It is the owned rectangle grown, on
+ * every side that has a neighbour, by the largest reach with which a pass of the pipeline reads the G-buffer images outside the rectangle (DESIGN.md "Rasterising
+ * in a partition" derives it pass by pass), rounded out to whole tiles and clipped to the frame; the whole grid for an unpartitioned frame and for whole-image halos.
+ * A pure host function: no backend call, valid without a GPU. It does not depend on band_raster. */
+int plrf_raster_window_for(const plrf_settings* settings, uint32_t out_tiles[4]);
+/* The wrap strips of that window: out_tiles receives *out_count (0 .. 3) more tile rectangles, four words each. The temporal GI filter reads last frame's motion with
+ * repeat addressing, so from a window that touches a frame edge without spanning the frame it reaches the tile column / row at the OPPOSITE edge; a partition
+ * rasterises those tiles too, one more execution of the pass per strip. Outside the window and its strips no G-buffer texel is written or read. */
+int plrf_raster_wrap_strips_for(const plrf_settings* settings, uint32_t out_tiles[12], uint32_t* out_count);
+/* the same for a pipeline's current settings: the window its depth prepass is recorded with when band_raster is 1 */
+int plrf_get_raster_window(void* pipeline, uint32_t out_tiles[4]);
 
 /* ---- band rendering: halo exchange hooks ----
  * While plrf_frame launches the passes it calls the exchange callback, in pass order, at the points where rows produced by
@@ -256,7 +277,7 @@ int plrf_apply_changes(void* pipeline); /* apply what was recorded now: a caller
  * plrf_set_shadow_caster_cutouts (below) gives them an alpha test - is DESIGN.md "Sun shadow cascades as a compute pass".
  * plrf_set_shadow_casters copies the meshes (positions and a uint32 triangle list each) and the draws; draw_count 0 removes the casters. PLR_ERR_INVALID_ARGUMENT,
  * with a message that names the cause: a mesh index or a vertex index out of range, an index count that is no multiple of 3, a model matrix whose last row is not
- * exactly (0, 0, 0, 1) (the pass does not divide by w). PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing.
+ * exactly (0, 0, 0, 1) (the pass does not divide by w). PLR_ERR_UNSUPPORTED: a band / tile pipeline without band_raster. A refused call changes nothing.
  * plrf_set_shadow_caster_transforms replaces the draws' model matrices (draw_count x 16 floats) from the next frame on, like setStorageBufferData: queued, applied
  * in call order; a draw_count other than the casters' is PLR_ERR_INVALID_ARGUMENT.
  * plrf_get_shadow_raster_stats: the counters of the last frame's execution for one cascade; waits for the GPU. submitted = triangles of all draws, drawn = back
@@ -279,7 +300,7 @@ int plrf_get_shadow_raster_stats(void* pipeline, uint32_t cascade, plrf_shadow_r
  * texels (R in the low byte) every pixel of the draw stores to albedo and specular.
  * plrf_set_scene_meshes copies everything; draw_count 0 removes the scene and the uploaded G-buffer is used again. PLR_ERR_INVALID_ARGUMENT, with a message that
  * names the cause: a mesh index or a vertex index out of range, an index count that is no multiple of 3, a non-finite matrix element. PLR_ERR_UNSUPPORTED: a
- * band / tile pipeline, for every call, a removal (draw_count 0) included - it could only be a no-op there. A refused call changes nothing.
+ * band / tile pipeline without band_raster, for every call, a removal (draw_count 0) included - it could only be a no-op there. A refused call changes nothing.
  * plrf_set_scene_mesh_transforms replaces the draws' model matrices (draw_count x 16 floats) from the next frame on; a draw_count other than the scene's is
  * PLR_ERR_INVALID_ARGUMENT. A draw's previous model matrix (motion vectors) is the one the last recorded frame used; on the first frame after
  * plrf_set_scene_meshes and after a camera cut it equals the current one.
@@ -304,7 +325,7 @@ int plrf_set_scene_mesh_transforms(void* pipeline, const float* matrices16, uint
  * plrf_set_scene_mesh_transforms, plrf_set_resolution and plrf_update_settings. Visibility, depth, motion, normal and the counters never depend on textures.
  * PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: no scene set, a count mismatch, a texture size of 0 or above 16384, too many mips for the size,
  * NULL texels, a material index that is neither PLRF_NO_TEXTURE nor < texture_count, more than 2^28 texels in total, a non-finite UV. PLR_ERR_UNSUPPORTED: a band /
- * tile pipeline. A refused call changes nothing. */
+ * tile pipeline without band_raster. A refused call changes nothing. */
 #define PLRF_NO_TEXTURE 0xffffffffu
 typedef struct plrf_scene_texture { const uint32_t* texels; uint32_t width, height, mip_count; } plrf_scene_texture;
 typedef struct plrf_scene_material { uint32_t albedo_texture, specular_texture; } plrf_scene_material;
@@ -320,7 +341,7 @@ int plrf_set_scene_textures(void* pipeline, const plrf_scene_texture* textures, 
  * plrf_set_scene_textures': the stores replace one another, texture_count 0 removes, and alpha cutoffs and normal maps set afterwards index this store. A call whose
  * entries are all RGBA8 records exactly the pass plrf_set_scene_textures records. PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: what
  * plrf_set_scene_textures refuses, an unknown format, mip_count 0 on a compressed entry, a bytes mismatch, more than 2^28 words in total (a compressed entry starts
- * at a multiple of 16 bytes). PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing. */
+ * at a multiple of 16 bytes). PLR_ERR_UNSUPPORTED: a band / tile pipeline without band_raster. A refused call changes nothing. */
 typedef struct plrf_scene_texture_data {
     const void* data;
     uint64_t bytes;
@@ -337,7 +358,7 @@ int plrf_set_scene_textures_formatted(void* pipeline, const plrf_scene_texture_d
  * call order. draw_count 0 removes them, and so does every plrf_set_scene_meshes and every plrf_set_scene_textures; they survive
  * plrf_set_scene_mesh_transforms, plrf_set_resolution and plrf_update_settings. While all cutoffs are 0, or none are set, every frame is what it is without this
  * call. PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: no scene set, no textures set, a count mismatch, NULL cutoffs with a non-zero count, a
- * value above 255. PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing. The sun shadow pass has an alpha test of its own, for its own
+ * value above 255. PLR_ERR_UNSUPPORTED: a band / tile pipeline without band_raster. A refused call changes nothing. The sun shadow pass has an alpha test of its own, for its own
  * meshes: plrf_set_shadow_caster_cutouts below. */
 #define PLRF_ALPHA_CUTOFF_REFERENCE 128u
 int plrf_set_scene_alpha_cutoffs(void* pipeline, const uint32_t* cutoffs, uint32_t draw_count);
@@ -358,7 +379,7 @@ int plrf_set_scene_alpha_cutoffs(void* pipeline, const uint32_t* cutoffs, uint32
  * plrf_set_scene_mesh_transforms, plrf_set_scene_alpha_cutoffs, plrf_set_resolution and plrf_update_settings. PLR_ERR_INVALID_ARGUMENT, with a message that names
  * the cause: no scene set, no textures set, a count mismatch, NULL normal_textures with a non-zero count, an index that is neither PLRF_NO_TEXTURE nor <
  * texture_count, a non-finite tangent or bitangent (vertex and mesh are named), a decode other than 1 or 2, NULL bitangents with non-NULL tangents for a mesh
- * given without normals. PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing. */
+ * given without normals. PLR_ERR_UNSUPPORTED: a band / tile pipeline without band_raster. A refused call changes nothing. */
 #define PLRF_NORMAL_DECODE_REFERENCE 1u
 #define PLRF_NORMAL_DECODE_UNIT 2u
 int plrf_set_scene_normal_maps(void* pipeline, const float* const* mesh_tangents, const float* const* mesh_bitangents, uint32_t mesh_count,
@@ -372,7 +393,7 @@ int plrf_set_scene_normal_maps(void* pipeline, const float* const* mesh_tangents
  * sampler), from the next recorded frame, in call order. One scalar of pipeline state: it needs neither a scene nor textures (while the scene has none the pass
  * record is what it was) and survives plrf_set_scene_meshes, plrf_set_scene_textures, plrf_set_scene_textures_formatted, plrf_set_scene_alpha_cutoffs,
  * plrf_set_scene_normal_maps, plrf_set_scene_mesh_transforms, plrf_set_resolution and plrf_update_settings. The sun shadow raster's cutout sampling stays
- * isotropic. PLR_ERR_INVALID_ARGUMENT, with a message that names the value: a value above 16. PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call
+ * isotropic. PLR_ERR_INVALID_ARGUMENT, with a message that names the value: a value above 16. PLR_ERR_UNSUPPORTED: a band / tile pipeline without band_raster. A refused call
  * changes nothing. */
 #define PLRF_ANISOTROPY_REFERENCE 8u
 int plrf_set_scene_anisotropy(void* pipeline, uint32_t max_anisotropy);
@@ -389,7 +410,7 @@ int plrf_set_scene_anisotropy(void* pipeline, uint32_t max_anisotropy);
  * plrf_set_shadow_caster_transforms, plrf_set_resolution and plrf_update_settings. While none are set, or all cutoffs are 0, every frame is what it is without
  * this call. PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: no casters set, a count mismatch, a texture size of 0 or above 16384, too many mips
  * for the size, NULL texels, a texture index that is neither PLRF_NO_TEXTURE nor < texture_count, a cutoff above 255, more than 2^28 texels in total, a non-finite
- * UV. PLR_ERR_UNSUPPORTED: a band / tile pipeline. A refused call changes nothing. */
+ * UV. PLR_ERR_UNSUPPORTED: a band / tile pipeline without band_raster. A refused call changes nothing. */
 typedef struct plrf_shadow_cutout { uint32_t albedo_texture, alpha_cutoff; } plrf_shadow_cutout; /* PLRF_NO_TEXTURE; 0 .. 255, 0 = opaque */
 int plrf_set_shadow_caster_cutouts(void* pipeline, const plrf_scene_texture* textures, uint32_t texture_count,
                                    const float* const* mesh_uvs, uint32_t mesh_count,

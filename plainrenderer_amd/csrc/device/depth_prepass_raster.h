@@ -23,6 +23,11 @@ struct AlphaPushConstants { uint32_t drawCount, triangleCount, textureCount, alp
 struct NormalPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest, normalMap; }; // the optional fifth word: 0, or absent, is the pass without normal maps
 struct FormatPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest, normalMap, textureFormats; }; // the optional sixth word: 0, or absent, is the pass whose textures are all RGBA8
 struct AnisoPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest, normalMap, textureFormats, maxAnisotropy; }; // the optional seventh word: 0, 1, or absent, is the pass with isotropic trilinear filtering
+// the optional words 7 - 10 (a 44-byte record, words 0 - 6 as above and 0 where a feature is off): the tile window {x0, y0, x1, y1}, half-open, in 64 x 64 tiles of the
+// bound images. The execution is the unwindowed one restricted to the pixels of those tiles; the four counters do not depend on it
+struct WindowPushConstants { uint32_t drawCount, triangleCount, textureCount, alphaTest, normalMap, textureFormats, maxAnisotropy, windowTileX0, windowTileY0, windowTileX1, windowTileY1; };
+static_assert(sizeof(WindowPushConstants) == 44, "the windowed pass record");
+constexpr bool pushSizeDefined(size_t bytes) { return bytes == 8u || bytes == 12u || bytes == 16u || bytes == 20u || bytes == 24u || bytes == 28u || bytes == 44u; }
 // anisotropic filtering ("Anisotropic filtering in the depth prepass"): maxAnisotropy 2 .. kMaxAnisotropy selects the anisotropic instantiations; the reference's
 // sampler has 8 (ResourceDescriptions.h:169, VulkanSampler.cpp:23)
 constexpr uint32_t kMaxAnisotropy = 16, kAnisotropyReference = 8;
@@ -74,9 +79,9 @@ constexpr float kGuardNdc = 32.f;                        // the four side planes
 // scratch: header, one {draw, triangle within the draw} per submitted triangle (the resolve finds a winner's vertices through it), then one 4-byte tile
 // rectangle and one set-up record per sub-triangle slot, 6 slots per triangle: nothing can overflow
 struct alignas(8) ScratchHeader {
-    uint32_t cursor;     // sub-triangles appended = entries of the two arrays } one 64-bit word for the set-up kernel's atomic
-    uint32_t submitted;  // triangles the draws hold                            }
-    uint32_t drawn;      // = cursor, copied by the tile kernel
+    uint32_t cursor;     // records appended = entries of the two arrays: the drawn sub-triangles whose tile rectangle meets the window } one 64-bit word for the set-up
+    uint32_t submitted;  // triangles the draws hold                                                                               } kernel's atomic
+    uint32_t drawn;      // sub-triangles with a non-empty box, counted by the set-up kernel (= cursor without a window)
     uint32_t rejects;    // triangles outside their buffers or with a non-finite clip component, and sub-triangles with a vertex w <= 0 or outside the 2^20-pixel band
     uint32_t clipped;    // triangles the clip changed
     uint32_t pad[11];

@@ -38,6 +38,7 @@ int plrf_default_settings(plrf_settings* o, uint32_t width, uint32_t height) {
     o->sdf_debug_use_influence_radius = d.sdfDebug.useInfluenceRadiusForDebug;
     o->run_sky = d.runSky;
     o->taa_use_separate_supersampling = d.taa.useSeparateSupersampling; o->taa_supersample_use_tonemapping = d.taa.supersampleUseTonemapping;
+    o->band_raster = d.band.raster ? 1u : 0u;
     // the denoiser's disc is 1.5 m in WORLD space: its reach in rows grows with the frame height, and so does the halo that keeps the band deviation
     // where it is at 2160 rows (measured at 8K in four bands, tests/test_config5_8k.py: 64 rows 98.6 %, 128 rows 99.3 %, 192 rows 99.4 % of a band's
     // pixels within one code of the unpartitioned frame)
@@ -67,6 +68,7 @@ static FramePipelineSettings toPipelineSettings(const plrf_settings* s) {
     f.sdfDebug.useInfluenceRadiusForDebug = s->sdf_debug_use_influence_radius;
     f.runSky = s->run_sky != 0;
     f.taa.useSeparateSupersampling = s->taa_use_separate_supersampling; f.taa.supersampleUseTonemapping = s->taa_supersample_use_tonemapping;
+    f.band.raster = s->band_raster != 0;
     return f;
 }
 
@@ -185,6 +187,19 @@ int plrf_get_prepass_raster_stats(void* p, plrf_prepass_raster_stats* out) {
         const PrepassRasterStats s = ((FramePipeline*)p)->prepassRasterStats();
         out->triangles_submitted = s.trianglesSubmitted; out->triangles_clipped = s.trianglesClipped; out->subtriangles_drawn = s.subtrianglesDrawn; out->rejects = s.rejects;
     })
+}
+
+int plrf_raster_window_for(const plrf_settings* s, uint32_t out[4]) {
+    if (!s || !out) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY(rasterWindowTiles(toPipelineSettings(s), out))
+}
+int plrf_raster_wrap_strips_for(const plrf_settings* s, uint32_t out[12], uint32_t* outCount) {
+    if (!s || !out || !outCount) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY(*outCount = rasterWrapStrips(toPipelineSettings(s), out))
+}
+int plrf_get_raster_window(void* p, uint32_t out[4]) {
+    if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY(((FramePipeline*)p)->rasterWindow(out))
 }
 
 int plrf_destroy(void* p) { delete (FramePipeline*)p; return PLR_OK; }

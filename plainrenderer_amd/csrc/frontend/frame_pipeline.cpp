@@ -1240,6 +1240,74 @@ void FramePipeline::computeSunLightMatrices() { // RenderFrontend.cpp:840-872
     m_be.setComputePassExecution(exe);
 }
 
+// the scene and caster calls on a partitioned pipeline: refused unless it was created with band.raster
+static bool partitionedWithoutRaster(const FramePipelineSettings& s) { return (s.band.enabled() || s.band.tiled()) && !s.band.raster; }
+
+// THE RASTER WINDOW (DESIGN.md "Rasterising in a partition"). Which full-resolution texels of the G-buffer images - the current frame's depth, motion, normal,
+// albedo, specular and shadingNormal, last frame's depth and motion - does a recorder of this file read outside the owned rectangle? Per recorder, in pixels:
+//   computeDepthPyramid / computeDepthApexOfTiles: workgroups of 64 x 64 pixels over scaleRows(bandRows(0), 64): inside the rectangle rounded out to 64 - reach 0
+//     after the rounding below
+//   downscaleDepth: half-resolution texels bandRows(depthHalo, 2) with depthHalo = 2 (giHalo + giHistoryHalo) + 16, each from a 2 x 2 footprint; the range's end is
+//     rounded up to a whole half-resolution texel: depthHalo + 1
+//   SDFGI: the camera-tile culling reads the pyramid only; the trace, both spatial filters (normal at the centre texel; depth from depthHalfRes, or with a
+//     full-resolution trace from depth at the disc samples the valid rows admit: giHalo + 1 with the pRight / pUp taps) and the request passes run over
+//     bandRows(0, div) and read the full-resolution images at the 2 x 2 footprint of their own texel: 1; a requested texel arrives with its depthHalfRes texel.
+//     The temporal GI filter reads last frame's motion bilinearly at uv + motion, which is unbounded; but the value read decides something only where the
+//     pixel's own motion is at most 3 pixels on both axes - above that threshold the filter takes alpha = alphaMin whatever last frame's motion is, and a
+//     reprojection off the frame takes alpha = 0 (gi_filters.hip temporalGiFilterKernel, pixelThreshold; the fast set's kernel in stream_fast.hip has the same
+//     rule). So: the trace texel's own 2 x 2 footprint, 3 pixels of motion, one texel of the bilinear footprint: 3 + 2. A change of that threshold changes this
+//     term (kTemporalGiMotionThresholdPixels below)
+//   the upscale, computeDeferredShading, computeSkyAndSunSprite: their own pixel over bandRows(colorHalo): colorHalo
+//   TAA::computeTemporalFilter: over bandRows(0), the 3 x 3 neighbourhood of depth and motion (the motion vector dilation): 1; the window keeps that 1 on top of
+//     colorHalo, so that a temporal filter recorded over the shaded rows stays inside it: colorHalo + 1
+//   bloom, tonemap, histogram: no G-buffer image
+// The window is the rectangle grown by the largest of these on every side that has a neighbour, rounded out to 64 and clipped to the frame. A whole-image halo
+// (giHalo clamped to max(width, height)) makes it the whole frame.
+// THE WRAP STRIPS. One read does not fit a rectangle: the temporal GI filter samples last frame's motion with REPEAT addressing (sic, the reference's
+// linearRepeat), so a reprojection within half a texel of a frame edge reads the texel column (row) at the OPPOSITE edge (found by the bounded-halo test of
+// tests/test_band_raster.py: a handful of pixels next to the frame's edge differed, and only with the far edge's motion poisoned). A window that touches a frame
+// edge without spanning the frame in that direction therefore gets a strip: the opposite edge's tile column over the window's tile rows, the opposite edge's
+// tile row over its tile columns, and the tile in the opposite corner where both hold. renderDepthPrepass records one more execution per strip.
+void rasterWindowTiles(const FramePipelineSettings& s, uint32_t outTiles[4]) {
+    const uint64_t W = s.width, H = s.height, T = bandAlignment;
+    const uint64_t gridX = (W + T - 1) / T, gridY = (H + T - 1) / T;
+    outTiles[0] = outTiles[1] = 0u; outTiles[2] = (uint32_t)gridX; outTiles[3] = (uint32_t)gridY;
+    const BandSettings& b = s.band;
+    if (!b.enabled()) return;
+    const uint64_t cap = std::max(W, H); // the constructor's clamps
+    const uint64_t giHalo = b.giRequested || b.giHalo == 0xfffffffeu ? 0u : std::min<uint64_t>(b.giHalo, cap), giHistoryHalo = std::min<uint64_t>(b.giHistoryHalo, cap);
+    uint64_t reach = 1u;                                                   // the trace's and the filters' own texel, the temporal filter's 3 x 3
+    reach = std::max(reach, 2u * (giHalo + giHistoryHalo) + 16u + 1u);      // downscaleDepth
+    reach = std::max(reach, giHalo + 1u);                                  // the spatial filters of a full-resolution trace
+    const uint64_t kTemporalGiMotionThresholdPixels = 3u;                  // pixelThreshold of the temporal GI filter kernels
+    reach = std::max(reach, kTemporalGiMotionThresholdPixels + 2u);        // the temporal GI filter: last frame's motion, where its value matters
+    reach = std::max(reach, (uint64_t)b.colorHalo + 1u);                   // upscale, shade, sky; the motion dilation on top
+    auto grow = [&](uint64_t begin, uint64_t end, uint64_t size, uint64_t grid, uint32_t* t0, uint32_t* t1) {
+        const uint64_t lo = begin > 0u ? (begin > reach ? begin - reach : 0u) : 0u;
+        const uint64_t hi = end < size ? std::min(end + reach, size) : size;
+        *t0 = (uint32_t)(lo / T);
+        *t1 = (uint32_t)std::min((hi + T - 1) / T, grid);
+    };
+    grow(b.rowBegin, std::min<uint64_t>(b.rowEnd, H), H, gridY, &outTiles[1], &outTiles[3]);
+    if (b.tiled()) grow(b.colBegin, std::min<uint64_t>(b.colEnd, W), W, gridX, &outTiles[0], &outTiles[2]);
+}
+
+uint32_t rasterWrapStrips(const FramePipelineSettings& s, uint32_t outTiles[12]) {
+    uint32_t w[4];
+    rasterWindowTiles(s, w);
+    const uint32_t gridX = (s.width + bandAlignment - 1) / bandAlignment, gridY = (s.height + bandAlignment - 1) / bandAlignment;
+    // the far tile column / row a wrapped read lands in: none where the window spans the frame in that direction (it holds both edges) or touches no edge
+    const bool spansX = w[0] == 0 && w[2] == gridX, spansY = w[1] == 0 && w[3] == gridY;
+    const int farX = spansX ? -1 : w[0] == 0 ? (int)gridX - 1 : w[2] == gridX ? 0 : -1;
+    const int farY = spansY ? -1 : w[1] == 0 ? (int)gridY - 1 : w[3] == gridY ? 0 : -1;
+    uint32_t n = 0;
+    auto add = [&](uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) { outTiles[4 * n] = x0; outTiles[4 * n + 1] = y0; outTiles[4 * n + 2] = x1; outTiles[4 * n + 3] = y1; n++; };
+    if (farX >= 0) add((uint32_t)farX, w[1], (uint32_t)farX + 1, w[3]);
+    if (farY >= 0) add(w[0], (uint32_t)farY, w[2], (uint32_t)farY + 1);
+    if (farX >= 0 && farY >= 0) add((uint32_t)farX, (uint32_t)farY, (uint32_t)farX + 1, (uint32_t)farY + 1);
+    return n;
+}
+
 // ---- RenderFrontend::renderSunShadowCascades (RenderFrontend.cpp:760-774, pass :1565-1590) as one compute execution per cascade ("sunShadowRaster.comp",
 // kernels/sun_shadow_raster.hip). The reference's coarse CPU frustum culling of the draws (:611-646) is not rebuilt: the set-up kernel rejects per triangle.
 void FramePipeline::renderSunShadowCascades() {
@@ -1289,7 +1357,7 @@ static void refuseUnlessAffine(const float* m, uint32_t draw, const char* call) 
 }
 
 void FramePipeline::setShadowCasters(const ShadowCasterMesh* meshes, uint32_t meshCount, const ShadowCasterDraw* draws, uint32_t drawCount) {
-    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+    if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setShadowCasters: a band / tile pipeline cannot rasterise shadow casters (every partition would draw every cascade)");
     if (drawCount == 0) {
         m_casterDrawCount = m_casterTriangleCount = m_casterTextureCount = 0;
@@ -1357,7 +1425,7 @@ void FramePipeline::setShadowCasters(const ShadowCasterMesh* meshes, uint32_t me
 }
 
 void FramePipeline::setShadowCasterCutouts(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts, uint32_t drawCount) {
-    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+    if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setShadowCasterCutouts: a band / tile pipeline cannot rasterise shadow casters");
     if (textureCount == 0) { m_casterTextureCount = 0; m_casterAlphaTested = false; return; }
     const PackedShadowCutouts packed = packShadowCasterCutouts(textures, textureCount, meshUvs, meshCount, cutouts, drawCount, m_casterMeshVertexCounts.data(),
@@ -1427,6 +1495,21 @@ void FramePipeline::renderDepthPrepass(const FrameRenderTargets& current) {
             exe.genericInfo.resources.storageImages.push_back(ImageResource(m_shadingNormalImage, 0, pp::kShadingNormalBinding));
         }
     }
+    if (settings.band.enabled()) { // (only with band.raster: a scene cannot be set otherwise) the 44-byte record: words 0 - 6 as above, then this rank's raster window
+        uint32_t w[4];
+        rasterWindowTiles(settings, w);
+        pp::WindowPushConstants wpc{pc.drawCount, pc.triangleCount, pc.textureCount, pc.alphaTest, pc.normalMap, pc.textureFormats, pc.maxAnisotropy, w[0], w[1], w[2], w[3]};
+        exe.pushConstants = dataToCharArray(&wpc, sizeof(wpc));
+        // the wrap strips (rasterWrapStrips): the same record with another window, in front of the main execution - the counters each leaves are the same
+        uint32_t strips[12];
+        const uint32_t stripCount = rasterWrapStrips(settings, strips);
+        for (uint32_t k = 0; k < stripCount; k++) {
+            ComputePassExecution strip = exe;
+            wpc.windowTileX0 = strips[4 * k]; wpc.windowTileY0 = strips[4 * k + 1]; wpc.windowTileX1 = strips[4 * k + 2]; wpc.windowTileY1 = strips[4 * k + 3];
+            strip.pushConstants = dataToCharArray(&wpc, sizeof(wpc));
+            m_be.setComputePassExecution(strip);
+        }
+    }
     m_be.setComputePassExecution(exe);
     m_sceneRecorded = true;
 }
@@ -1450,7 +1533,7 @@ void FramePipeline::updateMainPassMatrices() {
 }
 
 void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const SceneDraw* draws, uint32_t drawCount) {
-    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+    if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneMeshes: a band / tile pipeline cannot rasterise scene meshes (a partition would have to rasterise only its own rectangle)");
     if (drawCount == 0) {
         m_sceneDrawCount = m_sceneTriangleCount = m_sceneTextureCount = 0;
@@ -1487,7 +1570,7 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
 }
 
 void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {
-    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+    if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneTextures: a band / tile pipeline cannot rasterise scene meshes");
     if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = m_sceneTexturesCompressed = false; m_sceneNormalDecode = 0; return; }
     const PackedTextures packed = packSceneTextures(textures, textureCount, meshUvs, meshCount, materials, drawCount, m_sceneMeshVertexCounts.data(),
@@ -1504,7 +1587,7 @@ void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t text
 }
 
 void FramePipeline::setSceneTexturesFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {
-    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+    if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneTexturesFormatted: a band / tile pipeline cannot rasterise scene meshes");
     if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = m_sceneTexturesCompressed = false; m_sceneNormalDecode = 0; return; }
     const PackedFormattedTextures packed = packSceneTexturesFormatted(textures, textureCount, meshUvs, meshCount, materials, drawCount, m_sceneMeshVertexCounts.data(),
@@ -1523,7 +1606,7 @@ void FramePipeline::setSceneTexturesFormatted(const SceneTextureData* textures, 
 
 void FramePipeline::setSceneNormalMaps(const float* const* meshTangents, const float* const* meshBitangents, uint32_t meshCount, const uint32_t* normalTextures, uint32_t drawCount,
                                        uint32_t decode) {
-    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+    if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneNormalMaps: a band / tile pipeline cannot rasterise scene meshes");
     if (drawCount == 0) { m_sceneNormalDecode = 0; return; }
     SceneNormalMapContext scene;
@@ -1541,7 +1624,7 @@ void FramePipeline::setSceneNormalMaps(const float* const* meshTangents, const f
 }
 
 void FramePipeline::setSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawCount) {
-    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+    if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneAlphaCutoffs: a band / tile pipeline cannot rasterise scene meshes");
     if (drawCount == 0) { m_sceneAlphaTested = false; return; }
     const PackedAlphaCutoffs packed = packSceneAlphaCutoffs(cutoffs, drawCount, m_sceneDrawCount, m_sceneTextureCount); // validates everything before anything is changed
@@ -1550,7 +1633,7 @@ void FramePipeline::setSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawC
 }
 
 void FramePipeline::setSceneAnisotropy(uint32_t maxAnisotropy) {
-    if (m_requestedSettings.band.enabled() || m_requestedSettings.band.tiled())
+    if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneAnisotropy: a band / tile pipeline cannot rasterise scene meshes");
     if (maxAnisotropy > plr::prepass::kMaxAnisotropy)
         throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setSceneAnisotropy: max anisotropy " + std::to_string(maxAnisotropy) + " is above 16 (0 or 1: off, 2 .. 16: on)");
@@ -1986,7 +2069,7 @@ static const char* fixedFieldChanged(const FramePipelineSettings& a, const Frame
     const BandSettings &x = a.band, &y = b.band;
     if (x.rowBegin != y.rowBegin || x.rowEnd != y.rowEnd || x.colBegin != y.colBegin || x.colEnd != y.colEnd || x.giHalo != y.giHalo || x.giRequested != y.giRequested ||
         x.giHistoryHalo != y.giHistoryHalo || x.colorHalo != y.colorHalo || x.postHalo != y.postHalo || x.taaHistoryHalo != y.taaHistoryHalo ||
-        x.overlapExchange != y.overlapExchange || x.rowsFirst != y.rowsFirst)
+        x.overlapExchange != y.overlapExchange || x.rowsFirst != y.rowsFirst || x.raster != y.raster)
         return "band_*";
     return nullptr;
 }

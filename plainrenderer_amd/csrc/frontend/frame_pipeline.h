@@ -89,9 +89,20 @@ struct BandSettings {
     // (plr.h first_rows) instead of an edge and an interior execution; false = the split recording of round 3
     bool rowsFirst = true;
     bool enabled() const { return rowEnd > rowBegin; }
+    // a partitioned pipeline rasterises scene meshes and shadow casters (plr_frame.h band_raster): the depth prepass in this rank's raster window
+    // (rasterWindowTiles), every shadow cascade in full on every rank. Off: the scene and caster calls are refused on a partitioned pipeline
+    bool raster = false;
     // default giHalo for a frame of `height` rows: 64 trace rows per 2160 rows of frame height (plrf_default_settings)
     static uint32_t giHaloForHeight(uint32_t height) { return 64u * ((height + 2159u) / 2160u); }
 };
+struct FramePipelineSettings;
+// The raster window of a pipeline with settings `s` (as given to the constructor, or its current ones), in 64 x 64 tiles, half-open {x0, y0, x1, y1}: the owned
+// rectangle grown, per side with a neighbour, by the largest reach with which a recorder of the pipeline reads the G-buffer images outside the rectangle (derived
+// pass by pass at the definition and in DESIGN.md "Rasterising in a partition"), rounded out to tiles and clipped to the frame. No backend call.
+void rasterWindowTiles(const FramePipelineSettings& s, uint32_t outTiles[4]);
+// the wrap strips of that window (at most 3, four words each as above; returns their number): the tiles at the opposite frame edge that the temporal GI filter's
+// repeat-addressed read of last frame's motion reaches from a window that touches a frame edge
+uint32_t rasterWrapStrips(const FramePipelineSettings& s, uint32_t outTiles[12]);
 // phase bits or-ed into the exchange id a callback receives (0: start the exchange and wait for it)
 enum ExchangePhase : int { ExchangeBegin = 0x100, ExchangeEnd = 0x200, ExchangeIdMask = 0xff };
 // ExchangeDepthApex (only with runLightMatrix): all-reduce of the band's depth range, min on .r / max on .g of a 1 x 1 RG32F image (depthApexImage())
@@ -475,6 +486,7 @@ public:
     void setSceneAnisotropy(uint32_t maxAnisotropy);
     // counters of the last frame's execution for the scene now set; waits for the GPU. Zero while no scene is set and before the first frame of a newly set scene.
     PrepassRasterStats prepassRasterStats();
+    void rasterWindow(uint32_t outTiles[4]) const { rasterWindowTiles(settings, outTiles); }
     // RenderFrontend::setResolution (RenderFrontend.cpp:408-421): recorded, applied at the start of the next frame() (prepareNewFrame, :199-222). Every image and
     // buffer whose size follows the screen is re-created zero-filled, as the constructor creates it, and the next frame is a camera cut; a resize to the size the
     // images already have (back from minimized) keeps them and only cuts. Width or height 0: minimized, frame() renders nothing and advances nothing.

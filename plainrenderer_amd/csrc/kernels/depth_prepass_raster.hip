@@ -157,6 +157,14 @@
 // N or 2 N steps - a step is one (probe, level) pair, so one copy of the taps serves both levels and L1's steps do not exist where fw == 0 - to each lane's own
 // count, and divides by a truncated fp32 quotient that is exact for T >> 24 < 2^12 and N <= 16.
 //
+// THE TILE WINDOW (DESIGN.md "Rasterising in a partition"; tests/test_prepass_window.py). A push of 44 bytes - words 0 - 6 as above, 0 where a feature is off, then
+// {windowTileX0, windowTileY0, windowTileX1, windowTileY1}, half-open, in 64 x 64 tiles of the bound images - restricts the execution to the pixels of those tiles:
+// every texel of the five images (and of shadingNormal) inside the window gets exactly the bits of the unwindowed execution - snapping, coverage, keys, attributes
+// and samples are computed in full-frame coordinates -, no kernel stores to a texel outside it, and the four counters do not depend on it. Every shorter record is
+// the whole grid. Refused: an empty or inverted window, one that reaches past the tile grid, a push size that is none of 8, 12, 16, 20, 24, 28, 44. The tile
+// kernel's grid is the window's tiles (a block's tile is blockIdx + the window's origin), the shading-normal kernel's the window's columns and rows; set-up counts
+// every sub-triangle with a non-empty box as drawn but appends a record only where its tile rectangle meets the window.
+//
 // Two kernels. SET-UP: a lane per triangle finds its draw (block-wide prefix sum, LDS bisection), transforms, clips (the polygon lives in LDS, a column per lane),
 // projects, snaps, culls and boxes; the block's sub-triangles are appended through one 64-bit atomic per block to a dense array of 4-byte tile rectangles and an
 // array of records that carry t. TILES: a 256-thread block per 64 x 64 tile keeps the tile's 64-bit keys in LDS (32 KB); each wave reads 256 rectangles per step
@@ -193,7 +201,12 @@ struct SetupParams {
     ScratchHeader* header; TriangleOrigin* origins; uint32_t* rects; Record* records;
     uint32_t drawCount, triangleCount, capacity, transformCount, vertexCount, indexCount;
     int32_t width, height;
+    uint32_t window; // the tile window in a tile rectangle's form: first tile x | first tile y << 8 | last tile x << 16 | last tile y << 24 (the whole grid without a window)
 };
+// do two tile rectangles (inclusive, four bytes) share a tile?
+PLR_DI bool rectanglesMeet(uint32_t a, uint32_t b) {
+    return (a & 255u) <= ((b >> 16) & 255u) && (b & 255u) <= ((a >> 16) & 255u) && ((a >> 8) & 255u) <= (b >> 24) && ((b >> 8) & 255u) <= (a >> 24);
+}
 
 PLR_DI float planeDistance(int plane, float x, float y, float z, float w) {
     switch (plane) {
@@ -306,19 +319,25 @@ __global__ __launch_bounds__(256) void depthPrepassSetupKernel(SetupParams p) {
             }
         }
     }
-    // pass 1: which sub-triangles survive
-    uint32_t surviveMask = 0;
+    // pass 1: which sub-triangles survive (they count as drawn), and which of those get a record: the ones whose tile rectangle meets the window
+    uint32_t surviveMask = 0, drawnMine = 0;
     for (int k = 0; k + 2 < n; k++) {
-        const int what = setupSubTriangle(polyA, k, tid, p.width, p.height, nullptr, nullptr);
+        SetupRecord unused;
+        uint32_t rect = 0;
+        const int what = setupSubTriangle(polyA, k, tid, p.width, p.height, &unused, &rect);
         if (what == 1) rejects++;
-        if (what == 2) surviveMask |= 1u << k;
+        if (what == 2) {
+            drawnMine++;
+            if (rectanglesMeet(rect, p.window)) surviveMask |= 1u << k;
+        }
     }
     const uint32_t mine = (uint32_t)__popc(surviveMask);
     // one 64-bit atomic per block hands it a run of slots (the low word is the cursor) and counts its triangles (the high word); a lane appends 0 .. 6
     // records, so the block's prefix sum is over counts (the shadow pass appends one survivor per lane by ballot; neither form serves the other)
+    // the drawn count rides in the prefix sum's high half: a wave appends at most 384 records and draws at most 384 sub-triangles, a block four times as many
     __shared__ uint32_t waveSurvivors[4], blockFound, blockRejects, blockClipped, blockBase;
     if (threadIdx.x == 0) blockFound = blockRejects = blockClipped = 0u;
-    uint32_t incl = mine;
+    uint32_t incl = mine | (drawnMine << 16);
     for (int off = 1; off < 64; off <<= 1) {
         const uint32_t up = (uint32_t)__shfl_up((int)incl, off);
         if ((int)lane >= off) incl += up;
@@ -330,15 +349,17 @@ __global__ __launch_bounds__(256) void depthPrepassSetupKernel(SetupParams p) {
     if (rejects) atomicAdd(&blockRejects, rejects);
     __syncthreads();
     if (threadIdx.x == 0) {
-        const uint32_t survivors = waveSurvivors[0] + waveSurvivors[1] + waveSurvivors[2] + waveSurvivors[3];
+        const uint32_t both = waveSurvivors[0] + waveSurvivors[1] + waveSurvivors[2] + waveSurvivors[3];
+        const uint32_t survivors = both & 0xffffu, blockDrawn = both >> 16;
         const unsigned long long old = atomicAdd((unsigned long long*)&p.header->cursor, (unsigned long long)survivors | ((unsigned long long)blockFound << 32));
         blockBase = (uint32_t)old;
         if (blockRejects) atomicAdd(&p.header->rejects, blockRejects);
         if (blockClipped) atomicAdd(&p.header->clipped, blockClipped);
+        if (blockDrawn) atomicAdd(&p.header->drawn, blockDrawn); // (not the cursor: a window drops records, the counter does not depend on it)
     }
     __syncthreads();
-    uint32_t slot = blockBase + incl - mine;
-    for (uint32_t w = 0; w < wave; w++) slot += waveSurvivors[w];
+    uint32_t slot = blockBase + (incl & 0xffffu) - mine;
+    for (uint32_t w = 0; w < wave; w++) slot += waveSurvivors[w] & 0xffffu;
     // pass 2: the records
     for (int k = 0; k + 2 < n; k++) {
         if (!((surviveMask >> k) & 1u)) continue;
@@ -386,6 +407,7 @@ struct TileParams {
     float* depth; uint32_t* motion; uint32_t* normal; uint32_t* albedo; uint32_t* specular;
     uint32_t capacity, triangleCount;
     int32_t width, height;
+    int32_t windowTileX0, windowTileY0; // the window's first tile: the grid is the window's tiles (0, 0 without a window)
     TextureInputs tex; // a textured execution only (behind everything else: the untextured kernel's argument offsets stay)
     const uint32_t* alphaCutoffs; // an alpha-tested execution only: tex.drawCount words
 };
@@ -947,7 +969,7 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(typename TileParam
     static_assert(kTextured || !kNormalMap, "the shading normal is a texture sample");
     __shared__ Key tile[kTileSize * kTileSize];
     __shared__ uint32_t hitQueue[4][256]; // per wave: the entries of the current step that touch the tile
-    const int tx = (int)blockIdx.x, ty = (int)blockIdx.y;
+    const int tx = (int)blockIdx.x + p.windowTileX0, ty = (int)blockIdx.y + p.windowTileY0;
     const int ox = tx * kTileSize, oy = ty * kTileSize;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint32_t i = threadIdx.x; i < (uint32_t)(kTileSize * kTileSize); i += 256u) tile[i] = 0ull;
@@ -972,7 +994,6 @@ __global__ __launch_bounds__(256) void depthPrepassTileKernel(typename TileParam
     __syncthreads();
     const Params& q = *(kAlphaTest ? &sharedParams : &p);
     const uint32_t n = min(q.header->cursor, q.capacity);
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) q.header->drawn = n;
     const rastercov::TileWindow window{tx, ty, ox, oy, min(ox + kTileSize - 1, q.width - 1), min(oy + kTileSize - 1, q.height - 1)};
     if constexpr (kAlphaTest) {
         AlphaWalk<Tex> walk{AlphaScan<Tex>{candidates[wave], alphaRecords[wave], &sharedTex, 0.f, 0, 0, tile, ox, oy, lane, 0u}, &q, &sharedAlpha, kAlphaCutoffOpaque, kAlphaCutoffOpaque};
@@ -1010,6 +1031,7 @@ struct ShadingNormalParams {
     uint64_t tangentVertexCount, bitangentVertexCount;
     uint32_t triangleCount, normalMaterialCount, decode;
     int32_t width, height;
+    int32_t windowX0, windowY0; // the window's first pixel: the grid covers the window's rows and columns (0, 0 without a window)
     TextureInputs tex;
 };
 
@@ -1079,7 +1101,7 @@ template <> struct ShadingNormalParamsOf<true, true> { typedef AnisoShadingNorma
 template <bool kFormats = false, bool kAniso = false>
 __global__ __launch_bounds__(256) void depthPrepassShadingNormalKernel(typename ShadingNormalParamsOf<kFormats, kAniso>::type p) {
     static_assert(kFormats || !kAniso, "the anisotropic instantiation exists in the format-aware form only");
-    const int x = (int)(blockIdx.x * 64u + (threadIdx.x & 63u)), y = (int)(blockIdx.y * 4u + (threadIdx.x >> 6));
+    const int x = p.windowX0 + (int)(blockIdx.x * 64u + (threadIdx.x & 63u)), y = p.windowY0 + (int)(blockIdx.y * 4u + (threadIdx.x >> 6));
     if (y >= p.height) return; // (wave-uniform)
     const bool inside = x < p.width;
     const size_t at = (size_t)y * (size_t)p.width + (size_t)(inside ? x : 0);
@@ -1117,8 +1139,11 @@ __global__ __launch_bounds__(256) void depthPrepassShadingNormalKernel(typename 
 
 static int launchDepthPrepassRaster(const PassCtx& c) {
     if (c.push.size() < sizeof(PushConstants)) return c.fail(-1, "depthPrepassRaster: push constants {drawCount, triangleCount} missing");
-    AnisoPushConstants pc{};
-    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0; 12: alphaTest 0; 16: normalMap 0; 20: textureFormats 0; 24: maxAnisotropy 0
+    if (!pushSizeDefined(c.push.size()))
+        return c.fail(-1, "depthPrepassRaster: the push constants are " + std::to_string(c.push.size()) + " bytes, the record has 8, 12, 16, 20, 24, 28 or 44 (words 0 - 6, or all of them and the tile window)");
+    WindowPushConstants pc{};
+    std::memcpy(&pc, c.push.data(), c.push.size()); // 8 bytes: {drawCount, triangleCount}, textureCount 0; 12: alphaTest 0; 16: normalMap 0; 20: textureFormats 0; 24: maxAnisotropy 0; 28: no window
+    const bool windowed = c.push.size() == sizeof(WindowPushConstants);
     const bool aniso = pc.maxAnisotropy >= 2u; // 0 and 1: the isotropic pass, word for word
     if (c.dispatch[0] != 1u || c.dispatch[1] != 1u || c.dispatch[2] != 1u || c.base[0] != 0u || c.base[1] != 0u)
         return c.fail(-1, "depthPrepassRaster: the dispatch is {1, 1, 1} (the launcher derives its grids from the push constants and the images)");
@@ -1199,6 +1224,18 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
             if (c.sbuf[b].ptr == c.sbuf[kScratchBinding].ptr)
                 return c.fail(-4, "depthPrepassRaster: the scratch buffer is also bound as an input (binding " + std::to_string(b) + ", a normal map input)");
     }
+    // the tile window: the whole grid without one (every shorter record), and then today's grids
+    const uint32_t gridX = divUp((unsigned)depth.w, (unsigned)kTileSize), gridY = divUp((unsigned)depth.h, (unsigned)kTileSize);
+    uint32_t wx0 = 0u, wy0 = 0u, wx1 = gridX, wy1 = gridY;
+    if (windowed) {
+        const std::string given = "{" + std::to_string(pc.windowTileX0) + ", " + std::to_string(pc.windowTileY0) + ", " + std::to_string(pc.windowTileX1) + ", " + std::to_string(pc.windowTileY1) + "}";
+        if (pc.windowTileX0 >= pc.windowTileX1 || pc.windowTileY0 >= pc.windowTileY1)
+            return c.fail(-1, "depthPrepassRaster: the tile window " + given + " is empty or inverted (it is half-open: x0 < x1 and y0 < y1)");
+        if (pc.windowTileX1 > gridX || pc.windowTileY1 > gridY)
+            return c.fail(-1, "depthPrepassRaster: the tile window " + given + " reaches past the tile grid of the bound images, " + std::to_string(gridX) + " x " + std::to_string(gridY) +
+                                  " tiles of 64 x 64 (" + std::to_string(depth.w) + " x " + std::to_string(depth.h) + " pixels)");
+        wx0 = pc.windowTileX0; wy0 = pc.windowTileY0; wx1 = pc.windowTileX1; wy1 = pc.windowTileY1;
+    }
 
     uint8_t* scratch = (uint8_t*)c.sbuf[kScratchBinding].ptr;
     if (hipMemsetAsync(scratch, 0, sizeof(ScratchHeader), c.stream) != hipSuccess) return c.fail(-2, "depthPrepassRaster: clearing the scratch header failed");
@@ -1214,6 +1251,7 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
         s.vertexCount = (uint32_t)std::min<size_t>(std::min(c.sbuf[kPositionBinding].size, c.sbuf[kNormalBinding].size) / 12u, 0xffffffffu);
         s.indexCount = (uint32_t)std::min<size_t>(c.sbuf[kIndexBinding].size / 4u, 0xffffffffu);
         s.width = depth.w; s.height = depth.h;
+        s.window = wx0 | (wy0 << 8) | ((wx1 - 1u) << 16) | ((wy1 - 1u) << 24); // (the grid is at most 256 x 256 tiles)
         depthPrepassSetupKernel<<<divUp(pc.triangleCount, 256u), 256, 0, c.stream>>>(s);
         PLR_CHECK_LAUNCH(c);
         c.splitTiming("set-up");
@@ -1227,7 +1265,8 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
     t.depth = (float*)depth.ptr; t.motion = (uint32_t*)c.storage[kMotionBinding].ptr; t.normal = (uint32_t*)c.storage[kNormalImageBinding].ptr;
     t.albedo = (uint32_t*)c.storage[kAlbedoBinding].ptr; t.specular = (uint32_t*)c.storage[kSpecularBinding].ptr;
     t.capacity = capacity; t.triangleCount = pc.triangleCount; t.width = depth.w; t.height = depth.h;
-    const dim3 tiles(divUp((unsigned)depth.w, (unsigned)kTileSize), divUp((unsigned)depth.h, (unsigned)kTileSize));
+    t.windowTileX0 = (int32_t)wx0; t.windowTileY0 = (int32_t)wy0;
+    const dim3 tiles(wx1 - wx0, wy1 - wy0);
     if (pc.textureCount) {
         t.tex.uvs = (const float*)c.sbuf[kUvBinding].ptr; t.tex.materials = (const Material*)c.sbuf[kMaterialBinding].ptr;
         t.tex.textures = (const Texture*)c.sbuf[kTextureBinding].ptr; t.tex.texels = (const uint32_t*)c.sbuf[kTexelBinding].ptr;
@@ -1266,7 +1305,9 @@ static int launchDepthPrepassRaster(const PassCtx& c) {
             s.triangleCount = pc.triangleCount; s.normalMaterialCount = (uint32_t)std::min<size_t>(c.sbuf[kNormalMaterialBinding].size / 4u, 0xffffffffu);
             s.decode = pc.normalMap; s.width = depth.w; s.height = depth.h; s.tex = t.tex;
             s.formats = formats; s.maxAnisotropy = pc.maxAnisotropy;
-            const dim3 rows(divUp((unsigned)depth.w, 64u), divUp((unsigned)depth.h, 4u));
+            s.windowX0 = (int32_t)(wx0 * (uint32_t)kTileSize); s.windowY0 = (int32_t)(wy0 * (uint32_t)kTileSize);
+            // the window's columns and rows (the kernel drops what lies past the image's last row and column)
+            const dim3 rows(wx1 - wx0, divUp(std::min((unsigned)depth.h, wy1 * (unsigned)kTileSize) - wy0 * (unsigned)kTileSize, 4u));
             if (aniso) depthPrepassShadingNormalKernel<true, true><<<rows, 256, 0, c.stream>>>(s);
             else if (formats) depthPrepassShadingNormalKernel<true><<<rows, 256, 0, c.stream>>>(static_cast<const FormatShadingNormalParams&>(s));
             else depthPrepassShadingNormalKernel<false><<<rows, 256, 0, c.stream>>>(static_cast<const ShadingNormalParams&>(s));

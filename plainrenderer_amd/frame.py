@@ -26,7 +26,7 @@ class PlrfSettings(C.Structure):
                                                                               ("sdf_debug_mode", C.c_uint32), ("sdf_debug_tile_usage_with_hiz", C.c_uint32),
                                                                               ("sdf_debug_use_influence_radius", C.c_uint32), ("band_taa_history_halo", C.c_uint32), ("run_volumetrics", C.c_uint32),
                                                                               ("run_sky_luts", C.c_uint32), ("band_overlap_exchange", C.c_uint32), ("band_col_begin", C.c_uint32),
-                                                                              ("band_col_end", C.c_uint32), ("run_sky", C.c_uint32)]
+                                                                              ("band_col_end", C.c_uint32), ("band_raster", C.c_uint32), ("run_sky", C.c_uint32)]
 
 
 class PlrfExchangeItem(C.Structure):
@@ -441,6 +441,12 @@ class FramePipeline:
         s = PlrfPrepassRasterStats()
         self._check(self.lib.plrf_get_prepass_raster_stats(self.handle, C.byref(s)))
         return int(s.triangles_submitted), int(s.triangles_clipped), int(s.subtriangles_drawn), int(s.rejects)
+
+    def raster_window(self):
+        """(x0, y0, x1, y1), half-open, in 64 x 64 tiles: the window the depth prepass of a partitioned pipeline with band_raster = 1 is restricted to"""
+        out = (C.c_uint32 * 4)()
+        self._check(self.lib.plrf_get_raster_window(self.handle, out))
+        return tuple(int(v) for v in out)
 
     def frame(self, cam: Camera, delta_time=1.0 / 60.0, time=0.0):
         c = PlrfCamera()

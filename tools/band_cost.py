@@ -2,10 +2,12 @@
 config 5: 2 x 2) - are timed one after the other, each with the halo it recomputes and the NATIVE exchange (csrc/frontend/band_exchange.cpp) over its in-process
 transport: all ranks render the warm-up frames together (every exchange moves what a multi-GPU run moves), then the group is frozen and each rank is timed alone
 with its neighbours' last frame in its halos (measure_all). Their times are summed and compared with the time of the unpartitioned frame.
-    python tools/band_cost.py [N] [--tiles GXxGY] [--passes] [--balance] [--requested | --exact] [--loopback]
+    python tools/band_cost.py [N] [--tiles GXxGY] [--passes] [--balance] [--requested | --exact] [--loopback] [--scene]
 default N = 4: the 8K frame; --tiles 2x2: config 5's partition (GX * GY = N); --balance: rectangle sizes from measured times, as bench.py does;
 --requested: band_gi_halo = PLRF_HALO_REQUESTED (request lists: byte-identical to the unpartitioned frame), --exact: PLRF_HALO_WHOLE_IMAGE, default: the bounded halo;
---loopback: the replay of rounds 3 - 5 (every partition on its own with the exchange in loopback: a tile's halos are its own texels, a band's halos nothing)"""
+--loopback: the replay of rounds 3 - 5 (every partition on its own with the exchange in loopback: a tile's halos are its own texels, a band's halos nothing);
+--scene: every pipeline gets the cost scene of tools/prepass_raster_cost.py (202 instances of the three test meshes, about 100 k triangles) as scene meshes, the
+partitions with band_raster = 1: each rasterises its raster window only"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -26,6 +28,7 @@ kind = "tiles %dx%d" % (gx, gy) if gx > 1 else "%d bands" % n
 
 
 MODE = {"halo": None, "exact": 0xffffffff, "requested": 0xfffffffe}[os.environ.get("PLR_BAND_COST_MODE", "requested" if "--requested" in sys.argv else ("exact" if "--exact" in sys.argv else "halo"))]
+SCENE = "--scene" in sys.argv
 LOOPBACK = "--loopback" in sys.argv  # the old replay: every partition on its own, the exchange in loopback (a tile's halos are its own texels, a band's halos nothing)
 
 
@@ -44,6 +47,8 @@ def make_pipeline(rects, index, group=None):
         kw.update(band_gi_halo=int(os.environ["PLR_BAND_COST_GI_HALO"]))
     if index is not None and "PLR_BAND_COST_OVERLAP" in os.environ:  # experiment hook: band_overlap_exchange (plr_frame.h; 2 = edges first in one launch, the default)
         kw.update(band_overlap_exchange=int(os.environ["PLR_BAND_COST_OVERLAP"]))
+    if index is not None and SCENE:
+        kw.update(band_raster=1)
     fp = FramePipeline(be, w, h, shadow_map_res=2048, **kw)
     if index is not None:
         if group is not None:
@@ -54,6 +59,14 @@ def make_pipeline(rects, index, group=None):
     whole_inputs = MODE is not None or "PLR_BAND_COST_GI_HALO" in os.environ
     scene, cams, inputs = bench.build_scene(args, "cuda:0", w, h, None if whole_inputs else band)
     inputs.upload(fp)
+    if SCENE:
+        sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"), os.path.dirname(os.path.abspath(__file__))]
+        import prepass_raster_cases as pc
+        import shadow_raster_cost
+        raw, draws = shadow_raster_cost.instances(cams[1], 202, 1.0)
+        fp.set_scene_meshes([pc.mesh_arrays(m, k != 0) for k, m in enumerate(raw)], [(m, t, *pc.material(d)) for d, (m, t) in enumerate(draws)])
+        if index is not None:
+            print("    partition %d: raster window %r (tiles)" % (index, fp.raster_window()))
     be.waitForGPUIdle()
     return be, fp, cams
 

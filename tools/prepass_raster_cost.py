@@ -1,6 +1,7 @@
 """What the depth prepass costs as a compute pass ("depthPrepassRaster.comp", plrf_set_scene_meshes) in bench.py's 4K frame.
 
     python tools/prepass_raster_cost.py [--out FILE] [--frames N] [--instances K] [--textured [--bc] | --alpha | --normal-mapped] [--aniso N] [--floor]
+                                        [--window tx0,ty0,tx1,ty1]
 
 One process, one build. The scene is the instance set of tools/shadow_raster_cost.py: the three meshes of tests/shadow_raster_cases.py (box, uv_sphere, torus:
 1496 triangles) instanced K times (default 202: about 100 k triangles) over the view frustum in front of bench.py's camera, rasterised into the 3840 x 2160
@@ -20,6 +21,13 @@ kernel and the shading-normal kernel behind it are reported separately; compare 
 angle, with the textures of the option at 2 UV units per world unit. The instance scenes' footprints are mostly near-isotropic; this one's are not. With --aniso its
 line is followed by the distribution of N over the covered pixels, from tests/prepass_aniso_reference.py on the same view at 480 x 270 (the ratio of a
 footprint's axes, and with it N, does not depend on the resolution).
+--window tx0,ty0,tx1,ty1: the pass restricted to that tile window (half-open, 64 x 64 tiles; the 4K frame is 60 x 34). The pipeline is then a partition with
+band_raster = 1 and halos of 0 whose owned rectangle is the window less one tile on every side that has a neighbour - the rectangle whose raster window
+(plrf_get_raster_window) is the one asked for; no exchange is attached: the other passes' halos are stale, the prepass does not read them. A window that touches
+a frame edge without spanning the frame also runs its wrap strips (plrf_raster_wrap_strips_for): up to three more executions of the pass per frame. The times
+reported are then the SUM over the frame's executions, and a further line gives the main window's execution and the strips' apart. The counters stay the whole
+frame's, `covered` counts the window's pixels only. With the tool's halos of 0 the reach is 17 pixels: 0,0,31,18 is the window of a 4K quadrant (three strips),
+0,8,60,18 that of the second of four bands (none).
 It also reports that a frame WITHOUT scene meshes records the passes and runs the general kernels it did before a scene was ever set.
 The report goes to stdout and to --out.
 """
@@ -124,10 +132,11 @@ def probe_count_histogram(matrices, positions, indices, uvs, textures, mip_bias,
     return {int(v): float(c) / float(counts.sum()) for v, c in zip(values, counts)}
 
 
-def pass_times(be, fp, cams, first, frames):
-    """-> ({pass name: mean us} of the prepass, number of timed entries of the last frame)"""
+def pass_times(be, fp, cams, first, frames, parts=None):
+    """-> ({pass name: mean us per frame} of the prepass, summed over a frame's executions of the pass - a partition runs one per wrap strip and one for its
+    window -, number of timed entries of the last frame). parts (a dict): {pass name: [mean us of the frame's k-th execution]}, in recording order"""
     be.setPassTiming(True)
-    acc, entries = {}, 0
+    acc, entries, each = {}, 0, {}
     for i in range(frames + 1):
         fp.frame(cams[first + i], 1.0 / 60.0, 0.5)
         be.waitForGPUIdle()
@@ -135,10 +144,17 @@ def pass_times(be, fp, cams, first, frames):
             continue
         timings = be.getRenderpassTimings()
         entries = len(timings)
+        frame = {}
         for name, ms in timings:
             if name.startswith("Depth prepass"):
-                acc.setdefault(name, []).append(ms * 1e3)
+                frame.setdefault(name, []).append(ms * 1e3)
+        for name, values in frame.items():
+            acc.setdefault(name, []).append(sum(values))
+            for k, v in enumerate(values):
+                each.setdefault(name, {}).setdefault(k, []).append(v)
     be.setPassTiming(False)
+    if parts is not None:
+        parts.update({name: [float(np.mean(v)) for _, v in sorted(by_k.items())] for name, by_k in each.items()})
     return {k: float(np.mean(v)) for k, v in acc.items()}, entries
 
 
@@ -152,8 +168,22 @@ def main():
     ap.add_argument("--normal-mapped", action="store_true")
     ap.add_argument("--aniso", type=int, default=0)
     ap.add_argument("--floor", action="store_true")
+    ap.add_argument("--window")
     ap.add_argument("--out")
     a = ap.parse_args()
+    partition, window = {}, None
+    if a.window:
+        window = tuple(int(v) for v in a.window.split(","))
+        gx, gy = (W + 63) // 64, (H + 63) // 64
+        if len(window) != 4 or not (0 <= window[0] < window[2] <= gx and 0 <= window[1] < window[3] <= gy):
+            ap.error("--window tx0,ty0,tx1,ty1 must be a non-empty half-open tile rectangle inside the %d x %d grid" % (gx, gy))
+        x0, x1 = (0 if window[0] == 0 else (window[0] + 1) * 64), (W if window[2] == gx else (window[2] - 1) * 64)
+        y0, y1 = (0 if window[1] == 0 else (window[1] + 1) * 64), (H if window[3] == gy else (window[3] - 1) * 64)
+        if x0 >= x1 or y0 >= y1:
+            ap.error("--window: too narrow for a partition (the window is the owned rectangle and one more tile per side with a neighbour)")
+        partition = dict(band_row_begin=y0, band_row_end=y1, band_raster=1, band_gi_halo=0, band_gi_history_halo=0, band_color_halo=0)
+        if (x0, x1) != (0, W):
+            partition.update(band_col_begin=x0, band_col_end=x1)
     if a.aniso >= 2 and not (a.textured or a.alpha or a.normal_mapped):
         ap.error("--aniso needs one of --textured, --alpha, --normal-mapped: it is a property of the texture samples")
     import torch  # noqa: F401  (first: it brings its own HIP runtime)
@@ -164,10 +194,14 @@ def main():
     from plainrenderer_amd.frame import FramePipeline
     args = argparse.Namespace(steps=a.frames * 6 + 20, warmup=5, profile_frames=0, grid=16, sdf_res=64, shadow_res=2048, scene="default")
     be = RenderBackend(W, H, device=0)
-    fp = FramePipeline(be, W, H, shadow_map_res=2048)
+    fp = FramePipeline(be, W, H, shadow_map_res=2048, **partition)
+    if window is not None and fp.raster_window() != window:
+        raise SystemExit("the partition's raster window is %r, not %r" % (fp.raster_window(), window))
+    if window is not None:
+        be.setPassFusion(1)  # a partition without an attached exchange: keep every intermediate image in memory
     _, cams, inputs = bench.build_scene(args, "cuda:0", W, H, None)
     inputs.upload(fp)
-    lines = ["# python tools/prepass_raster_cost.py%s: bench.py's scene at %d x %d, fast kernel set, %d frames per figure" % ((" --normal-mapped" if a.normal_mapped else " --alpha" if a.alpha else " --textured --bc" if a.textured and a.bc else " --textured" if a.textured else "") + (" --aniso %d" % a.aniso if a.aniso else "") + (" --floor" if a.floor else ""), W, H, a.frames)]
+    lines = ["# python tools/prepass_raster_cost.py%s: bench.py's scene at %d x %d, fast kernel set, %d frames per figure" % ((" --normal-mapped" if a.normal_mapped else " --alpha" if a.alpha else " --textured --bc" if a.textured and a.bc else " --textured" if a.textured else "") + (" --aniso %d" % a.aniso if a.aniso else "") + (" --floor" if a.floor else "") + (" --window " + a.window if a.window else ""), W, H, a.frames)]
     cursor = 1
     for i in range(args.warmup):
         fp.frame(cams[cursor + i], 1.0 / 60.0, 0.5)
@@ -202,7 +236,8 @@ def main():
             fp.set_scene_textures(*on_floor(scene_textures(len(draws), alpha_checker=a.alpha)))
         if a.alpha:
             fp.set_scene_alpha_cutoffs([128] * len(draws))
-        times, _ = pass_times(be, fp, cams, cursor, a.frames)
+        parts = {}
+        times, _ = pass_times(be, fp, cams, cursor, a.frames, parts)
         cursor += a.frames + 1
         submitted, clipped, drawn, rejects = fp.prepass_raster_stats()
         matrices = be.downloadStorageBuffer(fp.storage_buffer("mainPassMatrices"), 192 * len(draws), dtype=np.float32).reshape(-1, 48)
@@ -213,6 +248,9 @@ def main():
                                                                  times.get("Depth prepass (tiles)", times.get("Depth prepass", float("nan")))))
         if a.normal_mapped:
             lines.append("  shading-normal kernel: %.2f us" % times.get("Depth prepass", float("nan")))
+        if parts and max(len(v) for v in parts.values()) > 1:  # in recording order: the wrap strips, then the window
+            lines.append("  per execution (wrap strips first, the window last): " + "; ".join("%s %s us" % (n.replace("Depth prepass", "").strip(" ()") or "last kernel", " + ".join("%.2f" % v for v in vs))
+                                                                                                for n, vs in sorted(parts.items())))
         lines.append("  %d draws; %d of %d tiles touched, %.1f rectangles per tile on average" % (len(draws), touched, tiles, mean_hits))
         if floor_uvs is not None and a.aniso >= 2 and a.textured and not a.bc:
             g = np.frombuffer(fp.submitted_globals(), np.float32)
@@ -221,6 +259,8 @@ def main():
     if a.textured and not a.alpha and not a.normal_mapped:
         chain = sum(max(1, 256 >> l) ** 2 for l in range(9))
         lines.append("texture store: %d bytes" % (sum(t[0].size for t in scene_textures_bc(1)[0]) if a.bc else 2 * chain * 4))
+    if window is not None:
+        lines.append("tile window %r: %d of %d tiles" % (window, (window[2] - window[0]) * (window[3] - window[1]), tiles))
     general_with = be.getGeneralKernelExecutions()
     fp.set_scene_meshes([], [])
     _, entries_after = pass_times(be, fp, cams, cursor, 2)
