@@ -357,6 +357,14 @@ int plr_debug_sky_lut_eval(plr_image_handle sky_lut, const float* directions, fl
  * 256 x 12 x 2 floats = unit-disc offsets (cos(angle) d, sin(angle) d) of noise byte k, tap i at [(k * 12 + i) * 2]). The oracle's orc_kat_pcf_taps
  * evaluates the shader's expressions for the same 3072 entries; the two must agree bit for bit. */
 int plr_debug_pcf_tap_table(float* out_xy, size_t floats);
+/* the fused upscale + deferred shade (kernels_fast/shading_fast.hip upscaleAndShadeKernel): a wave without a geometry pixel writes its sky colours without
+ * resolving the GI upscale, where the upscaled texels are neither stored (pass fusion level 2) nor signed. No byte of any output changes; on unless the environment
+ * says PLR_SHADE_SKY_EXIT=0 (read per launch).
+ * plr_debug_shade_sky_exit_switch: *out_on = the switch as the next launch would read it (needs no GPU).
+ * plr_debug_shade_sky_exit_waves: *out_waves (may be null) = waves that took the exit since the counter was last armed (0 if it is not), then enable != 0 zeroes
+ *   and arms the counter, 0 frees it. Costs the kernel nothing while disarmed. */
+int plr_debug_shade_sky_exit_switch(uint32_t* out_on);
+int plr_debug_shade_sky_exit_waves(int enable, uint64_t* out_waves);
 /* sampler probe: evaluates one of the global samplers of resources/shaders/global.inc:35-42 on an image, with the device sampler code the pass
  * kernels are built from. filter: 0 nearest, 1 linear, 2 textureGather (component 0); address: 0 clamp-to-edge, 1 repeat, 2 border white,
  * 3 border black. coords: n x 2 (2D) or n x 3 (3D image) normalised coordinates, out: n x 4 floats; both host memory.

@@ -225,9 +225,17 @@ EXPORTED_SYMBOLS = [
     "plr_get_last_frame_cpu_time", "plr_get_image_description", "plr_set_pass_timing", "plr_get_last_frame_gpu_time",
     "plr_replay_frame", "plr_upload_image", "plr_download_image", "plr_download_storage_buffer", "plr_download_uniform_buffer",
     "plr_get_image_device_pointer", "plr_get_storage_buffer_device_pointer", "plr_get_stream", "plr_get_launch_stream", "plr_copy_device_memory", "plr_read_device_memory", "plr_write_device_memory", "plr_get_supported_shaders",
-    "plr_debug_math_eval", "plr_debug_codec_eval", "plr_debug_sampler_eval", "plr_debug_sky_lut_eval", "plr_debug_verify_histogram_thresholds", "plr_debug_verify_r11g11b10_fast", "plr_debug_set_decision_signature", "plr_debug_read_decision_signature", "plr_set_math_mode", "plr_get_math_mode", "plr_set_stream_overlap", "plr_get_stream_overlap", "plr_set_pass_fusion", "plr_get_pass_fusion", "plr_set_pass_fusion_reorder", "plr_get_general_kernel_executions", "plr_get_edge_signal", "plr_set_async_tail", "plr_get_async_tail", "plr_set_early_parts", "plr_get_early_parts", "plr_set_host_callback_execution", "plr_set_host_callback_execution_on", "plr_upload_image_rows",
+    "plr_debug_math_eval", "plr_debug_codec_eval", "plr_debug_sampler_eval", "plr_debug_sky_lut_eval", "plr_debug_verify_histogram_thresholds", "plr_debug_verify_r11g11b10_fast", "plr_debug_shade_sky_exit_switch", "plr_debug_shade_sky_exit_waves", "plr_debug_set_decision_signature", "plr_debug_read_decision_signature", "plr_set_math_mode", "plr_get_math_mode", "plr_set_stream_overlap", "plr_get_stream_overlap", "plr_set_pass_fusion", "plr_get_pass_fusion", "plr_set_pass_fusion_reorder", "plr_get_general_kernel_executions", "plr_get_edge_signal", "plr_set_async_tail", "plr_get_async_tail", "plr_set_early_parts", "plr_get_early_parts", "plr_set_host_callback_execution", "plr_set_host_callback_execution_on", "plr_upload_image_rows",
     "plr_copy_device_memory_2d", "plr_set_global_descriptor_set_layout",
 ]
+
+
+def shade_sky_exit_switch():
+    """-> the fused shade's sky exit as its next launch would read it from the environment (include/plr.h: on unless PLR_SHADE_SKY_EXIT=0); needs no GPU"""
+    on = C.c_uint32()
+    if _load().plr_debug_shade_sky_exit_switch(C.byref(on)) != 0:
+        raise PlrError("plr_debug_shade_sky_exit_switch failed")
+    return bool(on.value)
 
 
 class RenderBackend:
@@ -530,6 +538,12 @@ class RenderBackend:
         out = (C.c_uint64 * 4)()
         self._check(self.lib.plr_debug_verify_r11g11b10_fast(out))
         return tuple(int(v) for v in out)
+
+    def debugShadeSkyExitWaves(self, enable):
+        """-> waves of the fused shade that took the sky exit since the counter was last armed; then arms (and zeroes) or frees the counter"""
+        n = C.c_uint64()
+        self._check(self.lib.plr_debug_shade_sky_exit_waves(C.c_int(int(bool(enable))), C.byref(n)))
+        return n.value
 
     def setPassFusion(self, level):
         """0 / False: off; 1 / True: on, every intermediate image written; 2 (the default): on, and a fused launch may keep an intermediate that

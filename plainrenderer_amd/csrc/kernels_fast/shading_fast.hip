@@ -197,6 +197,11 @@ struct ShadeParams {
     const uint32_t* lutEnergyNonFinite; // one word next to the footprint (null with it): non-zero if a .y half of the LUT is Inf / NaN
     // skip what the sun cannot light (shadeDirect, "unlit pixels"): set by the launcher unless decision signatures are written or PLR_SHADE_SKIP_UNLIT=0
     uint32_t skipUnlit;
+    // upscaleAndShadeKernel only (0 in every other launch), set by its launcher: a wave without a geometry pixel writes its sky colours without resolving the GI
+    // upscale - only when the upscaled texels are neither stored nor signed; PLR_SHADE_SKY_EXIT=0: off. Same bytes either way (DESIGN.md section 3,
+    // tests/test_shade_sky_exit.py; measured: profiles/r08_shade_sky_srgb.txt)
+    uint32_t skyExit;
+    uint32_t* skyExitWaves; // debug counter of the waves that took the exit (plr_debug_shade_sky_exit_waves) or null
 };
 PLR_DI float uniformValue(float x) { return u2f((uint32_t)__builtin_amdgcn_readfirstlane((int)f2u(x))); } // the first active lane's value, in a scalar register
 PLR_DI bool finiteBits(float x) { return (f2u(x) & 0x7f800000u) != 0x7f800000u; } // integer test: on a uniform value it stays on the scalar unit
@@ -670,6 +675,13 @@ __global__ __launch_bounds__(256, PLR_SHADE_WAVES) void upscaleAndShadeKernel(Sh
     const ViewRay vr = exactViewRay(g, cpx, cpy);
     __syncthreads();
     if (!covered) return;
+    // ---- a wave of sky: a sky pixel's colour is the sky LUT's, and its upscaled texel goes nowhere when it is neither stored nor signed (P.skyExit, uniform, says so).
+    // One ballot over the depths the upscale is about to wait for anyway; a wave with a geometry lane goes on as before
+    if (P.skyExit && __builtin_amdgcn_ballot_w64(in.depth != 0.f) == 0ull) {
+        ((uint32_t*)P.color.ptr)[idx] = packR11G11B10(fastm::sampleSkyLut(-vr.Vn, P.skyLut));
+        if (P.skyExitWaves && __builtin_amdgcn_readfirstlane(t) == t) atomicAdd(P.skyExitWaves, 1u);
+        return;
+    }
     // ---- the pixel's upscaled GI texel: upscaleQuad's statements for pixel (parity p, q) of quad (k, m) (upscale_quad.h)
     uint32_t upSig;
     {
@@ -1150,17 +1162,27 @@ static int earlyShadeDirect(const PassCtx* const* ctxs, size_t count, EarlyPart&
     return 0;
 }
 
+static bool skyExitSwitchOn() { // on unless the environment says PLR_SHADE_SKY_EXIT=0
+    const char* v = std::getenv("PLR_SHADE_SKY_EXIT");
+    return !(v && v[0] == '0' && v[1] == 0);
+}
+static uint32_t* g_skyExitWaves = nullptr; // plr_debug_shade_sky_exit_waves
+
 static int launchUpscaleAndShade(const PassCtx* const* ctxs, size_t count) {
     FusedShade f;
     DirectRecords R{};
     const bool late = count == 2 && ctxs[0]->earlyPartDone; // the backend launched earlyShadeDirect for this pair in this frame: the combine is what is left
     if (int rc = fusedShadeSetup(ctxs, count, &f, true, late ? &R : nullptr)) return rc;
     const PassCtx &u = *ctxs[0], &c = *ctxs[1];
-    const ShadeParams& P = f.P;
+    ShadeParams& P = f.P;
     FusedUpscale& U = f.U;
     if (P.coverH <= P.yBase || P.coverW <= P.xBase) return 0;
     U.storeUpscaled = (u.elidableStorage & 3u) == 3u ? 0 : 1;
     if (!U.storeUpscaled) u.elidedStorage = 3u;
+    // the single launch's sky exit (ShadeParams::skyExit): the upscaled texels of sky pixels must be read by nobody - not stored (fusion level 2), not signed.
+    // PLR_SHADE_SKY_EXIT=0 (read per launch, as PLR_SHADE_SKIP_UNLIT: tests switch it) turns it off
+    P.skyExit = (!U.storeUpscaled && !P.sig && skyExitSwitchOn()) ? 1u : 0u;
+    P.skyExitWaves = g_skyExitWaves;
     const dim3 grid(divUp((unsigned)(P.coverW - P.xBase), 64u), divUp((unsigned)(P.coverH - P.yBase), 4u));
     if (late) {
         switch (f.multi) {
@@ -1295,3 +1317,31 @@ PLR_REGISTER_EARLY_PART(fastshade_upscale_and_shade, fastshade_early_direct, "di
 static int fastshade_brdf_lut(const PassCtx& c) { return fastshade::launchBrdfLutFast(c); }
 PLR_REGISTER_SHADER_FAST("brdfLut.comp", fastshade_brdf_lut);
 } // namespace plr
+
+// ---- debug exports of the fused shade's sky exit (include/plr.h)
+extern "C" int plr_debug_shade_sky_exit_switch(uint32_t* out_on) {
+    using namespace plr;
+    if (!out_on) return setLastError(-1, "plr_debug_shade_sky_exit_switch: null argument");
+    *out_on = fastshade::skyExitSwitchOn() ? 1u : 0u;
+    return 0;
+}
+extern "C" int plr_debug_shade_sky_exit_waves(int enable, uint64_t* out_waves) {
+    using namespace plr;
+    uint32_t count = 0;
+    if (fastshade::g_skyExitWaves) {
+        if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&count, fastshade::g_skyExitWaves, 4, hipMemcpyDeviceToHost) != hipSuccess)
+            return setLastError(-2, "plr_debug_shade_sky_exit_waves: cannot read the counter");
+    }
+    if (out_waves) *out_waves = count;
+    if (enable) {
+        if (!fastshade::g_skyExitWaves && hipMalloc((void**)&fastshade::g_skyExitWaves, 4) != hipSuccess) {
+            fastshade::g_skyExitWaves = nullptr;
+            return setLastError(-2, "plr_debug_shade_sky_exit_waves: hipMalloc failed");
+        }
+        if (hipMemset(fastshade::g_skyExitWaves, 0, 4) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return setLastError(-2, "plr_debug_shade_sky_exit_waves: cannot zero the counter");
+    } else if (fastshade::g_skyExitWaves) {
+        hipFree(fastshade::g_skyExitWaves);
+        fastshade::g_skyExitWaves = nullptr;
+    }
+    return 0;
+}
