@@ -246,7 +246,9 @@ int plrf_get_uniform_buffer(void* pipeline, const char* name, plr_uniform_buffer
 int plrf_add_sdf_volume(void* pipeline, uint32_t res, const void* half_data, size_t bytes, uint32_t* out_texture_index);
 /* the same from a DDS file written by the asset pipeline (plr_write_dds_file / the reference's writeDDSFile): any width x height x depth */
 int plrf_add_sdf_volume_dds(void* pipeline, const char* path, uint32_t* out_texture_index, uint32_t out_size[3]);
-/* {uint count; uint pad[3]; SDFInstance[count]} and {vec3 min; float; vec3 max; float}[count] (SDFGI::updateSDFScene) */
+/* {uint count; uint pad[3]; SDFInstance[count]} and {vec3 min; float; vec3 max; float}[count] (SDFGI::updateSDFScene). While a scene SDF is set
+ * (plrf_set_scene_sdf below) the pipeline writes both buffers itself every frame: the call then returns PLR_ERR_UNSUPPORTED and changes nothing. After the scene
+ * SDF was removed the instance count is 0 until the caller uploads again. */
 int plrf_set_sdf_scene(void* pipeline, const void* instance_buffer, size_t instance_bytes, const void* world_bbs, size_t bb_bytes);
 int plrf_set_sun_direction(void* pipeline, const float direction[3]);
 int plrf_set_camera_intrinsic(void* pipeline, float fov_degrees, float near_plane, float far_plane);
@@ -415,6 +417,35 @@ typedef struct plrf_shadow_cutout { uint32_t albedo_texture, alpha_cutoff; } plr
 int plrf_set_shadow_caster_cutouts(void* pipeline, const plrf_scene_texture* textures, uint32_t texture_count,
                                    const float* const* mesh_uvs, uint32_t mesh_count,
                                    const plrf_shadow_cutout* cutouts, uint32_t draw_count);
+/* ---- SDF instances of the GI trace from the scene: SDFGI::updateSDFScene (Techniques/SDFGI.cpp:260-313, called from renderScene every frame) as the compute pass
+ * "sdfInstanceUpdate.comp", and computeMeanAlbedo (ModelImport.cpp:78-112) as "sceneMeanAlbedo.comp" (DESIGN.md "SDF instances from the scene": the instance
+ * contract - padded boxes as plr_sdf_padded_bounds, the world box of the eight transformed corners, worldToLocal = inverse(model translate(bbOffset)) as adjugate
+ * over determinant in fp64 rounded once to fp32 - and the mean albedo contract in exact integer sums).
+ * plrf_scene_sdf_mesh, one per mesh of the scene: sdf_texture is an index plrf_add_sdf_volume / plrf_add_sdf_volume_dds returned, PLRF_SDF_BAKE (the mesh is baked
+ * now, with the asset pipeline's bake at plr_sdf_texture_description's resolution for its local box - the fp32 min / max of its positions -, and registered in the
+ * global texture array), or PLRF_NO_TEXTURE (the mesh has no SDF: its draws make no instance, SDFGI.cpp:277-280). The draws whose mesh has an SDF, in draw
+ * order, are instances 0 .. n - 1. While a scene SDF is set, every plrf_frame that records the GI trace or the SDF debug view records one execution of
+ * "sdfInstanceUpdate.comp" in front of the camera frustum culling: a lane per instance writes sdfInstances ({n, 0, 0, 0}, then n records) and sdfWorldBBs from the
+ * model matrices in mainPassMatrices, so an object moved with plrf_set_scene_mesh_transforms takes its occluder and its bounce light with it. "sceneMeanAlbedo.comp"
+ * is recorded in front of it in a frame after the texture store or the materials changed (plrf_set_scene_textures*, plrf_set_scene_sdf): an instance's meanAlbedo
+ * is the mean of its draw's albedo texture (level 0, the reference's rule: no sRGB decode, the alpha-weighted term truncated per texel; BC5 counts as (R, G, 0,
+ * 255)), or the same rule on the draw's constant albedo_rgba8 as a one-texel image (the reference's 0.5 for an untextured mesh is not used: here the constant word
+ * is the material), or what plrf_set_scene_sdf_mean_albedo gave for the draw (3 floats per draw; a NaN red = derive; draw_count 0 removes the overrides, and so
+ * does every plrf_set_scene_sdf). Without the call nothing is recorded, created or allocated.
+ * plrf_set_scene_sdf needs a scene; mesh_count must be the scene's; mesh_count 0 removes the scene SDF, and so does every plrf_set_scene_meshes. It survives
+ * plrf_set_scene_mesh_transforms, plrf_set_scene_textures*, plrf_set_resolution and plrf_update_settings. Volumes baked for it are released when it is replaced or
+ * removed, and a repeated call re-uses their images: plrf_get_scene_sdf_stats (instances now set, volumes baked and their bytes) does not grow. While it is set,
+ * plrf_set_sdf_scene returns PLR_ERR_UNSUPPORTED, and plrf_set_scene_sdf and plrf_set_scene_mesh_transforms refuse a model matrix of an instance whose determinant -
+ * the contract's fp64 expression - is zero or not finite; the message names the draw. PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: no scene
+ * set, a count mismatch, NULL meshes, an SDF mesh without vertices or with a non-finite position, more instances than max_sdf_instances, a singular matrix, a
+ * non-finite override. PLR_ERR_UNSUPPORTED: a band / tile pipeline without band_raster; with band_raster = 1 every rank writes every instance (the SDF scene is
+ * not screen-partitioned). A refused call changes nothing. */
+#define PLRF_SDF_BAKE 0xfffffffeu
+typedef struct plrf_scene_sdf_mesh { uint32_t sdf_texture; } plrf_scene_sdf_mesh;
+int plrf_set_scene_sdf(void* pipeline, const plrf_scene_sdf_mesh* meshes, uint32_t mesh_count);
+int plrf_set_scene_sdf_mean_albedo(void* pipeline, const float* rgb_or_nan, uint32_t draw_count);
+typedef struct plrf_scene_sdf_stats { uint32_t instances, volumes_baked; uint64_t volume_bytes; } plrf_scene_sdf_stats;
+int plrf_get_scene_sdf_stats(void* pipeline, plrf_scene_sdf_stats* out);
 typedef struct plrf_prepass_raster_stats { uint64_t triangles_submitted, triangles_clipped, subtriangles_drawn, rejects; } plrf_prepass_raster_stats;
 int plrf_get_prepass_raster_stats(void* pipeline, plrf_prepass_raster_stats* out);
 /* one iteration of the reference's main loop: record the frame, update camera/UBOs, submit (does not wait for the GPU) */

@@ -189,6 +189,27 @@ int plrf_get_prepass_raster_stats(void* p, plrf_prepass_raster_stats* out) {
     })
 }
 
+// ---- the scene's SDF ("sdfInstanceUpdate.comp", "sceneMeanAlbedo.comp")
+int plrf_set_scene_sdf(void* p, const plrf_scene_sdf_mesh* meshes, uint32_t meshCount) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        std::vector<uint32_t> m(meshes ? meshCount : 0u);
+        for (size_t i = 0; i < m.size(); i++) m[i] = meshes[i].sdf_texture;
+        ((FramePipeline*)p)->setSceneSdf(meshes ? m.data() : nullptr, meshCount);
+    })
+}
+int plrf_set_scene_sdf_mean_albedo(void* p, const float* rgbOrNan, uint32_t drawCount) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL(((FramePipeline*)p)->setSceneSdfMeanAlbedo(rgbOrNan, drawCount))
+}
+int plrf_get_scene_sdf_stats(void* p, plrf_scene_sdf_stats* out) {
+    if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        const FramePipeline::SceneSdfStats s = ((FramePipeline*)p)->sceneSdfStats();
+        out->instances = s.instances; out->volumes_baked = s.volumesBaked; out->volume_bytes = s.volumeBytes;
+    })
+}
+
 int plrf_raster_window_for(const plrf_settings* s, uint32_t out[4]) {
     if (!s || !out) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY(rasterWindowTiles(toPipelineSettings(s), out))
@@ -234,7 +255,7 @@ int plrf_add_sdf_volume_dds(void* p, const char* path, uint32_t* out, uint32_t o
         if (outSize) { outSize[0] = d.width; outSize[1] = d.height; outSize[2] = d.depth; }
     })
 }
-int plrf_set_sdf_scene(void* p, const void* inst, size_t ib, const void* bb, size_t bbb) { PLRF_TRY(((FramePipeline*)p)->setSdfScene(inst, ib, bb, bbb)) }
+int plrf_set_sdf_scene(void* p, const void* inst, size_t ib, const void* bb, size_t bbb) { PLRF_TRY_REFUSAL(((FramePipeline*)p)->setSdfScene(inst, ib, bb, bbb)) }
 int plrf_set_sun_direction(void* p, const float d[3]) { PLRF_TRY(((FramePipeline*)p)->setSunDirection(d)) }
 int plrf_set_camera_intrinsic(void* p, float fov, float n, float f) { PLRF_TRY(((FramePipeline*)p)->setCameraIntrinsic(fov, n, f)) }
 int plrf_set_camera_cut(void* p) { PLRF_TRY(((FramePipeline*)p)->setCameraCut()) }

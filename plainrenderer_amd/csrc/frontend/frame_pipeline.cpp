@@ -1,9 +1,13 @@
 // See frame_pipeline.h. Pass order, bindings, specialisation constants and dispatch counts follow the cited reference code.
 #include "frame_pipeline.h"
 #include "../device/depth_prepass_raster.h"
+#include "../device/scene_sdf.h"
 #include "../device/sun_shadow_raster.h"
 
 #include "../../../include/plr_image_io.h"
+#include "../../../include/plr_sdf_bake.h"
+
+#include <hip/hip_runtime_api.h> // hipGetDevice: the device the scene's SDF volumes are baked on
 
 #include <algorithm>
 #include <cmath>
@@ -1046,7 +1050,11 @@ uint32_t FramePipeline::addSdfVolumeFromDds(const std::string& path, ImageDescri
     return m_be.getImageGlobalTextureArrayIndex(h);
 }
 
-void FramePipeline::setSdfScene(const void* inst, size_t instBytes, const void* bb, size_t bbBytes) { m_sdfGi.updateSDFScene(m_be, inst, instBytes, bb, bbBytes); }
+void FramePipeline::setSdfScene(const void* inst, size_t instBytes, const void* bb, size_t bbBytes) {
+    if (m_sceneSdfSet)
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSdfScene: a scene SDF is set (setSceneSdf): sdfInstances and sdfWorldBBs are written by sdfInstanceUpdate.comp every frame; remove it first");
+    m_sdfGi.updateSDFScene(m_be, inst, instBytes, bb, bbBytes);
+}
 void FramePipeline::setSunDirection(const float d[3]) { m_globalShaderInfo.sunDirection[0] = d[0]; m_globalShaderInfo.sunDirection[1] = d[1]; m_globalShaderInfo.sunDirection[2] = d[2]; m_globalShaderInfo.sunDirection[3] = 0.f; }
 void FramePipeline::setCameraIntrinsic(float fov, float n, float f) { m_cameraIntrinsic.fov = fov; m_cameraIntrinsic.near = n; m_cameraIntrinsic.far = f; }
 
@@ -1540,9 +1548,12 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
         m_scenePreviousValid = m_sceneRecorded = m_sceneAlphaTested = m_sceneTexturesCompressed = false;
         m_sceneNormalDecode = 0;
         m_sceneMeshVertexCounts.clear(); m_sceneMeshHasNormals.clear(); m_sceneNormalsHost.clear();
+        removeSceneSdf(); // its mesh indices named the scene that is gone
+        m_scenePositionsHost.clear(); m_sceneIndicesHost.clear(); m_sceneDrawMeshes.clear(); m_sceneMeshFirstIndex.clear(); m_sceneMeshIndexCounts.clear();
         return;
     }
     const PackedScene packed = packSceneMeshes(meshes, meshCount, draws, drawCount); // validates everything before anything is changed
+    removeSceneSdf(); // mesh indices no longer mean what they meant
     if (!m_scenePassCreated) {
         ComputePassDescription d; // RenderFrontend.cpp:1717-1735
         d.name = "Depth prepass";
@@ -1567,12 +1578,14 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
     m_sceneNormalDecode = 0;    // and the normal maps
     m_sceneMeshHasNormals = packed.meshHasNormals;
     m_sceneNormalsHost = packed.normals;
+    m_scenePositionsHost = packed.positions; m_sceneIndicesHost = packed.indices; // what a later setSceneSdf takes the local boxes and the bake from
+    m_sceneDrawMeshes = packed.drawMeshes; m_sceneMeshFirstIndex = packed.meshFirstIndex; m_sceneMeshIndexCounts = packed.meshIndexCounts;
 }
 
 void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {
     if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneTextures: a band / tile pipeline cannot rasterise scene meshes");
-    if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = m_sceneTexturesCompressed = false; m_sceneNormalDecode = 0; return; }
+    if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = m_sceneTexturesCompressed = false; m_sceneNormalDecode = 0; noteSceneTexturesChanged(0); return; }
     const PackedTextures packed = packSceneTextures(textures, textureCount, meshUvs, meshCount, materials, drawCount, m_sceneMeshVertexCounts.data(),
                                                     (uint32_t)m_sceneMeshVertexCounts.size(), m_sceneDrawCount); // validates everything before anything is changed
     auto fill = [&](SceneBuffer& b, const std::vector<uint32_t>& data) { fillCasterBuffer(b.handle, b.bytes, data.data(), data.size() * sizeof(uint32_t)); };
@@ -1584,12 +1597,15 @@ void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t text
     m_sceneTexturesCompressed = false;
     m_sceneAlphaTested = false; // the cutoffs belonged to the materials that were replaced
     m_sceneNormalDecode = 0;    // and the normal maps named textures that were replaced
+    uint32_t largest = 0;
+    for (uint32_t t = 0; t < textureCount; t++) largest = std::max(largest, packed.textures[4u * t + 1u] * packed.textures[4u * t + 2u]);
+    noteSceneTexturesChanged(largest);
 }
 
 void FramePipeline::setSceneTexturesFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {
     if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneTexturesFormatted: a band / tile pipeline cannot rasterise scene meshes");
-    if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = m_sceneTexturesCompressed = false; m_sceneNormalDecode = 0; return; }
+    if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = m_sceneTexturesCompressed = false; m_sceneNormalDecode = 0; noteSceneTexturesChanged(0); return; }
     const PackedFormattedTextures packed = packSceneTexturesFormatted(textures, textureCount, meshUvs, meshCount, materials, drawCount, m_sceneMeshVertexCounts.data(),
                                                                       (uint32_t)m_sceneMeshVertexCounts.size(), m_sceneDrawCount); // validates everything before anything is changed
     auto fill = [&](SceneBuffer& b, const std::vector<uint32_t>& data) { fillCasterBuffer(b.handle, b.bytes, data.data(), data.size() * sizeof(uint32_t)); };
@@ -1602,6 +1618,9 @@ void FramePipeline::setSceneTexturesFormatted(const SceneTextureData* textures, 
     m_sceneTexturesCompressed = packed.compressed;
     m_sceneAlphaTested = false; // the cutoffs belonged to the materials that were replaced
     m_sceneNormalDecode = 0;    // and the normal maps named textures that were replaced
+    uint32_t largest = 0;
+    for (uint32_t t = 0; t < textureCount; t++) largest = std::max(largest, packed.textures[4u * t + 1u] * packed.textures[4u * t + 2u]);
+    noteSceneTexturesChanged(largest);
 }
 
 void FramePipeline::setSceneNormalMaps(const float* const* meshTangents, const float* const* meshBitangents, uint32_t meshCount, const uint32_t* normalTextures, uint32_t drawCount,
@@ -1647,7 +1666,168 @@ void FramePipeline::setSceneMeshTransforms(const float* matrices16, uint32_t dra
     if (drawCount == 0) return;
     if (!matrices16) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setSceneMeshTransforms: matrices are null");
     refuseNonFiniteMatrices(matrices16, drawCount, "setSceneMeshTransforms");
+    if (m_sceneSdfSet) refuseSingularSceneSdfMatrices(matrices16, drawCount, m_sceneSdf, m_sceneDrawMeshes.data(), "setSceneMeshTransforms");
     m_sceneModel.assign(matrices16, matrices16 + (size_t)drawCount * 16u);
+}
+
+// ---- SDFGI::updateSDFScene (Techniques/SDFGI.cpp:260-313) as "sdfInstanceUpdate.comp", with computeMeanAlbedo (ModelImport.cpp:78-112) as "sceneMeanAlbedo.comp"
+// (kernels/scene_sdf.hip; DESIGN.md "SDF instances from the scene")
+void FramePipeline::removeSceneSdf() {
+    if (!m_sceneSdfSet) return;
+    m_sceneSdfSet = false;
+    m_sceneSdf = PackedSceneSdf{};
+    ImageDescription released; // the backend has no call that frees an image: a released volume keeps its slot of the texture array with one texel, for the next bake
+    released.width = released.height = released.depth = 1;
+    released.type = ImageType::Type3D; released.format = ImageFormat::R16_sFloat; released.usageFlags = ImageUsageFlags::Sampled;
+    for (BakedVolume& v : m_sceneSdfVolumes)
+        if (v.inUse) { m_be.recreateImage(v.image, released); v.inUse = false; v.bytes = 0; }
+    m_sdfGi.setInstanceCount(0);
+    const uint32_t header[4] = {0, 0, 0, 0}; // the instance count is 0 until the caller uploads again (setSdfScene)
+    m_be.setStorageBufferData(m_sdfGi.m_sdfInstanceBuffer, header, sizeof(header));
+}
+
+void FramePipeline::setSceneSdf(const uint32_t* sdfTextures, uint32_t meshCount) {
+    if (partitionedWithoutRaster(m_requestedSettings))
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneSdf: a band / tile pipeline cannot rasterise scene meshes, so it has no scene to take SDF instances from (band_raster)");
+    if (meshCount == 0) { removeSceneSdf(); return; }
+    SceneSdfContext scene;
+    scene.positions = m_scenePositionsHost.data(); scene.meshVertexCounts = m_sceneMeshVertexCounts.data(); scene.drawMeshes = m_sceneDrawMeshes.data(); scene.models = m_sceneModel.data();
+    scene.meshCount = (uint32_t)m_sceneMeshVertexCounts.size(); scene.drawCount = m_sceneDrawCount; scene.maxInstances = settings.maxSdfInstances;
+    PackedSceneSdf packed = packSceneSdf(sdfTextures, meshCount, scene); // validates everything before anything is changed
+    // the bakes, into host memory: the asset-pipeline boundary, once per scene (a failure here still changes nothing)
+    struct Bake { ImageDescription desc; std::vector<uint16_t> voxels; };
+    std::vector<Bake> bakes(packed.bakedMeshes.size());
+    int device = 0;
+    if (!bakes.empty() && hipGetDevice(&device) != hipSuccess) throw std::runtime_error("setSceneSdf: no current device for the bake");
+    std::vector<size_t> vertexOffset(meshCount, 0);
+    for (uint32_t m = 1; m < meshCount; m++) vertexOffset[m] = vertexOffset[m - 1] + m_sceneMeshVertexCounts[m - 1];
+    for (size_t k = 0; k < bakes.size(); k++) {
+        const uint32_t m = packed.bakedMeshes[k];
+        plr_aabb bb;
+        std::memcpy(bb.min, packed.meshBoxes.data() + (size_t)m * 6u, 12); std::memcpy(bb.max, packed.meshBoxes.data() + (size_t)m * 6u + 3u, 12);
+        plr_image_desc cd{};
+        if (plr_sdf_texture_description(&bb, &cd) != PLR_OK) throw std::runtime_error(plr_last_error());
+        Bake& b = bakes[k];
+        b.desc.width = cd.width; b.desc.height = cd.height; b.desc.depth = cd.depth;
+        b.desc.type = ImageType::Type3D; b.desc.format = ImageFormat::R16_sFloat; b.desc.usageFlags = ImageUsageFlags::Sampled;
+        b.voxels.resize((size_t)cd.width * cd.height * cd.depth);
+        const plr_mesh_data mesh{m_scenePositionsHost.data() + vertexOffset[m] * 3u, m_sceneMeshVertexCounts[m], m_sceneIndicesHost.data() + m_sceneMeshFirstIndex[m], m_sceneMeshIndexCounts[m]};
+        if (plr_compute_sdf(device, &mesh, &bb, cd.width, cd.height, cd.depth, b.voxels.data(), b.voxels.size() * 2u) != PLR_OK)
+            throw std::runtime_error(std::string("setSceneSdf: baking mesh ") + std::to_string(m) + ": " + plr_last_error());
+    }
+    // the volumes of the SDF that is replaced are released; the new ones take their images first, so that repeated calls do not grow the image count
+    std::vector<uint8_t> wasInUse(m_sceneSdfVolumes.size());
+    for (size_t v = 0; v < m_sceneSdfVolumes.size(); v++) { wasInUse[v] = m_sceneSdfVolumes[v].inUse; m_sceneSdfVolumes[v].inUse = false; }
+    std::vector<uint32_t> meshTextureIndices(packed.meshSdf);
+    for (size_t k = 0; k < bakes.size(); k++) {
+        const Bake& b = bakes[k];
+        const size_t bytes = b.voxels.size() * 2u;
+        size_t slot = 0;
+        while (slot < m_sceneSdfVolumes.size() && m_sceneSdfVolumes[slot].inUse) slot++;
+        if (slot == m_sceneSdfVolumes.size()) {
+            BakedVolume v;
+            v.image = m_be.createImage(b.desc, b.voxels.data(), bytes);
+            m_sceneSdfVolumes.push_back(v);
+            wasInUse.push_back(0);
+        } else {
+            m_be.recreateImage(m_sceneSdfVolumes[slot].image, b.desc);
+            if (plr_upload_image(RenderBackend::toC(m_sceneSdfVolumes[slot].image), 0, b.voxels.data(), bytes) != PLR_OK) throw std::runtime_error(plr_last_error());
+        }
+        m_sceneSdfVolumes[slot].inUse = true; m_sceneSdfVolumes[slot].bytes = bytes;
+        meshTextureIndices[packed.bakedMeshes[k]] = m_be.getImageGlobalTextureArrayIndex(m_sceneSdfVolumes[slot].image);
+    }
+    {
+        ImageDescription released;
+        released.width = released.height = released.depth = 1;
+        released.type = ImageType::Type3D; released.format = ImageFormat::R16_sFloat; released.usageFlags = ImageUsageFlags::Sampled;
+        for (size_t v = 0; v < m_sceneSdfVolumes.size(); v++)
+            if (wasInUse[v] && !m_sceneSdfVolumes[v].inUse) { m_be.recreateImage(m_sceneSdfVolumes[v].image, released); m_sceneSdfVolumes[v].bytes = 0; }
+    }
+    if (!m_sceneSdfPassesCreated) {
+        ComputePassDescription d;
+        d.name = "SDF instance update";
+        d.shaderDescription.srcPathRelative = "sdfInstanceUpdate.comp";
+        m_sdfInstanceUpdatePass = m_be.createComputePass(d);
+        d.name = "Scene mean albedo";
+        d.shaderDescription.srcPathRelative = "sceneMeanAlbedo.comp";
+        m_sceneMeanAlbedoPass = m_be.createComputePass(d);
+        m_sceneSdfPassesCreated = true;
+    }
+    const std::vector<uint32_t> table = sceneSdfInstanceTable(packed, m_sceneDrawMeshes.data(), meshTextureIndices.data());
+    fillCasterBuffer(m_sceneSdfTable.handle, m_sceneSdfTable.bytes, table.empty() ? nullptr : table.data(), std::max<size_t>(table.size() * sizeof(uint32_t), sizeof(plr::scenesdf::InstanceEntry)));
+    const std::vector<float> derive((size_t)m_sceneDrawCount * 3u, std::nanf("")); // no overrides: every draw derives
+    fillCasterBuffer(m_sceneSdfOverrides.handle, m_sceneSdfOverrides.bytes, derive.data(), derive.size() * sizeof(float));
+    m_sceneSdf = std::move(packed);
+    m_sceneSdfSet = true;
+    m_sdfGi.setInstanceCount((uint32_t)m_sceneSdf.instanceDraws.size());
+    noteSceneTexturesChanged(0);
+}
+
+// the mean albedos belong to the texture store and the materials: stale whenever either changed, or the SDF was set. largestLevel0Texels 0: keep the group count
+void FramePipeline::noteSceneTexturesChanged(uint32_t largestLevel0Texels) {
+    // a group of 256 lanes takes 16 texels per lane and round at least; a texture gets at most 1024 groups (the kernel strides: the result does not depend on it)
+    if (largestLevel0Texels) m_sceneSdfMeanGroups = std::min(1024u, std::max(1u, (largestLevel0Texels + 4095u) / 4096u));
+    m_sceneSdfMeansStale = true;
+    if (!m_sceneSdfSet || m_sceneTextureCount == 0) return;
+    fillCasterBuffer(m_sceneSdfMeans.handle, m_sceneSdfMeans.bytes, nullptr, (size_t)m_sceneTextureCount * 16u);
+    fillCasterBuffer(m_sceneSdfMeanScratch.handle, m_sceneSdfMeanScratch.bytes, nullptr, plr::scenesdf::meanScratchBytes(m_sceneTextureCount));
+}
+
+void FramePipeline::setSceneSdfMeanAlbedo(const float* rgbOrNan, uint32_t drawCount) {
+    if (partitionedWithoutRaster(m_requestedSettings))
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneSdfMeanAlbedo: a band / tile pipeline cannot rasterise scene meshes, so it has no scene SDF (band_raster)");
+    if (drawCount == 0) {
+        if (!m_sceneSdfSet) return;
+        const std::vector<float> derive((size_t)m_sceneDrawCount * 3u, std::nanf(""));
+        fillCasterBuffer(m_sceneSdfOverrides.handle, m_sceneSdfOverrides.bytes, derive.data(), derive.size() * sizeof(float));
+        return;
+    }
+    const std::vector<float> values = packSceneSdfMeanAlbedo(rgbOrNan, drawCount, m_sceneDrawCount, m_sceneSdfSet); // validates everything before anything is changed
+    fillCasterBuffer(m_sceneSdfOverrides.handle, m_sceneSdfOverrides.bytes, values.data(), values.size() * sizeof(float));
+}
+
+FramePipeline::SceneSdfStats FramePipeline::sceneSdfStats() const {
+    SceneSdfStats out;
+    out.instances = m_sceneSdfSet ? (uint32_t)m_sceneSdf.instanceDraws.size() : 0u;
+    for (const BakedVolume& v : m_sceneSdfVolumes)
+        if (v.inUse) { out.volumesBaked++; out.volumeBytes += v.bytes; }
+    return out;
+}
+
+void FramePipeline::updateSceneSdfInstances() {
+    if (!m_sceneSdfSet) return;
+    namespace ss = plr::scenesdf;
+    const uint32_t textures = m_sceneTextureCount;
+    if (textures && m_sceneSdfMeansStale) { // only in a frame after the texture store or the materials changed
+        ComputePassExecution exe;
+        exe.genericInfo.handle = m_sceneMeanAlbedoPass;
+        exe.dispatchCount[0] = m_sceneSdfMeanGroups; exe.dispatchCount[1] = textures; exe.dispatchCount[2] = 1;
+        const bool formats = m_sceneTexturesCompressed;
+        const ss::MeanPushConstants pc{textures, m_sceneDrawCount, formats ? 1u : 0u};
+        exe.pushConstants = dataToCharArray(&pc, sizeof(pc));
+        exe.genericInfo.resources.storageBuffers = {StorageBufferResource(m_sceneTextures.handle, true, ss::kMeanTextureBinding), StorageBufferResource(m_sceneTexels.handle, true, ss::kMeanTexelBinding),
+                                                    StorageBufferResource(m_sceneMaterials.handle, true, ss::kMeanMaterialBinding),
+                                                    StorageBufferResource(m_sceneSdfMeanScratch.handle, false, ss::kMeanScratchBinding),
+                                                    StorageBufferResource(m_sceneSdfMeans.handle, false, ss::kMeanOutBinding)};
+        if (formats) exe.genericInfo.resources.storageBuffers.push_back(StorageBufferResource(m_sceneTextureFormats.handle, true, ss::kMeanFormatBinding));
+        m_be.setComputePassExecution(exe);
+    }
+    m_sceneSdfMeansStale = false;
+    const uint32_t instances = (uint32_t)m_sceneSdf.instanceDraws.size();
+    ComputePassExecution exe;
+    exe.genericInfo.handle = m_sdfInstanceUpdatePass;
+    exe.dispatchCount[0] = (std::max(instances, 1u) + 63u) / 64u; exe.dispatchCount[1] = exe.dispatchCount[2] = 1;
+    const ss::InstancePushConstants pc{instances, m_sceneDrawCount, textures};
+    exe.pushConstants = dataToCharArray(&pc, sizeof(pc));
+    exe.genericInfo.resources.storageBuffers = {StorageBufferResource(m_sceneMatrices.handle, true, ss::kMatricesBinding), StorageBufferResource(m_sceneSdfTable.handle, true, ss::kTableBinding),
+                                                StorageBufferResource(m_sceneDraws.handle, true, ss::kDrawBinding), StorageBufferResource(m_sceneSdfOverrides.handle, true, ss::kOverrideBinding),
+                                                StorageBufferResource(m_sdfGi.m_sdfInstanceBuffer, false, ss::kInstanceBinding),
+                                                StorageBufferResource(m_sdfGi.m_sdfInstanceWorldBBBuffer, false, ss::kWorldBBBinding)};
+    if (textures) {
+        exe.genericInfo.resources.storageBuffers.push_back(StorageBufferResource(m_sceneMaterials.handle, true, ss::kMaterialBinding));
+        exe.genericInfo.resources.storageBuffers.push_back(StorageBufferResource(m_sceneSdfMeans.handle, true, ss::kMeanAlbedoBinding));
+    }
+    m_be.setComputePassExecution(exe);
 }
 
 PrepassRasterStats FramePipeline::prepassRasterStats() {
@@ -1829,6 +2009,7 @@ void FramePipeline::prepareRenderpasses() { // RenderFrontend.cpp:313-406
         if (settings.runSkyLuts) updateSkyLut();
         if (settings.runLightMatrix) computeSunLightMatrices();
         renderSunShadowCascades(); // (RenderFrontend.cpp:331) only with mesh casters set; the uploaded maps otherwise
+        updateSceneSdfInstances(); // (SDFGI::updateSDFScene, called from renderScene every frame) only with a scene SDF set; the uploaded instances otherwise
         SDFTraceDependencies deps = m_frustumScratch;
         deps.currentFrame = currentRenderTarget;
         deps.previousFrame = previousRenderTarget;
@@ -1865,6 +2046,7 @@ void FramePipeline::prepareRenderpasses() { // RenderFrontend.cpp:313-406
     renderSunShadowCascades(); // (RenderFrontend.cpp:354) only with mesh casters set; the uploaded maps otherwise
     if (settings.runGI && settings.shading.indirectLightingTech == IndirectLightingTech::SDFTrace) {
         if (settings.sdfTrace.halfResTrace) downscaleDepth(currentRenderTarget);
+        updateSceneSdfInstances(); // in front of sdfCameraFrustumCulling; only with a scene SDF set, the uploaded instances otherwise
         SDFTraceDependencies deps = m_frustumScratch; // frustum points/normals from setCameraExtrinsic (fillOutSdfGiDependencies, :1073-1090)
         deps.currentFrame = currentRenderTarget;
         deps.previousFrame = previousRenderTarget;

@@ -240,6 +240,9 @@ public:
                                 const SDFTraceSettings& traceSettings) const;
     // packed { uint count; uint pad[3]; SDFInstance[] } and { vec3 min; pad; vec3 max; pad }[] as SDFGI::updateSDFScene builds them
     void updateSDFScene(RenderBackend& be, const void* instanceBufferData, size_t instanceBytes, const void* worldBBData, size_t bbBytes);
+    // the instance count of a scene SDF ("sdfInstanceUpdate.comp" writes the buffers): what the culling dispatches are sized by
+    void setInstanceCount(uint32_t count) { m_sdfInstanceCount = count; }
+    uint32_t instanceCount() const { return m_sdfInstanceCount; }
     void computeIndirectLighting(RenderBackend& be, const FrameIndexCounter& fi, const SDFTraceDependencies& deps, const SDFTraceSettings& s, const GiBand* band = nullptr) const;
     struct IndirectLightingImages { ImageHandle Y_SH, CoCg; };
     IndirectLightingImages getIndirectLightingResults(bool tracedHalfRes) const;
@@ -342,6 +345,8 @@ struct PackedScene {
     uint32_t triangleCount = 0;
     std::vector<uint32_t> meshVertexCounts;        // per mesh, in the order the positions are packed: what packSceneTextures lays the UVs out by
     std::vector<uint8_t> meshHasNormals;           // per mesh: given with vertex normals (packSceneNormalMaps derives bitangents from them)
+    std::vector<uint32_t> drawMeshes;              // per draw: its mesh (packSceneSdf maps draws to SDF instances by it)
+    std::vector<uint32_t> meshFirstIndex, meshIndexCounts; // per mesh: where its triangle list lies in `indices` (setSceneSdf bakes from it)
 };
 PackedScene packSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const SceneDraw* draws, uint32_t drawCount);
 void refuseNonFiniteMatrices(const float* matrices16, uint32_t drawCount, const char* call);
@@ -413,6 +418,32 @@ struct PackedShadowCutouts {
 // casterMeshVertexCounts / casterDrawCount: of the casters the pipeline holds (casterDrawCount 0: none). Throws FramePipelineRefusal.
 PackedShadowCutouts packShadowCasterCutouts(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts,
                                             uint32_t drawCount, const uint32_t* casterMeshVertexCounts, uint32_t casterMeshCount, uint32_t casterDrawCount);
+// the scene's SDF (plr_frame.h plrf_set_scene_sdf): per mesh an index from addSdfVolume*, kSceneSdfBake, or kNoSceneTexture (no SDF: its draws make no instance)
+constexpr uint32_t kSceneSdfBake = 0xfffffffeu;
+// of the scene the pipeline holds: the packed positions and per mesh its vertex count, per draw its mesh and its current model matrix
+struct SceneSdfContext {
+    const float* positions = nullptr; const uint32_t* meshVertexCounts = nullptr; const uint32_t* drawMeshes = nullptr; const float* models = nullptr;
+    uint32_t meshCount = 0, drawCount = 0, maxInstances = 0;
+};
+// what setSceneSdf validates and derives, without a backend: the local boxes and the instance map of "sdfInstanceUpdate.comp" (device/scene_sdf.h)
+struct PackedSceneSdf {
+    std::vector<uint32_t> meshSdf;       // per mesh, as given
+    std::vector<float> meshBoxes;        // 6 floats per mesh: the fp32 min and max of its positions (zeros for a mesh without an SDF)
+    std::vector<uint32_t> instanceDraws; // instance i is draw instanceDraws[i]: the draws whose mesh has an SDF, in draw order
+    std::vector<uint32_t> bakedMeshes;   // the meshes that asked for kSceneSdfBake, ascending
+};
+// Throws FramePipelineRefusal: no scene, a mesh count other than the scene's, null input, an SDF mesh without vertices or with a non-finite position, more
+// instances than maxInstances, an instance whose determinant (below) is zero or not finite
+PackedSceneSdf packSceneSdf(const uint32_t* sdfTextures, uint32_t meshCount, const SceneSdfContext& scene);
+// the fp64 determinant of model * translate(bbOffset) the instance contract divides by (device/scene_sdf.h instanceDeterminant); localBox6 = min, max
+double sceneSdfDeterminant(const float* model16, const float* localBox6);
+// refuses (PLR_ERR_INVALID_ARGUMENT, naming the draw) a model matrix of a draw that is an SDF instance whose determinant is zero or not finite
+void refuseSingularSceneSdfMatrices(const float* matrices16, uint32_t drawCount, const PackedSceneSdf& sdf, const uint32_t* drawMeshes, const char* call);
+// the instance table (8 words per instance: plr::scenesdf::InstanceEntry) once every SDF mesh has its global texture array index
+std::vector<uint32_t> sceneSdfInstanceTable(const PackedSceneSdf& sdf, const uint32_t* drawMeshes, const uint32_t* meshTextureIndices);
+// 3 floats per draw, a NaN red = derive. Throws FramePipelineRefusal: no scene SDF, a draw count other than the scene's, null values, a non-finite component
+// of an entry whose red is a number
+std::vector<float> packSceneSdfMeanAlbedo(const float* rgbOrNan, uint32_t drawCount, uint32_t sceneDrawCount, bool sceneSdfSet);
 // appends levels 1 .. of the full chain of a width x height level 0 (already the last `width * height` texels of `texels`): level l + 1 texel (x, y) per channel
 // is (a + b + c + d + 2) >> 2 of the level-l texels at (min(2x, W - 1) | min(2x + 1, W - 1), min(2y, H - 1) | min(2y + 1, H - 1))
 void appendMipChain(std::vector<uint32_t>& texels, uint32_t width, uint32_t height);
@@ -486,6 +517,19 @@ public:
     void setSceneAnisotropy(uint32_t maxAnisotropy);
     // counters of the last frame's execution for the scene now set; waits for the GPU. Zero while no scene is set and before the first frame of a newly set scene.
     PrepassRasterStats prepassRasterStats();
+    // SDFGI::updateSDFScene (Techniques/SDFGI.cpp:260-313) as "sdfInstanceUpdate.comp" (kernels/scene_sdf.hip; DESIGN.md "SDF instances from the scene"): while a
+    // scene SDF is set every frame that records the GI trace or the SDF debug view records one execution in front of the camera frustum culling that writes
+    // sdfInstances and sdfWorldBBs from mainPassMatrices, and - in a frame after the texture store or the materials changed - "sceneMeanAlbedo.comp" in front of it.
+    // sdfTextures[m]: an index from addSdfVolume*, kSceneSdfBake (baked now with the asset pipeline's bake at plr_sdf_texture_description's resolution and
+    // registered in the global texture array), or kNoSceneTexture. meshCount 0 removes it; setSceneMeshes removes it too; volumes baked for it are released then,
+    // and a repeated call re-uses their images. While it is set setSdfScene is refused (PLR_ERR_UNSUPPORTED) and setSceneMeshTransforms refuses a singular
+    // matrix; after a removal the instance count is 0. Refusals: packSceneSdf's are PLR_ERR_INVALID_ARGUMENT; a band / tile pipeline without band.raster is
+    // PLR_ERR_UNSUPPORTED. A refused call changes nothing.
+    void setSceneSdf(const uint32_t* sdfTextures, uint32_t meshCount);
+    // per draw the mean albedo of its instance instead of the derived one (3 floats, a NaN red = derive); drawCount 0 removes the overrides, and so does setSceneSdf
+    void setSceneSdfMeanAlbedo(const float* rgbOrNan, uint32_t drawCount);
+    struct SceneSdfStats { uint32_t instances = 0, volumesBaked = 0; uint64_t volumeBytes = 0; };
+    SceneSdfStats sceneSdfStats() const;
     void rasterWindow(uint32_t outTiles[4]) const { rasterWindowTiles(settings, outTiles); }
     // RenderFrontend::setResolution (RenderFrontend.cpp:408-421): recorded, applied at the start of the next frame() (prepareNewFrame, :199-222). Every image and
     // buffer whose size follows the screen is re-created zero-filled, as the constructor creates it, and the next frame is a camera cut; a resize to the size the
@@ -626,6 +670,20 @@ private:
     bool m_shadingNormalCreated = false;
     bool normalMapped() const { return m_sceneNormalDecode != 0 && m_sceneTextureCount != 0 && m_sceneDrawCount != 0; }
     std::vector<float> m_sceneModel, m_scenePreviousModel; // 16 floats per draw: what the next frame uses, what the last recorded frame used
+    // the scene's SDF: passes and buffers created by the first setSceneSdf. The host keeps the scene's positions, indices and draw -> mesh map for it (the
+    // local boxes and the bake need them when setSceneSdf comes)
+    std::vector<float> m_scenePositionsHost;
+    std::vector<uint32_t> m_sceneIndicesHost, m_sceneDrawMeshes, m_sceneMeshFirstIndex, m_sceneMeshIndexCounts;
+    bool m_sceneSdfSet = false, m_sceneSdfPassesCreated = false, m_sceneSdfMeansStale = false;
+    PackedSceneSdf m_sceneSdf;
+    RenderPassHandle m_sdfInstanceUpdatePass, m_sceneMeanAlbedoPass;
+    SceneBuffer m_sceneSdfTable, m_sceneSdfOverrides, m_sceneSdfMeans, m_sceneSdfMeanScratch;
+    uint32_t m_sceneSdfMeanGroups = 1; // dispatch_count[0] of "sceneMeanAlbedo.comp": from the largest level 0 of the store
+    struct BakedVolume { ImageHandle image; bool inUse = false; uint64_t bytes = 0; };
+    std::vector<BakedVolume> m_sceneSdfVolumes; // images of baked volumes: released (re-created at 1 x 1 x 1) with the scene's SDF, re-used by the next bake
+    void removeSceneSdf();
+    void updateSceneSdfInstances();
+    void noteSceneTexturesChanged(uint32_t maxLevel0Texels);
 public:
     AtmosphereSettings atmosphereSettings;
     VolumetricsSettings volumetricsSettings;

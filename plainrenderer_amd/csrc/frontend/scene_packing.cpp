@@ -72,6 +72,11 @@ PackedScene packSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const S
     out.meshVertexCounts.resize(meshCount);
     out.meshHasNormals.resize(meshCount);
     for (uint32_t m = 0; m < meshCount; m++) { out.meshVertexCounts[m] = meshes[m].vertexCount; out.meshHasNormals[m] = meshes[m].normals ? 1 : 0; }
+    out.drawMeshes.resize(drawCount);
+    for (uint32_t d = 0; d < drawCount; d++) out.drawMeshes[d] = draws[d].mesh;
+    out.meshFirstIndex = firstIndex;
+    out.meshIndexCounts.resize(meshCount);
+    for (uint32_t m = 0; m < meshCount; m++) out.meshIndexCounts[m] = meshes[m].indexCount;
     return out;
 }
 

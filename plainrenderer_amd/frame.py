@@ -91,6 +91,17 @@ class PlrfPrepassRasterStats(C.Structure):
     _fields_ = [("triangles_submitted", C.c_uint64), ("triangles_clipped", C.c_uint64), ("subtriangles_drawn", C.c_uint64), ("rejects", C.c_uint64)]
 
 
+SDF_BAKE = 0xFFFFFFFE  # PLRF_SDF_BAKE
+
+
+class PlrfSceneSdfMesh(C.Structure):
+    _fields_ = [("sdf_texture", C.c_uint32)]
+
+
+class PlrfSceneSdfStats(C.Structure):
+    _fields_ = [("instances", C.c_uint32), ("volumes_baked", C.c_uint32), ("volume_bytes", C.c_uint64)]
+
+
 class LocalExchangeGroup:
     """shared state of the in-process transport of the native exchange (include/plr_frame.h plrf_local_group_*): one per partition, created before its ranks'
     pipelines attach (FramePipeline.attach_local_rects), destroyed after they are gone"""
@@ -441,6 +452,27 @@ class FramePipeline:
         s = PlrfPrepassRasterStats()
         self._check(self.lib.plrf_get_prepass_raster_stats(self.handle, C.byref(s)))
         return int(s.triangles_submitted), int(s.triangles_clipped), int(s.subtriangles_drawn), int(s.rejects)
+
+    # ---- the scene's SDF (include/plr_frame.h plrf_set_scene_sdf): sdfInstances and sdfWorldBBs written every frame by "sdfInstanceUpdate.comp"
+    def set_scene_sdf(self, sdf_textures):
+        """one entry per mesh of the scene: an index add_sdf_volume / add_sdf_volume_dds returned, SDF_BAKE (baked now and registered), or NO_TEXTURE (the mesh
+        has no SDF: its draws make no instance). The draws whose mesh has an SDF, in draw order, are the instances. None or empty: the scene SDF is removed"""
+        values = [int(v) for v in (sdf_textures if sdf_textures is not None else [])]
+        m = (PlrfSceneSdfMesh * max(len(values), 1))()
+        for k, v in enumerate(values):
+            m[k].sdf_texture = v
+        self._check(self.lib.plrf_set_scene_sdf(self.handle, m, C.c_uint32(len(values))))
+
+    def set_scene_sdf_mean_albedo(self, rgb_or_nan):
+        """one (r, g, b) per draw instead of the derived mean albedo; a NaN red = derive. None or empty: the overrides are removed"""
+        a = np.ascontiguousarray(rgb_or_nan if rgb_or_nan is not None else np.zeros((0, 3)), np.float32).reshape(-1, 3)
+        self._check(self.lib.plrf_set_scene_sdf_mean_albedo(self.handle, a.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(a.shape[0])))
+
+    def scene_sdf_stats(self):
+        """(instances, volumes baked, bytes of the baked volumes) of the scene SDF now set; zeros without one"""
+        s = PlrfSceneSdfStats()
+        self._check(self.lib.plrf_get_scene_sdf_stats(self.handle, C.byref(s)))
+        return int(s.instances), int(s.volumes_baked), int(s.volume_bytes)
 
     def raster_window(self):
         """(x0, y0, x1, y1), half-open, in 64 x 64 tiles: the window the depth prepass of a partitioned pipeline with band_raster = 1 is restricted to"""
