@@ -283,7 +283,8 @@ int plrf_apply_changes(void* pipeline); /* apply what was recorded now: a caller
  * plrf_set_shadow_caster_transforms replaces the draws' model matrices (draw_count x 16 floats) from the next frame on, like setStorageBufferData: queued, applied
  * in call order; a draw_count other than the casters' is PLR_ERR_INVALID_ARGUMENT.
  * plrf_get_shadow_raster_stats: the counters of the last frame's execution for one cascade; waits for the GPU. submitted = triangles of all draws, drawn = back
- * faces inside the guard band whose pixel box meets the map, guard_band_rejects = triangles with a non-finite or out-of-band vertex. */
+ * faces inside the guard band whose pixel box meets the map, guard_band_rejects = triangles with a non-finite or out-of-band vertex. While
+ * plrf_set_draw_culling has PLRF_CULL_SHADOW_CASTERS set, the three counters count the draws the cull kept for that cascade only. */
 typedef struct plrf_shadow_draw { uint32_t mesh; float model_matrix[16]; } plrf_shadow_draw; /* glm column-major */
 int plrf_set_shadow_casters(void* pipeline, const plr_mesh_data* meshes, uint32_t mesh_count, const plrf_shadow_draw* draws, uint32_t draw_count);
 int plrf_set_shadow_caster_transforms(void* pipeline, const float* matrices16, uint32_t draw_count);
@@ -310,7 +311,8 @@ int plrf_get_shadow_raster_stats(void* pipeline, uint32_t cascade, plrf_shadow_r
  * removal) and before the first frame of a newly set scene. submitted = triangles of all draws, clipped = triangles the clip
  * changed, subtriangles_drawn = front-facing sub-triangles whose pixel box meets the frame, rejects = triangles outside their buffers or with a non-finite clip
  * coordinate plus sub-triangles with a vertex w <= 0 or outside the 2^20-pixel band. The storage buffer "mainPassMatrices" (plrf_get_storage_buffer) holds the
- * {model, mvp, mvpPrevious} the last frame wrote, 48 floats per draw. */
+ * {model, mvp, mvpPrevious} the last frame wrote, 48 floats per draw. While plrf_set_draw_culling has PLRF_CULL_SCENE set, the four counters count the draws the
+ * cull kept only. */
 typedef struct plrf_scene_mesh { const float* positions; const float* normals; uint32_t vertex_count; const uint32_t* indices; uint32_t index_count; } plrf_scene_mesh;
 typedef struct plrf_scene_draw { uint32_t mesh; float model_matrix[16]; uint32_t albedo_rgba8, specular_rgba8; } plrf_scene_draw; /* glm column-major */
 int plrf_set_scene_meshes(void* pipeline, const plrf_scene_mesh* meshes, uint32_t mesh_count, const plrf_scene_draw* draws, uint32_t draw_count);
@@ -448,6 +450,36 @@ typedef struct plrf_scene_sdf_stats { uint32_t instances, volumes_baked; uint64_
 int plrf_get_scene_sdf_stats(void* pipeline, plrf_scene_sdf_stats* out);
 typedef struct plrf_prepass_raster_stats { uint64_t triangles_submitted, triangles_clipped, subtriangles_drawn, rejects; } plrf_prepass_raster_stats;
 int plrf_get_prepass_raster_stats(void* pipeline, plrf_prepass_raster_stats* out);
+/* ---- frustum culling of whole draws on the GPU: the bounding-box tests of RenderFrontend::renderScene (RenderFrontend.cpp:565-569 for the camera, :611-646 for
+ * the sun) as the compute pass "drawCulling.comp" (DESIGN.md "Frustum culling of draws": the cull contract and the proof). With PLRF_CULL_SCENE every frame
+ * that records the depth prepass records one execution in front of it: a lane per draw tests the eight corners of the draw's local box - the fp32 min / max of
+ * its mesh's positions, kept by the host from plrf_set_scene_meshes on - under that frame's own jittered mvp against the near plane and the four side planes, with
+ * a tolerance of 2^-16 of the box's magnitude (at least 2^-100), and writes a copy of the draw array in which a draw outside one plane has index_count 0. The prepass binds the copy
+ * (every wrap strip of a band / tile pipeline too; the test is against the whole frame, never a partition's window). With PLRF_CULL_SHADOW_CASTERS one execution
+ * behind lightMatrix.comp does the same for the casters of plrf_set_shadow_casters, per cascade, against the four side planes of that frame's light matrix times
+ * the caster's model matrix - the matrices exist only on the GPU when run_light_matrix is 1 -, and each cascade binds its own copy. There is no far plane and no
+ * shadow depth plane (the raster contracts decide those per fragment), and a box outside across a frustum edge or corner is kept.
+ * Every image the two rasterisers write is byte for byte what it is without culling. While culling is on for a view, plrf_get_prepass_raster_stats and
+ * plrf_get_shadow_raster_stats count the kept draws only: submitted, clipped, drawn and rejects are those of the same pass run on the kept draws alone.
+ * The flags take effect with the next frame and hold for the pipeline's life until changed, across plrf_set_scene_meshes, plrf_set_shadow_casters,
+ * plrf_set_*_transforms, plrf_set_resolution and plrf_update_settings; a flag whose mesh set is absent does nothing until one is set. Flags 0 (the default):
+ * nothing is recorded, created or allocated, and every frame is what it is without this call. PLR_ERR_INVALID_ARGUMENT: unknown bits. PLR_ERR_UNSUPPORTED: a
+ * band / tile pipeline without band_raster. A refused call changes nothing.
+ * plrf_get_draw_culling_stats: the counters of the last frame's cull execution for view 0 (the main pass) or 1 + c (cascade c); waits for the GPU. draws and
+ * triangles are the view's totals, visible_* those of the kept draws, culled_by_plane the culled draws by the first plane, in test order, they are outside of.
+ * All zero for a view that is off, whose mesh set is absent, or that no frame has rendered yet. A view at or past 1 + sun_shadow_cascade_count is
+ * PLR_ERR_INVALID_ARGUMENT. plrf_get_storage_buffer names the outputs once they exist: "sceneCulledDraws" (24 bytes per draw), "sceneCullStats" (8 uint32:
+ * visible draws, visible triangles, culled by plane [5], pad), "casterCulledDraws0" .. "casterCulledDraws3" (16 bytes per draw), "casterCullStats" (8 uint32 per
+ * cascade). */
+#define PLRF_CULL_SCENE          1u   /* the depth prepass's draws, against the frame's own jittered viewProjection */
+#define PLRF_CULL_SHADOW_CASTERS 2u   /* the casters, per cascade, against that frame's light matrices */
+int plrf_set_draw_culling(void* pipeline, uint32_t flags);
+typedef struct plrf_draw_culling_stats {
+    uint32_t draws, visible_draws;
+    uint64_t triangles, visible_triangles;
+    uint32_t culled_by_plane[5];            /* near, +x, -x, +y, -y; shadow views leave [0] at 0 */
+} plrf_draw_culling_stats;
+int plrf_get_draw_culling_stats(void* pipeline, uint32_t view, plrf_draw_culling_stats* out); /* view 0: main pass; 1 + c: cascade c */
 /* one iteration of the reference's main loop: record the frame, update camera/UBOs, submit (does not wait for the GPU) */
 int plrf_frame(void* pipeline, const plrf_camera* camera, float delta_time, float time);
 /* host copies of what the last plrf_frame submitted (340-byte global UBO image, 9 TAA resolve weights) */

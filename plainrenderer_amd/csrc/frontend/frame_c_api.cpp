@@ -189,6 +189,20 @@ int plrf_get_prepass_raster_stats(void* p, plrf_prepass_raster_stats* out) {
     })
 }
 
+// ---- frustum culling of draws ("drawCulling.comp")
+int plrf_set_draw_culling(void* p, uint32_t flags) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL(((FramePipeline*)p)->setDrawCulling(flags))
+}
+int plrf_get_draw_culling_stats(void* p, uint32_t view, plrf_draw_culling_stats* out) {
+    if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        const FramePipeline::DrawCullingStats s = ((FramePipeline*)p)->drawCullingStats(view);
+        out->draws = s.draws; out->visible_draws = s.visibleDraws; out->triangles = s.triangles; out->visible_triangles = s.visibleTriangles;
+        for (int k = 0; k < 5; k++) out->culled_by_plane[k] = s.culledByPlane[k];
+    })
+}
+
 // ---- the scene's SDF ("sdfInstanceUpdate.comp", "sceneMeanAlbedo.comp")
 int plrf_set_scene_sdf(void* p, const plrf_scene_sdf_mesh* meshes, uint32_t meshCount) {
     if (!p) return PLR_ERR_INVALID_ARGUMENT;

@@ -1,6 +1,7 @@
 // See frame_pipeline.h. Pass order, bindings, specialisation constants and dispatch counts follow the cited reference code.
 #include "frame_pipeline.h"
 #include "../device/depth_prepass_raster.h"
+#include "../device/draw_culling.h"
 #include "../device/scene_sdf.h"
 #include "../device/sun_shadow_raster.h"
 
@@ -1005,6 +1006,10 @@ bool FramePipeline::storageBuffer(const std::string& n, StorageBufferHandle* out
     else if (n == "light") *out = m_lightBuffer;
     else if (n == "sunShadowInfo") *out = m_sunShadowInfoBuffer;
     else if (n == "mainPassMatrices" && m_sceneMatrices.bytes) *out = m_sceneMatrices.handle; // (exists once a scene was set)
+    else if (n == "sceneCulledDraws" && m_sceneCulledDraws.bytes) *out = m_sceneCulledDraws.handle; // (the cull buffers exist once culling was on with the mesh set present)
+    else if (n == "sceneCullStats" && m_sceneCullStats.bytes) *out = m_sceneCullStats.handle;
+    else if (n == "casterCullStats" && m_casterCullStats.bytes) *out = m_casterCullStats.handle; // 32 bytes per cascade
+    else if (n.size() == 18 && n.compare(0, 17, "casterCulledDraws") == 0 && n[17] >= '0' && n[17] <= '3' && m_casterCulledDraws[n[17] - '0'].bytes) *out = m_casterCulledDraws[n[17] - '0'].handle;
     else if (n == "sdfInstances") *out = m_sdfGi.m_sdfInstanceBuffer;
     else if (n == "sdfCulledInstances") *out = m_sdfGi.m_sdfCameraFrustumCulledInstances;
     else if (n == "sdfCulledTiles") *out = m_sdfGi.m_sdfCameraCulledTiles;
@@ -1317,9 +1322,13 @@ uint32_t rasterWrapStrips(const FramePipelineSettings& s, uint32_t outTiles[12])
 }
 
 // ---- RenderFrontend::renderSunShadowCascades (RenderFrontend.cpp:760-774, pass :1565-1590) as one compute execution per cascade ("sunShadowRaster.comp",
-// kernels/sun_shadow_raster.hip). The reference's coarse CPU frustum culling of the draws (:611-646) is not rebuilt: the set-up kernel rejects per triangle.
+// kernels/sun_shadow_raster.hip). The reference's coarse CPU frustum culling of the draws (:611-646) is "drawCulling.comp" here, while setDrawCulling has
+// kCullShadowCasters set: one execution for all cascades, behind computeSunLightMatrices and against the matrices it fitted, writes a culled copy of the draw
+// array per cascade, and each cascade binds its copy at the draw binding. Everything else of a cascade's record is what it is without culling.
 void FramePipeline::renderSunShadowCascades() {
     if (m_casterDrawCount == 0) return;
+    const bool culled = cullCasters();
+    if (culled) recordDrawCulling(true);
     for (int c = 0; c < settings.shading.sunShadowCascadeCount; c++) {
         ComputePassExecution exe;
         exe.genericInfo.handle = m_sunShadowRasterPass[c];
@@ -1329,7 +1338,7 @@ void FramePipeline::renderSunShadowCascades() {
                                                     StorageBufferResource(m_casterTransforms, true, plr::sunraster::kTransformBinding),
                                                     StorageBufferResource(m_casterPositions, true, plr::sunraster::kPositionBinding),
                                                     StorageBufferResource(m_casterIndices, true, plr::sunraster::kIndexBinding),
-                                                    StorageBufferResource(m_casterDraws, true, plr::sunraster::kDrawBinding),
+                                                    StorageBufferResource(culled ? m_casterCulledDraws[c].handle : m_casterDraws, true, plr::sunraster::kDrawBinding),
                                                     StorageBufferResource(m_casterScratch[c], false, plr::sunraster::kScratchBinding)};
         // without cutouts, or while every cutoff is 0: the 8-byte record
         const bool tested = m_casterAlphaTested && m_casterTextureCount;
@@ -1371,6 +1380,8 @@ void FramePipeline::setShadowCasters(const ShadowCasterMesh* meshes, uint32_t me
         m_casterDrawCount = m_casterTriangleCount = m_casterTextureCount = 0;
         m_casterAlphaTested = false;
         m_casterMeshVertexCounts.clear();
+        m_casterBoundsHost.clear();
+        m_casterBoundsUploaded = m_casterCullRecorded = false;
         return;
     }
     if (!meshes || !draws || meshCount == 0) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: draws without meshes");
@@ -1430,6 +1441,15 @@ void FramePipeline::setShadowCasters(const ShadowCasterMesh* meshes, uint32_t me
     for (uint32_t m = 0; m < meshCount; m++) m_casterMeshVertexCounts[m] = meshes[m].vertexCount;
     m_casterTextureCount = 0; // the cutouts belonged to the casters that were replaced
     m_casterAlphaTested = false;
+    { // the draws' local boxes: they live and die with the meshes
+        std::vector<const float*> meshPositions(meshCount);
+        std::vector<uint32_t> drawMeshes(drawCount);
+        for (uint32_t m = 0; m < meshCount; m++) meshPositions[m] = meshes[m].positions;
+        for (uint32_t d = 0; d < drawCount; d++) drawMeshes[d] = draws[d].mesh;
+        m_casterBoundsHost = packDrawBounds(meshPositions.data(), m_casterMeshVertexCounts.data(), meshCount, drawMeshes.data(), drawCount);
+    }
+    m_casterBoundsUploaded = m_casterCullRecorded = false;
+    prepareDrawCulling();
 }
 
 void FramePipeline::setShadowCasterCutouts(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts, uint32_t drawCount) {
@@ -1470,9 +1490,14 @@ ShadowRasterStats FramePipeline::shadowRasterStats(uint32_t cascade) {
 }
 
 // ---- RenderFrontend::renderDepthPrepass (RenderFrontend.cpp:792-802, pass :1717-1735) as one compute execution ("depthPrepassRaster.comp",
-// kernels/depth_prepass_raster.hip). No frustum culling of the draws on the host (:565-569): the set-up kernel clips and rejects per triangle.
+// kernels/depth_prepass_raster.hip). The reference's frustum culling of the draws on the host (:565-569) is "drawCulling.comp" here, while setDrawCulling has
+// kCullScene set: one execution in front of the pass writes a culled copy of the draw array, against the whole frame's jittered mvp (never a partition's
+// window), and the pass - every wrap strip of a band / tile pipeline included - binds the copy at the draw binding. Everything else of the record, drawCount and
+// triangleCount included, is what it is without culling: the set-up kernel still clips and rejects per triangle.
 void FramePipeline::renderDepthPrepass(const FrameRenderTargets& current) {
     if (m_sceneDrawCount == 0) return;
+    const bool culled = cullScene();
+    if (culled) recordDrawCulling(false);
     namespace pp = plr::prepass;
     ComputePassExecution exe;
     exe.genericInfo.handle = m_depthPrepassRasterPass;
@@ -1482,7 +1507,8 @@ void FramePipeline::renderDepthPrepass(const FrameRenderTargets& current) {
                                                ImageResource(m_specularImage, 0, pp::kSpecularBinding)};
     exe.genericInfo.resources.storageBuffers = {StorageBufferResource(m_sceneMatrices.handle, true, pp::kTransformBinding), StorageBufferResource(m_scenePositions.handle, true, pp::kPositionBinding),
                                                 StorageBufferResource(m_sceneNormals.handle, true, pp::kNormalBinding), StorageBufferResource(m_sceneIndices.handle, true, pp::kIndexBinding),
-                                                StorageBufferResource(m_sceneDraws.handle, true, pp::kDrawBinding), StorageBufferResource(m_sceneScratch.handle, false, pp::kScratchBinding)};
+                                                StorageBufferResource(culled ? m_sceneCulledDraws.handle : m_sceneDraws.handle, true, pp::kDrawBinding),
+                                                StorageBufferResource(m_sceneScratch.handle, false, pp::kScratchBinding)};
     const bool alphaTested = m_sceneAlphaTested && m_sceneTextureCount;
     const bool compressed = m_sceneTexturesCompressed && m_sceneTextureCount;
     const bool anisotropic = m_sceneMaxAnisotropy >= 2u && m_sceneTextureCount;
@@ -1522,6 +1548,90 @@ void FramePipeline::renderDepthPrepass(const FrameRenderTargets& current) {
     m_sceneRecorded = true;
 }
 
+// ---- "drawCulling.comp" (kernels/draw_culling.hip; DESIGN.md "Frustum culling of draws")
+void FramePipeline::setDrawCulling(uint32_t flags) {
+    if (flags & ~(kCullScene | kCullShadowCasters))
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setDrawCulling: unknown flag bits " + std::to_string(flags & ~(kCullScene | kCullShadowCasters)) + " (1: the scene's draws, 2: the shadow casters)");
+    if (partitionedWithoutRaster(m_requestedSettings))
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setDrawCulling: a band / tile pipeline cannot rasterise scene meshes or shadow casters, so there is nothing to cull");
+    if ((flags ^ m_cullFlags) & kCullScene) m_sceneCullRecorded = false;
+    if ((flags ^ m_cullFlags) & kCullShadowCasters) m_casterCullRecorded = false;
+    m_cullFlags = flags;
+    prepareDrawCulling();
+}
+
+// the passes and the buffers of the views that are on and have their mesh set: created or grown here, from the calls that change either, never while a frame is
+// recorded. A view that is off allocates nothing
+void FramePipeline::prepareDrawCulling() {
+    namespace dc = plr::drawcull;
+    if (!cullScene() && !cullCasters()) return;
+    if (!m_cullPassesCreated) {
+        for (int k = 0; k < 2; k++) {
+            ComputePassDescription d;
+            d.name = k == 0 ? "Draw culling, main view" : "Draw culling, shadow cascades";
+            d.shaderDescription.srcPathRelative = "drawCulling.comp";
+            m_drawCullingPass[k] = m_be.createComputePass(d);
+        }
+        m_cullPassesCreated = true;
+    }
+    auto fill = [&](SceneBuffer& b, const void* data, size_t bytes) { fillCasterBuffer(b.handle, b.bytes, data, bytes); };
+    if (cullScene() && !m_sceneBoundsUploaded) {
+        fill(m_sceneBounds, m_sceneBoundsHost.data(), m_sceneBoundsHost.size() * sizeof(float));
+        fill(m_sceneCulledDraws, nullptr, (size_t)m_sceneDrawCount * sizeof(plr::prepass::Draw));
+        fill(m_sceneCullStats, nullptr, dc::statsBytes(1));
+        m_sceneBoundsUploaded = true;
+    }
+    if (cullCasters() && !m_casterBoundsUploaded) {
+        fill(m_casterBounds, m_casterBoundsHost.data(), m_casterBoundsHost.size() * sizeof(float));
+        for (int c = 0; c < settings.shading.sunShadowCascadeCount; c++) fill(m_casterCulledDraws[c], nullptr, (size_t)m_casterDrawCount * sizeof(plr::sunraster::Draw));
+        fill(m_casterCullStats, nullptr, dc::statsBytes(dc::kMaxViews));
+        m_casterBoundsUploaded = true;
+    }
+}
+
+void FramePipeline::recordDrawCulling(bool shadowViews) {
+    namespace dc = plr::drawcull;
+    ComputePassExecution exe;
+    exe.genericInfo.handle = m_drawCullingPass[shadowViews ? 1 : 0];
+    exe.dispatchCount[0] = exe.dispatchCount[1] = exe.dispatchCount[2] = 1;
+    auto& buffers = exe.genericInfo.resources.storageBuffers;
+    if (!shadowViews) {
+        buffers = {StorageBufferResource(m_sceneDraws.handle, true, dc::kDrawBinding), StorageBufferResource(m_sceneBounds.handle, true, dc::kBoundsBinding),
+                   StorageBufferResource(m_sceneMatrices.handle, true, dc::kTransformBinding), StorageBufferResource(m_sceneCullStats.handle, false, dc::kStatsBinding),
+                   StorageBufferResource(m_sceneCulledDraws.handle, false, dc::kCulledDrawBinding)};
+        const dc::PushConstants pc{m_sceneDrawCount, dc::kViewMain, 1u};
+        exe.pushConstants = dataToCharArray(&pc, sizeof(pc));
+        m_sceneCullRecorded = true;
+    } else {
+        const uint32_t cascades = (uint32_t)settings.shading.sunShadowCascadeCount;
+        buffers = {StorageBufferResource(m_casterDraws, true, dc::kDrawBinding), StorageBufferResource(m_casterBounds.handle, true, dc::kBoundsBinding),
+                   StorageBufferResource(m_casterTransforms, true, dc::kTransformBinding), StorageBufferResource(m_sunShadowInfoBuffer, true, dc::kSunShadowInfoBinding),
+                   StorageBufferResource(m_casterCullStats.handle, false, dc::kStatsBinding)};
+        for (uint32_t c = 0; c < cascades; c++) buffers.push_back(StorageBufferResource(m_casterCulledDraws[c].handle, false, dc::kCulledDrawBinding + (int)c));
+        const dc::PushConstants pc{m_casterDrawCount, dc::kViewShadow, cascades};
+        exe.pushConstants = dataToCharArray(&pc, sizeof(pc));
+        m_casterCullRecorded = true;
+    }
+    m_be.setComputePassExecution(exe);
+}
+
+FramePipeline::DrawCullingStats FramePipeline::drawCullingStats(uint32_t view) {
+    namespace dc = plr::drawcull;
+    const uint32_t cascades = (uint32_t)settings.shading.sunShadowCascadeCount;
+    if (view >= 1u + cascades)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "drawCullingStats: view " + std::to_string(view) + " of " + std::to_string(1u + cascades) + " (0: the main pass, 1 + c: cascade c)");
+    DrawCullingStats out;
+    const bool main = view == 0u;
+    if (main ? !(cullScene() && m_sceneCullRecorded) : !(cullCasters() && m_casterCullRecorded)) return out;
+    dc::ViewStats s{};
+    const StorageBufferHandle buffer = main ? m_sceneCullStats.handle : m_casterCullStats.handle;
+    if (plr_download_storage_buffer(buffer.index, &s, main ? 0u : (size_t)(view - 1u) * sizeof(s), sizeof(s)) != PLR_OK) throw std::runtime_error(plr_last_error());
+    out.draws = main ? m_sceneDrawCount : m_casterDrawCount; out.triangles = main ? m_sceneTriangleCount : m_casterTriangleCount;
+    out.visibleDraws = s.visibleDraws; out.visibleTriangles = s.visibleTriangles;
+    for (uint32_t k = 0; k < dc::kPlaneCount; k++) out.culledByPlane[k] = s.culledByPlane[k];
+    return out;
+}
+
 // MainPassMatrices per draw (RenderFrontend.cpp:581-585): {model, mvp = viewProjection * model, mvpPrevious = viewProjectionPrevious * previousModel}. A draw's
 // previous model matrix is the one the last recorded frame used (obj.previousModelMatrix, :584); the current one on the first frame of a scene and on a camera cut
 void FramePipeline::updateMainPassMatrices() {
@@ -1550,6 +1660,8 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
         m_sceneMeshVertexCounts.clear(); m_sceneMeshHasNormals.clear(); m_sceneNormalsHost.clear();
         removeSceneSdf(); // its mesh indices named the scene that is gone
         m_scenePositionsHost.clear(); m_sceneIndicesHost.clear(); m_sceneDrawMeshes.clear(); m_sceneMeshFirstIndex.clear(); m_sceneMeshIndexCounts.clear();
+        m_sceneBoundsHost.clear();
+        m_sceneBoundsUploaded = m_sceneCullRecorded = false;
         return;
     }
     const PackedScene packed = packSceneMeshes(meshes, meshCount, draws, drawCount); // validates everything before anything is changed
@@ -1580,6 +1692,9 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
     m_sceneNormalsHost = packed.normals;
     m_scenePositionsHost = packed.positions; m_sceneIndicesHost = packed.indices; // what a later setSceneSdf takes the local boxes and the bake from
     m_sceneDrawMeshes = packed.drawMeshes; m_sceneMeshFirstIndex = packed.meshFirstIndex; m_sceneMeshIndexCounts = packed.meshIndexCounts;
+    m_sceneBoundsHost = packed.drawBounds; // they live and die with the meshes
+    m_sceneBoundsUploaded = m_sceneCullRecorded = false;
+    prepareDrawCulling();
 }
 
 void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {

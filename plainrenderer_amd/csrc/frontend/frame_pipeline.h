@@ -347,7 +347,12 @@ struct PackedScene {
     std::vector<uint8_t> meshHasNormals;           // per mesh: given with vertex normals (packSceneNormalMaps derives bitangents from them)
     std::vector<uint32_t> drawMeshes;              // per draw: its mesh (packSceneSdf maps draws to SDF instances by it)
     std::vector<uint32_t> meshFirstIndex, meshIndexCounts; // per mesh: where its triangle list lies in `indices` (setSceneSdf bakes from it)
+    std::vector<float> drawBounds;                 // 6 floats per draw {lo.xyz, hi.xyz}: packDrawBounds ("drawCulling.comp"'s bounds)
 };
+// the bounds buffer of "drawCulling.comp" (device/draw_culling.h): per draw the local box of its mesh over ALL the mesh's vertices (indexed or not), exact fp32
+// minima and maxima; an axis on which a vertex is a NaN gets NaN bounds (the pass keeps such a draw), a mesh without vertices an all-zero box. Throws
+// FramePipelineRefusal for a draw that names no mesh
+std::vector<float> packDrawBounds(const float* const* meshPositions, const uint32_t* meshVertexCounts, uint32_t meshCount, const uint32_t* drawMeshes, uint32_t drawCount);
 PackedScene packSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const SceneDraw* draws, uint32_t drawCount);
 void refuseNonFiniteMatrices(const float* matrices16, uint32_t drawCount, const char* call);
 // material textures of the scene meshes (plr_frame.h plrf_set_scene_textures): RGBA8 texels, R in the low byte; mipCount levels back to back, or 0: level 0
@@ -517,6 +522,20 @@ public:
     void setSceneAnisotropy(uint32_t maxAnisotropy);
     // counters of the last frame's execution for the scene now set; waits for the GPU. Zero while no scene is set and before the first frame of a newly set scene.
     PrepassRasterStats prepassRasterStats();
+    // frustum culling of whole draws on the GPU ("drawCulling.comp", kernels/draw_culling.hip; DESIGN.md "Frustum culling of draws"): kCullScene culls the depth
+    // prepass's draws against the frame's own jittered viewProjection (one execution in front of the prepass, wherever the prepass is recorded), kCullShadowCasters
+    // the casters per cascade against that frame's light matrices (one execution for all cascades behind computeSunLightMatrices, in front of the first cascade).
+    // The rasterisers then bind the culled copy of their draw array - wrap strips of a band / tile pipeline the same copy -, and their images are byte for byte
+    // what they are without culling; their counters count the kept draws only. The flags take effect with the next frame and hold until changed, across
+    // setSceneMeshes, setShadowCasters, setResolution and updateSettings; a flag whose mesh set is absent does nothing until one is set. A pipeline that never
+    // sets a flag records, creates and allocates nothing for it. Refusals: unknown bits are PLR_ERR_INVALID_ARGUMENT, a band / tile pipeline without band.raster
+    // is PLR_ERR_UNSUPPORTED. A refused call changes nothing.
+    static constexpr uint32_t kCullScene = 1u, kCullShadowCasters = 2u;
+    void setDrawCulling(uint32_t flags);
+    // counters of the last frame's cull execution; view 0: the main pass, 1 + c: cascade c. Waits for the GPU. All zero for a view that is off, absent or not yet
+    // rendered; a view at or past 1 + the cascade count is refused (PLR_ERR_INVALID_ARGUMENT)
+    struct DrawCullingStats { uint32_t draws = 0, visibleDraws = 0; uint64_t triangles = 0, visibleTriangles = 0; uint32_t culledByPlane[5] = {0, 0, 0, 0, 0}; };
+    DrawCullingStats drawCullingStats(uint32_t view);
     // SDFGI::updateSDFScene (Techniques/SDFGI.cpp:260-313) as "sdfInstanceUpdate.comp" (kernels/scene_sdf.hip; DESIGN.md "SDF instances from the scene"): while a
     // scene SDF is set every frame that records the GI trace or the SDF debug view records one execution in front of the camera frustum culling that writes
     // sdfInstances and sdfWorldBBs from mainPassMatrices, and - in a frame after the texture store or the materials changed - "sceneMeanAlbedo.comp" in front of it.
@@ -681,6 +700,18 @@ private:
     uint32_t m_sceneSdfMeanGroups = 1; // dispatch_count[0] of "sceneMeanAlbedo.comp": from the largest level 0 of the store
     struct BakedVolume { ImageHandle image; bool inUse = false; uint64_t bytes = 0; };
     std::vector<BakedVolume> m_sceneSdfVolumes; // images of baked volumes: released (re-created at 1 x 1 x 1) with the scene's SDF, re-used by the next bake
+    // draw culling: the pass and the GPU buffers are created by the first setDrawCulling with a flag (and by a mesh call while a flag is set); the host keeps the
+    // per-draw local boxes of both mesh sets from the moment the meshes are set - they live and die with the meshes
+    uint32_t m_cullFlags = 0;
+    bool m_cullPassesCreated = false, m_sceneCullRecorded = false, m_casterCullRecorded = false; // recorded: a frame has run the cull for the mesh set and flags now set
+    RenderPassHandle m_drawCullingPass[2]; // main view, shadow views
+    std::vector<float> m_sceneBoundsHost, m_casterBoundsHost;
+    bool m_sceneBoundsUploaded = false, m_casterBoundsUploaded = false;
+    SceneBuffer m_sceneBounds, m_sceneCulledDraws, m_sceneCullStats, m_casterBounds, m_casterCulledDraws[4], m_casterCullStats;
+    bool cullScene() const { return (m_cullFlags & kCullScene) != 0 && m_sceneDrawCount != 0; }
+    bool cullCasters() const { return (m_cullFlags & kCullShadowCasters) != 0 && m_casterDrawCount != 0; }
+    void prepareDrawCulling();
+    void recordDrawCulling(bool shadowViews);
     void removeSceneSdf();
     void updateSceneSdfInstances();
     void noteSceneTexturesChanged(uint32_t maxLevel0Texels);

@@ -2,7 +2,7 @@
 // (FramePipeline::setSceneMeshes, setSceneTextures, setSceneTexturesFormatted, setSceneAlphaCutoffs, setSceneNormalMaps) and of the shadow casters' cutouts for
 // "sunShadowRaster.comp" (setShadowCasterCutouts), and the host's decoder of BC1 / BC3 / BC5 blocks: host code without a backend call, so that a stand-alone
 // program can run it under a sanitizer (tools/scene_packing_check.cpp, tools/scene_texture_check.cpp, tools/scene_alpha_check.cpp, tools/scene_normal_check.cpp,
-// tools/shadow_cutout_check.cpp, tools/scene_bc_check.cpp).
+// tools/shadow_cutout_check.cpp, tools/scene_bc_check.cpp, tools/draw_bounds_check.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -19,6 +19,35 @@ void refuseNonFiniteMatrices(const float* matrices16, uint32_t drawCount, const 
             if (!std::isfinite(matrices16[(size_t)d * 16u + e]))
                 throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": non-finite matrix element: element " + std::to_string(e) + " of the model matrix of draw " +
                                            std::to_string(d));
+}
+
+std::vector<float> packDrawBounds(const float* const* meshPositions, const uint32_t* meshVertexCounts, uint32_t meshCount, const uint32_t* drawMeshes, uint32_t drawCount) {
+    std::vector<float> boxes((size_t)meshCount * 6u, 0.f); // (a mesh without vertices: all zero; its draws hold no triangle)
+    for (uint32_t m = 0; m < meshCount; m++) {
+        const float* p = meshPositions[m];
+        const uint32_t n = meshVertexCounts[m];
+        if (n == 0 || !p) continue;
+        float* box = boxes.data() + (size_t)m * 6u;
+        for (int a = 0; a < 3; a++) {
+            float lo = p[a], hi = p[a];
+            bool nan = lo != lo;
+            for (uint32_t v = 1; v < n; v++) {
+                const float x = p[(size_t)v * 3u + a];
+                if (x != x) nan = true;
+                if (x < lo) lo = x;
+                if (x > hi) hi = x;
+            }
+            box[a] = nan ? std::nanf("") : lo;
+            box[3 + a] = nan ? std::nanf("") : hi;
+        }
+    }
+    std::vector<float> out((size_t)drawCount * 6u);
+    for (uint32_t d = 0; d < drawCount; d++) {
+        if (drawMeshes[d] >= meshCount)
+            throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "packDrawBounds: mesh index out of range: draw " + std::to_string(d) + " names mesh " + std::to_string(drawMeshes[d]) + " of " + std::to_string(meshCount));
+        std::memcpy(out.data() + (size_t)d * 6u, boxes.data() + (size_t)drawMeshes[d] * 6u, 24);
+    }
+    return out;
 }
 
 // everything is validated before anything is built; the caller changes its state only with the result in hand
@@ -77,6 +106,9 @@ PackedScene packSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const S
     out.meshFirstIndex = firstIndex;
     out.meshIndexCounts.resize(meshCount);
     for (uint32_t m = 0; m < meshCount; m++) out.meshIndexCounts[m] = meshes[m].indexCount;
+    std::vector<const float*> meshPositions(meshCount);
+    for (uint32_t m = 0; m < meshCount; m++) meshPositions[m] = meshes[m].positions;
+    out.drawBounds = packDrawBounds(meshPositions.data(), out.meshVertexCounts.data(), meshCount, out.drawMeshes.data(), drawCount);
     return out;
 }
 

@@ -91,6 +91,12 @@ class PlrfPrepassRasterStats(C.Structure):
     _fields_ = [("triangles_submitted", C.c_uint64), ("triangles_clipped", C.c_uint64), ("subtriangles_drawn", C.c_uint64), ("rejects", C.c_uint64)]
 
 
+class PlrfDrawCullingStats(C.Structure):
+    _fields_ = [("draws", C.c_uint32), ("visible_draws", C.c_uint32), ("triangles", C.c_uint64), ("visible_triangles", C.c_uint64), ("culled_by_plane", C.c_uint32 * 5)]
+
+
+CULL_SCENE, CULL_SHADOW_CASTERS = 1, 2  # PLRF_CULL_SCENE, PLRF_CULL_SHADOW_CASTERS
+
 SDF_BAKE = 0xFFFFFFFE  # PLRF_SDF_BAKE
 
 
@@ -452,6 +458,23 @@ class FramePipeline:
         s = PlrfPrepassRasterStats()
         self._check(self.lib.plrf_get_prepass_raster_stats(self.handle, C.byref(s)))
         return int(s.triangles_submitted), int(s.triangles_clipped), int(s.subtriangles_drawn), int(s.rejects)
+
+    # ---- frustum culling of draws (include/plr_frame.h plrf_set_draw_culling): "drawCulling.comp" in front of the two rasterisers
+    def set_draw_culling(self, flags):
+        """CULL_SCENE (1): the depth prepass's draws against the frame's own jittered viewProjection; CULL_SHADOW_CASTERS (2): the casters, per cascade, against
+        that frame's light matrices. From the next frame on, until changed; 0 turns it off. The rasterisers' images do not change, their counters count the kept
+        draws only"""
+        self.lib.plrf_set_draw_culling.argtypes = [C.c_void_p, C.c_uint32]
+        self._check(self.lib.plrf_set_draw_culling(self.handle, C.c_uint32(int(flags))))
+
+    def draw_culling_stats(self, view):
+        """dict(draws, visible_draws, triangles, visible_triangles, culled_by_plane [near, +x, -x, +y, -y]) of the last frame's cull execution for view 0 (the
+        main pass) or 1 + c (cascade c); waits for the GPU. All zero for a view that is off, absent or not yet rendered"""
+        s = PlrfDrawCullingStats()
+        self.lib.plrf_get_draw_culling_stats.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        self._check(self.lib.plrf_get_draw_culling_stats(self.handle, C.c_uint32(int(view)), C.byref(s)))
+        return dict(draws=int(s.draws), visible_draws=int(s.visible_draws), triangles=int(s.triangles), visible_triangles=int(s.visible_triangles),
+                    culled_by_plane=[int(v) for v in s.culled_by_plane])
 
     # ---- the scene's SDF (include/plr_frame.h plrf_set_scene_sdf): sdfInstances and sdfWorldBBs written every frame by "sdfInstanceUpdate.comp"
     def set_scene_sdf(self, sdf_textures):
