@@ -1430,7 +1430,8 @@ static int refuseStaleReads(const Execution& x, const Execution* group, size_t g
 
 // Pass fusion level 2 for a producer whose consumer takes its output through another channel (PassCtx::consumer: the spatial GI filter gathers the packed
 // texels its producer writes, fused_gi.h): a storage image of the producer is elidable when nothing can ever read what the producer would have written to it:
-//  * behind the producer, nothing but the consumer touches it in this frame (a later "write" may read as well: a storage binding, an exchange callback);
+//  * behind the producer, nothing but the consumer touches it in this frame (a later "write" may read as well: a storage binding, an exchange callback) -
+//    except a write by a producer of a consumer link, which only stores (below): the temporal filter overwrites the trace's two targets behind spatial filter 0;
 //  * the frame's first access to it is a write by a producer of a consumer link - this execution itself or another (the trace): those launchers only store to
 //    their outputs, so the next frame, recorded alike, overwrites the image before anything reads it.
 // (A host that asks for the image gets the loud "not written" error, as for a fused launch.)
@@ -1452,7 +1453,7 @@ static void markElidableBehindConsumer(Execution& x) {
             for (const Access& a : g->executions[j].access) {
                 if (a.key != key) continue;
                 if (first) { first = false; if (!a.write || !linkProducer(g->executions[j])) ok = false; }
-                if (j > index && &g->executions[j].ctx != x.ctx.consumer) ok = false;
+                if (j > index && &g->executions[j].ctx != x.ctx.consumer && !(a.write && linkProducer(g->executions[j]))) ok = false;
             }
         if (ok) x.ctx.elidableStorage |= 1u << b;
     }

@@ -263,7 +263,9 @@ struct RayInfo { float nx, ny, nz, depth, cr, cg, cb; };
 // SIG: also write the decision signature of every pixel (plr_debug_set_decision_signature; bit layout in oracle/oracle.h)
 // PACK: also write the packed texel the spatial filter gathers (fused_gi.h); 0 = no, else the format of packDepth (F_R16F / F_D32)
 // BRICKS: march through the volumes' copies in cache-line bricks (device/sdf_bricks.h; PLR_TRACE_BRICKS=1: measured, not the default)
-template <bool STRICT_CUTOFF, bool SIG, int PACK, bool PER_LANE = false, bool BRICKS = false>
+// PACKED_ONLY: the packed texel is all anybody will read of this pass's result (PassCtx::elidableStorage on both outputs, as
+// temporalGiFilterFastKernel<PACK, PACKED_ONLY>): the two image stores (12 of the pass's 28 output bytes per pixel, 25 MB of the 4K frame) are left out
+template <bool STRICT_CUTOFF, bool SIG, int PACK, bool PER_LANE = false, bool BRICKS = false, bool PACKED_ONLY = false>
 __global__ __launch_bounds__(256) PLR_TRACE_OCC void sdfDiffuseTraceFastKernel(ImgView outYSH, ImgView outCoCg, ImgView depthTexture, ImgView normalTexture, ImgView skyLut,
                                                                  const LightBuffer* __restrict__ light, const SdfInstanceBuffer* __restrict__ instanceBuffer,
                                                                  const CulledInstancesPerTile* __restrict__ tiles, const float* __restrict__ influenceRangeP,
@@ -451,10 +453,17 @@ __global__ __launch_bounds__(256) PLR_TRACE_OCC void sdfDiffuseTraceFastKernel(I
         const vec4 ysh(YCoCg.x * 0.5f, YCoCg.x * (-0.8660254f * L.y), YCoCg.x * (0.8660254f * L.z), YCoCg.x * (-0.8660254f * L.x));
         const size_t idx = (size_t)py * (size_t)outYSH.w + px;
         const uint2 yBits = make_uint2(floatToHalfBits(ysh.x) | (floatToHalfBits(ysh.y) << 16), floatToHalfBits(ysh.z) | (floatToHalfBits(ysh.w) << 16));
-        const uint32_t cBits = floatToHalfBits(YCoCg.y) | (floatToHalfBits(YCoCg.z) << 16);
+        // Cg must exist as a rounded fp32 number before it is converted: the compiler otherwise folds its last subtraction into the conversion (v_fma_mixlo_f16,
+        // one rounding less) in the instantiations where the fp32 value has no other use - PACKED_ONLY did, the storing ones did not, and a texel in some
+        // thousands differed by a half-float ulp between a fused and an unfused frame. (Co is a single v_fma_mixlo_f16 of two exact products in every instantiation.)
+        float cg = YCoCg.z;
+        asm("" : "+v"(cg));
+        const uint32_t cBits = floatToHalfBits(YCoCg.y) | (floatToHalfBits(cg) << 16);
         const bool through = ranges.isEdge((int)blockIdx.y); // rows a neighbouring GPU is waiting for: written through (backend.h TwoRanges)
-        storeOut((uint2*)outYSH.ptr + idx, yBits, through);
-        storeOut((uint32_t*)outCoCg.ptr + idx, cBits, through);
+        if (!PACKED_ONLY) {
+            storeOut((uint2*)outYSH.ptr + idx, yBits, through);
+            storeOut((uint32_t*)outCoCg.ptr + idx, cBits, through);
+        }
         if (PACK) packedOut[idx] = packGiTexel(yBits, cBits, Texel<PACK == 0 ? F_R16F : PACK>::load(packDepth.ptr, idx).x, g->nearPlane, g->farPlane);
         if (SIG) sig[idx] = raySig | (takeMask << 3);
     }
@@ -526,6 +535,11 @@ static int brickedVolumeTable(const PassCtx& c, const uint16_t* const** out) {
     return 0;
 }
 
+static bool packedOnlySwitchOn() { // on unless the environment says PLR_TRACE_PACKED_ONLY=0
+    const char* v = std::getenv("PLR_TRACE_PACKED_ONLY");
+    return !(v && v[0] == '0' && v[1] == 0);
+}
+
 static int launchImpl(const PassCtx& c) {
     if (int rc = c.needGlobal()) return rc;
     if (int rc = c.needStorage(0, F_RGBA16F, "sdfDiffuseTrace imageOut_Y_SH")) return rc;
@@ -579,6 +593,12 @@ static int launchImpl(const PassCtx& c) {
     const SpatialPackTarget* pack = !sig && spatialPackTargetOfConsumer(c, 0, 1, &packTarget) == 0 ? &packTarget : nullptr;
     // (what the launch packs is noted as a rectangle: the columns of the dispatch, not whole rows - ADVICE r03)
     if (pack && (pack->depth.w != out.w || pack->depth.h != out.h || (pack->depth.fmt != F_R16F && pack->depth.fmt != F_D32))) pack = nullptr;
+    // a launch that packs every texel of the consumer's input, and whose two output images nothing else will read (fusion level 2): packed texels only, as
+    // launchTemporalGi selects it (a signature run has no pack target). PLR_TRACE_PACKED_ONLY=0 (read per launch, as PLR_SHADE_SKIP_UNLIT: tests switch it) keeps
+    // the stores. The PER_LANE and BRICKS variants always store.
+    const bool packedOnly = pack && (c.elidableStorage & 3u) == 3u && groupX0 == 0 && groupY0 == 0 && groupsX * 8 >= (int)out.w && groupsY * 8 >= (int)out.h &&
+                            !c.extraCountY && !c.firstRows[0] && !c.firstRows[1] && !c.firstCols[0] && !c.firstCols[1] && packedOnlySwitchOn();
+    bool elided = false;
     if (pack) {
         // fused with the spatial filter that reads this pass's output (fused_gi.h); never together with a signature run
         if (pack->depth.w != out.w || pack->depth.h != out.h) return kUseGeneralKernel;
@@ -595,10 +615,14 @@ static int launchImpl(const PassCtx& c) {
             if (bricksMode >= 2 && !brickedVolumes) return c.fail(-1, "sdfDiffuseTrace: PLR_TRACE_BRICKS=2 but this launch cannot march bricked volumes");
             if (brickedVolumes) sdfDiffuseTraceFastKernel<true, false, F_R16F, false, true><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS);
             else if (strict && perLane) sdfDiffuseTraceFastKernel<true, false, F_R16F, true><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS);
+            else if (strict && packedOnly) { sdfDiffuseTraceFastKernel<true, false, F_R16F, false, false, true><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS); elided = true; }
             else if (strict) sdfDiffuseTraceFastKernel<true, false, F_R16F><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS);
+            else if (packedOnly) { sdfDiffuseTraceFastKernel<false, false, F_R16F, false, false, true><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS); elided = true; }
             else sdfDiffuseTraceFastKernel<false, false, F_R16F><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS);
         } else if (pack->depth.fmt == F_D32) {
-            if (strict) sdfDiffuseTraceFastKernel<true, false, F_D32><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS);
+            if (strict && packedOnly) { sdfDiffuseTraceFastKernel<true, false, F_D32, false, false, true><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS); elided = true; }
+            else if (strict) sdfDiffuseTraceFastKernel<true, false, F_D32><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS);
+            else if (packedOnly) { sdfDiffuseTraceFastKernel<false, false, F_D32, false, false, true><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS); elided = true; }
             else sdfDiffuseTraceFastKernel<false, false, F_D32><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS);
         } else return kUseGeneralKernel;
     } else if (sig) {
@@ -607,6 +631,7 @@ static int launchImpl(const PassCtx& c) {
     } else if (strict) sdfDiffuseTraceFastKernel<true, false, 0><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS);
     else sdfDiffuseTraceFastKernel<false, false, 0><<<grid, 256, 0, c.stream>>>(PLR_TRACE_ARGS);
 #undef PLR_TRACE_ARGS
+    if (elided) c.elidedStorage = 3u;
     PLR_CHECK_LAUNCH(c);
     if (pack) {
         const int px0 = std::min(groupX0 * 8, (int)out.w), px1 = std::min(groupsX * 8, (int)out.w);
