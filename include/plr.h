@@ -371,6 +371,19 @@ int plr_debug_shade_sky_exit_waves(int enable, uint64_t* out_waves);
  * Same arguments as the oracle's orc_sampler_eval. */
 int plr_debug_sampler_eval(plr_image_handle image, uint32_t mip_level, int filter, int address, const float* coords, float* out, int64_t n);
 
+/* ---- the input tables of the noise passes "blueNoiseVoidAndCluster.comp" and "perlinNoise3D.comp" (DESIGN.md "Noise textures as compute passes": the reference's
+ * generateBlueNoiseTexture and generate3DPerlinNoise, Common/Noise.cpp:232-300 and :422-497, as compute passes). Host code: both work without a GPU and before
+ * plr_setup. The passes take the tables as storage buffers, so their bytes are a function of the tables and the seed alone.
+ * plr_noise_gaussian_table: out[dy * width + dx] = the influence of a pixel on the pixel (dx, dy) further on, on the torus: exp, in double and rounded once to fp32,
+ *   of the fp32 argument -float(r2) / (2.f * (1.9f * 1.9f)), r2 = min(dx, width - dx)^2 + min(dy, height - dy)^2 (gaussianFilter, Noise.cpp:80-85). width and
+ *   height 4 .. 64; out holds width * height floats.
+ * plr_noise_perlin_gradients: out[4 c ..] = (sin rx cos ry, sin rx sin rx, cos rx, 0) for cell c = (x g + y) g + z - the repeated sin rx is the reference's
+ *   (Noise.cpp:444) -, in double from the fp32 angles rx = float(lowbias32(key + 2 c) >> 8) * 2^-24 * (2.f * 3.1415f), ry the same with key + 2 c + 1, rounded once
+ *   to fp32; key = lowbias32(seed ^ (0x9E3779B9u * 9)) (stream 8 of the seed). grid_cell_count 1 .. 32; out holds 4 * grid_cell_count^3 floats.
+ * PLR_ERR_INVALID_ARGUMENT: a null pointer or a size outside the range. */
+int plr_noise_gaussian_table(uint32_t width, uint32_t height, float* out);
+int plr_noise_perlin_gradients(uint32_t seed, uint32_t grid_cell_count, float* out);
+
 #ifdef __cplusplus
 }
 #endif

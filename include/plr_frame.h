@@ -480,6 +480,25 @@ typedef struct plrf_draw_culling_stats {
     uint32_t culled_by_plane[5];            /* near, +x, -x, +y, -y; shadow views leave [0] at 0 */
 } plrf_draw_culling_stats;
 int plrf_get_draw_culling_stats(void* pipeline, uint32_t view, plrf_draw_culling_stats* out); /* view 0: main pass; 1 + c: cascade c */
+/* ---- the frame's noise inputs, generated on the GPU: the four 32 x 32 RG8 void-and-cluster blue-noise textures "noise0" .. "noise3" (generateBlueNoiseTexture,
+ * Common/Noise.cpp:232-300, called at RenderFrontend.cpp:1251-1269) as the compute pass "blueNoiseVoidAndCluster.comp", and the 32^3 R8 Perlin volume
+ * "perlinNoise3D" of the froxel material pass (generate3DPerlinNoise, Noise.cpp:422-497, Volumetrics.cpp:71-90: 8 grid cells) as "perlinNoise3D.comp" (DESIGN.md
+ * "Noise textures as compute passes": the contract in integers and IEEE fp32, and its four deviations from Noise.cpp - rand() is a hash of the seed, the index pitch
+ * is the width, the prototype loop stops after N swaps at the latest, the cluster search needs no FLT_MIN start).
+ * The next plrf_frame records, once and in front of everything else, four executions of the blue-noise pass (texture t takes streams 2 t and 2 t + 1 of the seed, one
+ * 1024-lane block per channel) and / or one of the Perlin pass; the tables the passes read come from plr_noise_gaussian_table and plr_noise_perlin_gradients
+ * (plr.h). After that frame the images stay as written until the caller uploads to them or calls again; a call before that frame replaces the seed of the kinds it
+ * names. Everything the frame derives from a noise texture (the deferred shade's tap table by noise-texel position) rebuilds itself, as after an upload. Without
+ * the call nothing is recorded, created or allocated, and the images hold what the caller uploads (zeros if nothing). The bytes are a pure function of the seed:
+ * the ranks of a band / tile partition call it with one seed and agree without an exchange.
+ * plrf_get_noise_stats: {swaps, converged, ones, 0} of the prototype loop per texture and channel, as the last blue-noise generation a frame has run wrote them
+ * (32 x 32: ones = 102, 28 .. 41 swaps for seeds 1 .. 8); waits for the GPU; zeros before there is one.
+ * PLR_ERR_INVALID_ARGUMENT: flags 0 or unknown bits; PLRF_NOISE_PERLIN on a pipeline that has no perlinNoise3D image. A refused call changes nothing. */
+#define PLRF_NOISE_BLUE   1u
+#define PLRF_NOISE_PERLIN 2u
+int plrf_generate_noise(void* pipeline, uint32_t seed, uint32_t flags);
+typedef struct plrf_noise_stats { uint32_t status[4][2][4]; } plrf_noise_stats; /* [texture][channel]{swaps, converged, ones, 0} */
+int plrf_get_noise_stats(void* pipeline, plrf_noise_stats* out);
 /* one iteration of the reference's main loop: record the frame, update camera/UBOs, submit (does not wait for the GPU) */
 int plrf_frame(void* pipeline, const plrf_camera* camera, float delta_time, float time);
 /* host copies of what the last plrf_frame submitted (340-byte global UBO image, 9 TAA resolve weights) */

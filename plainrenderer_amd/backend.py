@@ -226,8 +226,27 @@ EXPORTED_SYMBOLS = [
     "plr_replay_frame", "plr_upload_image", "plr_download_image", "plr_download_storage_buffer", "plr_download_uniform_buffer",
     "plr_get_image_device_pointer", "plr_get_storage_buffer_device_pointer", "plr_get_stream", "plr_get_launch_stream", "plr_copy_device_memory", "plr_read_device_memory", "plr_write_device_memory", "plr_get_supported_shaders",
     "plr_debug_math_eval", "plr_debug_codec_eval", "plr_debug_sampler_eval", "plr_debug_sky_lut_eval", "plr_debug_verify_histogram_thresholds", "plr_debug_verify_r11g11b10_fast", "plr_debug_shade_sky_exit_switch", "plr_debug_shade_sky_exit_waves", "plr_debug_set_decision_signature", "plr_debug_read_decision_signature", "plr_set_math_mode", "plr_get_math_mode", "plr_set_stream_overlap", "plr_get_stream_overlap", "plr_set_pass_fusion", "plr_get_pass_fusion", "plr_set_pass_fusion_reorder", "plr_get_general_kernel_executions", "plr_get_edge_signal", "plr_set_async_tail", "plr_get_async_tail", "plr_set_early_parts", "plr_get_early_parts", "plr_set_host_callback_execution", "plr_set_host_callback_execution_on", "plr_upload_image_rows",
-    "plr_copy_device_memory_2d", "plr_set_global_descriptor_set_layout",
+    "plr_copy_device_memory_2d", "plr_set_global_descriptor_set_layout", "plr_noise_gaussian_table", "plr_noise_perlin_gradients",
 ]
+
+
+def noise_gaussian_table(width, height):
+    """-> (height * width,) float32: the influence table "blueNoiseVoidAndCluster.comp" takes at binding 1 (include/plr.h plr_noise_gaussian_table); needs no GPU"""
+    lib = _load()
+    out = np.empty(max(int(width) * int(height), 1), np.float32)
+    if lib.plr_noise_gaussian_table(C.c_uint32(int(width)), C.c_uint32(int(height)), out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise PlrError(lib.plr_last_error().decode())
+    return out
+
+
+def noise_perlin_gradients(seed, grid_cell_count):
+    """-> (grid_cell_count^3, 4) float32: the gradients "perlinNoise3D.comp" takes at binding 1 (include/plr.h plr_noise_perlin_gradients); needs no GPU"""
+    lib = _load()
+    g = int(grid_cell_count)
+    out = np.empty((max(g, 1) ** 3 if g <= 32 else 1, 4), np.float32)
+    if lib.plr_noise_perlin_gradients(C.c_uint32(int(seed) & 0xFFFFFFFF), C.c_uint32(g), out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise PlrError(lib.plr_last_error().decode())
+    return out
 
 
 def shade_sky_exit_switch():

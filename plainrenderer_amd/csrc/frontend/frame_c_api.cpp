@@ -224,6 +224,20 @@ int plrf_get_scene_sdf_stats(void* p, plrf_scene_sdf_stats* out) {
     })
 }
 
+// ---- the frame's noise inputs ("blueNoiseVoidAndCluster.comp", "perlinNoise3D.comp")
+int plrf_generate_noise(void* p, uint32_t seed, uint32_t flags) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL(((FramePipeline*)p)->generateNoise(seed, flags))
+}
+int plrf_get_noise_stats(void* p, plrf_noise_stats* out) {
+    if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        const FramePipeline::NoiseStats s = ((FramePipeline*)p)->noiseStats();
+        static_assert(sizeof(s.status) == sizeof(out->status), "noise status layout");
+        std::memcpy(out->status, s.status, sizeof(out->status));
+    })
+}
+
 int plrf_raster_window_for(const plrf_settings* s, uint32_t out[4]) {
     if (!s || !out) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY(rasterWindowTiles(toPipelineSettings(s), out))

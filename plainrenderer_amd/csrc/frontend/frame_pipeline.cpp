@@ -2,6 +2,7 @@
 #include "frame_pipeline.h"
 #include "../device/depth_prepass_raster.h"
 #include "../device/draw_culling.h"
+#include "../device/noise.h"
 #include "../device/scene_sdf.h"
 #include "../device/sun_shadow_raster.h"
 
@@ -929,7 +930,7 @@ FramePipeline::FramePipeline(const FramePipelineSettings& s) : settings(s), m_re
     }
     {
         // Volumetrics::init (Techniques/Volumetrics.cpp:19-117): froxel volumes of the integration volume's size; the 32^3 R8 Perlin noise is an
-        // input (generate3DPerlinNoise is asset code), uploaded by the caller into "perlinNoise3D"
+        // input (generate3DPerlinNoise is asset code): uploaded by the caller into "perlinNoise3D", or written by generateNoise
         ImageDescription fd = m_be.getImageDescription(m_volumetricIntegrationVolume);
         m_scatteringTransmittanceVolume = m_be.createImage(fd, nullptr, 0);
         m_volumetricLightingHistory[0] = m_be.createImage(fd, nullptr, 0);
@@ -1945,6 +1946,83 @@ void FramePipeline::updateSceneSdfInstances() {
     m_be.setComputePassExecution(exe);
 }
 
+// ---- the frame's noise inputs: generateBlueNoiseTexture (Common/Noise.cpp:232-300; RenderFrontend.cpp:1251-1269) as "blueNoiseVoidAndCluster.comp" and
+// generate3DPerlinNoise (Noise.cpp:422-497; Volumetrics.cpp:71-90) as "perlinNoise3D.comp" (kernels/noise.hip; DESIGN.md "Noise textures as compute passes")
+void FramePipeline::generateNoise(uint32_t seed, uint32_t flags) {
+    namespace nz = plr::noise;
+    if (flags == 0 || (flags & ~(kNoiseBlue | kNoisePerlin)) != 0)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "generateNoise: flags are " + std::to_string(flags) + ", they must be PLRF_NOISE_BLUE (1), PLRF_NOISE_PERLIN (2) or both");
+    if ((flags & kNoisePerlin) && m_perlinNoise3D.index == invalidIndex)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "generateNoise: PLRF_NOISE_PERLIN on a pipeline that has no perlinNoise3D image");
+    // the tables first, in host memory: a failure here still changes nothing
+    std::vector<float> gaussian, gradients;
+    if (flags & kNoiseBlue) {
+        gaussian.resize((size_t)noiseTextureWidth * noiseTextureHeight);
+        if (plr_noise_gaussian_table(noiseTextureWidth, noiseTextureHeight, gaussian.data()) != PLR_OK) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, plr_last_error());
+    }
+    if (flags & kNoisePerlin) {
+        gradients.resize((size_t)nz::kPerlinFrameCells * nz::kPerlinFrameCells * nz::kPerlinFrameCells * 4u);
+        if (plr_noise_perlin_gradients(seed, nz::kPerlinFrameCells, gradients.data()) != PLR_OK) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, plr_last_error());
+    }
+    if (!m_noisePassesCreated) {
+        ComputePassDescription d;
+        d.name = "Blue noise void and cluster";
+        d.shaderDescription.srcPathRelative = "blueNoiseVoidAndCluster.comp";
+        m_blueNoisePass = m_be.createComputePass(d);
+        d.name = "Perlin noise 3D";
+        d.shaderDescription.srcPathRelative = "perlinNoise3D.comp";
+        m_perlinNoisePass = m_be.createComputePass(d);
+        StorageBufferDescription sb;
+        sb.size = (size_t)noiseTextureWidth * noiseTextureHeight * sizeof(float);
+        m_noiseGaussianTable = m_be.createStorageBuffer(sb);
+        sb.size = (size_t)nz::kPerlinFrameCells * nz::kPerlinFrameCells * nz::kPerlinFrameCells * 4u * sizeof(float);
+        m_noisePerlinGradients = m_be.createStorageBuffer(sb);
+        sb.size = 2u * nz::kBlueStatusWords * sizeof(uint32_t);
+        for (StorageBufferHandle& s : m_noiseStatus) s = m_be.createStorageBuffer(sb);
+        m_noisePassesCreated = true;
+    }
+    if (flags & kNoiseBlue) { m_be.setStorageBufferData(m_noiseGaussianTable, gaussian.data(), gaussian.size() * sizeof(float)); m_noiseBlueSeed = seed; }
+    if (flags & kNoisePerlin) m_be.setStorageBufferData(m_noisePerlinGradients, gradients.data(), gradients.size() * sizeof(float));
+    m_noisePending |= flags;
+}
+
+void FramePipeline::recordNoiseGeneration() {
+    if (m_noisePending == 0) return;
+    namespace nz = plr::noise;
+    if (m_noisePending & kNoiseBlue)
+        for (uint32_t t = 0; t < 4; t++) { // texture t: streams 2 t (red) and 2 t + 1 (green)
+            ComputePassExecution exe;
+            exe.genericInfo.handle = m_blueNoisePass;
+            exe.genericInfo.resources.storageImages = {ImageResource(m_noiseTextures[t], 0, nz::kBlueImageBinding)};
+            exe.genericInfo.resources.storageBuffers = {StorageBufferResource(m_noiseGaussianTable, true, nz::kBlueTableBinding),
+                                                        StorageBufferResource(m_noiseStatus[t], false, nz::kBlueStatusBinding)};
+            const nz::BluePushConstants pc{m_noiseBlueSeed, 2u * t};
+            exe.pushConstants = dataToCharArray(&pc, sizeof(pc));
+            exe.dispatchCount[0] = 2; exe.dispatchCount[1] = exe.dispatchCount[2] = 1;
+            m_be.setComputePassExecution(exe);
+        }
+    if (m_noisePending & kNoisePerlin) {
+        const ImageDescription nd = m_be.getImageDescription(m_perlinNoise3D);
+        ComputePassExecution exe;
+        exe.genericInfo.handle = m_perlinNoisePass;
+        exe.genericInfo.resources.storageImages = {ImageResource(m_perlinNoise3D, 0, nz::kPerlinImageBinding)};
+        exe.genericInfo.resources.storageBuffers = {StorageBufferResource(m_noisePerlinGradients, true, nz::kPerlinGradientBinding)};
+        const nz::PerlinPushConstants pc{nz::kPerlinFrameCells};
+        exe.pushConstants = dataToCharArray(&pc, sizeof(pc));
+        exe.dispatchCount[0] = (nd.width * nd.height * nd.depth + nz::kPerlinThreads - 1u) / nz::kPerlinThreads; exe.dispatchCount[1] = exe.dispatchCount[2] = 1;
+        m_be.setComputePassExecution(exe);
+    }
+    m_noisePending = 0;
+}
+
+FramePipeline::NoiseStats FramePipeline::noiseStats() {
+    NoiseStats out;
+    if (!m_noisePassesCreated) return out;
+    for (uint32_t t = 0; t < 4; t++)
+        if (plr_download_storage_buffer(m_noiseStatus[t].index, out.status[t], 0, sizeof(out.status[t])) != PLR_OK) throw std::runtime_error(plr_last_error());
+    return out;
+}
+
 PrepassRasterStats FramePipeline::prepassRasterStats() {
     PrepassRasterStats out;
     if (m_sceneDrawCount == 0 || !m_sceneRecorded) return out; // no scene, or no frame since it was set: the scratch header is not this scene's
@@ -2112,6 +2190,7 @@ void FramePipeline::prepareRenderpasses() { // RenderFrontend.cpp:313-406
     m_sceneRenderTargetIndex = (m_sceneRenderTargetIndex + 1) % 2;
     const FrameRenderTargets currentRenderTarget = m_frameRenderTargets[m_sceneRenderTargetIndex];
 
+    recordNoiseGeneration(); // only in the frame after generateNoise: in front of everything else
     const bool bandMode = settings.band.enabled();
     if (settings.sdfDebug.visualisationMode != SDFVisualisationMode::None) { // RenderFrontend.cpp:321-340
         if (bandMode) throw std::runtime_error("the SDF debug visualisation is not supported in band rendering");

@@ -549,6 +549,18 @@ public:
     void setSceneSdfMeanAlbedo(const float* rgbOrNan, uint32_t drawCount);
     struct SceneSdfStats { uint32_t instances = 0, volumesBaked = 0; uint64_t volumeBytes = 0; };
     SceneSdfStats sceneSdfStats() const;
+    // the frame's noise inputs as compute passes (kernels/noise.hip; DESIGN.md "Noise textures as compute passes"): generateBlueNoiseTexture for noise0 .. noise3
+    // (RenderFrontend.cpp:1251-1269) as four executions of "blueNoiseVoidAndCluster.comp" - texture t takes streams 2 t and 2 t + 1 of the seed -, and
+    // generate3DPerlinNoise for perlinNoise3D (Volumetrics.cpp:71-90, 8 cells) as one of "perlinNoise3D.comp". The next frame() records them once, in front of
+    // everything else; after that the images stay as written until the caller uploads to them or calls again. A later call before that frame replaces the seed
+    // of the kinds it names. The result is a pure function of the seed, so the ranks of a band / tile partition agree without an exchange. A pipeline that never
+    // calls this records, creates and allocates nothing for it. Refusals (PLR_ERR_INVALID_ARGUMENT): flags 0 or unknown bits; kNoisePerlin on a pipeline
+    // without a perlinNoise3D image. A refused call changes nothing.
+    static constexpr uint32_t kNoiseBlue = 1u, kNoisePerlin = 2u;
+    void generateNoise(uint32_t seed, uint32_t flags);
+    // {swaps, converged, ones, 0} per texture and channel of the last blue-noise generation a frame has run; waits for the GPU. Zero before there is one.
+    struct NoiseStats { uint32_t status[4][2][4] = {}; };
+    NoiseStats noiseStats();
     void rasterWindow(uint32_t outTiles[4]) const { rasterWindowTiles(settings, outTiles); }
     // RenderFrontend::setResolution (RenderFrontend.cpp:408-421): recorded, applied at the start of the next frame() (prepareNewFrame, :199-222). Every image and
     // buffer whose size follows the screen is re-created zero-filled, as the constructor creates it, and the next frame is a camera cut; a resize to the size the
@@ -712,6 +724,12 @@ private:
     bool cullCasters() const { return (m_cullFlags & kCullShadowCasters) != 0 && m_casterDrawCount != 0; }
     void prepareDrawCulling();
     void recordDrawCulling(bool shadowViews);
+    // noise generation: passes and buffers created by the first generateNoise
+    bool m_noisePassesCreated = false;
+    uint32_t m_noisePending = 0, m_noiseBlueSeed = 0; // kinds the next frame records; the Perlin seed lives in the queued fill of the gradients
+    RenderPassHandle m_blueNoisePass, m_perlinNoisePass;
+    StorageBufferHandle m_noiseGaussianTable, m_noisePerlinGradients, m_noiseStatus[4];
+    void recordNoiseGeneration();
     void removeSceneSdf();
     void updateSceneSdfInstances();
     void noteSceneTexturesChanged(uint32_t maxLevel0Texels);

@@ -99,6 +99,8 @@ CULL_SCENE, CULL_SHADOW_CASTERS = 1, 2  # PLRF_CULL_SCENE, PLRF_CULL_SHADOW_CAST
 
 SDF_BAKE = 0xFFFFFFFE  # PLRF_SDF_BAKE
 
+NOISE_BLUE, NOISE_PERLIN = 1, 2  # PLRF_NOISE_BLUE, PLRF_NOISE_PERLIN
+
 
 class PlrfSceneSdfMesh(C.Structure):
     _fields_ = [("sdf_texture", C.c_uint32)]
@@ -496,6 +498,20 @@ class FramePipeline:
         s = PlrfSceneSdfStats()
         self._check(self.lib.plrf_get_scene_sdf_stats(self.handle, C.byref(s)))
         return int(s.instances), int(s.volumes_baked), int(s.volume_bytes)
+
+    # ---- the frame's noise inputs (include/plr_frame.h plrf_generate_noise): "blueNoiseVoidAndCluster.comp" and "perlinNoise3D.comp"
+    def generate_noise(self, seed, flags=NOISE_BLUE | NOISE_PERLIN):
+        """the next frame() writes noise0 .. noise3 (NOISE_BLUE: void-and-cluster blue noise, texture t from streams 2 t and 2 t + 1 of the seed) and / or
+        perlinNoise3D (NOISE_PERLIN: the 32^3 Perlin volume, 8 cells) on the GPU, once and in front of everything else; they stay until uploaded to or generated again"""
+        self.lib.plrf_generate_noise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
+        self._check(self.lib.plrf_generate_noise(self.handle, C.c_uint32(int(seed) & 0xFFFFFFFF), C.c_uint32(int(flags))))
+
+    def noise_stats(self):
+        """-> (4, 2, 4) uint32: {swaps, converged, ones, 0} per texture and channel of the last blue-noise generation a frame has run; waits for the GPU"""
+        out = np.zeros((4, 2, 4), np.uint32)
+        self.lib.plrf_get_noise_stats.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(self.lib.plrf_get_noise_stats(self.handle, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def raster_window(self):
         """(x0, y0, x1, y1), half-open, in 64 x 64 tiles: the window the depth prepass of a partitioned pipeline with band_raster = 1 is restricted to"""
