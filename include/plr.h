@@ -247,6 +247,34 @@ int plr_set_stream_overlap(int enabled);
  * the last plr_render_frame launched on the tail stream. plr_get_last_frame_gpu_time covers the launch stream only. */
 int plr_set_async_tail(int enabled);
 int plr_get_async_tail(int* out_enabled, uint32_t* out_async_executions);
+/* Host-side hold of the tail: an instrument for TESTS, off by default (position PLR_TAIL_HOLD_OFF = -2; PLR_TAIL_HOLD in the environment sets it at plr_setup).
+ * With any other position plr_render_frame does not launch a run of async_tail executions: it keeps them (all bookkeeping - what the pending tail touches, the
+ * count of plr_get_async_tail - is done where the run was recorded) and launches them later on the tail stream, behind an event recorded on the launch stream at
+ * that moment. The held run is launched ("flushed") at the first of: a join of the tail (a hazard of a later execution, buffer fill or host callback with it, or an
+ * entry point that touches device memory from the host: downloads, plr_wait_for_gpu_idle, plr_get_stream, ...); the next run of async_tail executions; the end
+ * of a frame launched with pass timing on; a change of the settings a launch depends on; plr_shutdown; and, for position k >= 0, immediately in front of the k-th
+ * launch-stream operation (kernel launch, fill kernel, copy, host callback) counted from the hold. PLR_TAIL_HOLD_FORCED = -1: only when forced.
+ * Every position is one serial schedule out of those the hazard tracking permits, so every position must give the bytes of plr_set_async_tail(0)
+ * (tests/test_tail_hold.py). No kernel, no wait on memory, no sleep is involved. Not combinable with plr_set_early_parts (PLR_ERR_UNSUPPORTED); a no-op with
+ * plr_set_stream_overlap(1) or the tail off. Setting a position flushes a held run and clears the statistics. */
+#define PLR_TAIL_HOLD_OFF (-2)
+#define PLR_TAIL_HOLD_FORCED (-1)
+typedef struct plr_tail_hold_stats {
+    uint32_t held_runs;           /* runs of async_tail executions that were held */
+    uint32_t held_executions;     /* executions in them */
+    uint32_t flushes_join;        /* flushes forced by a join of the tail */
+    uint32_t flushes_position;    /* flushes at position k */
+    uint32_t flushes_next_tail;   /* flushes in front of the next run of async_tail executions */
+    uint32_t flushes_host;        /* flushes by a host entry point that joins nothing: timed frame, settings, shutdown */
+    uint32_t max_ahead;           /* the largest number of launch-stream operations that went ahead of a held run */
+    uint32_t last_ahead;          /* the same of the run flushed last */
+    uint32_t ahead_sum;           /* sum over all flushed runs */
+    uint32_t held_now;            /* 1: a run is held at this moment */
+    uint32_t general_executions;  /* held executions that ran the general kernel in PLR_MATH_FAST (plr_get_general_kernel_executions counts a frame's own launches) */
+    uint32_t frame_operations;    /* launch-stream operations of the last plr_render_frame, its buffer fills included */
+} plr_tail_hold_stats;
+int plr_set_async_tail_hold(int position);
+int plr_get_async_tail_hold(int* out_position, plr_tail_hold_stats* out_stats);
 /* Early parts (round 6; default OFF - measured slower on MI355X, see the end of this comment; PLR_EARLY_PARTS=1 turns it on; PLR_MATH_FAST with pass fusion only). A fused launch may have a part that depends on none of
  * the frame's intermediate results: the deferred shade's DIRECT lighting (triangle.frag:146-290 - material, cascade select, twelve-tap PCF, diffuse + GGX +
  * multiscattering response to the sun, the froxel lookup) needs the G-buffer, the shadow cascades and the LUTs, not the GI chain recorded in front of it

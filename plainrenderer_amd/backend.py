@@ -215,6 +215,11 @@ def _load():
     return lib
 
 
+class _TailHoldStats(C.Structure):  # plr_tail_hold_stats (include/plr.h)
+    _fields_ = [(n, C.c_uint32) for n in ("held_runs", "held_executions", "flushes_join", "flushes_position", "flushes_next_tail", "flushes_host", "max_ahead", "last_ahead",
+                                          "ahead_sum", "held_now", "general_executions", "frame_operations")]
+
+
 EXPORTED_SYMBOLS = [
     "plr_debug_pcf_tap_table", "plr_setup", "plr_shutdown", "plr_recreate_swapchain", "plr_last_error", "plr_wait_for_gpu_idle", "plr_update_shader_code",
     "plr_resize_images", "plr_recreate_image", "plr_resize_storage_buffer", "plr_new_frame", "plr_set_compute_pass_execution", "plr_prepare_for_drawcall_recording",
@@ -225,7 +230,7 @@ EXPORTED_SYMBOLS = [
     "plr_get_last_frame_cpu_time", "plr_get_image_description", "plr_set_pass_timing", "plr_get_last_frame_gpu_time",
     "plr_replay_frame", "plr_upload_image", "plr_download_image", "plr_download_storage_buffer", "plr_download_uniform_buffer",
     "plr_get_image_device_pointer", "plr_get_storage_buffer_device_pointer", "plr_get_stream", "plr_get_launch_stream", "plr_copy_device_memory", "plr_read_device_memory", "plr_write_device_memory", "plr_get_supported_shaders",
-    "plr_debug_math_eval", "plr_debug_codec_eval", "plr_debug_sampler_eval", "plr_debug_sky_lut_eval", "plr_debug_verify_histogram_thresholds", "plr_debug_verify_r11g11b10_fast", "plr_debug_shade_sky_exit_switch", "plr_debug_shade_sky_exit_waves", "plr_debug_set_decision_signature", "plr_debug_read_decision_signature", "plr_set_math_mode", "plr_get_math_mode", "plr_set_stream_overlap", "plr_get_stream_overlap", "plr_set_pass_fusion", "plr_get_pass_fusion", "plr_set_pass_fusion_reorder", "plr_get_general_kernel_executions", "plr_get_edge_signal", "plr_set_async_tail", "plr_get_async_tail", "plr_set_early_parts", "plr_get_early_parts", "plr_set_host_callback_execution", "plr_set_host_callback_execution_on", "plr_upload_image_rows",
+    "plr_debug_math_eval", "plr_debug_codec_eval", "plr_debug_sampler_eval", "plr_debug_sky_lut_eval", "plr_debug_verify_histogram_thresholds", "plr_debug_verify_r11g11b10_fast", "plr_debug_shade_sky_exit_switch", "plr_debug_shade_sky_exit_waves", "plr_debug_set_decision_signature", "plr_debug_read_decision_signature", "plr_set_math_mode", "plr_get_math_mode", "plr_set_stream_overlap", "plr_get_stream_overlap", "plr_set_pass_fusion", "plr_get_pass_fusion", "plr_set_pass_fusion_reorder", "plr_get_general_kernel_executions", "plr_get_edge_signal", "plr_set_async_tail", "plr_get_async_tail", "plr_set_async_tail_hold", "plr_get_async_tail_hold", "plr_set_early_parts", "plr_get_early_parts", "plr_set_host_callback_execution", "plr_set_host_callback_execution_on", "plr_upload_image_rows",
     "plr_copy_device_memory_2d", "plr_set_global_descriptor_set_layout", "plr_noise_gaussian_table", "plr_noise_perlin_gradients",
 ]
 
@@ -605,6 +610,21 @@ class RenderBackend:
         e, n = C.c_int(), C.c_uint32()
         self._check(self.lib.plr_get_async_tail(C.byref(e), C.byref(n)))
         return bool(e.value), n.value
+
+    TAIL_HOLD_OFF, TAIL_HOLD_FORCED = -2, -1
+
+    def setAsyncTailHold(self, position):
+        """host-side hold of the tail, an instrument for tests (include/plr.h plr_set_async_tail_hold): -2 off (default), -1 a held run of async_tail executions
+        is launched only when something forces it, k >= 0 in front of the k-th launch-stream operation counted from the hold. Clears the statistics."""
+        if isinstance(position, bool) or not isinstance(position, (int, np.integer)):
+            raise TypeError("setAsyncTailHold: position is an integer (-2 off, -1 only when forced, k >= 0)")
+        self._check(self.lib.plr_set_async_tail_hold(C.c_int(int(position))))
+
+    def getAsyncTailHold(self):
+        """-> (position, statistics as a dict: the fields of plr_tail_hold_stats, include/plr.h)"""
+        pos, st = C.c_int(), _TailHoldStats()
+        self._check(self.lib.plr_get_async_tail_hold(C.byref(pos), C.byref(st)))
+        return pos.value, {name: int(getattr(st, name)) for name, _ in _TailHoldStats._fields_}
 
     def setEarlyParts(self, enabled):
         """early parts of fused launches (the deferred shade's direct lighting as a launch of its own beside the GI chain; include/plr.h)"""

@@ -248,6 +248,18 @@ struct FillOrder {
 };
 
 struct EarlyPlan { size_t at = 0, group = 0, count = 0; const FusionEntry* f = nullptr; hipEvent_t done = nullptr; bool launched = false; }; // planEarlyParts below
+// a run of async_tail executions that launchAll did not launch (plr_set_async_tail_hold): the frame it belongs to as it was recorded and ordered - a fused
+// launch looks at the whole frame (elision) -, the run's range in it, and the host state of that frame a launcher may read (global buffer copy, its shadow)
+constexpr int kTailHoldOff = -2;
+struct HeldTail {
+    bool active = false;
+    std::vector<Execution> frame;
+    size_t begin = 0, end = 0;
+    const GlobalUbo* globalPtr = nullptr;
+    GlobalUbo shadow{};
+    bool shadowValid = false;
+    uint64_t frameSerial = 0, opsAtHold = 0;
+};
 struct Backend {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -343,6 +355,13 @@ struct Backend {
     uint32_t lastAsync = 0;              // executions of the last frame that ran on the tail stream
     void* globalCopies[2] = {nullptr, nullptr}; // rotating device copies of the global uniform buffer: a tail that still reads frame N's must not see frame N + 1's fill
     uint32_t globalCopyIndex = 0;
+    // host-side hold of the tail (plr_set_async_tail_hold; a test instrument, off by default): launchAll keeps a run of async_tail executions instead of launching
+    // it and flushHeldTail launches it later, strictly behind what the launch stream holds by then - one fully serial member of the schedules the hazard tracking permits
+    int tailHold = kTailHoldOff;
+    HeldTail held;
+    bool flushingHeld = false;
+    hipEvent_t holdEvent = nullptr;      // recorded on the launch stream by a flush; the tail stream waits for it
+    plr_tail_hold_stats holdStats{};
     std::set<std::string> fusedNames;    // stable storage for the timing labels of fused launches
     // content versions of image allocations (backend.h contentVersionOf): key = allocation base; absent = not seen yet (gets a version on first query)
     std::unordered_map<const void*, uint64_t> contentVersion;
@@ -453,8 +472,19 @@ static int joinAsyncTail();
     if (int jrc_ = joinAsyncTail()) return jrc_
 
 // the main stream waits for everything launched on the tail stream so far (a no-op when nothing is pending)
+enum TailFlushCause { kFlushJoin, kFlushPosition, kFlushNextTail, kFlushHost };
+static int flushHeldTail(TailFlushCause cause);
+// in front of every operation that goes onto the launch stream: a run held for position k is launched when k operations have gone ahead of it
+static inline int tailHoldPoint() {
+    if (!g->held.active || g->flushingHeld || g->tailHold < 0 || g->mainOps - g->held.opsAtHold < (uint64_t)g->tailHold) return PLR_OK;
+    return flushHeldTail(kFlushPosition);
+}
 static int joinAsyncTail() {
     if (!g || g->tailPending.empty()) return PLR_OK;
+    if (g->held.active) { // a held run is part of the pending tail: it goes onto the tail stream in front of the wait
+        if (g->flushingHeld) return setErr(PLR_ERR_HIP, "a join of the asynchronous tail while its held run is being launched");
+        if (int rc = flushHeldTail(kFlushJoin)) return rc;
+    }
     HIP_TRY(hipStreamWaitEvent(g->stream, g->tailDone, 0));
     g->tailPending.clear();
     return PLR_OK;
@@ -701,6 +731,7 @@ int plr_setup(int device_ordinal, uint32_t width, uint32_t height) {
     }
     if (const char* es = std::getenv("PLR_EDGE_SIGNAL")) if (std::atoi(es) == 0 && g->edgeSignal) { hipFree(g->edgeSignal); hipFree(g->edgeCounter); g->edgeSignal = g->edgeCounter = nullptr; }
     if (const char* at = std::getenv("PLR_ASYNC_TAIL")) g->asyncTail = std::atoi(at) != 0;
+    if (const char* th = std::getenv("PLR_TAIL_HOLD")) g->tailHold = std::max(std::atoi(th), kTailHoldOff); // (tools; with PLR_EARLY_PARTS the first held frame reports the conflict)
     if (const char* ov = std::getenv("PLR_STREAM_OVERLAP")) g->overlap = std::atoi(ov) != 0;
     if (const char* pf = std::getenv("PLR_PASS_FUSION")) g->fusion = std::min(std::max(std::atoi(pf), 0), 2);
     if (const char* ns = std::getenv("PLR_SIDE_STREAMS")) g->activeSideStreams = std::min(std::max(std::atoi(ns), 1), (int)Backend::kSideStreams);
@@ -711,8 +742,10 @@ int plr_shutdown(void) {
     if (!resolveBackend()) return PLR_OK;
     if (g_adopted) return setErr(PLR_ERR_INVALID_ARGUMENT, "plr_shutdown: this thread uses the backend another thread set up; that thread shuts it down");
     hipSetDevice(g->device);
+    (void)flushHeldTail(kFlushHost); // a held run is launched, not lost
     hipDeviceSynchronize();
     g->tailPending.clear();
+    if (g->holdEvent) hipEventDestroy(g->holdEvent);
     if (g->tailStream) hipStreamDestroy(g->tailStream);
     if (g->tailDone) hipEventDestroy(g->tailDone);
     if (g->tailStart) hipEventDestroy(g->tailStart);
@@ -1076,6 +1109,7 @@ static int fillPass(PassRes& p, const plr_compute_pass_desc* desc) {
 int plr_update_compute_pass_shader_description(plr_pass_handle pass, const plr_compute_pass_desc* desc) {
     NEED_INIT();
     if (pass >= g->passes.size()) return setErr(PLR_ERR_INVALID_ARGUMENT, "invalid pass handle");
+    if (int rc = flushHeldTail(kFlushHost)) return rc; // a held run reads its passes' specialisation constants when it is launched
     plr_compute_pass_desc d = *desc;
     std::string keepName = g->passes[pass]->name;
     int rc = fillPass(*g->passes[pass], &d);
@@ -1107,12 +1141,19 @@ __global__ __launch_bounds__(256) void applyFillsKernel(uint8_t* __restrict__ sl
 // the table - one dependent launch less in front of every frame) or applies it now.
 static int applyPendingFillsNow() {
     if (!g->pendingFillSlot) return PLR_OK;
+    if (int hrc = tailHoldPoint()) return hrc;
     applyFillsKernel<<<1, 256, 0, g->stream>>>(g->pendingFillSlot, 0);
     HIP_TRY(hipGetLastError());
     g->mainOps++;
     g->pendingFillSlot = nullptr;
     if (g->pendingFillEvent) { HIP_TRY(hipEventRecord(g->pendingFillEvent, g->stream)); g->pendingFillEvent = nullptr; }
     return PLR_OK;
+}
+
+// what a fused launcher that takes the frame's fills calls when it cannot host them (PassCtx::applyPendingFillsNow): its own kernels follow the fill kernel
+static int applyPendingFillsForLauncher() {
+    if (int rc = applyPendingFillsNow()) return rc;
+    return tailHoldPoint();
 }
 
 static int flushFills() {
@@ -1167,6 +1208,7 @@ static int flushFills() {
                 HIP_TRY(hipStreamSynchronize(g->stream));
                 count = 0;
             }
+            if (int hrc = tailHoldPoint()) return hrc;
             HIP_TRY(hipMemcpyAsync(f.dst, host + payloadBase + f.stagingOffset, f.size, hipMemcpyHostToDevice, g->stream));
             g->mainOps++;
             usedCopyEngine = true;
@@ -1189,6 +1231,7 @@ static int flushFills() {
         } else {
             // a partial fill of the global buffer: the copy must be the whole buffer as it is after the fills
             if (count) { *(uint32_t*)host = count; applyFillsKernel<<<1, 256, 0, g->stream>>>(host, 0); HIP_TRY(hipGetLastError()); HIP_TRY(hipStreamSynchronize(g->stream)); count = 0; }
+            if (int hrc = tailHoldPoint()) return hrc;
             HIP_TRY(hipMemcpyAsync(g->globalCopies[next], globalDev, sizeof(GlobalUbo), hipMemcpyDeviceToDevice, g->stream));
             g->mainOps++;
         }
@@ -1200,6 +1243,7 @@ static int flushFills() {
     if (count && !usedCopyEngine && pollSlot) {
         *(uint32_t*)host = count;
         *(volatile uint64_t*)(host + 8) = 0;
+        if (int hrc = tailHoldPoint()) return hrc;
         applyFillsKernel<<<1, 256, 0, g->stream>>>(host, slot.serial);
         HIP_TRY(hipGetLastError());
         g->mainOps++;
@@ -1207,6 +1251,7 @@ static int flushFills() {
         slot.eventPending = true; // its event is recorded behind whatever reads the slot last
         if (count && !usedCopyEngine) { *(uint32_t*)host = count; g->pendingFillSlot = host; g->pendingFillEvent = slot.free; } // applied by the frame's first launch
         else {
+            if (int hrc = tailHoldPoint()) return hrc;
             if (count) { *(uint32_t*)host = count; applyFillsKernel<<<1, 256, 0, g->stream>>>(host, 0); HIP_TRY(hipGetLastError()); }
             g->mainOps++;
             HIP_TRY(hipEventRecord(slot.free, g->stream)); // a copy-engine transfer read the slot too (set-up frames): an event covers both
@@ -1471,7 +1516,7 @@ static int launchExecution(Execution& x, hipStream_t stream, const GlobalUbo* gl
     touchAccesses(x.access); // the images it writes have new contents from here on (contentVersionOf)
     const bool signalled = x.edgesFirst() && g->edgeSignal;
     if (signalled) { x.ctx.edgeSignal = g->edgeSignal; x.ctx.edgeCounter = g->edgeCounter; x.ctx.edgeValue = ++g->edgeSerial; }
-    if (stream == g->stream) g->mainOps++;
+    if (stream == g->stream) { if (int hrc = tailHoldPoint()) return hrc; g->mainOps++; }
     int rc = (g->mathMode == PLR_MATH_FAST && p.fast) ? p.fast(x.ctx) : kUseGeneralKernel;
     if (rc == kUseGeneralKernel) {
         x.ctx.edgeSignalHonoured = false; // (a fast launcher that ordered its blocks and then declined: the general kernel raises nothing - ADVICE r04)
@@ -1654,10 +1699,11 @@ static int tryFusedLaunch(size_t i, size_t last, hipStream_t stream, const Globa
         Execution& first = g->executions[i];
         first.ctx.pendingFillSlot = nullptr; first.ctx.pendingFillsTaken = false; first.ctx.applyPendingFillsNow = nullptr;
         if (g->pendingFillSlot) {
-            if (f.takesFills && stream == g->stream) { first.ctx.pendingFillSlot = g->pendingFillSlot; first.ctx.applyPendingFillsNow = &applyPendingFillsNow; }
+            if (f.takesFills && stream == g->stream) { first.ctx.pendingFillSlot = g->pendingFillSlot; first.ctx.applyPendingFillsNow = &applyPendingFillsForLauncher; }
             else if (int frc = applyPendingFillsNow()) return frc;
         }
         for (size_t k = 0; k < n; k++) if (int src = refuseStaleReads(g->executions[i + k], &g->executions[i], n)) return src;
+        if (stream == g->stream) if (int hrc = tailHoldPoint()) return hrc;
         const int rc = f.fn(ctxs, n);
         if (first.ctx.pendingFillSlot) {
             if (rc == 0 && first.ctx.pendingFillsTaken) { // applied by a block of the launcher's first kernel: the slot is free behind this launch
@@ -1796,6 +1842,80 @@ static void linkConsumers(const GlobalUbo* globalPtr) {
     }
 }
 
+// ---- host-side hold of the tail (plr.h plr_set_async_tail_hold). holdTailRun keeps the run [begin, end) of the frame being launched; flushHeldTail launches it:
+// an event on the launch stream, the tail stream waits for it, the run goes through the same tryFusedLaunch / launchExecution path as an unheld one, tailDone is
+// recorded behind it. The held frame's executions and the host state its launchers may read stand in for the current ones while it is launched; the current
+// frame's pending buffer fills stay where they are (the launch stream applies them, in front of ITS next launch).
+namespace plr { // (flushHeldTail is declared there, in front of joinAsyncTail)
+static int holdTailRun(size_t begin, size_t end, const GlobalUbo* globalPtr) {
+    if (g->earlyParts) return setErr(PLR_ERR_UNSUPPORTED, "plr_set_async_tail_hold and plr_set_early_parts exclude each other: an early part orders itself behind the tail's start event, which a held run does not record");
+    HeldTail& h = g->held;
+    h.frame = g->executions;
+    for (Execution& y : h.frame) { // producer -> consumer links point into the recorded list
+        if (!y.ctx.consumer) continue;
+        const PassCtx* linked = nullptr;
+        for (size_t j = 0; j < g->executions.size(); j++) if (&g->executions[j].ctx == y.ctx.consumer) linked = &h.frame[j].ctx;
+        y.ctx.consumer = linked;
+    }
+    h.begin = begin; h.end = end;
+    h.globalPtr = globalPtr;
+    h.shadow = g->globalShadow; h.shadowValid = g->globalShadowValid;
+    h.frameSerial = g->frameSerial;
+    h.opsAtHold = g->mainOps;
+    h.active = true;
+    g->holdStats.held_runs++;
+    g->holdStats.held_executions += (uint32_t)(end - begin);
+    return PLR_OK;
+}
+static int flushHeldTail(TailFlushCause cause) {
+    if (!g || !g->held.active || g->flushingHeld) return PLR_OK;
+    HeldTail& h = g->held;
+    g->flushingHeld = true;
+    plr_tail_hold_stats& st = g->holdStats;
+    const uint32_t ahead = (uint32_t)(g->mainOps - h.opsAtHold);
+    (cause == kFlushJoin ? st.flushes_join : cause == kFlushPosition ? st.flushes_position : cause == kFlushNextTail ? st.flushes_next_tail : st.flushes_host)++;
+    st.last_ahead = ahead; st.ahead_sum += ahead; st.max_ahead = std::max(st.max_ahead, ahead);
+    const bool sameFrame = h.frameSerial == g->frameSerial; // no later launchAll has begun: the frame's counters are still this run's frame's
+    const bool timed = sameFrame && g->timingNow;
+    // the held frame stands in for the current one
+    std::swap(g->executions, h.frame);
+    std::swap(g->globalShadow, h.shadow); std::swap(g->globalShadowValid, h.shadowValid);
+    std::vector<EarlyPlan> plans; std::swap(plans, g->earlyPlans);
+    const uint64_t serial = g->frameSerial; g->frameSerial = h.frameSerial;
+    hipStream_t curStream = g->curStream; const char* passName = g->currentPassName;
+    uint8_t* fillSlot = g->pendingFillSlot; hipEvent_t fillEvent = g->pendingFillEvent;
+    g->pendingFillSlot = nullptr; g->pendingFillEvent = nullptr;
+    const uint32_t fused = g->lastFused, general = g->lastGeneral;
+    std::string generalNames = g->lastGeneralNames;
+    auto launch = [&]() -> int {
+        if (!g->holdEvent) HIP_TRY(hipEventCreateWithFlags(&g->holdEvent, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(g->holdEvent, g->stream));
+        HIP_TRY(hipStreamWaitEvent(g->tailStream, g->holdEvent, 0));
+        for (size_t i = h.begin; i < h.end;) {
+            size_t covered = 0;
+            if (int rc = tryFusedLaunch(i, h.end, g->tailStream, h.globalPtr, timed, &covered)) return rc;
+            if (!covered) if (int rc = launchExecution(g->executions[i], g->tailStream, h.globalPtr, timed)) return rc;
+            i += covered ? covered : 1;
+        }
+        HIP_TRY(hipEventRecord(g->tailDone, g->tailStream));
+        return PLR_OK;
+    };
+    const int rc = launch();
+    st.general_executions += g->lastGeneral - general;
+    if (!sameFrame) { g->lastFused = fused; g->lastGeneral = general; g->lastGeneralNames = std::move(generalNames); }
+    g->pendingFillSlot = fillSlot; g->pendingFillEvent = fillEvent;
+    g->curStream = curStream; g->currentPassName = passName;
+    g->frameSerial = serial;
+    std::swap(plans, g->earlyPlans);
+    std::swap(g->globalShadow, h.shadow); std::swap(g->globalShadowValid, h.shadowValid);
+    std::swap(g->executions, h.frame);
+    h.frame.clear();
+    h.active = false;
+    g->flushingHeld = false;
+    return rc;
+}
+} // namespace plr
+
 static int launchAll(bool timed) {
     const size_t n = g->executions.size();
     // unique across backends: host-side bookkeeping of the launchers (the spatial filter's packed rows) is keyed by device addresses, which a
@@ -1841,6 +1961,7 @@ static int launchAll(bool timed) {
             if (x.callbackAccessKnown) { if (int rc = refuseStaleReads(x, nullptr, 0)) return rc; }
             if (x.callbackAccessKnown) touchAccesses(x.access);
             else g->contentVersion.clear(); // may have written anything: every image gets a new version at its next query
+            if (int hrc = tailHoldPoint()) return hrc;
             g->mainOps++;
             const int crc = x.callback(x.callbackUser, (void*)g->stream);
             if (crc) return setErr(crc, "host callback '" + std::string(x.callbackName) + "' failed with code " + std::to_string(crc));
@@ -1859,6 +1980,23 @@ static int launchAll(bool timed) {
                 if (async) if (int rc = applyPendingFillsNow()) return rc; // (a frame whose first launch is a tail launch: the fills go in front of the tail's start)
                 size_t runEnd = i + 1; // [i, runEnd): executions of the same kind (a fused launch never mixes the two)
                 while (runEnd < last && (tailAllowed && g->executions[runEnd].asyncTail) == async) runEnd++;
+                if (async && g->tailHold != kTailHoldOff) {
+                    // plr_set_async_tail_hold: the run is kept, not launched. What the pending tail touches, the global buffer copy it reads and the count are
+                    // noted here, where the run was recorded; a run still held from the frame before goes first (stream order of the tails)
+                    if (int rc = flushHeldTail(kFlushNextTail)) return rc;
+                    auto note = [&](const Access& a) {
+                        for (Access& t : g->tailPending) if (t.key == a.key) { t.write = t.write || a.write; return; }
+                        g->tailPending.push_back(a);
+                    };
+                    for (size_t k = i; k < runEnd; k++)
+                        for (const Access& a : g->executions[k].access) note(a);
+                    note(Access{(const void*)globalPtr, false});
+                    g->lastAsync += (uint32_t)(runEnd - i);
+                    g->tailStartCoversLate = false; // no start event of this tail on the launch stream
+                    if (int rc = holdTailRun(i, runEnd, globalPtr)) return rc;
+                    i = runEnd;
+                    continue;
+                }
                 hipStream_t stream = g->stream;
                 if (async) {
                     if (!tailOpen) {
@@ -1949,6 +2087,7 @@ static int launchAll(bool timed) {
         }
         i = last;
     }
+    if (timed) if (int rc = flushHeldTail(kFlushHost)) return rc; // a timed frame's segments belong to this launchAll
     if (int rc = closeTail()) return rc;
     g->curStream = g->stream;
     g->timingNow = false;
@@ -1958,6 +2097,7 @@ static int launchAll(bool timed) {
 int plr_render_frame(int /*present_to_screen*/) {
     NEED_INIT();
     const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t opsBefore = g->mainOps;
     g->lastFillDsts.clear();
     int rc = flushFills();
     if (rc) return rc;
@@ -1973,6 +2113,7 @@ int plr_render_frame(int /*present_to_screen*/) {
     if (rc) return rc;
     if (int frc = applyPendingFillsNow()) return frc; // a frame without a launch
     if (frameTimed) HIP_TRY(hipEventRecord(g->frameEnd, g->stream));
+    if (g->tailHold != kTailHoldOff) g->holdStats.frame_operations = (uint32_t)(g->mainOps - opsBefore);
     g->frameRecorded = frameTimed;
     g->timedExecutions = g->passTiming ? g->segments.size() : 0;
     if (g->passTiming) {
@@ -1985,6 +2126,7 @@ int plr_render_frame(int /*present_to_screen*/) {
 
 int plr_set_pass_fusion(int enabled) {
     NEED_INIT();
+    if (int rc = flushHeldTail(kFlushHost)) return rc; // (a held run is launched as it would have been where it was recorded)
     g->fusion = std::min(std::max(enabled, 0), 2);
     return PLR_OK;
 }
@@ -2027,6 +2169,21 @@ int plr_set_async_tail(int enabled) {
     g->asyncTail = enabled != 0;
     return PLR_OK;
 }
+int plr_set_async_tail_hold(int position) {
+    if (position < kTailHoldOff) return setErr(PLR_ERR_INVALID_ARGUMENT, "plr_set_async_tail_hold: position must be PLR_TAIL_HOLD_OFF (-2), PLR_TAIL_HOLD_FORCED (-1) or a count >= 0");
+    NEED_INIT();
+    if (position != kTailHoldOff && g->earlyParts) return setErr(PLR_ERR_UNSUPPORTED, "plr_set_async_tail_hold: not together with plr_set_early_parts");
+    if (int rc = flushHeldTail(kFlushHost)) return rc;
+    g->tailHold = position;
+    g->holdStats = plr_tail_hold_stats{};
+    return PLR_OK;
+}
+int plr_get_async_tail_hold(int* out_position, plr_tail_hold_stats* out_stats) {
+    NEED_INIT();
+    if (out_position) *out_position = g->tailHold;
+    if (out_stats) { *out_stats = g->holdStats; out_stats->held_now = g->held.active ? 1u : 0u; }
+    return PLR_OK;
+}
 int plr_get_async_tail(int* out_enabled, uint32_t* out_async_executions) {
     NEED_INIT();
     if (out_enabled) *out_enabled = g->asyncTail ? 1 : 0;
@@ -2036,6 +2193,7 @@ int plr_get_async_tail(int* out_enabled, uint32_t* out_async_executions) {
 
 int plr_set_early_parts(int enabled) {
     NEED_INIT();
+    if (enabled && g->tailHold != kTailHoldOff) return setErr(PLR_ERR_UNSUPPORTED, "plr_set_early_parts: not together with plr_set_async_tail_hold");
     g->earlyParts = std::min(std::max(enabled, 0), 2);
     return PLR_OK;
 }
