@@ -480,6 +480,33 @@ typedef struct plrf_draw_culling_stats {
     uint32_t culled_by_plane[5];            /* near, +x, -x, +y, -y; shadow views leave [0] at 0 */
 } plrf_draw_culling_stats;
 int plrf_get_draw_culling_stats(void* pipeline, uint32_t view, plrf_draw_culling_stats* out); /* view 0: main pass; 1 + c: cascade c */
+/* ---- debug geometry: the reference's renderDebugGeometry (RenderFrontend.cpp:375-378, 947-956; debug.vert / debug.frag) as the compute pass
+ * "debugGeometry.comp" (DESIGN.md "Debug geometry as a compute pass": the line contract in integers, IEEE fp32 and fp64). While flags are set every frame records
+ * one execution right behind the deferred shade, in front of skyAndSunSprite.comp and everything else that reads the colour buffer. It draws one-pixel lines into
+ * that frame's "color<i>" and "depth<i>", depth-tested GreaterEqual against what the frame wrote, with depth write on as in the reference: a line pixel over the
+ * sky gets a depth above 0, so the sky pass leaves it alone, and TAA and the next frame's reprojection see the line's depth. The colour is stored as given, not
+ * pre-exposed. PLRF_DEBUG_DRAW_BOXES: the twelve edges of the axis-aligned world box of every scene draw - the eight corners of the mesh's local box under the
+ * model matrix of "mainPassMatrices", their fp32 minimum and maximum -, red; with PLRF_CULL_SCENE set only the draws the cull kept. PLRF_DEBUG_SDF_BOXES: the
+ * twelve edges of every padded world box the scene SDF (plrf_set_scene_sdf) wrote to "sdfWorldBBs" this frame, green. PLRF_DEBUG_LINES: the caller's segments
+ * (camera and cascade frusta, rays, normals). Everything comes from buffers the GPU already holds: no host round trip. A flagged source that is absent - no
+ * scene, no scene SDF or a frame without the GI trace, no lines - contributes no segment. Not recorded under sdf_debug_mode, nor on a minimized frame.
+ * Flags and lines are copied, take effect with the next recorded frame in call order, and hold across plrf_set_scene_meshes, plrf_set_scene_mesh_transforms,
+ * the texture calls, plrf_set_resolution and plrf_update_settings. Flags 0 (the default): nothing is recorded, created or allocated, and every frame is what it
+ * is without these calls. PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: an unknown flag bit; null lines with a non-zero count; more than 2^20
+ * lines; a non-finite coordinate or colour component, or a negative colour (the line is named). PLR_ERR_UNSUPPORTED: a band / tile pipeline (the pass writes
+ * depth and has no halo plan); a pipeline without run_shading. A refused call changes nothing.
+ * plrf_get_debug_geometry_stats: the counters of the last frame that recorded the pass; waits for the GPU. submitted: segments the sources held (12 per box,
+ * 1 per line); clipped: segments with an end replaced on a clip plane; rejected: segments dropped by a plane or by an end outside the 2^20-pixel band; drawn:
+ * segments that reach a pixel column (row, for a steep one) of the image; fragments: fragments that passed the depth test; pixels_written: pixels that changed
+ * hands. All zero before the first such frame. plrf_get_storage_buffer names "debugGeometryStats" (8 uint32) and "sceneBounds" (6 floats per draw) once they exist. */
+#define PLRF_DEBUG_DRAW_BOXES 1u   /* world AABB of every scene draw: the reference's "Render bounding boxes" */
+#define PLRF_DEBUG_SDF_BOXES  2u   /* the padded world boxes of the SDF instances, from "sdfWorldBBs" */
+#define PLRF_DEBUG_LINES      4u   /* the caller's segments */
+int plrf_set_debug_geometry(void* pipeline, uint32_t flags);          /* 0 = off */
+typedef struct plrf_debug_line { float a[3], b[3], rgb[3]; } plrf_debug_line;   /* world space; linear colour, stored as is */
+int plrf_set_debug_lines(void* pipeline, const plrf_debug_line* lines, uint32_t count);   /* copied; count 0 removes */
+typedef struct plrf_debug_geometry_stats { uint32_t submitted, clipped, rejected, drawn, fragments, pixels_written, pad[2]; } plrf_debug_geometry_stats;
+int plrf_get_debug_geometry_stats(void* pipeline, plrf_debug_geometry_stats* out);   /* last frame; waits for the GPU */
 /* ---- the frame's noise inputs, generated on the GPU: the four 32 x 32 RG8 void-and-cluster blue-noise textures "noise0" .. "noise3" (generateBlueNoiseTexture,
  * Common/Noise.cpp:232-300, called at RenderFrontend.cpp:1251-1269) as the compute pass "blueNoiseVoidAndCluster.comp", and the 32^3 R8 Perlin volume
  * "perlinNoise3D" of the froxel material pass (generate3DPerlinNoise, Noise.cpp:422-497, Volumetrics.cpp:71-90: 8 grid cells) as "perlinNoise3D.comp" (DESIGN.md

@@ -203,6 +203,26 @@ int plrf_get_draw_culling_stats(void* p, uint32_t view, plrf_draw_culling_stats*
     })
 }
 
+// ---- debug geometry ("debugGeometry.comp")
+int plrf_set_debug_geometry(void* p, uint32_t flags) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL(((FramePipeline*)p)->setDebugGeometry(flags))
+}
+int plrf_set_debug_lines(void* p, const plrf_debug_line* lines, uint32_t count) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    static_assert(sizeof(plrf_debug_line) == sizeof(FramePipeline::DebugLine), "a debug line is 9 floats on both sides");
+    PLRF_TRY_REFUSAL(((FramePipeline*)p)->setDebugLines((const FramePipeline::DebugLine*)lines, count))
+}
+int plrf_get_debug_geometry_stats(void* p, plrf_debug_geometry_stats* out) {
+    if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        const FramePipeline::DebugGeometryStats s = ((FramePipeline*)p)->debugGeometryStats();
+        std::memset(out, 0, sizeof(*out));
+        out->submitted = s.submitted; out->clipped = s.clipped; out->rejected = s.rejected; out->drawn = s.drawn; out->fragments = s.fragments;
+        out->pixels_written = s.pixelsWritten;
+    })
+}
+
 // ---- the scene's SDF ("sdfInstanceUpdate.comp", "sceneMeanAlbedo.comp")
 int plrf_set_scene_sdf(void* p, const plrf_scene_sdf_mesh* meshes, uint32_t meshCount) {
     if (!p) return PLR_ERR_INVALID_ARGUMENT;

@@ -1,6 +1,7 @@
 // See frame_pipeline.h. Pass order, bindings, specialisation constants and dispatch counts follow the cited reference code.
 #include "frame_pipeline.h"
 #include "../device/depth_prepass_raster.h"
+#include "../device/debug_geometry.h"
 #include "../device/draw_culling.h"
 #include "../device/noise.h"
 #include "../device/scene_sdf.h"
@@ -1011,6 +1012,8 @@ bool FramePipeline::storageBuffer(const std::string& n, StorageBufferHandle* out
     else if (n == "sceneCullStats" && m_sceneCullStats.bytes) *out = m_sceneCullStats.handle;
     else if (n == "casterCullStats" && m_casterCullStats.bytes) *out = m_casterCullStats.handle; // 32 bytes per cascade
     else if (n.size() == 18 && n.compare(0, 17, "casterCulledDraws") == 0 && n[17] >= '0' && n[17] <= '3' && m_casterCulledDraws[n[17] - '0'].bytes) *out = m_casterCulledDraws[n[17] - '0'].handle;
+    else if (n == "sceneBounds" && m_sceneBoundsOnGpu) *out = m_sceneBounds.handle; // 6 floats per draw, once draw culling or the debug boxes asked for them
+    else if (n == "debugGeometryStats" && m_debugStats.bytes) *out = m_debugStats.handle; // 8 uint32, once setDebugGeometry set a flag
     else if (n == "sdfInstances") *out = m_sdfGi.m_sdfInstanceBuffer;
     else if (n == "sdfCulledInstances") *out = m_sdfGi.m_sdfCameraFrustumCulledInstances;
     else if (n == "sdfCulledTiles") *out = m_sdfGi.m_sdfCameraCulledTiles;
@@ -1577,7 +1580,7 @@ void FramePipeline::prepareDrawCulling() {
     }
     auto fill = [&](SceneBuffer& b, const void* data, size_t bytes) { fillCasterBuffer(b.handle, b.bytes, data, bytes); };
     if (cullScene() && !m_sceneBoundsUploaded) {
-        fill(m_sceneBounds, m_sceneBoundsHost.data(), m_sceneBoundsHost.size() * sizeof(float));
+        uploadSceneBounds();
         fill(m_sceneCulledDraws, nullptr, (size_t)m_sceneDrawCount * sizeof(plr::prepass::Draw));
         fill(m_sceneCullStats, nullptr, dc::statsBytes(1));
         m_sceneBoundsUploaded = true;
@@ -1614,6 +1617,103 @@ void FramePipeline::recordDrawCulling(bool shadowViews) {
         m_casterCullRecorded = true;
     }
     m_be.setComputePassExecution(exe);
+}
+
+void FramePipeline::uploadSceneBounds() {
+    if (m_sceneBoundsOnGpu || m_sceneDrawCount == 0) return;
+    fillCasterBuffer(m_sceneBounds.handle, m_sceneBounds.bytes, m_sceneBoundsHost.data(), m_sceneBoundsHost.size() * sizeof(float));
+    m_sceneBoundsOnGpu = true;
+}
+
+// ---- "debugGeometry.comp" (kernels/debug_geometry.hip; DESIGN.md "Debug geometry as a compute pass")
+void FramePipeline::refuseDebugGeometryUnsupported(const char* call) const {
+    if (m_requestedSettings.band.enabled())
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, std::string(call) + ": a band / tile pipeline cannot draw debug geometry (the pass writes depth and has no halo plan)");
+    if (!m_requestedSettings.runShading)
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, std::string(call) + ": a pipeline without run_shading has no shaded colour buffer to draw debug geometry into");
+}
+
+void FramePipeline::setDebugGeometry(uint32_t flags) {
+    const uint32_t known = kDebugDrawBoxes | kDebugSdfBoxes | kDebugLines;
+    if (flags & ~known)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setDebugGeometry: unknown flag bits " + std::to_string(flags & ~known) + " (1: draw boxes, 2: SDF boxes, 4: lines)");
+    refuseDebugGeometryUnsupported("setDebugGeometry");
+    m_debugFlags = flags;
+    if (flags == 0) m_debugRecorded = false;
+    prepareDebugGeometry();
+}
+
+void FramePipeline::setDebugLines(const DebugLine* lines, uint32_t count) {
+    namespace dg = plr::debuggeo;
+    if (count && !lines) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setDebugLines: lines are null with a count of " + std::to_string(count));
+    if (count > dg::kMaxLines) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setDebugLines: " + std::to_string(count) + " lines, at most " + std::to_string(dg::kMaxLines) + " (2^20) are accepted");
+    for (uint32_t l = 0; l < count; l++) {
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(lines[l].a[k]) || !std::isfinite(lines[l].b[k]))
+                throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setDebugLines: line " + std::to_string(l) + " has a non-finite coordinate");
+        for (int k = 0; k < 3; k++)
+            if (!std::isfinite(lines[l].rgb[k]) || lines[l].rgb[k] < 0.f)
+                throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setDebugLines: line " + std::to_string(l) + " has a non-finite or negative colour component");
+    }
+    refuseDebugGeometryUnsupported("setDebugLines");
+    static_assert(sizeof(DebugLine) == dg::kLineFloats * sizeof(float), "a line is 9 floats");
+    m_debugLinesHost.assign((const float*)lines, (const float*)lines + (size_t)count * dg::kLineFloats);
+    m_debugLinesUploaded = false;
+    prepareDebugGeometry();
+}
+
+// the pass and the buffers of the sources that are flagged and present: created or grown here, from the calls that change either, never while a frame is
+// recorded. Flags 0 allocate nothing
+void FramePipeline::prepareDebugGeometry() {
+    if (m_debugFlags == 0) return;
+    if (!m_debugPassCreated) {
+        ComputePassDescription d; // RenderFrontend.cpp:1599-1617
+        d.name = "Debug geometry";
+        d.shaderDescription.srcPathRelative = "debugGeometry.comp";
+        m_debugGeometryPass = m_be.createComputePass(d);
+        const plr::debuggeo::Stats zero{};
+        fillCasterBuffer(m_debugStats.handle, m_debugStats.bytes, &zero, sizeof(zero));
+        m_debugPassCreated = true;
+    }
+    if (m_debugFlags & kDebugDrawBoxes) uploadSceneBounds();
+    if ((m_debugFlags & kDebugLines) && !m_debugLinesUploaded && !m_debugLinesHost.empty()) {
+        fillCasterBuffer(m_debugLines.handle, m_debugLines.bytes, m_debugLinesHost.data(), m_debugLinesHost.size() * sizeof(float));
+        m_debugLinesUploaded = true;
+    }
+}
+
+// one execution behind the deferred shade. sdfBoxesWritten: this frame recorded "sdfInstanceUpdate.comp" in front of it (sdfWorldBBs holds the scene's boxes)
+void FramePipeline::recordDebugGeometry(const FrameRenderTargets& current, bool sdfBoxesWritten) {
+    namespace dg = plr::debuggeo;
+    const bool drawBoxes = (m_debugFlags & kDebugDrawBoxes) && m_sceneDrawCount != 0 && m_sceneBoundsOnGpu;
+    const bool sdfBoxes = (m_debugFlags & kDebugSdfBoxes) && sdfBoxesWritten && !m_sceneSdf.instanceDraws.empty();
+    const bool lines = (m_debugFlags & kDebugLines) && m_debugLinesUploaded && !m_debugLinesHost.empty();
+    const bool culled = drawBoxes && cullScene() && m_sceneRecorded; // (the prepass of this frame ran the cull in front of it)
+    ComputePassExecution exe;
+    exe.genericInfo.handle = m_debugGeometryPass;
+    exe.dispatchCount[0] = exe.dispatchCount[1] = exe.dispatchCount[2] = 1;
+    exe.genericInfo.resources.storageImages = {ImageResource(current.colorBuffer, 0, dg::kColorBinding), ImageResource(current.depthBuffer, 0, dg::kDepthBinding)};
+    auto& buffers = exe.genericInfo.resources.storageBuffers;
+    if (drawBoxes)
+        buffers = {StorageBufferResource(culled ? m_sceneCulledDraws.handle : m_sceneDraws.handle, true, dg::kDrawBinding), StorageBufferResource(m_sceneBounds.handle, true, dg::kBoundsBinding),
+                   StorageBufferResource(m_sceneMatrices.handle, true, dg::kTransformBinding)};
+    if (sdfBoxes) buffers.push_back(StorageBufferResource(m_sdfGi.m_sdfInstanceWorldBBBuffer, true, dg::kSdfBoxBinding));
+    if (lines) buffers.push_back(StorageBufferResource(m_debugLines.handle, true, dg::kLineBinding));
+    buffers.push_back(StorageBufferResource(m_debugStats.handle, false, dg::kStatsBinding));
+    const dg::PushConstants pc{drawBoxes ? m_sceneDrawCount : 0u, sdfBoxes ? (uint32_t)m_sceneSdf.instanceDraws.size() : 0u,
+                               lines ? (uint32_t)(m_debugLinesHost.size() / dg::kLineFloats) : 0u, culled ? 1u : 0u};
+    exe.pushConstants = dataToCharArray(&pc, sizeof(pc));
+    m_be.setComputePassExecution(exe);
+    m_debugRecorded = true;
+}
+
+FramePipeline::DebugGeometryStats FramePipeline::debugGeometryStats() {
+    DebugGeometryStats out;
+    if (!m_debugRecorded) return out;
+    plr::debuggeo::Stats s{};
+    if (plr_download_storage_buffer(m_debugStats.handle.index, &s, 0, sizeof(s)) != PLR_OK) throw std::runtime_error(plr_last_error());
+    out.submitted = s.submitted; out.clipped = s.clipped; out.rejected = s.rejected; out.drawn = s.drawn; out.fragments = s.fragments; out.pixelsWritten = s.pixelsWritten;
+    return out;
 }
 
 FramePipeline::DrawCullingStats FramePipeline::drawCullingStats(uint32_t view) {
@@ -1662,7 +1762,7 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
         removeSceneSdf(); // its mesh indices named the scene that is gone
         m_scenePositionsHost.clear(); m_sceneIndicesHost.clear(); m_sceneDrawMeshes.clear(); m_sceneMeshFirstIndex.clear(); m_sceneMeshIndexCounts.clear();
         m_sceneBoundsHost.clear();
-        m_sceneBoundsUploaded = m_sceneCullRecorded = false;
+        m_sceneBoundsUploaded = m_sceneCullRecorded = m_sceneBoundsOnGpu = false;
         return;
     }
     const PackedScene packed = packSceneMeshes(meshes, meshCount, draws, drawCount); // validates everything before anything is changed
@@ -1694,8 +1794,9 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
     m_scenePositionsHost = packed.positions; m_sceneIndicesHost = packed.indices; // what a later setSceneSdf takes the local boxes and the bake from
     m_sceneDrawMeshes = packed.drawMeshes; m_sceneMeshFirstIndex = packed.meshFirstIndex; m_sceneMeshIndexCounts = packed.meshIndexCounts;
     m_sceneBoundsHost = packed.drawBounds; // they live and die with the meshes
-    m_sceneBoundsUploaded = m_sceneCullRecorded = false;
+    m_sceneBoundsUploaded = m_sceneCullRecorded = m_sceneBoundsOnGpu = false;
     prepareDrawCulling();
+    prepareDebugGeometry();
 }
 
 void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {
@@ -2238,9 +2339,11 @@ void FramePipeline::prepareRenderpasses() { // RenderFrontend.cpp:313-406
         computeSunLightMatrices();
     }
     renderSunShadowCascades(); // (RenderFrontend.cpp:354) only with mesh casters set; the uploaded maps otherwise
+    bool sceneSdfUpdated = false; // this frame records "sdfInstanceUpdate.comp": what the debug geometry's SDF boxes need
     if (settings.runGI && settings.shading.indirectLightingTech == IndirectLightingTech::SDFTrace) {
         if (settings.sdfTrace.halfResTrace) downscaleDepth(currentRenderTarget);
         updateSceneSdfInstances(); // in front of sdfCameraFrustumCulling; only with a scene SDF set, the uploaded instances otherwise
+        sceneSdfUpdated = m_sceneSdfSet;
         SDFTraceDependencies deps = m_frustumScratch; // frustum points/normals from setCameraExtrinsic (fillOutSdfGiDependencies, :1073-1090)
         deps.currentFrame = currentRenderTarget;
         deps.previousFrame = previousRenderTarget;
@@ -2301,6 +2404,8 @@ void FramePipeline::prepareRenderpasses() { // RenderFrontend.cpp:313-406
         computeVolumetricLighting(m_lastDeltaTime);
     }
     if (settings.runShading) computeDeferredShading(currentRenderTarget.colorBuffer, currentRenderTarget);
+    // renderDebugGeometry (RenderFrontend.cpp:373-385): behind the shade, in front of the sky and of everything else that reads the colour buffer
+    if (settings.runShading && m_debugFlags != 0) recordDebugGeometry(currentRenderTarget, sceneSdfUpdated);
     // renderSky (RenderFrontend.cpp:691-694, Techniques/Sky.cpp:318-353): the deferred pass writes the plain sky LUT colour on depth == 0 pixels; with runSky
     // the sky pass overwrites those pixels with the dithered, in-scattered sky and the sun disc before anything else reads the colour buffer
     if (settings.runShading && settings.runSky) computeSkyAndSunSprite(currentRenderTarget.colorBuffer, currentRenderTarget);

@@ -536,6 +536,23 @@ public:
     // rendered; a view at or past 1 + the cascade count is refused (PLR_ERR_INVALID_ARGUMENT)
     struct DrawCullingStats { uint32_t draws = 0, visibleDraws = 0; uint64_t triangles = 0, visibleTriangles = 0; uint32_t culledByPlane[5] = {0, 0, 0, 0, 0}; };
     DrawCullingStats drawCullingStats(uint32_t view);
+    // RenderFrontend::renderDebugGeometry (RenderFrontend.cpp:375-378, 947-956) as "debugGeometry.comp" (kernels/debug_geometry.hip; DESIGN.md "Debug geometry as a
+    // compute pass"): while flags are set, every frame records one execution right behind the deferred shade - in front of the sky pass and everything else that
+    // reads the colour buffer - that draws one-pixel lines into the frame's colour and depth images, depth-tested (GreaterEqual) and with depth write on:
+    // kDebugDrawBoxes the twelve edges of the axis-aligned world box of every scene draw, red (the reference's "Render bounding boxes"; with kCullScene set only
+    // the draws the cull kept), kDebugSdfBoxes those of the padded world box of every instance the scene SDF wrote this frame, green, kDebugLines the caller's
+    // segments. A flagged source that is absent contributes nothing. Not recorded with the SDF debug view on, nor on a minimized frame. Flags and lines are
+    // copied, take effect with the next frame and hold across setSceneMeshes, setSceneMeshTransforms, the texture calls, setResolution and updateSettings. A
+    // pipeline that never sets a flag records, creates and allocates nothing for it. Refusals: unknown bits, null lines with a count, more than 2^20 lines, a
+    // non-finite coordinate or colour component or a negative colour are PLR_ERR_INVALID_ARGUMENT; a band / tile pipeline (the pass writes depth and has no
+    // halo plan) and a pipeline without runShading are PLR_ERR_UNSUPPORTED. A refused call changes nothing.
+    static constexpr uint32_t kDebugDrawBoxes = 1u, kDebugSdfBoxes = 2u, kDebugLines = 4u;
+    struct DebugLine { float a[3], b[3], rgb[3]; }; // world space; linear colour, stored as is
+    void setDebugGeometry(uint32_t flags);
+    void setDebugLines(const DebugLine* lines, uint32_t count); // count 0 removes them
+    // counters of the last frame that recorded the pass; waits for the GPU. All zero before there is one
+    struct DebugGeometryStats { uint32_t submitted = 0, clipped = 0, rejected = 0, drawn = 0, fragments = 0, pixelsWritten = 0; };
+    DebugGeometryStats debugGeometryStats();
     // SDFGI::updateSDFScene (Techniques/SDFGI.cpp:260-313) as "sdfInstanceUpdate.comp" (kernels/scene_sdf.hip; DESIGN.md "SDF instances from the scene"): while a
     // scene SDF is set every frame that records the GI trace or the SDF debug view records one execution in front of the camera frustum culling that writes
     // sdfInstances and sdfWorldBBs from mainPassMatrices, and - in a frame after the texture store or the materials changed - "sceneMeanAlbedo.comp" in front of it.
@@ -724,6 +741,17 @@ private:
     bool cullCasters() const { return (m_cullFlags & kCullShadowCasters) != 0 && m_casterDrawCount != 0; }
     void prepareDrawCulling();
     void recordDrawCulling(bool shadowViews);
+    bool m_sceneBoundsOnGpu = false; // m_sceneBounds holds m_sceneBoundsHost: draw culling and the debug boxes both read it
+    void uploadSceneBounds();
+    // debug geometry: the pass and its buffers are created by the first setDebugGeometry with a flag; the host keeps the caller's lines
+    uint32_t m_debugFlags = 0;
+    bool m_debugPassCreated = false, m_debugRecorded = false, m_debugLinesUploaded = false; // recorded: a frame has run the pass since the flags were last 0
+    RenderPassHandle m_debugGeometryPass;
+    std::vector<float> m_debugLinesHost; // 9 floats per line
+    SceneBuffer m_debugLines, m_debugStats;
+    void refuseDebugGeometryUnsupported(const char* call) const;
+    void prepareDebugGeometry();
+    void recordDebugGeometry(const FrameRenderTargets& current, bool sdfBoxesWritten);
     // noise generation: passes and buffers created by the first generateNoise
     bool m_noisePassesCreated = false;
     uint32_t m_noisePending = 0, m_noiseBlueSeed = 0; // kinds the next frame records; the Perlin seed lives in the queued fill of the gradients

@@ -179,7 +179,8 @@
 // it takes in the other two; the lane path and the wave path of a tested record queue the fragments whose key is above their cell (the early out), and the wave
 // samples 64 queued fragments at a time, one per lane. That kernel takes all its arguments from LDS.
 // The draw lookup and the step from three snapped vertices to a record are device/raster_setup.h's, the scan, the walk and a fragment's coverage and depth
-// device/raster_tile_walk.h's, both shared with "sunShadowRaster.comp"; this file holds the clip, the block's append, what becomes of a fragment (the key, the
+// device/raster_tile_walk.h's, both shared with "sunShadowRaster.comp"; the clip planes, clipComponent and the step from a clipped vertex to the sub-pixel grid device/raster_clip.h's, shared
+// with "debugGeometry.comp"; this file holds the polygon clip, the block's append, what becomes of a fragment (the key, the
 // alpha test's queue), the resolve and the launcher.
 #include <algorithm>
 
@@ -187,6 +188,7 @@
 #include "../device/bc_decode.h"
 #include "../device/depth_prepass_raster.h"
 #include "../device/detmath.h"
+#include "../device/raster_clip.h"
 #include "../device/raster_setup.h"
 #include "../device/raster_tile_walk.h"
 
@@ -207,16 +209,6 @@ struct SetupParams {
 // do two tile rectangles (inclusive, four bytes) share a tile?
 PLR_DI bool rectanglesMeet(uint32_t a, uint32_t b) {
     return (a & 255u) <= ((b >> 16) & 255u) && (b & 255u) <= ((a >> 16) & 255u) && ((a >> 8) & 255u) <= (b >> 24) && ((b >> 8) & 255u) <= (a >> 24);
-}
-
-PLR_DI float planeDistance(int plane, float x, float y, float z, float w) {
-    switch (plane) {
-    case 0: return w - z;
-    case 1: return kGuardNdc * w - x;
-    case 2: return kGuardNdc * w + x;
-    case 3: return kGuardNdc * w - y;
-    default: return kGuardNdc * w + y;
-    }
 }
 
 // one Sutherland-Hodgman step of this lane's polygon: src (n vertices) -> dst (at most `cap`), both LDS arrays [slot * 4 + component][thread]
@@ -245,9 +237,6 @@ PLR_DI int clipPolygon(const float (*src)[256], int n, float (*dst)[256], int ca
     }
     return m;
 }
-
-// clip = M * (p, 1) for a glm column-major matrix, component i
-PLR_DI float clipComponent(const float* M, int i, float x, float y, float z) { return ((M[0 * 4 + i] * x + M[1 * 4 + i] * y) + M[2 * 4 + i] * z) + M[3 * 4 + i]; }
 
 // sub-triangle (0, k + 1, k + 2) of the projected polygon in `poly` ({X, Y as int bits, z, ok}): 0 nothing, 1 a reject, 2 a record (with its tile rectangle)
 PLR_DI int setupSubTriangle(const float (*poly)[256], int k, uint32_t tid, int32_t width, int32_t height, SetupRecord* rec, uint32_t* rect) {
@@ -309,11 +298,11 @@ __global__ __launch_bounds__(256) void depthPrepassSetupKernel(SetupParams p) {
                 const float wf = (float)p.width, hf = (float)p.height;
                 for (int i = 0; i < n; i++) { // project in place: {X, Y (int bits), z, ok}
                     const float x = polyA[i * 4 + 0][tid], y = polyA[i * 4 + 1][tid], z = polyA[i * 4 + 2][tid], w = polyA[i * 4 + 3][tid];
-                    const float nx = x / w, ny = y / w, nz = z / w;
-                    const float xf = (nx * 0.5f + 0.5f) * wf, yf = (ny * 0.5f + 0.5f) * hf;
-                    const bool ok = w > 0.f && fabsf(xf) < rastercov::kGuardBandPixels && fabsf(yf) < rastercov::kGuardBandPixels && fabsf(nz) < __builtin_inff();
-                    polyA[i * 4 + 0][tid] = u2f(ok ? (uint32_t)(int32_t)__builtin_rintf(xf * 256.f) : 0u);
-                    polyA[i * 4 + 1][tid] = u2f(ok ? (uint32_t)(int32_t)__builtin_rintf(yf * 256.f) : 0u);
+                    int32_t X, Y;
+                    float nz;
+                    const bool ok = projectAndSnap(x, y, z, w, wf, hf, &X, &Y, &nz);
+                    polyA[i * 4 + 0][tid] = u2f((uint32_t)X);
+                    polyA[i * 4 + 1][tid] = u2f((uint32_t)Y);
                     polyA[i * 4 + 2][tid] = nz;
                     polyA[i * 4 + 3][tid] = u2f(ok ? 1u : 0u);
                 }

@@ -97,6 +97,14 @@ class PlrfDrawCullingStats(C.Structure):
 
 CULL_SCENE, CULL_SHADOW_CASTERS = 1, 2  # PLRF_CULL_SCENE, PLRF_CULL_SHADOW_CASTERS
 
+
+class PlrfDebugGeometryStats(C.Structure):
+    _fields_ = [("submitted", C.c_uint32), ("clipped", C.c_uint32), ("rejected", C.c_uint32), ("drawn", C.c_uint32), ("fragments", C.c_uint32),
+                ("pixels_written", C.c_uint32), ("pad", C.c_uint32 * 2)]
+
+
+DEBUG_DRAW_BOXES, DEBUG_SDF_BOXES, DEBUG_LINES = 1, 2, 4  # PLRF_DEBUG_DRAW_BOXES, PLRF_DEBUG_SDF_BOXES, PLRF_DEBUG_LINES
+
 SDF_BAKE = 0xFFFFFFFE  # PLRF_SDF_BAKE
 
 NOISE_BLUE, NOISE_PERLIN = 1, 2  # PLRF_NOISE_BLUE, PLRF_NOISE_PERLIN
@@ -477,6 +485,31 @@ class FramePipeline:
         self._check(self.lib.plrf_get_draw_culling_stats(self.handle, C.c_uint32(int(view)), C.byref(s)))
         return dict(draws=int(s.draws), visible_draws=int(s.visible_draws), triangles=int(s.triangles), visible_triangles=int(s.visible_triangles),
                     culled_by_plane=[int(v) for v in s.culled_by_plane])
+
+    # ---- debug geometry (include/plr_frame.h plrf_set_debug_geometry): "debugGeometry.comp" behind the deferred shade
+    def set_debug_geometry(self, flags):
+        """DEBUG_DRAW_BOXES (1): the world box of every scene draw, red; DEBUG_SDF_BOXES (2): the padded world boxes of the scene SDF's instances, green;
+        DEBUG_LINES (4): the segments of set_debug_lines. One-pixel lines, depth-tested, with depth write on, into the frame's colour and depth images from the
+        next frame on, until changed; 0 turns it off"""
+        self.lib.plrf_set_debug_geometry.argtypes = [C.c_void_p, C.c_uint32]
+        self._check(self.lib.plrf_set_debug_geometry(self.handle, C.c_uint32(int(flags))))
+
+    def set_debug_lines(self, lines):
+        """an array of shape (n, 9): a.xyz, b.xyz in world space and a linear rgb per segment, copied. None or empty: the lines are removed"""
+        a = np.ascontiguousarray(lines if lines is not None else np.zeros((0, 9)), np.float32)
+        if a.size and (a.ndim != 2 or a.shape[1] != 9):
+            raise ValueError("set_debug_lines: the lines are an array of shape (n, 9), got %r" % (a.shape,))
+        a = a.reshape(-1, 9)
+        self.lib.plrf_set_debug_lines.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        self._check(self.lib.plrf_set_debug_lines(self.handle, a.ctypes.data_as(C.c_void_p) if a.shape[0] else None, C.c_uint32(a.shape[0])))
+
+    def debug_geometry_stats(self):
+        """dict(submitted, clipped, rejected, drawn, fragments, pixels_written) of the last frame that recorded the pass; waits for the GPU. All zero before one"""
+        s = PlrfDebugGeometryStats()
+        self.lib.plrf_get_debug_geometry_stats.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(self.lib.plrf_get_debug_geometry_stats(self.handle, C.byref(s)))
+        return dict(submitted=int(s.submitted), clipped=int(s.clipped), rejected=int(s.rejected), drawn=int(s.drawn), fragments=int(s.fragments),
+                    pixels_written=int(s.pixels_written))
 
     # ---- the scene's SDF (include/plr_frame.h plrf_set_scene_sdf): sdfInstances and sdfWorldBBs written every frame by "sdfInstanceUpdate.comp"
     def set_scene_sdf(self, sdf_textures):
