@@ -1339,91 +1339,50 @@ void FramePipeline::renderSunShadowCascades() {
         exe.dispatchCount[0] = exe.dispatchCount[1] = exe.dispatchCount[2] = 1;
         exe.genericInfo.resources.storageImages = {ImageResource(m_shadowMaps[c], 0, plr::sunraster::kMapBinding)};
         exe.genericInfo.resources.storageBuffers = {StorageBufferResource(m_sunShadowInfoBuffer, true, plr::sunraster::kSunShadowInfoBinding),
-                                                    StorageBufferResource(m_casterTransforms, true, plr::sunraster::kTransformBinding),
-                                                    StorageBufferResource(m_casterPositions, true, plr::sunraster::kPositionBinding),
-                                                    StorageBufferResource(m_casterIndices, true, plr::sunraster::kIndexBinding),
-                                                    StorageBufferResource(culled ? m_casterCulledDraws[c].handle : m_casterDraws, true, plr::sunraster::kDrawBinding),
-                                                    StorageBufferResource(m_casterScratch[c], false, plr::sunraster::kScratchBinding)};
+                                                    StorageBufferResource(m_casterTransforms.handle, true, plr::sunraster::kTransformBinding),
+                                                    StorageBufferResource(m_casterPositions.handle, true, plr::sunraster::kPositionBinding),
+                                                    StorageBufferResource(m_casterIndices.handle, true, plr::sunraster::kIndexBinding),
+                                                    StorageBufferResource(culled ? m_casterCulledDraws[c].handle : m_casterDraws.handle, true, plr::sunraster::kDrawBinding),
+                                                    StorageBufferResource(m_casterScratch[c].handle, false, plr::sunraster::kScratchBinding)};
         // without cutouts, or while every cutoff is 0: the 8-byte record
         const bool tested = m_casterAlphaTested && m_casterTextureCount;
         const plr::sunraster::CutoutPushConstants pc{m_casterDrawCount, m_casterTriangleCount, tested ? m_casterTextureCount : 0u};
         exe.pushConstants = dataToCharArray(&pc, tested ? sizeof(pc) : sizeof(plr::sunraster::PushConstants));
         if (tested) {
             auto& buffers = exe.genericInfo.resources.storageBuffers;
-            buffers.push_back(StorageBufferResource(m_casterUvs, true, plr::sunraster::kUvBinding));
-            buffers.push_back(StorageBufferResource(m_casterMaterials, true, plr::sunraster::kCasterMaterialBinding));
-            buffers.push_back(StorageBufferResource(m_casterTextures, true, plr::sunraster::kTextureBinding));
-            buffers.push_back(StorageBufferResource(m_casterTexels, true, plr::sunraster::kTexelBinding));
+            buffers.push_back(StorageBufferResource(m_casterUvs.handle, true, plr::sunraster::kUvBinding));
+            buffers.push_back(StorageBufferResource(m_casterMaterials.handle, true, plr::sunraster::kCasterMaterialBinding));
+            buffers.push_back(StorageBufferResource(m_casterTextures.handle, true, plr::sunraster::kTextureBinding));
+            buffers.push_back(StorageBufferResource(m_casterTexels.handle, true, plr::sunraster::kTexelBinding));
         }
         m_be.setComputePassExecution(exe);
     }
 }
 
-// a caster buffer that holds `bytes`: a new, larger one when the current is too small (the backend has no call that frees a buffer; casters change with the
-// scene, not per frame), then the contents as a queued fill (applied in call order at the next frame)
-void FramePipeline::fillCasterBuffer(StorageBufferHandle& buffer, size_t& capacity, const void* data, size_t bytes) {
-    if (capacity < bytes) {
+// a buffer that holds `bytes`: a new, larger one when the current is too small (the backend has no call that frees a buffer; meshes change with the scene, not
+// per frame; it never shrinks), then the contents as a queued fill (applied in call order at the next frame). data null: the size only
+void FramePipeline::fillBuffer(GrowableBuffer& buffer, const void* data, size_t bytes) {
+    if (buffer.bytes < bytes) {
         StorageBufferDescription sb;
         sb.size = (bytes + 255) & ~(size_t)255;
-        buffer = m_be.createStorageBuffer(sb);
-        capacity = sb.size;
+        buffer.handle = m_be.createStorageBuffer(sb);
+        buffer.bytes = sb.size;
     }
-    if (data) m_be.setStorageBufferData(buffer, data, bytes);
-}
-
-static void refuseUnlessAffine(const float* m, uint32_t draw, const char* call) {
-    if (m[3] != 0.f || m[7] != 0.f || m[11] != 0.f || m[15] != 1.f)
-        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": the model matrix of draw " + std::to_string(draw) +
-                                   " is not affine (its last row must be exactly (0, 0, 0, 1): the shadow pass does not divide by w)");
+    if (data) m_be.setStorageBufferData(buffer.handle, data, bytes);
 }
 
 void FramePipeline::setShadowCasters(const ShadowCasterMesh* meshes, uint32_t meshCount, const ShadowCasterDraw* draws, uint32_t drawCount) {
     if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setShadowCasters: a band / tile pipeline cannot rasterise shadow casters (every partition would draw every cascade)");
     if (drawCount == 0) {
-        m_casterDrawCount = m_casterTriangleCount = m_casterTextureCount = 0;
-        m_casterAlphaTested = false;
+        m_casterDrawCount = m_casterTriangleCount = 0;
+        dropCasterCutouts();
         m_casterMeshVertexCounts.clear();
         m_casterBoundsHost.clear();
         m_casterBoundsUploaded = m_casterCullRecorded = false;
         return;
     }
-    if (!meshes || !draws || meshCount == 0) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: draws without meshes");
-    // everything is validated before anything is changed
-    std::vector<uint32_t> firstIndex(meshCount), vertexOffset(meshCount);
-    uint64_t vertices = 0, indices = 0, triangles = 0;
-    for (uint32_t m = 0; m < meshCount; m++) {
-        const ShadowCasterMesh& mesh = meshes[m];
-        if ((mesh.vertexCount && !mesh.positions) || (mesh.indexCount && !mesh.indices)) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: mesh " + std::to_string(m) + " has null data");
-        if (mesh.indexCount % 3u != 0u)
-            throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: mesh " + std::to_string(m) + " has " + std::to_string(mesh.indexCount) + " indices, not a triangle list");
-        for (uint32_t i = 0; i < mesh.indexCount; i++)
-            if (mesh.indices[i] >= mesh.vertexCount)
-                throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: vertex index out of range: index " + std::to_string(i) + " of mesh " + std::to_string(m) + " is " +
-                                           std::to_string(mesh.indices[i]) + ", the mesh has " + std::to_string(mesh.vertexCount) + " vertices");
-        firstIndex[m] = (uint32_t)indices; vertexOffset[m] = (uint32_t)vertices;
-        vertices += mesh.vertexCount; indices += mesh.indexCount;
-    }
-    for (uint32_t d = 0; d < drawCount; d++) {
-        if (draws[d].mesh >= meshCount)
-            throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: mesh index out of range: draw " + std::to_string(d) + " names mesh " + std::to_string(draws[d].mesh) +
-                                       " of " + std::to_string(meshCount));
-        refuseUnlessAffine(draws[d].modelMatrix, d, "setShadowCasters");
-        triangles += meshes[draws[d].mesh].indexCount / 3u;
-    }
-    if (vertices == 0 || indices == 0 || triangles == 0) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: the draws hold no triangle");
-    if (vertices > 0xffffffffull || indices > 0xffffffffull || triangles > 0x7fffffffull) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasters: too many vertices, indices or triangles");
-    std::vector<float> positions((size_t)vertices * 3u), matrices((size_t)drawCount * 16u);
-    std::vector<uint32_t> indexData((size_t)indices);
-    std::vector<plr::sunraster::Draw> drawData(drawCount);
-    for (uint32_t m = 0; m < meshCount; m++) {
-        if (meshes[m].vertexCount) std::memcpy(positions.data() + (size_t)vertexOffset[m] * 3u, meshes[m].positions, (size_t)meshes[m].vertexCount * 12u);
-        if (meshes[m].indexCount) std::memcpy(indexData.data() + firstIndex[m], meshes[m].indices, (size_t)meshes[m].indexCount * 4u);
-    }
-    for (uint32_t d = 0; d < drawCount; d++) {
-        drawData[d] = {firstIndex[draws[d].mesh], meshes[draws[d].mesh].indexCount, vertexOffset[draws[d].mesh], d};
-        std::memcpy(matrices.data() + (size_t)d * 16u, draws[d].modelMatrix, 64);
-    }
+    const PackedCasters packed = packShadowCasters(meshes, meshCount, draws, drawCount); // validates everything before anything is changed
     if (!m_casterPassesCreated) {
         for (uint32_t c = 0; c < 4; c++) {
             ComputePassDescription d; // RenderFrontend.cpp:1565-1590, one pass per cascade (sunShadow.vert:8 cascadeIndex)
@@ -1434,40 +1393,31 @@ void FramePipeline::setShadowCasters(const ShadowCasterMesh* meshes, uint32_t me
         }
         m_casterPassesCreated = true;
     }
-    fillCasterBuffer(m_casterPositions, m_casterPositionBytes, positions.data(), positions.size() * sizeof(float));
-    fillCasterBuffer(m_casterIndices, m_casterIndexBytes, indexData.data(), indexData.size() * sizeof(uint32_t));
-    fillCasterBuffer(m_casterDraws, m_casterDrawBytes, drawData.data(), drawData.size() * sizeof(plr::sunraster::Draw));
-    fillCasterBuffer(m_casterTransforms, m_casterTransformBytes, matrices.data(), matrices.size() * sizeof(float));
-    for (int c = 0; c < settings.shading.sunShadowCascadeCount; c++)
-        fillCasterBuffer(m_casterScratch[c], m_casterScratchBytes[c], nullptr, plr::sunraster::scratchBytes((uint32_t)triangles));
-    m_casterDrawCount = drawCount; m_casterTriangleCount = (uint32_t)triangles;
-    m_casterMeshVertexCounts.resize(meshCount);
-    for (uint32_t m = 0; m < meshCount; m++) m_casterMeshVertexCounts[m] = meshes[m].vertexCount;
-    m_casterTextureCount = 0; // the cutouts belonged to the casters that were replaced
-    m_casterAlphaTested = false;
-    { // the draws' local boxes: they live and die with the meshes
-        std::vector<const float*> meshPositions(meshCount);
-        std::vector<uint32_t> drawMeshes(drawCount);
-        for (uint32_t m = 0; m < meshCount; m++) meshPositions[m] = meshes[m].positions;
-        for (uint32_t d = 0; d < drawCount; d++) drawMeshes[d] = draws[d].mesh;
-        m_casterBoundsHost = packDrawBounds(meshPositions.data(), m_casterMeshVertexCounts.data(), meshCount, drawMeshes.data(), drawCount);
-    }
+    fillBuffer(m_casterPositions, packed.positions);
+    fillBuffer(m_casterIndices, packed.indices);
+    fillBuffer(m_casterDraws, packed.draws);
+    fillBuffer(m_casterTransforms, packed.models);
+    for (int c = 0; c < settings.shading.sunShadowCascadeCount; c++) fillBuffer(m_casterScratch[c], nullptr, plr::sunraster::scratchBytes(packed.triangleCount));
+    m_casterDrawCount = drawCount; m_casterTriangleCount = packed.triangleCount;
+    m_casterMeshVertexCounts = packed.meshVertexCounts;
+    dropCasterCutouts();
+    m_casterBoundsHost = packed.drawBounds; // they live and die with the meshes
     m_casterBoundsUploaded = m_casterCullRecorded = false;
-    prepareDrawCulling();
+    prepareDrawCulling(); // (the removal has nothing to prepare: a view without its mesh set is off)
 }
 
 void FramePipeline::setShadowCasterCutouts(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts, uint32_t drawCount) {
     if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setShadowCasterCutouts: a band / tile pipeline cannot rasterise shadow casters");
-    if (textureCount == 0) { m_casterTextureCount = 0; m_casterAlphaTested = false; return; }
+    if (textureCount == 0) { dropCasterCutouts(); return; }
     const PackedShadowCutouts packed = packShadowCasterCutouts(textures, textureCount, meshUvs, meshCount, cutouts, drawCount, m_casterMeshVertexCounts.data(),
                                                                (uint32_t)m_casterMeshVertexCounts.size(), m_casterDrawCount); // validates everything before anything is changed
-    fillCasterBuffer(m_casterUvs, m_casterUvBytes, packed.uvs.data(), packed.uvs.size() * sizeof(float));
-    fillCasterBuffer(m_casterMaterials, m_casterMaterialBytes, packed.materials.data(), packed.materials.size() * sizeof(uint32_t));
-    fillCasterBuffer(m_casterTextures, m_casterTextureBytes, packed.textures.data(), packed.textures.size() * sizeof(uint32_t));
-    fillCasterBuffer(m_casterTexels, m_casterTexelBytes, packed.texels.data(), packed.texels.size() * sizeof(uint32_t));
+    fillBuffer(m_casterUvs, packed.uvs);
+    fillBuffer(m_casterMaterials, packed.materials);
+    fillBuffer(m_casterTextures, packed.textures);
+    fillBuffer(m_casterTexels, packed.texels);
     for (int c = 0; c < settings.shading.sunShadowCascadeCount; c++) // a tested execution's records are larger
-        fillCasterBuffer(m_casterScratch[c], m_casterScratchBytes[c], nullptr, plr::sunraster::cutoutScratchBytes(m_casterTriangleCount));
+        fillBuffer(m_casterScratch[c], nullptr, plr::sunraster::cutoutScratchBytes(m_casterTriangleCount));
     m_casterTextureCount = textureCount;
     m_casterAlphaTested = packed.tested;
 }
@@ -1479,16 +1429,16 @@ void FramePipeline::setShadowCasterTransforms(const float* matrices16, uint32_t 
     if (drawCount == 0) return;
     if (!matrices16) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "setShadowCasterTransforms: matrices are null");
     for (uint32_t d = 0; d < drawCount; d++) refuseUnlessAffine(matrices16 + (size_t)d * 16u, d, "setShadowCasterTransforms");
-    m_be.setStorageBufferData(m_casterTransforms, matrices16, (size_t)drawCount * 64u);
+    m_be.setStorageBufferData(m_casterTransforms.handle, matrices16, (size_t)drawCount * 64u);
 }
 
 ShadowRasterStats FramePipeline::shadowRasterStats(uint32_t cascade) {
     if (cascade >= (uint32_t)settings.shading.sunShadowCascadeCount)
         throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "shadowRasterStats: cascade " + std::to_string(cascade) + " of " + std::to_string(settings.shading.sunShadowCascadeCount));
     ShadowRasterStats out;
-    if (m_casterScratchBytes[cascade] == 0) return out;
+    if (m_casterScratch[cascade].bytes == 0) return out;
     plr::sunraster::ScratchHeader h{};
-    if (plr_download_storage_buffer(m_casterScratch[cascade].index, &h, 0, sizeof(h)) != PLR_OK) throw std::runtime_error(plr_last_error());
+    if (plr_download_storage_buffer(m_casterScratch[cascade].handle.index, &h, 0, sizeof(h)) != PLR_OK) throw std::runtime_error(plr_last_error());
     out.trianglesSubmitted = h.submitted; out.trianglesDrawn = h.drawn; out.guardBandRejects = h.guardBandRejects;
     return out;
 }
@@ -1578,17 +1528,16 @@ void FramePipeline::prepareDrawCulling() {
         }
         m_cullPassesCreated = true;
     }
-    auto fill = [&](SceneBuffer& b, const void* data, size_t bytes) { fillCasterBuffer(b.handle, b.bytes, data, bytes); };
     if (cullScene() && !m_sceneBoundsUploaded) {
         uploadSceneBounds();
-        fill(m_sceneCulledDraws, nullptr, (size_t)m_sceneDrawCount * sizeof(plr::prepass::Draw));
-        fill(m_sceneCullStats, nullptr, dc::statsBytes(1));
+        fillBuffer(m_sceneCulledDraws, nullptr, (size_t)m_sceneDrawCount * sizeof(plr::prepass::Draw));
+        fillBuffer(m_sceneCullStats, nullptr, dc::statsBytes(1));
         m_sceneBoundsUploaded = true;
     }
     if (cullCasters() && !m_casterBoundsUploaded) {
-        fill(m_casterBounds, m_casterBoundsHost.data(), m_casterBoundsHost.size() * sizeof(float));
-        for (int c = 0; c < settings.shading.sunShadowCascadeCount; c++) fill(m_casterCulledDraws[c], nullptr, (size_t)m_casterDrawCount * sizeof(plr::sunraster::Draw));
-        fill(m_casterCullStats, nullptr, dc::statsBytes(dc::kMaxViews));
+        fillBuffer(m_casterBounds, m_casterBoundsHost);
+        for (int c = 0; c < settings.shading.sunShadowCascadeCount; c++) fillBuffer(m_casterCulledDraws[c], nullptr, (size_t)m_casterDrawCount * sizeof(plr::sunraster::Draw));
+        fillBuffer(m_casterCullStats, nullptr, dc::statsBytes(dc::kMaxViews));
         m_casterBoundsUploaded = true;
     }
 }
@@ -1608,8 +1557,8 @@ void FramePipeline::recordDrawCulling(bool shadowViews) {
         m_sceneCullRecorded = true;
     } else {
         const uint32_t cascades = (uint32_t)settings.shading.sunShadowCascadeCount;
-        buffers = {StorageBufferResource(m_casterDraws, true, dc::kDrawBinding), StorageBufferResource(m_casterBounds.handle, true, dc::kBoundsBinding),
-                   StorageBufferResource(m_casterTransforms, true, dc::kTransformBinding), StorageBufferResource(m_sunShadowInfoBuffer, true, dc::kSunShadowInfoBinding),
+        buffers = {StorageBufferResource(m_casterDraws.handle, true, dc::kDrawBinding), StorageBufferResource(m_casterBounds.handle, true, dc::kBoundsBinding),
+                   StorageBufferResource(m_casterTransforms.handle, true, dc::kTransformBinding), StorageBufferResource(m_sunShadowInfoBuffer, true, dc::kSunShadowInfoBinding),
                    StorageBufferResource(m_casterCullStats.handle, false, dc::kStatsBinding)};
         for (uint32_t c = 0; c < cascades; c++) buffers.push_back(StorageBufferResource(m_casterCulledDraws[c].handle, false, dc::kCulledDrawBinding + (int)c));
         const dc::PushConstants pc{m_casterDrawCount, dc::kViewShadow, cascades};
@@ -1621,7 +1570,7 @@ void FramePipeline::recordDrawCulling(bool shadowViews) {
 
 void FramePipeline::uploadSceneBounds() {
     if (m_sceneBoundsOnGpu || m_sceneDrawCount == 0) return;
-    fillCasterBuffer(m_sceneBounds.handle, m_sceneBounds.bytes, m_sceneBoundsHost.data(), m_sceneBoundsHost.size() * sizeof(float));
+    fillBuffer(m_sceneBounds, m_sceneBoundsHost);
     m_sceneBoundsOnGpu = true;
 }
 
@@ -1672,12 +1621,12 @@ void FramePipeline::prepareDebugGeometry() {
         d.shaderDescription.srcPathRelative = "debugGeometry.comp";
         m_debugGeometryPass = m_be.createComputePass(d);
         const plr::debuggeo::Stats zero{};
-        fillCasterBuffer(m_debugStats.handle, m_debugStats.bytes, &zero, sizeof(zero));
+        fillBuffer(m_debugStats, &zero, sizeof(zero));
         m_debugPassCreated = true;
     }
     if (m_debugFlags & kDebugDrawBoxes) uploadSceneBounds();
     if ((m_debugFlags & kDebugLines) && !m_debugLinesUploaded && !m_debugLinesHost.empty()) {
-        fillCasterBuffer(m_debugLines.handle, m_debugLines.bytes, m_debugLinesHost.data(), m_debugLinesHost.size() * sizeof(float));
+        fillBuffer(m_debugLines, m_debugLinesHost);
         m_debugLinesUploaded = true;
     }
 }
@@ -1755,9 +1704,9 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
     if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneMeshes: a band / tile pipeline cannot rasterise scene meshes (a partition would have to rasterise only its own rectangle)");
     if (drawCount == 0) {
-        m_sceneDrawCount = m_sceneTriangleCount = m_sceneTextureCount = 0;
-        m_scenePreviousValid = m_sceneRecorded = m_sceneAlphaTested = m_sceneTexturesCompressed = false;
-        m_sceneNormalDecode = 0;
+        m_sceneDrawCount = m_sceneTriangleCount = 0;
+        m_scenePreviousValid = m_sceneRecorded = false;
+        dropSceneTextures();
         m_sceneMeshVertexCounts.clear(); m_sceneMeshHasNormals.clear(); m_sceneNormalsHost.clear();
         removeSceneSdf(); // its mesh indices named the scene that is gone
         m_scenePositionsHost.clear(); m_sceneIndicesHost.clear(); m_sceneDrawMeshes.clear(); m_sceneMeshFirstIndex.clear(); m_sceneMeshIndexCounts.clear();
@@ -1774,21 +1723,17 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
         m_depthPrepassRasterPass = m_be.createComputePass(d);
         m_scenePassCreated = true;
     }
-    auto fill = [&](SceneBuffer& b, const void* data, size_t bytes) { fillCasterBuffer(b.handle, b.bytes, data, bytes); };
-    fill(m_scenePositions, packed.positions.data(), packed.positions.size() * sizeof(float));
-    fill(m_sceneNormals, packed.normals.data(), packed.normals.size() * sizeof(float));
-    fill(m_sceneIndices, packed.indices.data(), packed.indices.size() * sizeof(uint32_t));
-    fill(m_sceneDraws, packed.draws.data(), packed.draws.size() * sizeof(uint32_t));
-    fill(m_sceneMatrices, nullptr, (size_t)drawCount * sizeof(plr::prepass::MainPassMatrices)); // filled by every frame
-    fill(m_sceneScratch, nullptr, plr::prepass::scratchBytes(packed.triangleCount));
+    fillBuffer(m_scenePositions, packed.positions);
+    fillBuffer(m_sceneNormals, packed.normals);
+    fillBuffer(m_sceneIndices, packed.indices);
+    fillBuffer(m_sceneDraws, packed.draws);
+    fillBuffer(m_sceneMatrices, nullptr, (size_t)drawCount * sizeof(plr::prepass::MainPassMatrices)); // filled by every frame
+    fillBuffer(m_sceneScratch, nullptr, plr::prepass::scratchBytes(packed.triangleCount));
     m_sceneModel = packed.models;
     m_scenePreviousValid = m_sceneRecorded = false;
     m_sceneDrawCount = drawCount; m_sceneTriangleCount = packed.triangleCount;
     m_sceneMeshVertexCounts = packed.meshVertexCounts;
-    m_sceneTextureCount = 0; // the textures belonged to the scene that was replaced
-    m_sceneTexturesCompressed = false;
-    m_sceneAlphaTested = false; // and so did the cutoffs
-    m_sceneNormalDecode = 0;    // and the normal maps
+    dropSceneTextures();
     m_sceneMeshHasNormals = packed.meshHasNormals;
     m_sceneNormalsHost = packed.normals;
     m_scenePositionsHost = packed.positions; m_sceneIndicesHost = packed.indices; // what a later setSceneSdf takes the local boxes and the bake from
@@ -1802,39 +1747,31 @@ void FramePipeline::setSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, 
 void FramePipeline::setSceneTextures(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {
     if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneTextures: a band / tile pipeline cannot rasterise scene meshes");
-    if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = m_sceneTexturesCompressed = false; m_sceneNormalDecode = 0; noteSceneTexturesChanged(0); return; }
+    if (textureCount == 0) { dropSceneTextures(); noteSceneTexturesChanged(0); return; } // (setSceneMeshes removes the scene's SDF instead: here it stays, its means stale)
     const PackedTextures packed = packSceneTextures(textures, textureCount, meshUvs, meshCount, materials, drawCount, m_sceneMeshVertexCounts.data(),
                                                     (uint32_t)m_sceneMeshVertexCounts.size(), m_sceneDrawCount); // validates everything before anything is changed
-    auto fill = [&](SceneBuffer& b, const std::vector<uint32_t>& data) { fillCasterBuffer(b.handle, b.bytes, data.data(), data.size() * sizeof(uint32_t)); };
-    fillCasterBuffer(m_sceneUvs.handle, m_sceneUvs.bytes, packed.uvs.data(), packed.uvs.size() * sizeof(float));
-    fill(m_sceneMaterials, packed.materials);
-    fill(m_sceneTextures, packed.textures);
-    fill(m_sceneTexels, packed.texels);
-    m_sceneTextureCount = textureCount;
-    m_sceneTexturesCompressed = false;
-    m_sceneAlphaTested = false; // the cutoffs belonged to the materials that were replaced
-    m_sceneNormalDecode = 0;    // and the normal maps named textures that were replaced
-    uint32_t largest = 0;
-    for (uint32_t t = 0; t < textureCount; t++) largest = std::max(largest, packed.textures[4u * t + 1u] * packed.textures[4u * t + 2u]);
-    noteSceneTexturesChanged(largest);
+    takeSceneTextures(packed, textureCount, nullptr);
 }
 
 void FramePipeline::setSceneTexturesFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {
     if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneTexturesFormatted: a band / tile pipeline cannot rasterise scene meshes");
-    if (textureCount == 0) { m_sceneTextureCount = 0; m_sceneAlphaTested = m_sceneTexturesCompressed = false; m_sceneNormalDecode = 0; noteSceneTexturesChanged(0); return; }
+    if (textureCount == 0) { dropSceneTextures(); noteSceneTexturesChanged(0); return; }
     const PackedFormattedTextures packed = packSceneTexturesFormatted(textures, textureCount, meshUvs, meshCount, materials, drawCount, m_sceneMeshVertexCounts.data(),
                                                                       (uint32_t)m_sceneMeshVertexCounts.size(), m_sceneDrawCount); // validates everything before anything is changed
-    auto fill = [&](SceneBuffer& b, const std::vector<uint32_t>& data) { fillCasterBuffer(b.handle, b.bytes, data.data(), data.size() * sizeof(uint32_t)); };
-    fillCasterBuffer(m_sceneUvs.handle, m_sceneUvs.bytes, packed.uvs.data(), packed.uvs.size() * sizeof(float));
-    fill(m_sceneMaterials, packed.materials);
-    fill(m_sceneTextures, packed.textures);
-    fill(m_sceneTexels, packed.texels);
-    if (packed.compressed) fill(m_sceneTextureFormats, packed.formats);
+    takeSceneTextures(packed, textureCount, packed.compressed ? &packed.formats : nullptr);
+}
+
+void FramePipeline::takeSceneTextures(const PackedTextures& packed, uint32_t textureCount, const std::vector<uint32_t>* formats) {
+    fillBuffer(m_sceneUvs, packed.uvs);
+    fillBuffer(m_sceneMaterials, packed.materials);
+    fillBuffer(m_sceneTextures, packed.textures);
+    fillBuffer(m_sceneTexels, packed.texels);
+    if (formats) fillBuffer(m_sceneTextureFormats, *formats);
     m_sceneTextureCount = textureCount;
-    m_sceneTexturesCompressed = packed.compressed;
-    m_sceneAlphaTested = false; // the cutoffs belonged to the materials that were replaced
-    m_sceneNormalDecode = 0;    // and the normal maps named textures that were replaced
+    m_sceneTexturesCompressed = formats != nullptr;
+    dropSceneAlphaCutoffs(); // of the materials that were replaced
+    dropSceneNormalMaps();   // they named textures that were replaced
     uint32_t largest = 0;
     for (uint32_t t = 0; t < textureCount; t++) largest = std::max(largest, packed.textures[4u * t + 1u] * packed.textures[4u * t + 2u]);
     noteSceneTexturesChanged(largest);
@@ -1844,14 +1781,14 @@ void FramePipeline::setSceneNormalMaps(const float* const* meshTangents, const f
                                        uint32_t decode) {
     if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneNormalMaps: a band / tile pipeline cannot rasterise scene meshes");
-    if (drawCount == 0) { m_sceneNormalDecode = 0; return; }
+    if (drawCount == 0) { dropSceneNormalMaps(); return; }
     SceneNormalMapContext scene;
     scene.meshVertexCounts = m_sceneMeshVertexCounts.data(); scene.meshHasNormals = m_sceneMeshHasNormals.data(); scene.normals = m_sceneNormalsHost.data();
     scene.meshCount = (uint32_t)m_sceneMeshVertexCounts.size(); scene.drawCount = m_sceneDrawCount; scene.textureCount = m_sceneTextureCount;
     const PackedNormalMaps packed = packSceneNormalMaps(meshTangents, meshBitangents, meshCount, normalTextures, drawCount, decode, scene); // validates everything before anything is changed
-    fillCasterBuffer(m_sceneTangents.handle, m_sceneTangents.bytes, packed.tangents.data(), packed.tangents.size() * sizeof(float));
-    fillCasterBuffer(m_sceneBitangents.handle, m_sceneBitangents.bytes, packed.bitangents.data(), packed.bitangents.size() * sizeof(float));
-    fillCasterBuffer(m_sceneNormalMaterials.handle, m_sceneNormalMaterials.bytes, packed.normalMaterials.data(), packed.normalMaterials.size() * sizeof(uint32_t));
+    fillBuffer(m_sceneTangents, packed.tangents);
+    fillBuffer(m_sceneBitangents, packed.bitangents);
+    fillBuffer(m_sceneNormalMaterials, packed.normalMaterials);
     if (!m_shadingNormalCreated) { // at the size the other G-buffer images have now: a pending resize re-creates it with them
         m_shadingNormalImage = m_be.createImage(desc2D(settings.width, settings.height, ImageFormat::RGBA8), nullptr, 0);
         m_shadingNormalCreated = true;
@@ -1862,9 +1799,9 @@ void FramePipeline::setSceneNormalMaps(const float* const* meshTangents, const f
 void FramePipeline::setSceneAlphaCutoffs(const uint32_t* cutoffs, uint32_t drawCount) {
     if (partitionedWithoutRaster(m_requestedSettings))
         throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setSceneAlphaCutoffs: a band / tile pipeline cannot rasterise scene meshes");
-    if (drawCount == 0) { m_sceneAlphaTested = false; return; }
+    if (drawCount == 0) { dropSceneAlphaCutoffs(); return; }
     const PackedAlphaCutoffs packed = packSceneAlphaCutoffs(cutoffs, drawCount, m_sceneDrawCount, m_sceneTextureCount); // validates everything before anything is changed
-    fillCasterBuffer(m_sceneAlphaCutoffs.handle, m_sceneAlphaCutoffs.bytes, packed.cutoffs.data(), packed.cutoffs.size() * sizeof(uint32_t));
+    fillBuffer(m_sceneAlphaCutoffs, packed.cutoffs);
     m_sceneAlphaTested = packed.tested;
 }
 
@@ -1889,15 +1826,20 @@ void FramePipeline::setSceneMeshTransforms(const float* matrices16, uint32_t dra
 
 // ---- SDFGI::updateSDFScene (Techniques/SDFGI.cpp:260-313) as "sdfInstanceUpdate.comp", with computeMeanAlbedo (ModelImport.cpp:78-112) as "sceneMeanAlbedo.comp"
 // (kernels/scene_sdf.hip; DESIGN.md "SDF instances from the scene")
+// the backend has no call that frees an image: a released volume keeps its slot of the texture array with one texel (1 x 1 x 1 R16), for the next bake
+static ImageDescription releasedSdfVolume() {
+    ImageDescription released;
+    released.width = released.height = released.depth = 1;
+    released.type = ImageType::Type3D; released.format = ImageFormat::R16_sFloat; released.usageFlags = ImageUsageFlags::Sampled;
+    return released;
+}
+
 void FramePipeline::removeSceneSdf() {
     if (!m_sceneSdfSet) return;
     m_sceneSdfSet = false;
     m_sceneSdf = PackedSceneSdf{};
-    ImageDescription released; // the backend has no call that frees an image: a released volume keeps its slot of the texture array with one texel, for the next bake
-    released.width = released.height = released.depth = 1;
-    released.type = ImageType::Type3D; released.format = ImageFormat::R16_sFloat; released.usageFlags = ImageUsageFlags::Sampled;
     for (BakedVolume& v : m_sceneSdfVolumes)
-        if (v.inUse) { m_be.recreateImage(v.image, released); v.inUse = false; v.bytes = 0; }
+        if (v.inUse) { m_be.recreateImage(v.image, releasedSdfVolume()); v.inUse = false; v.bytes = 0; }
     m_sdfGi.setInstanceCount(0);
     const uint32_t header[4] = {0, 0, 0, 0}; // the instance count is 0 until the caller uploads again (setSdfScene)
     m_be.setStorageBufferData(m_sdfGi.m_sdfInstanceBuffer, header, sizeof(header));
@@ -1953,13 +1895,8 @@ void FramePipeline::setSceneSdf(const uint32_t* sdfTextures, uint32_t meshCount)
         m_sceneSdfVolumes[slot].inUse = true; m_sceneSdfVolumes[slot].bytes = bytes;
         meshTextureIndices[packed.bakedMeshes[k]] = m_be.getImageGlobalTextureArrayIndex(m_sceneSdfVolumes[slot].image);
     }
-    {
-        ImageDescription released;
-        released.width = released.height = released.depth = 1;
-        released.type = ImageType::Type3D; released.format = ImageFormat::R16_sFloat; released.usageFlags = ImageUsageFlags::Sampled;
-        for (size_t v = 0; v < m_sceneSdfVolumes.size(); v++)
-            if (wasInUse[v] && !m_sceneSdfVolumes[v].inUse) { m_be.recreateImage(m_sceneSdfVolumes[v].image, released); m_sceneSdfVolumes[v].bytes = 0; }
-    }
+    for (size_t v = 0; v < m_sceneSdfVolumes.size(); v++)
+        if (wasInUse[v] && !m_sceneSdfVolumes[v].inUse) { m_be.recreateImage(m_sceneSdfVolumes[v].image, releasedSdfVolume()); m_sceneSdfVolumes[v].bytes = 0; }
     if (!m_sceneSdfPassesCreated) {
         ComputePassDescription d;
         d.name = "SDF instance update";
@@ -1971,9 +1908,9 @@ void FramePipeline::setSceneSdf(const uint32_t* sdfTextures, uint32_t meshCount)
         m_sceneSdfPassesCreated = true;
     }
     const std::vector<uint32_t> table = sceneSdfInstanceTable(packed, m_sceneDrawMeshes.data(), meshTextureIndices.data());
-    fillCasterBuffer(m_sceneSdfTable.handle, m_sceneSdfTable.bytes, table.empty() ? nullptr : table.data(), std::max<size_t>(table.size() * sizeof(uint32_t), sizeof(plr::scenesdf::InstanceEntry)));
+    fillBuffer(m_sceneSdfTable, table.empty() ? nullptr : table.data(), std::max<size_t>(table.size() * sizeof(uint32_t), sizeof(plr::scenesdf::InstanceEntry)));
     const std::vector<float> derive((size_t)m_sceneDrawCount * 3u, std::nanf("")); // no overrides: every draw derives
-    fillCasterBuffer(m_sceneSdfOverrides.handle, m_sceneSdfOverrides.bytes, derive.data(), derive.size() * sizeof(float));
+    fillBuffer(m_sceneSdfOverrides, derive);
     m_sceneSdf = std::move(packed);
     m_sceneSdfSet = true;
     m_sdfGi.setInstanceCount((uint32_t)m_sceneSdf.instanceDraws.size());
@@ -1986,8 +1923,8 @@ void FramePipeline::noteSceneTexturesChanged(uint32_t largestLevel0Texels) {
     if (largestLevel0Texels) m_sceneSdfMeanGroups = std::min(1024u, std::max(1u, (largestLevel0Texels + 4095u) / 4096u));
     m_sceneSdfMeansStale = true;
     if (!m_sceneSdfSet || m_sceneTextureCount == 0) return;
-    fillCasterBuffer(m_sceneSdfMeans.handle, m_sceneSdfMeans.bytes, nullptr, (size_t)m_sceneTextureCount * 16u);
-    fillCasterBuffer(m_sceneSdfMeanScratch.handle, m_sceneSdfMeanScratch.bytes, nullptr, plr::scenesdf::meanScratchBytes(m_sceneTextureCount));
+    fillBuffer(m_sceneSdfMeans, nullptr, (size_t)m_sceneTextureCount * 16u);
+    fillBuffer(m_sceneSdfMeanScratch, nullptr, plr::scenesdf::meanScratchBytes(m_sceneTextureCount));
 }
 
 void FramePipeline::setSceneSdfMeanAlbedo(const float* rgbOrNan, uint32_t drawCount) {
@@ -1996,11 +1933,11 @@ void FramePipeline::setSceneSdfMeanAlbedo(const float* rgbOrNan, uint32_t drawCo
     if (drawCount == 0) {
         if (!m_sceneSdfSet) return;
         const std::vector<float> derive((size_t)m_sceneDrawCount * 3u, std::nanf(""));
-        fillCasterBuffer(m_sceneSdfOverrides.handle, m_sceneSdfOverrides.bytes, derive.data(), derive.size() * sizeof(float));
+        fillBuffer(m_sceneSdfOverrides, derive);
         return;
     }
     const std::vector<float> values = packSceneSdfMeanAlbedo(rgbOrNan, drawCount, m_sceneDrawCount, m_sceneSdfSet); // validates everything before anything is changed
-    fillCasterBuffer(m_sceneSdfOverrides.handle, m_sceneSdfOverrides.bytes, values.data(), values.size() * sizeof(float));
+    fillBuffer(m_sceneSdfOverrides, values);
 }
 
 FramePipeline::SceneSdfStats FramePipeline::sceneSdfStats() const {

@@ -337,24 +337,33 @@ struct ShadowRasterStats { uint64_t trianglesSubmitted = 0, trianglesDrawn = 0, 
 struct SceneMesh { const float* positions = nullptr; const float* normals = nullptr; uint32_t vertexCount = 0; const uint32_t* indices = nullptr; uint32_t indexCount = 0; };
 struct SceneDraw { uint32_t mesh = 0; float modelMatrix[16] = {}; uint32_t albedo = 0, specular = 0; }; // glm column-major
 struct PrepassRasterStats { uint64_t trianglesSubmitted = 0, trianglesClipped = 0, subtrianglesDrawn = 0, rejects = 0; };
-// what setSceneMeshes validates and packs, without a backend: the buffers of "depthPrepassRaster.comp" (device/depth_prepass_raster.h). Throws FramePipelineRefusal.
-struct PackedScene {
-    std::vector<float> positions, normals, models; // 3 floats per vertex (normals: zeros for a mesh without), 16 floats per draw
+// what both mesh sets are validated and packed into, without a backend: the meshes back to back and the draws of either rasteriser. Throws FramePipelineRefusal.
+struct PackedMeshes {
+    std::vector<float> positions, models;          // 3 floats per vertex, 16 floats per draw
     std::vector<uint32_t> indices;
-    std::vector<uint32_t> draws;                   // 6 words per draw: {firstIndex, indexCount, vertexOffset, transformIndex, albedo, specular}
+    std::vector<uint32_t> draws;                   // the pass's record per draw: {firstIndex, indexCount, vertexOffset, transformIndex} and what the pass adds
     uint32_t triangleCount = 0;
-    std::vector<uint32_t> meshVertexCounts;        // per mesh, in the order the positions are packed: what packSceneTextures lays the UVs out by
+    std::vector<uint32_t> meshVertexCounts;        // per mesh, in the order the positions are packed: what the texture and cutout packers lay the UVs out by
+    std::vector<float> drawBounds;                 // 6 floats per draw {lo.xyz, hi.xyz}: packDrawBounds ("drawCulling.comp"'s bounds)
+};
+// setShadowCasters: the buffers of "sunShadowRaster.comp" (device/sun_shadow_raster.h), draws of 4 words (plr::sunraster::Draw)
+typedef PackedMeshes PackedCasters;
+// setSceneMeshes: the buffers of "depthPrepassRaster.comp" (device/depth_prepass_raster.h), draws of 6 words (plr::prepass::Draw: albedo and specular behind the four)
+struct PackedScene : PackedMeshes {
+    std::vector<float> normals;                    // 3 floats per vertex, zeros for a mesh without
     std::vector<uint8_t> meshHasNormals;           // per mesh: given with vertex normals (packSceneNormalMaps derives bitangents from them)
     std::vector<uint32_t> drawMeshes;              // per draw: its mesh (packSceneSdf maps draws to SDF instances by it)
     std::vector<uint32_t> meshFirstIndex, meshIndexCounts; // per mesh: where its triangle list lies in `indices` (setSceneSdf bakes from it)
-    std::vector<float> drawBounds;                 // 6 floats per draw {lo.xyz, hi.xyz}: packDrawBounds ("drawCulling.comp"'s bounds)
 };
 // the bounds buffer of "drawCulling.comp" (device/draw_culling.h): per draw the local box of its mesh over ALL the mesh's vertices (indexed or not), exact fp32
 // minima and maxima; an axis on which a vertex is a NaN gets NaN bounds (the pass keeps such a draw), a mesh without vertices an all-zero box. Throws
 // FramePipelineRefusal for a draw that names no mesh
 std::vector<float> packDrawBounds(const float* const* meshPositions, const uint32_t* meshVertexCounts, uint32_t meshCount, const uint32_t* drawMeshes, uint32_t drawCount);
 PackedScene packSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const SceneDraw* draws, uint32_t drawCount);
+PackedCasters packShadowCasters(const ShadowCasterMesh* meshes, uint32_t meshCount, const ShadowCasterDraw* draws, uint32_t drawCount);
 void refuseNonFiniteMatrices(const float* matrices16, uint32_t drawCount, const char* call);
+// refuses (PLR_ERR_INVALID_ARGUMENT, naming `draw`) a caster's model matrix whose last row is not exactly (0, 0, 0, 1)
+void refuseUnlessAffine(const float* matrix16, uint32_t draw, const char* call);
 // material textures of the scene meshes (plr_frame.h plrf_set_scene_textures): RGBA8 texels, R in the low byte; mipCount levels back to back, or 0: level 0
 // only and the host builds the full chain. A material names a texture per output or kNoSceneTexture
 constexpr uint32_t kNoSceneTexture = 0xffffffffu;
@@ -638,7 +647,11 @@ private:
     void renderSunShadowCascades();
     void renderDepthPrepass(const FrameRenderTargets& current);
     void updateMainPassMatrices();
-    void fillCasterBuffer(StorageBufferHandle& buffer, size_t& capacity, const void* data, size_t bytes);
+    // a storage buffer of either mesh set (or of the cull, debug and SDF passes on top of them) that grows with what is set: a buffer and the capacity that
+    // describes it are one object. bytes 0: never created
+    struct GrowableBuffer { StorageBufferHandle handle; size_t bytes = 0; };
+    void fillBuffer(GrowableBuffer& buffer, const void* data, size_t bytes);
+    template <class T> void fillBuffer(GrowableBuffer& buffer, const std::vector<T>& data) { fillBuffer(buffer, data.data(), data.size() * sizeof(T)); }
     void updateTransmissionLut();
     void computeVolumetricLighting(float deltaTime);
     void updateSkyLut();
@@ -684,39 +697,43 @@ private:
     uint32_t m_casterDrawCount = 0, m_casterTriangleCount = 0;
     bool m_casterPassesCreated = false;
     RenderPassHandle m_sunShadowRasterPass[4];
-    StorageBufferHandle m_casterTransforms, m_casterPositions, m_casterIndices, m_casterDraws, m_casterScratch[4];
-    size_t m_casterTransformBytes = 0, m_casterPositionBytes = 0, m_casterIndexBytes = 0, m_casterDrawBytes = 0, m_casterScratchBytes[4] = {0, 0, 0, 0};
+    GrowableBuffer m_casterTransforms, m_casterPositions, m_casterIndices, m_casterDraws, m_casterScratch[4];
     // cutouts: created by the first setShadowCasterCutouts; 0 textures, or no cutoff other than 0 = the 8-byte pass record
     uint32_t m_casterTextureCount = 0;
     bool m_casterAlphaTested = false;
     std::vector<uint32_t> m_casterMeshVertexCounts;
-    StorageBufferHandle m_casterUvs, m_casterMaterials, m_casterTextures, m_casterTexels;
-    size_t m_casterUvBytes = 0, m_casterMaterialBytes = 0, m_casterTextureBytes = 0, m_casterTexelBytes = 0;
-    // scene meshes: created by the first setSceneMeshes (a pipeline without a scene allocates and records nothing for them). A buffer and the capacity that
-    // describes it are one object
-    struct SceneBuffer { StorageBufferHandle handle; size_t bytes = 0; };
+    GrowableBuffer m_casterUvs, m_casterMaterials, m_casterTextures, m_casterTexels;
+    void dropCasterCutouts() { m_casterTextureCount = 0; m_casterAlphaTested = false; } // every setShadowCasters: they belonged to the casters that are gone
+    // scene meshes: created by the first setSceneMeshes (a pipeline without a scene allocates and records nothing for them)
     uint32_t m_sceneDrawCount = 0, m_sceneTriangleCount = 0;
     bool m_scenePassCreated = false, m_scenePreviousValid = false, m_sceneRecorded = false; // recorded: a frame has run the pass for the scene now set
     RenderPassHandle m_depthPrepassRasterPass;
-    SceneBuffer m_sceneMatrices, m_scenePositions, m_sceneNormals, m_sceneIndices, m_sceneDraws, m_sceneScratch;
+    GrowableBuffer m_sceneMatrices, m_scenePositions, m_sceneNormals, m_sceneIndices, m_sceneDraws, m_sceneScratch;
     // material textures: created by the first setSceneTextures; 0 textures = the untextured pass record
     uint32_t m_sceneTextureCount = 0;
     std::vector<uint32_t> m_sceneMeshVertexCounts;
-    SceneBuffer m_sceneUvs, m_sceneMaterials, m_sceneTextures, m_sceneTexels;
+    GrowableBuffer m_sceneUvs, m_sceneMaterials, m_sceneTextures, m_sceneTexels;
     bool m_sceneTexturesCompressed = false; // setSceneTexturesFormatted with a BC1 / BC3 / BC5 entry: the sixth push-constant word and binding 14
-    SceneBuffer m_sceneTextureFormats;
+    GrowableBuffer m_sceneTextureFormats;
     // alpha cutoffs: created by the first setSceneAlphaCutoffs; not tested = the pass record without the fourth push-constant word
     bool m_sceneAlphaTested = false;
-    SceneBuffer m_sceneAlphaCutoffs;
+    GrowableBuffer m_sceneAlphaCutoffs;
     // normal maps: buffers and the shadingNormal image created by the first setSceneNormalMaps; decode 0 = the pass record without the fifth push-constant word
     uint32_t m_sceneNormalDecode = 0;
     uint32_t m_sceneMaxAnisotropy = 0; // setSceneAnisotropy: >= 2 with textures set = the pass record with the seventh push-constant word; no scene call resets it
     std::vector<uint8_t> m_sceneMeshHasNormals;
     std::vector<float> m_sceneNormalsHost; // the packed normals: what absent bitangents are derived from
-    SceneBuffer m_sceneTangents, m_sceneBitangents, m_sceneNormalMaterials;
+    GrowableBuffer m_sceneTangents, m_sceneBitangents, m_sceneNormalMaterials;
     ImageHandle m_shadingNormalImage;
     bool m_shadingNormalCreated = false;
     bool normalMapped() const { return m_sceneNormalDecode != 0 && m_sceneTextureCount != 0 && m_sceneDrawCount != 0; }
+    // what a call drops of what was set on top of it, each rule once: the removal and the replacement branch of a setter call the same one. m_sceneMaxAnisotropy,
+    // the cull flags and the debug flags survive every one of them
+    void dropSceneNormalMaps() { m_sceneNormalDecode = 0; }    // they named textures
+    void dropSceneAlphaCutoffs() { m_sceneAlphaTested = false; } // they belonged to the materials
+    void dropSceneTextures() { m_sceneTextureCount = 0; m_sceneTexturesCompressed = false; dropSceneAlphaCutoffs(); dropSceneNormalMaps(); } // they belonged to the scene
+    // the tail of both texture calls: fills the store, takes the counts over and drops what the previous store carried. formats: of a store with a compressed entry
+    void takeSceneTextures(const PackedTextures& packed, uint32_t textureCount, const std::vector<uint32_t>* formats);
     std::vector<float> m_sceneModel, m_scenePreviousModel; // 16 floats per draw: what the next frame uses, what the last recorded frame used
     // the scene's SDF: passes and buffers created by the first setSceneSdf. The host keeps the scene's positions, indices and draw -> mesh map for it (the
     // local boxes and the bake need them when setSceneSdf comes)
@@ -725,7 +742,7 @@ private:
     bool m_sceneSdfSet = false, m_sceneSdfPassesCreated = false, m_sceneSdfMeansStale = false;
     PackedSceneSdf m_sceneSdf;
     RenderPassHandle m_sdfInstanceUpdatePass, m_sceneMeanAlbedoPass;
-    SceneBuffer m_sceneSdfTable, m_sceneSdfOverrides, m_sceneSdfMeans, m_sceneSdfMeanScratch;
+    GrowableBuffer m_sceneSdfTable, m_sceneSdfOverrides, m_sceneSdfMeans, m_sceneSdfMeanScratch;
     uint32_t m_sceneSdfMeanGroups = 1; // dispatch_count[0] of "sceneMeanAlbedo.comp": from the largest level 0 of the store
     struct BakedVolume { ImageHandle image; bool inUse = false; uint64_t bytes = 0; };
     std::vector<BakedVolume> m_sceneSdfVolumes; // images of baked volumes: released (re-created at 1 x 1 x 1) with the scene's SDF, re-used by the next bake
@@ -736,7 +753,7 @@ private:
     RenderPassHandle m_drawCullingPass[2]; // main view, shadow views
     std::vector<float> m_sceneBoundsHost, m_casterBoundsHost;
     bool m_sceneBoundsUploaded = false, m_casterBoundsUploaded = false;
-    SceneBuffer m_sceneBounds, m_sceneCulledDraws, m_sceneCullStats, m_casterBounds, m_casterCulledDraws[4], m_casterCullStats;
+    GrowableBuffer m_sceneBounds, m_sceneCulledDraws, m_sceneCullStats, m_casterBounds, m_casterCulledDraws[4], m_casterCullStats;
     bool cullScene() const { return (m_cullFlags & kCullScene) != 0 && m_sceneDrawCount != 0; }
     bool cullCasters() const { return (m_cullFlags & kCullShadowCasters) != 0 && m_casterDrawCount != 0; }
     void prepareDrawCulling();
@@ -748,7 +765,7 @@ private:
     bool m_debugPassCreated = false, m_debugRecorded = false, m_debugLinesUploaded = false; // recorded: a frame has run the pass since the flags were last 0
     RenderPassHandle m_debugGeometryPass;
     std::vector<float> m_debugLinesHost; // 9 floats per line
-    SceneBuffer m_debugLines, m_debugStats;
+    GrowableBuffer m_debugLines, m_debugStats;
     void refuseDebugGeometryUnsupported(const char* call) const;
     void prepareDebugGeometry();
     void recordDebugGeometry(const FrameRenderTargets& current, bool sdfBoxesWritten);

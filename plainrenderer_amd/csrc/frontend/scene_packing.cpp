@@ -1,24 +1,28 @@
 // Validation and packing of scene meshes, their material textures, their alpha cutoffs and their normal maps for "depthPrepassRaster.comp"
-// (FramePipeline::setSceneMeshes, setSceneTextures, setSceneTexturesFormatted, setSceneAlphaCutoffs, setSceneNormalMaps) and of the shadow casters' cutouts for
-// "sunShadowRaster.comp" (setShadowCasterCutouts), and the host's decoder of BC1 / BC3 / BC5 blocks: host code without a backend call, so that a stand-alone
-// program can run it under a sanitizer (tools/scene_packing_check.cpp, tools/scene_texture_check.cpp, tools/scene_alpha_check.cpp, tools/scene_normal_check.cpp,
-// tools/shadow_cutout_check.cpp, tools/scene_bc_check.cpp, tools/draw_bounds_check.cpp).
+// (FramePipeline::setSceneMeshes, setSceneTextures, setSceneTexturesFormatted, setSceneAlphaCutoffs, setSceneNormalMaps) and of the shadow casters and their
+// cutouts for "sunShadowRaster.comp" (setShadowCasters, setShadowCasterCutouts), and the host's decoder of BC1 / BC3 / BC5 blocks: host code without a backend
+// call, so that a stand-alone program can run it under a sanitizer (tools/scene_packing_check.cpp for both mesh sets, tools/scene_texture_check.cpp,
+// tools/scene_alpha_check.cpp, tools/scene_normal_check.cpp, tools/shadow_cutout_check.cpp, tools/scene_bc_check.cpp, tools/draw_bounds_check.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
 
 #include "../device/depth_prepass_raster.h"
+#include "../device/sun_shadow_raster.h"
 #include "frame_pipeline.h"
 
 namespace plrhost {
 
+static void refuseNonFiniteMatrix(const float* m, uint32_t draw, const char* call) {
+    for (int e = 0; e < 16; e++)
+        if (!std::isfinite(m[e]))
+            throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": non-finite matrix element: element " + std::to_string(e) + " of the model matrix of draw " +
+                                       std::to_string(draw));
+}
+
 void refuseNonFiniteMatrices(const float* matrices16, uint32_t drawCount, const char* call) {
-    for (uint32_t d = 0; d < drawCount; d++)
-        for (int e = 0; e < 16; e++)
-            if (!std::isfinite(matrices16[(size_t)d * 16u + e]))
-                throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": non-finite matrix element: element " + std::to_string(e) + " of the model matrix of draw " +
-                                           std::to_string(d));
+    for (uint32_t d = 0; d < drawCount; d++) refuseNonFiniteMatrix(matrices16 + (size_t)d * 16u, d, call);
 }
 
 std::vector<float> packDrawBounds(const float* const* meshPositions, const uint32_t* meshVertexCounts, uint32_t meshCount, const uint32_t* drawMeshes, uint32_t drawCount) {
@@ -50,65 +54,99 @@ std::vector<float> packDrawBounds(const float* const* meshPositions, const uint3
     return out;
 }
 
-// everything is validated before anything is built; the caller changes its state only with the result in hand
-PackedScene packSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const SceneDraw* draws, uint32_t drawCount) {
-    const char* call = "setSceneMeshes";
-    if (!meshes || !draws || meshCount == 0 || drawCount == 0) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": draws without meshes");
-    std::vector<uint32_t> firstIndex(meshCount), vertexOffset(meshCount);
+void refuseUnlessAffine(const float* m, uint32_t draw, const char* call) {
+    if (m[3] != 0.f || m[7] != 0.f || m[11] != 0.f || m[15] != 1.f)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": the model matrix of draw " + std::to_string(draw) +
+                                   " is not affine (its last row must be exactly (0, 0, 0, 1): the shadow pass does not divide by w)");
+}
+
+// ---- what the scene's meshes and the shadow casters share: the checks per mesh and of every draw's mesh index, the layout of the meshes back to back, the copies
+// and the bounds. `out.draws` stays empty: the draw record is the caller's, from the layout returned with the rest
+struct MeshLayout { std::vector<uint32_t> firstIndex, vertexOffset, drawMeshes; };
+// the matrix rules differ in their place as well: checkDraw(d) runs right behind the mesh index check of draw d, checkDraws() once behind the last draw, both in
+// front of the checks of the totals. Everything is validated before anything is built; the caller changes its state only with the result in hand
+template <class Mesh, class Draw, class CheckDraw, class CheckDraws>
+static MeshLayout packMeshes(const std::string& call, const Mesh* meshes, uint32_t meshCount, const Draw* draws, uint32_t drawCount, uint64_t maxTriangles, CheckDraw&& checkDraw,
+                             CheckDraws&& checkDraws, PackedMeshes& out) {
+    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
+    if (!meshes || !draws || meshCount == 0 || drawCount == 0) refuse("draws without meshes");
+    MeshLayout at{std::vector<uint32_t>(meshCount), std::vector<uint32_t>(meshCount), std::vector<uint32_t>(drawCount)};
     uint64_t vertices = 0, indices = 0, triangles = 0;
     for (uint32_t m = 0; m < meshCount; m++) {
-        const SceneMesh& mesh = meshes[m];
-        if ((mesh.vertexCount && !mesh.positions) || (mesh.indexCount && !mesh.indices)) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": mesh " + std::to_string(m) + " has null data");
-        if (mesh.indexCount % 3u != 0u)
-            throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": mesh " + std::to_string(m) + " has " + std::to_string(mesh.indexCount) + " indices, not a triangle list");
+        const Mesh& mesh = meshes[m];
+        if ((mesh.vertexCount && !mesh.positions) || (mesh.indexCount && !mesh.indices)) refuse("mesh " + std::to_string(m) + " has null data");
+        if (mesh.indexCount % 3u != 0u) refuse("mesh " + std::to_string(m) + " has " + std::to_string(mesh.indexCount) + " indices, not a triangle list");
         for (uint32_t i = 0; i < mesh.indexCount; i++)
             if (mesh.indices[i] >= mesh.vertexCount)
-                throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": vertex index out of range: index " + std::to_string(i) + " of mesh " + std::to_string(m) + " is " +
-                                           std::to_string(mesh.indices[i]) + ", the mesh has " + std::to_string(mesh.vertexCount) + " vertices");
-        firstIndex[m] = (uint32_t)indices; vertexOffset[m] = (uint32_t)vertices;
+                refuse("vertex index out of range: index " + std::to_string(i) + " of mesh " + std::to_string(m) + " is " + std::to_string(mesh.indices[i]) + ", the mesh has " +
+                       std::to_string(mesh.vertexCount) + " vertices");
+        at.firstIndex[m] = (uint32_t)indices; at.vertexOffset[m] = (uint32_t)vertices;
         vertices += mesh.vertexCount; indices += mesh.indexCount;
     }
     for (uint32_t d = 0; d < drawCount; d++) {
-        if (draws[d].mesh >= meshCount)
-            throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": mesh index out of range: draw " + std::to_string(d) + " names mesh " + std::to_string(draws[d].mesh) +
-                                       " of " + std::to_string(meshCount));
+        if (draws[d].mesh >= meshCount) refuse("mesh index out of range: draw " + std::to_string(d) + " names mesh " + std::to_string(draws[d].mesh) + " of " + std::to_string(meshCount));
+        checkDraw(d);
         triangles += meshes[draws[d].mesh].indexCount / 3u;
     }
-    for (uint32_t d = 0; d < drawCount; d++)
-        for (int e = 0; e < 16; e++)
-            if (!std::isfinite(draws[d].modelMatrix[e]))
-                throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": non-finite matrix element: element " + std::to_string(e) + " of the model matrix of draw " + std::to_string(d));
-    if (vertices == 0 || indices == 0 || triangles == 0) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": the draws hold no triangle");
-    if (vertices > 0xffffffffull || indices > 0xffffffffull || triangles > (uint64_t)plr::prepass::kMaxTriangles)
-        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, std::string(call) + ": too many vertices, indices or triangles");
-    PackedScene out;
+    checkDraws();
+    if (vertices == 0 || indices == 0 || triangles == 0) refuse("the draws hold no triangle");
+    if (vertices > 0xffffffffull || indices > 0xffffffffull || triangles > maxTriangles) refuse("too many vertices, indices or triangles");
     out.positions.resize((size_t)vertices * 3u);
-    out.normals.assign((size_t)vertices * 3u, 0.f); // all-zero: the pass takes the face normal
     out.indices.resize((size_t)indices);
     out.models.resize((size_t)drawCount * 16u);
-    out.draws.resize((size_t)drawCount * 6u);
+    out.meshVertexCounts.resize(meshCount);
+    std::vector<const float*> meshPositions(meshCount);
     for (uint32_t m = 0; m < meshCount; m++) {
-        if (meshes[m].vertexCount) std::memcpy(out.positions.data() + (size_t)vertexOffset[m] * 3u, meshes[m].positions, (size_t)meshes[m].vertexCount * 12u);
-        if (meshes[m].vertexCount && meshes[m].normals) std::memcpy(out.normals.data() + (size_t)vertexOffset[m] * 3u, meshes[m].normals, (size_t)meshes[m].vertexCount * 12u);
-        if (meshes[m].indexCount) std::memcpy(out.indices.data() + firstIndex[m], meshes[m].indices, (size_t)meshes[m].indexCount * 4u);
+        if (meshes[m].vertexCount) std::memcpy(out.positions.data() + (size_t)at.vertexOffset[m] * 3u, meshes[m].positions, (size_t)meshes[m].vertexCount * 12u);
+        if (meshes[m].indexCount) std::memcpy(out.indices.data() + at.firstIndex[m], meshes[m].indices, (size_t)meshes[m].indexCount * 4u);
+        out.meshVertexCounts[m] = meshes[m].vertexCount;
+        meshPositions[m] = meshes[m].positions;
     }
     for (uint32_t d = 0; d < drawCount; d++) {
-        const plr::prepass::Draw draw{firstIndex[draws[d].mesh], meshes[draws[d].mesh].indexCount, vertexOffset[draws[d].mesh], d, draws[d].albedo, draws[d].specular};
-        std::memcpy(out.draws.data() + (size_t)d * 6u, &draw, sizeof(draw));
         std::memcpy(out.models.data() + (size_t)d * 16u, draws[d].modelMatrix, 64);
+        at.drawMeshes[d] = draws[d].mesh;
     }
     out.triangleCount = (uint32_t)triangles;
-    out.meshVertexCounts.resize(meshCount);
+    out.drawBounds = packDrawBounds(meshPositions.data(), out.meshVertexCounts.data(), meshCount, at.drawMeshes.data(), drawCount);
+    return at;
+}
+
+PackedScene packSceneMeshes(const SceneMesh* meshes, uint32_t meshCount, const SceneDraw* draws, uint32_t drawCount) {
+    const char* call = "setSceneMeshes";
+    PackedScene out;
+    // every element of every matrix is finite: checked once every draw names a mesh
+    const MeshLayout at = packMeshes(call, meshes, meshCount, draws, drawCount, plr::prepass::kMaxTriangles, [](uint32_t) {},
+                                     [&] { for (uint32_t d = 0; d < drawCount; d++) refuseNonFiniteMatrix(draws[d].modelMatrix, d, call); }, out);
+    out.normals.assign(out.positions.size(), 0.f); // all-zero: the pass takes the face normal
     out.meshHasNormals.resize(meshCount);
-    for (uint32_t m = 0; m < meshCount; m++) { out.meshVertexCounts[m] = meshes[m].vertexCount; out.meshHasNormals[m] = meshes[m].normals ? 1 : 0; }
-    out.drawMeshes.resize(drawCount);
-    for (uint32_t d = 0; d < drawCount; d++) out.drawMeshes[d] = draws[d].mesh;
-    out.meshFirstIndex = firstIndex;
     out.meshIndexCounts.resize(meshCount);
-    for (uint32_t m = 0; m < meshCount; m++) out.meshIndexCounts[m] = meshes[m].indexCount;
-    std::vector<const float*> meshPositions(meshCount);
-    for (uint32_t m = 0; m < meshCount; m++) meshPositions[m] = meshes[m].positions;
-    out.drawBounds = packDrawBounds(meshPositions.data(), out.meshVertexCounts.data(), meshCount, out.drawMeshes.data(), drawCount);
+    for (uint32_t m = 0; m < meshCount; m++) {
+        if (meshes[m].vertexCount && meshes[m].normals) std::memcpy(out.normals.data() + (size_t)at.vertexOffset[m] * 3u, meshes[m].normals, (size_t)meshes[m].vertexCount * 12u);
+        out.meshHasNormals[m] = meshes[m].normals ? 1 : 0;
+        out.meshIndexCounts[m] = meshes[m].indexCount;
+    }
+    out.draws.resize((size_t)drawCount * 6u);
+    for (uint32_t d = 0; d < drawCount; d++) {
+        const uint32_t m = draws[d].mesh;
+        const plr::prepass::Draw draw{at.firstIndex[m], meshes[m].indexCount, at.vertexOffset[m], d, draws[d].albedo, draws[d].specular};
+        std::memcpy(out.draws.data() + (size_t)d * 6u, &draw, sizeof(draw));
+    }
+    out.drawMeshes = at.drawMeshes;
+    out.meshFirstIndex = at.firstIndex;
+    return out;
+}
+
+PackedCasters packShadowCasters(const ShadowCasterMesh* meshes, uint32_t meshCount, const ShadowCasterDraw* draws, uint32_t drawCount) {
+    const char* call = "setShadowCasters";
+    PackedCasters out;
+    // the last row of a matrix is (0, 0, 0, 1): checked draw by draw, behind the draw's mesh index
+    const MeshLayout at = packMeshes(call, meshes, meshCount, draws, drawCount, 0x7fffffffull, [&](uint32_t d) { refuseUnlessAffine(draws[d].modelMatrix, d, call); }, [] {}, out);
+    out.draws.resize((size_t)drawCount * 4u);
+    for (uint32_t d = 0; d < drawCount; d++) {
+        const uint32_t m = draws[d].mesh;
+        const plr::sunraster::Draw draw{at.firstIndex[m], meshes[m].indexCount, at.vertexOffset[m], d};
+        std::memcpy(out.draws.data() + (size_t)d * 4u, &draw, sizeof(draw));
+    }
     return out;
 }
 

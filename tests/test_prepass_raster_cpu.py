@@ -1,5 +1,9 @@
-"""The scene mesh entry points at the C boundary and the tests' own rasteriser (tests/prepass_raster_reference.py) against hand-computed cases; no GPU."""
+"""The scene mesh entry points at the C boundary, the tests' own rasteriser (tests/prepass_raster_reference.py) against hand-computed cases, and the host's
+validation and packing of both mesh sets under the sanitizers (tools/scene_packing_check.cpp, a stand-alone program); no GPU."""
 import ctypes as C
+import os
+import shutil
+import subprocess
 
 import numpy as np
 
@@ -8,6 +12,7 @@ import prepass_raster_reference as ref
 from shadow_raster_cases import quad
 
 F32 = np.float32
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def counters(r):
@@ -265,6 +270,18 @@ def test_matrices_follow_the_pipelines_product():
     assert np.allclose(ref.mat_mul(a, b), want, rtol=1e-5, atol=1e-5)
     m = ref.main_pass_matrices(a, b, [pc.IDENTITY], [pc.IDENTITY])
     assert m.shape == (1, 48) and np.array_equal(m[0, :16], pc.IDENTITY) and np.array_equal(m[0, 16:32], ref.mat_mul(a, pc.IDENTITY))
+
+
+def test_the_mesh_validation_and_packing_run_clean_under_the_sanitizers(tmp_path):
+    """packSceneMeshes and packShadowCasters: the packed bytes, every refusal and which defect of several is reported: tools/scene_packing_check.cpp"""
+    compiler = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert compiler, "no host C++ compiler"
+    exe = str(tmp_path / "scene_packing_check")
+    build = subprocess.run([compiler, "-std=c++17", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", os.path.join(ROOT, "tools", "scene_packing_check.cpp"),
+                            os.path.join(ROOT, "plainrenderer_amd", "csrc", "frontend", "scene_packing.cpp"), "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip() == "scene_packing_check: ok", run.stdout + run.stderr
 
 
 def test_the_scene_mesh_entry_points_are_exported():

@@ -217,8 +217,8 @@ def test_gpu_casters_survive_a_resize(backend):
 def test_gpu_refusals_name_their_cause(backend):
     from plainrenderer_amd.backend import PlrError
     from plainrenderer_amd.frame import FramePipeline
-    s = sc.mesh_scene()
-    fp = FramePipeline(backend, W, H, **FP_ARGS)
+    s, i = sc.mesh_scene(), _scene_inputs()
+    fp = _pipeline(backend)
     try:
         def refused(call, code, *words):
             with pytest.raises(PlrError) as e:
@@ -234,10 +234,29 @@ def test_gpu_refusals_name_their_cause(backend):
         projective = sc.IDENTITY.copy()
         projective[11] = 0.01
         refused(lambda: fp.set_shadow_casters(s["meshes"], [(0, projective)]), INVALID_ARGUMENT, "affine")
+        # nothing was set by the refused calls: a frame records no cascade and the uploaded maps stay
+        fp.frame(i["cams"][1], 1.0 / 60.0, 0.5)
+        assert all(fp.shadow_raster_stats(c) == (0, 0, 0) for c in range(3))
+        for m, pattern in zip(_maps(backend, fp), i["patterns"]):
+            assert np.array_equal(m, pattern)
         fp.set_shadow_casters(s["meshes"], s["draws"])
         refused(lambda: fp.set_shadow_caster_transforms([sc.IDENTITY, sc.IDENTITY]), INVALID_ARGUMENT, "transform count", "2", "3")
         refused(lambda: fp.set_shadow_caster_transforms([sc.IDENTITY, projective, sc.IDENTITY]), INVALID_ARGUMENT, "affine", "draw 1")
         refused(lambda: fp.shadow_raster_stats(3), INVALID_ARGUMENT, "cascade")
+        refused(lambda: fp.set_shadow_casters(s["meshes"], [(3, sc.IDENTITY)]), INVALID_ARGUMENT, "mesh index")
+        refused(lambda: fp.set_shadow_casters(s["meshes"], [s["draws"][0], (1, projective)]), INVALID_ARGUMENT, "affine", "draw 1")
+        # the casters set before the refusals are the ones the next frame draws
+        fp.frame(i["cams"][2], 1.0 / 60.0, 0.5 + 1.0 / 60.0)
+        info = backend.downloadStorageBuffer(fp.storage_buffer("sunShadowInfo"), 304, dtype=np.uint8).tobytes()
+        maps = _maps(backend, fp)
+        drawn = 0
+        for c in range(3):
+            r = _reference(info, c, "first")
+            assert np.array_equal(maps[c], r["map"]), "after refused calls, cascade %d" % c
+            assert fp.shadow_raster_stats(c) == (r["submitted"], r["drawn"], r["rejects"])
+            drawn += r["drawn"]
+        assert drawn > 0
+        assert np.array_equal(maps[3], i["patterns"][3])
     finally:
         fp.destroy()
     band = FramePipeline(backend, W, H, band_row_begin=0, band_row_end=H, **FP_ARGS)
