@@ -353,6 +353,39 @@ typedef struct plrf_scene_texture_data {
 } plrf_scene_texture_data;
 int plrf_set_scene_textures_formatted(void* pipeline, const plrf_scene_texture_data* textures, uint32_t texture_count, const float* const* mesh_uvs, uint32_t mesh_count,
                                       const plrf_scene_material* materials, uint32_t draw_count);
+/* ---- the texture store built on the GPU (DESIGN.md "Texture store built on the GPU": the chain, block gathering, colour block and alpha block contracts in
+ * integers): plrf_set_scene_textures_formatted for a caller that holds level 0, or RGBA8 texels it wants stored compressed. plrf_scene_texture_source is a
+ * plrf_scene_texture_data with the format the store is to hold. format RGBA8, store_format RGBA8: the levels as given, or with mip_count 0 level 0 and the GPU
+ * builds the chain by the rule given above for plrf_scene_texture, byte for byte the host's chain. format RGBA8, store_format BC1 / BC3 / BC5: every level - given, or built -
+ * is encoded on the GPU by the range-fit encode contract (BC1 ignores alpha, BC5 takes r and g). format BC1 / BC3 / BC5 with the same store_format: the levels as
+ * given, or with mip_count 0 the blocks of level 0, which are kept verbatim, and levels 1 .. are decode(level 0), the chain rule, encode. Every other pair is refused;
+ * the message names the texture and both formats. The store - table, formats, words - has exactly the layout plrf_set_scene_textures_formatted gives the same
+ * textures with all their levels supplied (a compressed entry at a multiple of 4 words, no format buffer for an all-RGBA8 store). The RGBA8 staging chains the
+ * build needs (every level of an entry that is encoded, levels 1 .. of a compressed source) count against a 2^28-word limit of their own.
+ * The call uploads the given levels. The next plrf_frame records, once and in front of everything else, "textureMipChain.comp" - one execution per level builds
+ * that level of every texture that has it, at most 14 whatever the texture count - and "textureBlockEncode.comp", one execution over every block to encode; they
+ * run before "sceneMeanAlbedo.comp". The staging buffer is released after that frame. In every other respect the call is plrf_set_scene_textures_formatted: the
+ * stores replace one another, texture_count 0 removes, cutoffs and normal maps set afterwards index this store, the same refusals (the bytes of a compressed
+ * entry with mip_count 0 are those of level 0), PLR_ERR_UNSUPPORTED on a band / tile pipeline without band_raster, and a refused call changes nothing.
+ * plrf_read_scene_texture_store: the words of the texel store as the kernels see it, whichever call made it. *out_word_count receives the count; the words are
+ * copied when out_words is not NULL and capacity_words suffices (call once with NULL to size the buffer). PLR_ERR_INVALID_ARGUMENT while there is no store, and
+ * before a frame has run since the call that set or built it - the message says so. Waits for the GPU.
+ * plrf_get_texture_build_stats: the last build a frame has recorded - executions per pass, texels the chain pass wrote, blocks encoded, bytes of the staging
+ * buffer; zeros before there is one. */
+typedef struct plrf_scene_texture_source {
+    const void* data;
+    uint64_t bytes;
+    uint32_t width, height, mip_count, format; /* exactly as plrf_scene_texture_data */
+    uint32_t store_format;                     /* PLR_FORMAT_RGBA8 | BC1 | BC3 | BC5: what the store is to hold */
+} plrf_scene_texture_source;
+int plrf_build_scene_textures(void* pipeline, const plrf_scene_texture_source* textures, uint32_t texture_count, const float* const* mesh_uvs, uint32_t mesh_count,
+                              const plrf_scene_material* materials, uint32_t draw_count);
+int plrf_read_scene_texture_store(void* pipeline, uint32_t* out_words, uint64_t capacity_words, uint64_t* out_word_count);
+typedef struct plrf_texture_build_stats {
+    uint32_t mip_chain_launches, block_encode_launches; /* executions of "textureMipChain.comp" and of "textureBlockEncode.comp" */
+    uint64_t chain_texels, blocks_encoded, staging_bytes;
+} plrf_texture_build_stats;
+int plrf_get_texture_build_stats(void* pipeline, plrf_texture_build_stats* out);
 /* ---- alpha-tested cutouts: depthPrepass.frag:27-30 (sample the albedo texture's alpha with g_mipBias, discard below 0.5) as a per-draw cutoff code 0 .. 255
  * (DESIGN.md "Alpha-tested cutouts in the depth prepass"). 0 is opaque; PLRF_ALPHA_CUTOFF_REFERENCE (128) is the reference's test, a / 255 < 0.5 <=> a <= 127.
  * The alpha code of a fragment is bits 24 - 31 of the albedo word the sampling contract yields for its triangle at that pixel (the draw's constant albedo_rgba8

@@ -3,8 +3,9 @@
  * Replaces  bool loadDDSFile(const std::filesystem::path&, ImageDescription*, std::vector<uint8_t>*)   (Common/ImageIO.cpp:342-431)
  *      and  void writeDDSFile(const std::filesystem::path&, const ImageDescription&, const std::vector<uint8_t>&)   (ImageIO.cpp:448-571).
  * File layout: magic 0x20534444 ("DDS "), the 124-byte DDS_header, for fourCC "DX10" the 20-byte DDS_headerDX10, then the raw texels
- * (x fastest, then y, then z; all mips consecutively). The writer always emits a DX10 header (formats RGBA8 and R16_sFloat, as the
- * reference); the reader understands DX10/R16_FLOAT and the legacy fourCCs DXT1 (BC1), DXT5 (BC3), ATI2 (BC5), as the reference.
+ * (x fastest, then y, then z; all mips consecutively). The writer emits a DX10 header for the formats RGBA8 and R16_sFloat, as the
+ * reference, and - beyond the reference - a legacy header with the fourCC DXT1 / DXT5 / ATI2 for a BC1 / BC3 / BC5 payload (the blocks
+ * plr_encode_rgba8_to_bc makes), which the reader takes back; the reader understands DX10/R16_FLOAT and the legacy fourCCs DXT1 (BC1), DXT5 (BC3), ATI2 (BC5), as the reference.
  * plr_decode_bc_to_rgba8 decodes the blocks of such a file's BC1 / BC3 / BC5 levels on the host.
  * All functions return PLR_OK (0) or a negative code; plr_last_error() (plr.h) explains. No GPU is involved. */
 #ifndef PLR_IMAGE_IO_H
@@ -35,6 +36,13 @@ int plr_decode_dds(const void* file, size_t file_size, plr_image_desc* out_desc,
  * the level's size; out_words receives width * height words. PLR_ERR_INVALID_ARGUMENT: another format, a side of 0 or above 16384, a NULL pointer, a byte count
  * other than the level's. */
 int plr_decode_bc_to_rgba8(int format, uint32_t width, uint32_t height, const void* blocks, uint64_t bytes, uint32_t* out_words);
+
+/* The twin of the decode: one level of width * height RGBA8 words into its BC1 / BC3 / BC5 blocks by the encode contract "textureBlockEncode.comp" applies
+ * (DESIGN.md "Texture store built on the GPU": range fit in integers - block (bx, by) gathers texel (min(4 bx + i, W - 1), min(4 by + j, H - 1)) at position
+ * 4 j + i; BC1 and BC3's colour block take r, g, b, BC3's alpha block a, BC5's two blocks r and g). The same bytes as the GPU pass writes, without a GPU: a
+ * caller can encode the cutouts it decodes for plrf_set_shadow_caster_cutouts, or write a compressed DDS file. bytes must be exactly the level's size, which
+ * out_blocks receives. PLR_ERR_INVALID_ARGUMENT: what the decode refuses. */
+int plr_encode_rgba8_to_bc(int format, uint32_t width, uint32_t height, const uint32_t* words, void* out_blocks, uint64_t bytes);
 
 #ifdef __cplusplus
 }

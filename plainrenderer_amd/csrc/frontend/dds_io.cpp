@@ -57,10 +57,21 @@ int encode(const plr_image_desc* desc, const void* data, size_t dataSize, std::v
     h.caps = kCapsTexture;
     if (h.mipMapCount != 1) h.caps |= kCapsMipmap | kCapsComplex;
     if (desc->depth != 1) { h.caps |= kCapsComplex; h.caps2 = kCaps2Volume; }
+    // beyond the reference: a block-compressed payload goes out under the legacy fourCC the reader maps back (no DX10 header)
+    const uint32_t legacy = desc->format == PLR_FORMAT_BC1 ? kFourCCDXT1 : desc->format == PLR_FORMAT_BC3 ? kFourCCDXT5 : desc->format == PLR_FORMAT_BC5 ? kFourCCBC5 : 0u;
+    if (legacy) {
+        h.pixelFormat.flags = kPfFourCC;
+        h.pixelFormat.compressionCode = legacy;
+        out.resize(4 + sizeof(Header) + dataSize);
+        std::memcpy(out.data(), &kMagic, 4);
+        std::memcpy(out.data() + 4, &h, sizeof(h));
+        if (dataSize) std::memcpy(out.data() + 4 + sizeof(h), data, dataSize);
+        return PLR_OK;
+    }
     HeaderDX10 x{};
     if (desc->format == PLR_FORMAT_RGBA8) x.dxgiFormat = kDxgiRGBA8Unorm;
     else if (desc->format == PLR_FORMAT_R16_SFLOAT) x.dxgiFormat = kDxgiR16Float;
-    else return setLastError(PLR_ERR_UNSUPPORTED, "plr_encode_dds: only RGBA8 and R16_sFloat can be written (as in the reference)");
+    else return setLastError(PLR_ERR_UNSUPPORTED, "plr_encode_dds: only RGBA8 and R16_sFloat (as in the reference) and BC1, BC3 and BC5 can be written");
     x.arraySize = 1;
     x.resourceDimension = desc->depth == 1 ? (desc->height == 1 ? kDimTexture1D : kDimTexture2D) : kDimTexture3D;
     out.resize(4 + sizeof(Header) + sizeof(HeaderDX10) + dataSize);
@@ -124,6 +135,16 @@ extern "C" int plr_decode_dds(const void* file, size_t fileSize, plr_image_desc*
 extern "C" int plr_decode_bc_to_rgba8(int format, uint32_t width, uint32_t height, const void* blocks, uint64_t bytes, uint32_t* outWords) {
     try {
         plrhost::decodeBlockCompressedLevel((uint32_t)format, width, height, blocks, bytes, outWords);
+    } catch (const plrhost::FramePipelineRefusal& e) {
+        return setLastError(e.code, e.what());
+    }
+    return PLR_OK;
+}
+
+// the encode contract on the host (frontend/scene_packing.cpp encodeBlockCompressedLevel)
+extern "C" int plr_encode_rgba8_to_bc(int format, uint32_t width, uint32_t height, const uint32_t* words, void* outBlocks, uint64_t bytes) {
+    try {
+        plrhost::encodeBlockCompressedLevel((uint32_t)format, width, height, words, outBlocks, bytes);
     } catch (const plrhost::FramePipelineRefusal& e) {
         return setLastError(e.code, e.what());
     }

@@ -168,6 +168,31 @@ int plrf_set_scene_textures_formatted(void* p, const plrf_scene_texture_data* te
         ((FramePipeline*)p)->setSceneTexturesFormatted(t.empty() ? nullptr : t.data(), textureCount, meshUvs, meshCount, m.empty() ? nullptr : m.data(), drawCount);
     })
 }
+// ---- the texture store built on the GPU ("textureMipChain.comp", "textureBlockEncode.comp")
+int plrf_build_scene_textures(void* p, const plrf_scene_texture_source* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount,
+                              const plrf_scene_material* materials, uint32_t drawCount) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        std::vector<SceneTextureSource> t(textures ? textureCount : 0u);
+        for (size_t i = 0; i < t.size(); i++)
+            t[i] = {textures[i].data, textures[i].bytes, textures[i].width, textures[i].height, textures[i].mip_count, textures[i].format, textures[i].store_format};
+        std::vector<SceneMaterial> m(materials ? drawCount : 0u);
+        for (size_t i = 0; i < m.size(); i++) m[i] = {materials[i].albedo_texture, materials[i].specular_texture};
+        ((FramePipeline*)p)->buildSceneTextures(t.empty() ? nullptr : t.data(), textureCount, meshUvs, meshCount, m.empty() ? nullptr : m.data(), drawCount);
+    })
+}
+int plrf_read_scene_texture_store(void* p, uint32_t* outWords, uint64_t capacityWords, uint64_t* outWordCount) {
+    if (!p || !outWordCount) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL(*outWordCount = ((FramePipeline*)p)->readSceneTextureStore(outWords, capacityWords))
+}
+int plrf_get_texture_build_stats(void* p, plrf_texture_build_stats* out) {
+    if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        const FramePipeline::TextureBuildStats s = ((FramePipeline*)p)->textureBuildStats();
+        out->mip_chain_launches = s.chainLaunches; out->block_encode_launches = s.encodeLaunches;
+        out->chain_texels = s.chainTexels; out->blocks_encoded = s.blocksEncoded; out->staging_bytes = s.stagingBytes;
+    })
+}
 int plrf_set_scene_alpha_cutoffs(void* p, const uint32_t* cutoffs, uint32_t drawCount) {
     if (!p) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY_REFUSAL(((FramePipeline*)p)->setSceneAlphaCutoffs(cutoffs, drawCount))

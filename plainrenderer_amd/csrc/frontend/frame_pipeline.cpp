@@ -6,6 +6,7 @@
 #include "../device/noise.h"
 #include "../device/scene_sdf.h"
 #include "../device/sun_shadow_raster.h"
+#include "../device/texture_build.h"
 
 #include "../../../include/plr_image_io.h"
 #include "../../../include/plr_sdf_bake.h"
@@ -1762,7 +1763,93 @@ void FramePipeline::setSceneTexturesFormatted(const SceneTextureData* textures, 
     takeSceneTextures(packed, textureCount, packed.compressed ? &packed.formats : nullptr);
 }
 
+// ---- the texture store built on the GPU: "textureMipChain.comp" and "textureBlockEncode.comp" (kernels/texture_build.hip; DESIGN.md "Texture store built on the GPU")
+void FramePipeline::buildSceneTextures(const SceneTextureSource* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount) {
+    if (partitionedWithoutRaster(m_requestedSettings))
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "buildSceneTextures: a band / tile pipeline cannot rasterise scene meshes");
+    if (textureCount == 0) { dropSceneTextures(); noteSceneTexturesChanged(0); return; }
+    const PackedTextureBuild packed = packSceneTextureBuild(textures, textureCount, meshUvs, meshCount, materials, drawCount, m_sceneMeshVertexCounts.data(),
+                                                            (uint32_t)m_sceneMeshVertexCounts.size(), m_sceneDrawCount); // validates everything before anything is changed
+    if (!m_textureBuildPassesCreated) {
+        ComputePassDescription d;
+        d.name = "Texture mip chain";
+        d.shaderDescription.srcPathRelative = "textureMipChain.comp";
+        m_textureMipChainPass = m_be.createComputePass(d);
+        d.name = "Texture block encode";
+        d.shaderDescription.srcPathRelative = "textureBlockEncode.comp";
+        m_textureBlockEncodePass = m_be.createComputePass(d);
+        m_textureBuildPassesCreated = true;
+    }
+    takeSceneTextures(packed, textureCount, packed.compressed ? &packed.formats : nullptr);
+    if (!packed.chainJobs.empty()) fillBuffer(m_textureChainJobs, packed.chainJobs);
+    if (!packed.encodeJobs.empty()) fillBuffer(m_textureEncodeJobs, packed.encodeJobs);
+    if (!packed.staging.empty()) { fillBuffer(m_textureStaging, packed.staging); m_textureStagingHeld = m_textureStagingQueued = true; }
+    m_textureChainLaunches = packed.chainLaunches;
+    m_textureEncodeJobCount = (uint32_t)(packed.encodeJobs.size() * 4u / sizeof(plr::texbuild::EncodeJob)); m_textureEncodeGroups = packed.encodeGroups;
+    m_textureBuildPendingStats = TextureBuildStats{(uint32_t)packed.chainLaunches.size(), m_textureEncodeJobCount ? 1u : 0u, packed.chainTexels, packed.blocksEncoded,
+                                                   packed.staging.size() * sizeof(uint32_t)};
+    m_textureBuildPending = true; // (takeSceneTextures cleared it: the passes of a build that was replaced are never recorded)
+}
+
+void FramePipeline::recordTextureBuild() {
+    releaseTextureStaging(); // of a build an earlier frame has run
+    m_sceneStoreInFrame = m_sceneTextureCount != 0;
+    m_textureStagingQueued = false; // this frame applies the fill
+    if (!m_textureBuildPending) return;
+    namespace tb = plr::texbuild;
+    const bool staging = m_textureBuildPendingStats.stagingBytes != 0;
+    for (const PackedTextureBuild::ChainLaunch& launch : m_textureChainLaunches) { // level by level: a level reads the one the execution before it wrote
+        ComputePassExecution exe;
+        exe.genericInfo.handle = m_textureMipChainPass;
+        exe.genericInfo.resources.storageBuffers = {StorageBufferResource(m_textureChainJobs.handle, true, tb::kChainJobBinding), StorageBufferResource(m_sceneTexels.handle, false, tb::kChainStoreBinding)};
+        if (staging) exe.genericInfo.resources.storageBuffers.push_back(StorageBufferResource(m_textureStaging.handle, false, tb::kChainStagingBinding));
+        const tb::ChainPushConstants pc{launch.firstJob, launch.jobCount, launch.groupCount, staging ? 1u : 0u};
+        exe.pushConstants = dataToCharArray(&pc, sizeof(pc));
+        exe.dispatchCount[0] = launch.groupCount; exe.dispatchCount[1] = exe.dispatchCount[2] = 1;
+        m_be.setComputePassExecution(exe);
+    }
+    if (m_textureEncodeJobCount) {
+        ComputePassExecution exe;
+        exe.genericInfo.handle = m_textureBlockEncodePass;
+        exe.genericInfo.resources.storageBuffers = {StorageBufferResource(m_textureEncodeJobs.handle, true, tb::kEncodeJobBinding), StorageBufferResource(m_sceneTexels.handle, false, tb::kEncodeStoreBinding),
+                                                    StorageBufferResource(m_textureStaging.handle, true, tb::kEncodeStagingBinding)};
+        const tb::EncodePushConstants pc{m_textureEncodeJobCount, m_textureEncodeGroups};
+        exe.pushConstants = dataToCharArray(&pc, sizeof(pc));
+        exe.dispatchCount[0] = m_textureEncodeGroups; exe.dispatchCount[1] = exe.dispatchCount[2] = 1;
+        m_be.setComputePassExecution(exe);
+    }
+    m_textureBuildStats = m_textureBuildPendingStats;
+    m_textureBuildPending = false;
+}
+
+// the staging chains have served once the frame that recorded the build has run: the buffer shrinks to one line (the backend frees the memory; this waits for
+// the GPU, once per build). Called at the start of the next frame and by the readback
+void FramePipeline::releaseTextureStaging() {
+    if (!m_textureStagingHeld || m_textureStagingQueued) return; // (queued: its fill waits for a frame, and a buffer with a queued fill cannot be resized)
+    m_be.resizeStorageBuffer(m_textureStaging.handle, 256);
+    m_textureStaging.bytes = 256;
+    m_textureStagingHeld = false;
+}
+
+uint64_t FramePipeline::readSceneTextureStore(uint32_t* outWords, uint64_t capacityWords) {
+    if (m_sceneTextureCount == 0) throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "readSceneTextureStore: no texture store is set");
+    if (m_textureBuildPending)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "readSceneTextureStore: the store is not built yet: no frame has run since plrf_build_scene_textures (the next plrf_frame records the build passes)");
+    if (!m_sceneStoreInFrame)
+        throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "readSceneTextureStore: the store is not uploaded yet: no frame has run since the call that set it");
+    if (outWords) {
+        if (capacityWords < m_sceneTexelWords)
+            throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, "readSceneTextureStore: room for " + std::to_string(capacityWords) + " words, the store holds " + std::to_string(m_sceneTexelWords));
+        if (m_sceneTexelWords && plr_download_storage_buffer(m_sceneTexels.handle.index, outWords, 0, (size_t)m_sceneTexelWords * 4u) != PLR_OK) throw std::runtime_error(plr_last_error());
+        releaseTextureStaging(); // (the download waited for the GPU)
+    }
+    return m_sceneTexelWords;
+}
+
 void FramePipeline::takeSceneTextures(const PackedTextures& packed, uint32_t textureCount, const std::vector<uint32_t>* formats) {
+    m_textureBuildPending = false; // a build that no frame has recorded is replaced with its store
+    m_sceneStoreInFrame = false;
+    m_sceneTexelWords = packed.texels.size();
     fillBuffer(m_sceneUvs, packed.uvs);
     fillBuffer(m_sceneMaterials, packed.materials);
     fillBuffer(m_sceneTextures, packed.textures);
@@ -2229,6 +2316,7 @@ void FramePipeline::prepareRenderpasses() { // RenderFrontend.cpp:313-406
     const FrameRenderTargets currentRenderTarget = m_frameRenderTargets[m_sceneRenderTargetIndex];
 
     recordNoiseGeneration(); // only in the frame after generateNoise: in front of everything else
+    recordTextureBuild();    // only in the frame after buildSceneTextures: likewise
     const bool bandMode = settings.band.enabled();
     if (settings.sdfDebug.visualisationMode != SDFVisualisationMode::None) { // RenderFrontend.cpp:321-340
         if (bandMode) throw std::runtime_error("the SDF debug visualisation is not supported in band rendering");

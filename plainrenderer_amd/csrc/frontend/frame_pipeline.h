@@ -395,6 +395,26 @@ PackedFormattedTextures packSceneTexturesFormatted(const SceneTextureData* textu
 // blocks, into width * height RGBA8 words, R in the low byte. Throws FramePipelineRefusal: another format, a size of 0 or above 16384, null pointers, a byte count
 // other than the level's
 void decodeBlockCompressedLevel(uint32_t format, uint32_t width, uint32_t height, const void* blocks, uint64_t bytes, uint32_t* outWords);
+// the encode contract on the host (plr_image_io.h plr_encode_rgba8_to_bc; device/texture_build.h holds the arithmetic the kernel shares): one width x height level
+// of RGBA8 words into the `bytes` bytes of its `format` blocks. Throws FramePipelineRefusal for what decodeBlockCompressedLevel refuses
+void encodeBlockCompressedLevel(uint32_t format, uint32_t width, uint32_t height, const uint32_t* words, void* outBlocks, uint64_t bytes);
+// a texture the GPU builds the store entry of (plr_frame.h plrf_build_scene_textures): SceneTextureData and the format the store is to hold
+struct SceneTextureSource { const void* data = nullptr; uint64_t bytes = 0; uint32_t width = 0, height = 0, mipCount = 0, format = 0, storeFormat = 0; };
+// what buildSceneTextures validates and lays out, without a backend (DESIGN.md "Texture store built on the GPU"): the store of packSceneTexturesFormatted for the
+// same textures with all their levels - `texels` holds the levels that are stored as given and zeros where a pass writes -, the RGBA8 staging chains with the given
+// levels in place (every level at a multiple of 4 words), and the job tables of the two passes (device/texture_build.h)
+struct PackedTextureBuild : PackedFormattedTextures {
+    std::vector<uint32_t> staging;
+    std::vector<uint32_t> chainJobs;      // ChainJob records, the jobs of one launch back to back, launches in level order
+    struct ChainLaunch { uint32_t firstJob, jobCount, groupCount; };
+    std::vector<ChainLaunch> chainLaunches;
+    std::vector<uint32_t> encodeJobs;     // EncodeJob records
+    uint32_t encodeGroups = 0;
+    uint64_t chainTexels = 0, blocksEncoded = 0;
+};
+// Throws FramePipelineRefusal.
+PackedTextureBuild packSceneTextureBuild(const SceneTextureSource* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials,
+                                         uint32_t drawCount, const uint32_t* sceneMeshVertexCounts, uint32_t sceneMeshCount, uint32_t sceneDrawCount);
 // what setSceneAlphaCutoffs validates and packs, without a backend: binding 10 of an alpha-tested "depthPrepassRaster.comp", one cutoff code per draw
 struct PackedAlphaCutoffs {
     std::vector<uint32_t> cutoffs;
@@ -506,6 +526,16 @@ public:
     // Lifetime, removal and what cutoffs and normal maps set afterwards index are setSceneTextures'. Further refusals (PLR_ERR_INVALID_ARGUMENT): an unknown
     // format, mipCount 0 on a compressed entry, a byte count other than the exact size of the entry's levels, more than 2^28 words in total.
     void setSceneTexturesFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount);
+    // setSceneTexturesFormatted with the mip chains and the BC1 / BC3 / BC5 blocks made on the GPU (DESIGN.md "Texture store built on the GPU"): the call uploads
+    // the given levels, the next frame records "textureMipChain.comp" (one execution per level, at most 14) and "textureBlockEncode.comp" (one execution) once, in
+    // front of everything else, and the staging buffer is released after that frame. The store has the layout setSceneTexturesFormatted gives the same textures
+    // with all their levels. Further refusals (PLR_ERR_INVALID_ARGUMENT): a format pair the build has no path for, more than 2^28 staging words.
+    void buildSceneTextures(const SceneTextureSource* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials, uint32_t drawCount);
+    // the texel store as the kernels see it: its word count, and the words when outWords is not null (capacityWords must suffice). Refused while there is no
+    // store, and before a frame has run since the call that set or built it (the upload and the build passes belong to that frame); waits for the GPU
+    uint64_t readSceneTextureStore(uint32_t* outWords, uint64_t capacityWords);
+    struct TextureBuildStats { uint32_t chainLaunches = 0, encodeLaunches = 0; uint64_t chainTexels = 0, blocksEncoded = 0, stagingBytes = 0; };
+    TextureBuildStats textureBuildStats() const { return m_textureBuildStats; } // of the last build a frame has recorded; zeros before there is one
     // alpha-tested cutouts for the scene and textures now set (DESIGN.md "Alpha-tested cutouts in the depth prepass"): one cutoff code 0 .. 255 per draw, 0 =
     // opaque, 128 = the reference's alpha < 0.5 -> discard. From the next frame on, while a cutoff is not 0, the pass is recorded with the fourth push-constant word
     // and binding 10, and a fragment whose sampled albedo alpha code is below its draw's cutoff is no fragment. Copied. drawCount 0 removes them; setSceneMeshes
@@ -731,7 +761,7 @@ private:
     // the cull flags and the debug flags survive every one of them
     void dropSceneNormalMaps() { m_sceneNormalDecode = 0; }    // they named textures
     void dropSceneAlphaCutoffs() { m_sceneAlphaTested = false; } // they belonged to the materials
-    void dropSceneTextures() { m_sceneTextureCount = 0; m_sceneTexturesCompressed = false; dropSceneAlphaCutoffs(); dropSceneNormalMaps(); } // they belonged to the scene
+    void dropSceneTextures() { m_sceneTextureCount = 0; m_sceneTexturesCompressed = false; m_textureBuildPending = false; dropSceneAlphaCutoffs(); dropSceneNormalMaps(); } // they belonged to the scene
     // the tail of both texture calls: fills the store, takes the counts over and drops what the previous store carried. formats: of a store with a compressed entry
     void takeSceneTextures(const PackedTextures& packed, uint32_t textureCount, const std::vector<uint32_t>* formats);
     std::vector<float> m_sceneModel, m_scenePreviousModel; // 16 floats per draw: what the next frame uses, what the last recorded frame used
@@ -775,6 +805,17 @@ private:
     RenderPassHandle m_blueNoisePass, m_perlinNoisePass;
     StorageBufferHandle m_noiseGaussianTable, m_noisePerlinGradients, m_noiseStatus[4];
     void recordNoiseGeneration();
+    // the texture build: passes created by the first buildSceneTextures; the job tables and the staging chains belong to the build that is pending
+    bool m_textureBuildPassesCreated = false, m_textureBuildPending = false, m_textureStagingHeld = false, m_textureStagingQueued = false;
+    bool m_sceneStoreInFrame = false; // a frame has run since the store was set or built: readSceneTextureStore reads what the kernels see
+    uint64_t m_sceneTexelWords = 0;
+    RenderPassHandle m_textureMipChainPass, m_textureBlockEncodePass;
+    GrowableBuffer m_textureChainJobs, m_textureEncodeJobs, m_textureStaging;
+    std::vector<PackedTextureBuild::ChainLaunch> m_textureChainLaunches;
+    uint32_t m_textureEncodeJobCount = 0, m_textureEncodeGroups = 0;
+    TextureBuildStats m_textureBuildStats, m_textureBuildPendingStats;
+    void recordTextureBuild();
+    void releaseTextureStaging();
     void removeSceneSdf();
     void updateSceneSdfInstances();
     void noteSceneTexturesChanged(uint32_t maxLevel0Texels);

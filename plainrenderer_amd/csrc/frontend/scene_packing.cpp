@@ -1,6 +1,7 @@
 // Validation and packing of scene meshes, their material textures, their alpha cutoffs and their normal maps for "depthPrepassRaster.comp"
 // (FramePipeline::setSceneMeshes, setSceneTextures, setSceneTexturesFormatted, setSceneAlphaCutoffs, setSceneNormalMaps) and of the shadow casters and their
-// cutouts for "sunShadowRaster.comp" (setShadowCasters, setShadowCasterCutouts), and the host's decoder of BC1 / BC3 / BC5 blocks: host code without a backend
+// cutouts for "sunShadowRaster.comp" (setShadowCasters, setShadowCasterCutouts), the host's decoder and encoder of BC1 / BC3 / BC5 blocks, and the layout and job
+// tables of the texture store the GPU builds (buildSceneTextures: "textureMipChain.comp", "textureBlockEncode.comp"): host code without a backend
 // call, so that a stand-alone program can run it under a sanitizer (tools/scene_packing_check.cpp for both mesh sets, tools/scene_texture_check.cpp,
 // tools/scene_alpha_check.cpp, tools/scene_normal_check.cpp, tools/shadow_cutout_check.cpp, tools/scene_bc_check.cpp, tools/draw_bounds_check.cpp).
 #include <algorithm>
@@ -10,6 +11,7 @@
 
 #include "../device/depth_prepass_raster.h"
 #include "../device/sun_shadow_raster.h"
+#include "../device/texture_build.h"
 #include "frame_pipeline.h"
 
 namespace plrhost {
@@ -383,6 +385,153 @@ void decodeBlockCompressedLevel(uint32_t format, uint32_t width, uint32_t height
             else word = alphaBlockTexel(b, i) | (alphaBlockTexel(b + 8, i) << 8) | (255u << 24);
             outWords[(size_t)y * width + x] = word;
         }
+}
+
+// ---- the texture store built on the GPU (DESIGN.md "Texture store built on the GPU")
+void encodeBlockCompressedLevel(uint32_t format, uint32_t width, uint32_t height, const uint32_t* words, void* outBlocks, uint64_t bytes) {
+    namespace pp = plr::prepass;
+    const std::string call = "plr_encode_rgba8_to_bc";
+    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
+    const int code = textureFormatCode(format);
+    if (code <= 0) refuse("format " + std::to_string(format) + " is not PLR_FORMAT_BC1, PLR_FORMAT_BC3 or PLR_FORMAT_BC5");
+    if (width < 1u || height < 1u || width > pp::kMaxTextureSize || height > pp::kMaxTextureSize)
+        refuse("the level is " + std::to_string(width) + " x " + std::to_string(height) + ", each side must be 1 .. 16384");
+    if (!words || !outBlocks) refuse("words or out_blocks are null");
+    const uint64_t need = pp::textureWords((uint32_t)code, width, height, 1) * 4u;
+    if (bytes != need)
+        refuse("bytes mismatch: " + std::to_string(bytes) + " bytes for a " + std::to_string(width) + " x " + std::to_string(height) + " level whose blocks hold " + std::to_string(need));
+    const size_t blockBytes = (size_t)pp::blockWords((uint32_t)code) * 4u, blocksX = ((size_t)width + 3u) / 4u, blocksY = ((size_t)height + 3u) / 4u;
+    uint8_t* out = (uint8_t*)outBlocks;
+    for (size_t by = 0; by < blocksY; by++)
+        for (size_t bx = 0; bx < blocksX; bx++) {
+            uint32_t t[16], block[4];
+            for (uint32_t j = 0; j < 4u; j++)
+                for (uint32_t i = 0; i < 4u; i++)
+                    t[4u * j + i] = words[std::min<size_t>(4u * by + j, height - 1u) * width + std::min<size_t>(4u * bx + i, width - 1u)];
+            plr::texbuild::encodeBlock((uint32_t)code, t, block);
+            std::memcpy(out + (by * blocksX + bx) * blockBytes, block, blockBytes); // (the caller's buffer may sit at any alignment)
+        }
+}
+
+// everything is validated before anything is laid out. The store's layout is packSceneTexturesFormatted's for the same textures with all their levels
+PackedTextureBuild packSceneTextureBuild(const SceneTextureSource* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials,
+                                         uint32_t drawCount, const uint32_t* sceneMeshVertexCounts, uint32_t sceneMeshCount, uint32_t sceneDrawCount) {
+    namespace pp = plr::prepass;
+    namespace tb = plr::texbuild;
+    const std::string call = "buildSceneTextures";
+    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
+    if (sceneDrawCount == 0) refuse("no scene set (plrf_set_scene_meshes comes first)");
+    if (meshCount != sceneMeshCount) refuse("mesh count " + std::to_string(meshCount) + " differs from the mesh count " + std::to_string(sceneMeshCount) + " of the scene");
+    if (drawCount != sceneDrawCount) refuse("draw count " + std::to_string(drawCount) + " differs from the draw count " + std::to_string(sceneDrawCount) + " of the scene");
+    if (!textures || !materials) refuse("textures or materials are null");
+    struct Plan { uint32_t source, stored, levels, given, offset; uint64_t staging; }; // format codes; levels of the store entry; levels the caller gave; word offsets
+    std::vector<Plan> plans(textureCount);
+    uint64_t total = 0, staging = 0;
+    auto levelWords = [](uint32_t code, uint32_t w, uint32_t h) { return pp::textureWords(code, w, h, 1); };
+    for (uint32_t t = 0; t < textureCount; t++) {
+        const SceneTextureSource& tex = textures[t];
+        const int source = textureFormatCode(tex.format), stored = textureFormatCode(tex.storeFormat);
+        if (source < 0 || stored < 0 || (source != (int)pp::kTextureFormatRgba8 && source != stored))
+            refuse("unsupported format pair: texture " + std::to_string(t) + " has format " + std::to_string(tex.format) + " and store_format " + std::to_string(tex.storeFormat) +
+                   " (an RGBA8 source is stored as RGBA8, BC1, BC3 or BC5; a BC1, BC3 or BC5 source as what it is)");
+        const uint32_t full = validateTextureShape(t, tex.width, tex.height, tex.mipCount, tex.data, refuse);
+        Plan& plan = plans[t];
+        plan.source = (uint32_t)source; plan.stored = (uint32_t)stored; plan.levels = tex.mipCount ? tex.mipCount : full; plan.given = std::max(1u, tex.mipCount);
+        const uint64_t given = pp::textureWords(plan.source, tex.width, tex.height, plan.given) * 4u;
+        if (tex.bytes != given)
+            refuse("bytes mismatch: texture " + std::to_string(t) + " (" + std::to_string(tex.width) + " x " + std::to_string(tex.height) + ", " + std::to_string(plan.given) +
+                   " level(s)) has " + std::to_string(tex.bytes) + " bytes, its levels hold " + std::to_string(given));
+        if (plan.stored != pp::kTextureFormatRgba8) total = (total + 3u) & ~(uint64_t)3u;
+        plan.offset = (uint32_t)std::min<uint64_t>(total, 0xffffffffu); // (a total that does not fit is refused below)
+        total += pp::textureWords(plan.stored, tex.width, tex.height, plan.levels);
+        // staging: every level of an RGBA8 source that is encoded; levels 1 .. of a compressed source whose chain is built. Each level at a multiple of 4 words
+        plan.staging = staging;
+        const bool encoded = plan.source == pp::kTextureFormatRgba8 && plan.stored != pp::kTextureFormatRgba8, chained = plan.source != pp::kTextureFormatRgba8 && tex.mipCount == 0;
+        if (encoded || chained)
+            for (uint32_t l = encoded ? 0u : 1u; l < plan.levels; l++) staging += (levelWords(pp::kTextureFormatRgba8, std::max(1u, tex.width >> l), std::max(1u, tex.height >> l)) + 3u) & ~(uint64_t)3u;
+    }
+    for (uint32_t d = 0; d < drawCount; d++)
+        for (uint32_t index : {materials[d].albedoTexture, materials[d].specularTexture})
+            if (index != kNoSceneTexture && index >= textureCount)
+                refuse("material texture index out of range: draw " + std::to_string(d) + " names texture " + std::to_string(index) + " of " + std::to_string(textureCount));
+    if (total > pp::kMaxTexels) refuse("too many texels: " + std::to_string(total) + " words in all levels of all textures, at most 2^28");
+    if (staging > tb::kMaxStagingWords) refuse("too many staging texels: the RGBA8 chains the build needs hold " + std::to_string(staging) + " words, at most 2^28");
+    PackedTextureBuild out;
+    out.uvs = packUvs(meshUvs, meshCount, sceneMeshVertexCounts, refuse);
+    out.materials.resize((size_t)drawCount * 2u);
+    for (uint32_t d = 0; d < drawCount; d++) { out.materials[2u * d] = materials[d].albedoTexture; out.materials[2u * d + 1u] = materials[d].specularTexture; }
+    out.textures.resize((size_t)textureCount * 4u);
+    out.texels.assign((size_t)total, 0u);
+    out.staging.assign((size_t)staging, 0u);
+    out.formats.resize(textureCount);
+    std::vector<std::vector<tb::ChainJob>> chain(tb::kMaxChainLaunches + 1u); // by the level built
+    std::vector<tb::EncodeJob> encode;
+    for (uint32_t t = 0; t < textureCount; t++) {
+        const SceneTextureSource& tex = textures[t];
+        const Plan& plan = plans[t];
+        const pp::Texture entry{plan.offset, tex.width, tex.height, plan.levels};
+        std::memcpy(out.textures.data() + (size_t)t * 4u, &entry, sizeof(entry));
+        out.formats[t] = plan.stored;
+        out.compressed = out.compressed || plan.stored != pp::kTextureFormatRgba8;
+        const bool rgbaSource = plan.source == pp::kTextureFormatRgba8, encoded = rgbaSource && plan.stored != pp::kTextureFormatRgba8;
+        // where level l lives while the build runs: {word offset, in the staging buffer}
+        std::vector<uint32_t> storeAt(plan.levels), stagingAt(plan.levels, 0u);
+        uint64_t s = plan.offset, g = plan.staging;
+        for (uint32_t l = 0; l < plan.levels; l++) {
+            const uint32_t w = std::max(1u, tex.width >> l), h = std::max(1u, tex.height >> l);
+            storeAt[l] = (uint32_t)s; s += levelWords(plan.stored, w, h);
+            if (encoded || (!rgbaSource && tex.mipCount == 0 && l >= 1u)) { stagingAt[l] = (uint32_t)g; g += ((uint64_t)w * h + 3u) & ~(uint64_t)3u; }
+        }
+        // the given levels: into the store where they are stored as given, into the staging chains where they are encoded
+        const uint8_t* data = (const uint8_t*)tex.data;
+        for (uint32_t l = 0; l < plan.given; l++) {
+            const uint32_t w = std::max(1u, tex.width >> l), h = std::max(1u, tex.height >> l);
+            const size_t words = (size_t)levelWords(plan.source, w, h);
+            std::memcpy((encoded ? out.staging.data() + stagingAt[l] : out.texels.data() + storeAt[l]), data, words * 4u); // (the caller's data may sit at any alignment)
+            data += words * 4u;
+        }
+        const bool staged = encoded || !rgbaSource; // where the chain's levels are built
+        for (uint32_t l = plan.given; l < plan.levels; l++) { // (only with mipCount 0: level l from level l - 1)
+            const uint32_t w = std::max(1u, tex.width >> (l - 1u)), h = std::max(1u, tex.height >> (l - 1u));
+            const bool fromBlocks = !rgbaSource && l == 1u; // level 0 of a compressed source: its blocks, in the store
+            tb::ChainJob job{};
+            job.src = fromBlocks || !staged ? storeAt[l - 1u] : stagingAt[l - 1u];
+            job.dst = staged ? stagingAt[l] : storeAt[l];
+            job.srcWidth = w; job.srcHeight = h;
+            job.flags = (fromBlocks ? plan.source : pp::kTextureFormatRgba8) | (staged && !fromBlocks ? tb::kChainSrcStaging : 0u) | (staged ? tb::kChainDstStaging : 0u);
+            chain[l].push_back(job);
+            out.chainTexels += (uint64_t)std::max(1u, w >> 1) * std::max(1u, h >> 1);
+        }
+        if (staged)
+            for (uint32_t l = encoded ? 0u : 1u; l < plan.levels; l++) {
+                if (!encoded && tex.mipCount != 0) break; // a compressed source with its levels: nothing to encode
+                tb::EncodeJob job{};
+                job.src = stagingAt[l]; job.dst = storeAt[l];
+                job.width = std::max(1u, tex.width >> l); job.height = std::max(1u, tex.height >> l); job.format = plan.stored;
+                encode.push_back(job);
+                out.blocksEncoded += (uint64_t)((job.width + 3u) / 4u) * ((job.height + 3u) / 4u);
+            }
+    }
+    // the workgroups of the jobs, launch by launch
+    for (uint32_t l = 1; l <= tb::kMaxChainLaunches; l++) {
+        if (chain[l].empty()) continue;
+        uint32_t groups = 0;
+        for (tb::ChainJob& job : chain[l]) {
+            job.firstGroup = groups;
+            groups += (std::max(1u, job.srcWidth >> 1) * std::max(1u, job.srcHeight >> 1) + tb::kGroupLanes - 1u) / tb::kGroupLanes;
+        }
+        out.chainLaunches.push_back({(uint32_t)(out.chainJobs.size() * 4u / sizeof(tb::ChainJob)), (uint32_t)chain[l].size(), groups});
+        const size_t at = out.chainJobs.size();
+        out.chainJobs.resize(at + chain[l].size() * (sizeof(tb::ChainJob) / 4u));
+        std::memcpy(out.chainJobs.data() + at, chain[l].data(), chain[l].size() * sizeof(tb::ChainJob));
+    }
+    for (tb::EncodeJob& job : encode) {
+        job.firstGroup = out.encodeGroups;
+        out.encodeGroups += (((job.width + 3u) / 4u) * ((job.height + 3u) / 4u) + tb::kGroupLanes - 1u) / tb::kGroupLanes;
+    }
+    out.encodeJobs.resize(encode.size() * (sizeof(tb::EncodeJob) / 4u));
+    if (!encode.empty()) std::memcpy(out.encodeJobs.data(), encode.data(), encode.size() * sizeof(tb::EncodeJob));
+    return out;
 }
 
 // everything is validated before anything is built

@@ -79,6 +79,16 @@ class PlrfSceneTextureData(C.Structure):
     _fields_ = [("data", C.c_void_p), ("bytes", C.c_uint64), ("width", C.c_uint32), ("height", C.c_uint32), ("mip_count", C.c_uint32), ("format", C.c_uint32)]
 
 
+class PlrfSceneTextureSource(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("bytes", C.c_uint64), ("width", C.c_uint32), ("height", C.c_uint32), ("mip_count", C.c_uint32), ("format", C.c_uint32),
+                ("store_format", C.c_uint32)]
+
+
+class PlrfTextureBuildStats(C.Structure):
+    _fields_ = [("mip_chain_launches", C.c_uint32), ("block_encode_launches", C.c_uint32), ("chain_texels", C.c_uint64), ("blocks_encoded", C.c_uint64),
+                ("staging_bytes", C.c_uint64)]
+
+
 class PlrfSceneMaterial(C.Structure):
     _fields_ = [("albedo_texture", C.c_uint32), ("specular_texture", C.c_uint32)]
 
@@ -428,6 +438,46 @@ class FramePipeline:
         self.lib.plrf_set_scene_textures_formatted.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
         self._check(self.lib.plrf_set_scene_textures_formatted(self.handle, C.cast(t, C.c_void_p), C.c_uint32(len(textures)), C.cast(u, C.c_void_p), C.c_uint32(len(mesh_uvs)),
                                                                C.cast(m, C.c_void_p), C.c_uint32(len(materials))))
+
+    def build_scene_textures(self, textures, mesh_uvs, materials):
+        """set_scene_textures_formatted with the mip chains and the BC1 / BC3 / BC5 blocks made on the GPU (include/plr_frame.h plrf_build_scene_textures):
+        textures: [(data, width, height, mip_count, format, store_format)] - an RGBA8 source is stored as RGBA8, BC1, BC3 or BC5, a compressed source as what it is;
+        mip_count 0: data is level 0 and the GPU builds the chain. The next frame records the build passes; the store has the layout
+        set_scene_textures_formatted gives the same textures with all their levels. mesh_uvs, materials, lifetime and removal as for set_scene_textures"""
+        def as_bytes(data, fmt):
+            if isinstance(data, (bytes, bytearray)):
+                return np.frombuffer(data, np.uint8)
+            return (np.ascontiguousarray(data, np.uint32) if int(fmt) == 2 else np.ascontiguousarray(data)).reshape(-1).view(np.uint8)
+        data = [as_bytes(t[0], t[4]) for t in textures]
+        uvs = [None if u is None else np.ascontiguousarray(u, np.float32).reshape(-1, 2) for u in mesh_uvs]
+        t = (PlrfSceneTextureSource * max(len(textures), 1))()
+        for k, (_, width, height, mips, fmt, store_fmt) in enumerate(textures):
+            t[k] = PlrfSceneTextureSource(data[k].ctypes.data if data[k].size else None, data[k].size, int(width), int(height), int(mips), int(fmt), int(store_fmt))
+        u = (C.POINTER(C.c_float) * max(len(uvs), 1))()
+        for k, a in enumerate(uvs):
+            u[k] = None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+        m = (PlrfSceneMaterial * max(len(materials), 1))()
+        for k, (albedo, specular) in enumerate(materials):
+            m[k] = PlrfSceneMaterial(int(albedo), int(specular))
+        self.lib.plrf_build_scene_textures.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        self._check(self.lib.plrf_build_scene_textures(self.handle, C.cast(t, C.c_void_p), C.c_uint32(len(textures)), C.cast(u, C.c_void_p), C.c_uint32(len(mesh_uvs)),
+                                                       C.cast(m, C.c_void_p), C.c_uint32(len(materials))))
+
+    def read_scene_texture_store(self):
+        """-> the uint32 words of the texel store as the kernels see it, whichever call made it; refused before a frame has run since that call. Waits for the GPU"""
+        n = C.c_uint64()
+        self.lib.plrf_read_scene_texture_store.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        self._check(self.lib.plrf_read_scene_texture_store(self.handle, None, C.c_uint64(0), C.byref(n)))
+        out = np.empty(n.value, np.uint32)
+        self._check(self.lib.plrf_read_scene_texture_store(self.handle, out.ctypes.data_as(C.c_void_p) if out.size else None, C.c_uint64(out.size), C.byref(n)))
+        return out
+
+    def texture_build_stats(self):
+        """the last build a frame has recorded: dict(mip_chain_launches, block_encode_launches, chain_texels, blocks_encoded, staging_bytes); zeros before one"""
+        s = PlrfTextureBuildStats()
+        self.lib.plrf_get_texture_build_stats.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(self.lib.plrf_get_texture_build_stats(self.handle, C.byref(s)))
+        return {name: int(getattr(s, name)) for name, _ in PlrfTextureBuildStats._fields_}
 
     def set_scene_alpha_cutoffs(self, cutoffs):
         """one alpha cutoff code 0 .. 255 per draw of the scene (0: opaque, ALPHA_CUTOFF_REFERENCE = 128: the reference's alpha < 0.5 -> discard); needs textures.

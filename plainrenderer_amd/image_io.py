@@ -5,7 +5,7 @@ import numpy as np
 
 from .backend import ImageDescription, ImageFormat, ImageType, MipCount, PlrError, _ImageDesc, _load
 
-IMAGE_IO_SYMBOLS = ["plr_write_dds_file", "plr_load_dds_file", "plr_encode_dds", "plr_decode_dds", "plr_decode_bc_to_rgba8"]
+IMAGE_IO_SYMBOLS = ["plr_write_dds_file", "plr_load_dds_file", "plr_encode_dds", "plr_decode_dds", "plr_decode_bc_to_rgba8", "plr_encode_rgba8_to_bc"]
 
 
 def _check(lib, rc):
@@ -73,4 +73,17 @@ def decode_bc_to_rgba8(fmt: ImageFormat, width, height, blocks):
     out = np.empty((max(int(height), 0), max(int(width), 0)), np.uint32)
     lib.plr_decode_bc_to_rgba8.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
     _check(lib, lib.plr_decode_bc_to_rgba8(int(fmt), int(width), int(height), src.ctypes.data if src.size else None, src.size, out.ctypes.data if out.size else None))
+    return out
+
+
+def encode_rgba8_to_bc(fmt: ImageFormat, width, height, words):
+    """one level of height x width uint32 RGBA8 words, R in the low byte -> the uint8 bytes of its BC1 / BC3 / BC5 blocks, by the encode contract the GPU's
+    "textureBlockEncode.comp" applies (include/plr_image_io.h plr_encode_rgba8_to_bc); needs no GPU"""
+    lib = _load()
+    src = np.ascontiguousarray(words, np.uint32).reshape(-1)
+    if src.size != max(int(width), 0) * max(int(height), 0):
+        raise ValueError("%d words for a %d x %d level" % (src.size, width, height))
+    out = np.empty(bc_level_bytes(fmt, max(int(width), 0), max(int(height), 0)), np.uint8)
+    lib.plr_encode_rgba8_to_bc.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64]
+    _check(lib, lib.plr_encode_rgba8_to_bc(int(fmt), int(width), int(height), src.ctypes.data if src.size else None, out.ctypes.data if out.size else None, out.size))
     return out
