@@ -201,6 +201,14 @@ def kat_pcf_taps():
     return out
 
 
+def kat_specular_multiscattering(lut_image, mode, tuples):
+    """shading.cpp computeSpecularMultiscatteringLobe for n x 11 floats (r, NoL, f0, single scattering lobe, LUT texel) -> n x 3"""
+    a = np.ascontiguousarray(tuples, np.float32).reshape(-1, 11)
+    out = np.zeros((a.shape[0], 3), np.float32)
+    lib().orc_kat_specular_multiscattering(lut_image.ref(), C.c_int32(mode), _p(a), _p(out), C.c_int64(a.shape[0]))
+    return out
+
+
 def kat_sky_lut(image, dirs):
     a = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
     out = np.zeros((a.shape[0], 3), np.float32)

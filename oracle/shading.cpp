@@ -196,6 +196,23 @@ vec3 computeSpecularMultiscatteringLobe(const ShadeCtx& c, float r, float NoL, v
     return multiScatteringLobe;
 }
 
+} // namespace
+
+// KAT: the shade's own computeSpecularMultiscatteringLobe for n tuples of 11 floats (r, NoL, f0.xyz, singleScatteringLobe.xyz, brdfLut texel .xyz) -> n x 3 floats.
+// The colour image cannot show this lobe to better than a storage code; tests/test_shade_reference_cpu.py holds it to the float64 reference directly.
+extern "C" void orc_kat_specular_multiscattering(const orc_image* brdfLutP, int32_t directMultiscatterBRDF, const float* in, float* out, int64_t n) {
+    ShadeCtx c{};
+    c.brdfLut = &img(brdfLutP);
+    c.multiscatter = directMultiscatterBRDF;
+    for (int64_t i = 0; i < n; i++) {
+        const float* t = in + 11 * i;
+        const vec3 lobe = computeSpecularMultiscatteringLobe(c, t[0], t[1], vec3(t[2], t[3], t[4]), vec3(t[5], t[6], t[7]), vec3(t[8], t[9], t[10]));
+        out[3 * i] = lobe.x; out[3 * i + 1] = lobe.y; out[3 * i + 2] = lobe.z;
+    }
+}
+
+namespace {
+
 // GeometricAA.inc:4-19 with explicit quad derivatives
 float modifiedRoughnessGeometricAA(vec3 N_U, vec3 N_V, float r) {
     const float kappa = 0.18f;

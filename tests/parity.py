@@ -2,7 +2,8 @@
 
 A pass output is compared with the oracle channel by channel:
   * R11G11B10 images: the packed codes may differ by at most ONE code step per channel (one storage quantum: 2^-6 relative for R and G,
-    2^-5 for B) - `r11g11b10_code_diff`.
+    2^-5 for B) - `r11g11b10_code_diff`. For the deferred shade this holds where the float64 reference's `slack` (tests/shade_reference.py: the forward error of
+    an fp32 evaluation) is below a quarter of a code; where it is not - the roughness floor under a mirror highlight - the bound is slack + one code of float64.
   * half-float images (GI): |got - ref| <= max(2^-7 * |ref|, ABS_FLOOR) on the decoded values, ABS_FLOOR stated per image
     as a fraction of the image's largest magnitude.
   * RGBA8 swapchain: +-1 LSB.

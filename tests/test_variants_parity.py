@@ -3,6 +3,8 @@
 cascades), the five TAA history samplers x clip / clamp (+ no dilation, no tonemapping), the SDF trace without the strict influence cut-off and
 the spatial filter on a full-resolution (D32) grid - at 1920 x 1088 on bench.py's scene (RenderFrontend.h:32-38, Techniques/TAA.h:8-17).
 Pixels whose decision signatures agree with the oracle's must meet the bound with NO outlier allowance; flipped decisions are counted under caps.
+(For the shade the one-code sentence holds where the float64 reference's `slack` is below a quarter of a code - tests/shade_reference.py - which is all of this
+scene: its roughness never reaches the max(r * r, 0.0045) floor. tests/test_shade_reference.py holds the variants to float64 at the floor.)
 PLR_VARIANT_SIZE=WxH (multiples of 64) changes the size."""
 import os
 
@@ -55,7 +57,7 @@ def test_gpu_every_shipped_shade_variant_meets_the_quantum_bound(backend, vs, br
     sky = (so.words & 128) != 0
     report("shade %d/%d/%d/%d/%d" % var, flipped=float(flip.mean()), clean_max_code_diff=int(d[~flip & ~sky].max()), sky_max_code_diff=int(d[~flip & sky].max(initial=0)),
            clean_differing=float((d[~flip] != 0).any(axis=1).mean()))
-    assert d[~flip & ~sky].max() <= 1, "same cascade, same number of lit PCF taps: every channel within one R11G11B10 code"
+    assert d[~flip & ~sky].max() <= 1, "same cascade, same number of lit PCF taps: every channel within one R11G11B10 code (where slack is below a quarter of a code: this scene)"
     assert d[~flip & sky].max(initial=0) <= 2
     assert flip.mean() <= 2e-3
 
