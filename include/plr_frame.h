@@ -276,7 +276,7 @@ int plrf_apply_changes(void* pipeline); /* apply what was recorded now: a caller
  * they rasterise the draws into shadow0 .. shadow<count - 1> with whatever sunShadowInfo holds, uploaded or computed (run_light_matrix). Maps at and above the
  * cascade count are not touched. Without casters nothing is recorded and the uploaded maps are used. The rasterisation contract - 8 sub-pixel bits, top-left
  * rule, front faces culled, depth clamp, round-to-nearest-even Depth16, a 2^20-pixel guard band with a counted reject instead of clipping, casters opaque unless
- * plrf_set_shadow_caster_cutouts (below) gives them an alpha test - is DESIGN.md "Sun shadow cascades as a compute pass".
+ * plrf_set_shadow_caster_cutouts or plrf_set_shadow_caster_cutouts_formatted (below) gives them an alpha test - is DESIGN.md "Sun shadow cascades as a compute pass".
  * plrf_set_shadow_casters copies the meshes (positions and a uint32 triangle list each) and the draws; draw_count 0 removes the casters. PLR_ERR_INVALID_ARGUMENT,
  * with a message that names the cause: a mesh index or a vertex index out of range, an index count that is no multiple of 3, a model matrix whose last row is not
  * exactly (0, 0, 0, 1) (the pass does not divide by w). PLR_ERR_UNSUPPORTED: a band / tile pipeline without band_raster. A refused call changes nothing.
@@ -396,7 +396,8 @@ int plrf_get_texture_build_stats(void* pipeline, plrf_texture_build_stats* out);
  * plrf_set_scene_mesh_transforms, plrf_set_resolution and plrf_update_settings. While all cutoffs are 0, or none are set, every frame is what it is without this
  * call. PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: no scene set, no textures set, a count mismatch, NULL cutoffs with a non-zero count, a
  * value above 255. PLR_ERR_UNSUPPORTED: a band / tile pipeline without band_raster. A refused call changes nothing. The sun shadow pass has an alpha test of its own, for its own
- * meshes: plrf_set_shadow_caster_cutouts below. */
+ * meshes: plrf_set_shadow_caster_cutouts below, and plrf_set_shadow_caster_cutouts_formatted for casters whose cutout textures are BC1 / BC3 / BC5 blocks - both
+ * passes take the blocks as they are, and no caller decodes them on the host. */
 #define PLRF_ALPHA_CUTOFF_REFERENCE 128u
 int plrf_set_scene_alpha_cutoffs(void* pipeline, const uint32_t* cutoffs, uint32_t draw_count);
 /* ---- normal maps: triangle.frag:180-196 (shade with normalize(passTBN * normalTexelReconstructed)) as a sixth image of the depth prepass, "shadingNormal" (RGBA8,
@@ -452,6 +453,24 @@ typedef struct plrf_shadow_cutout { uint32_t albedo_texture, alpha_cutoff; } plr
 int plrf_set_shadow_caster_cutouts(void* pipeline, const plrf_scene_texture* textures, uint32_t texture_count,
                                    const float* const* mesh_uvs, uint32_t mesh_count,
                                    const plrf_shadow_cutout* cutouts, uint32_t draw_count);
+/* ---- block-compressed cutout textures for the casters (DESIGN.md "Block-compressed cutout textures in the sun shadow raster"): plrf_set_shadow_caster_cutouts for
+ * textures that carry a format - plrf_scene_texture_data exactly as plrf_set_scene_textures_formatted takes it, so the payload of a DXT5 foliage or fence texture
+ * goes in as it is, with neither a host decode nor an RGBA8 copy four times its size. The alpha of a texel is bits 24 - 31 of what the block decode contract yields
+ * for it: BC3: its alpha block (both modes); BC1 and BC5: 255, so a draw that names such an entry stays opaque as a draw without a texture does. The pass decodes
+ * the alpha block of every BC3 tap in integers and filters the codes as it filters RGBA8 alphas: the maps and counters are exactly those of
+ * plrf_set_shadow_caster_cutouts with plr_decode_bc_to_rgba8 of the same levels. Semantics, lifetime and removal are plrf_set_shadow_caster_cutouts': the two
+ * calls replace one another's store, texture_count 0 and every plrf_set_shadow_casters remove it, and it survives plrf_set_shadow_caster_transforms,
+ * plrf_set_resolution and plrf_update_settings. A call whose entries are all RGBA8 records exactly the pass plrf_set_shadow_caster_cutouts records (an RGBA8 entry
+ * with mip_count 0 gets the host's chain). PLR_ERR_INVALID_ARGUMENT, with a message that names the cause: what plrf_set_shadow_caster_cutouts refuses, an unknown
+ * format, mip_count 0 on a compressed entry, a bytes mismatch, more than 2^28 words in total (a compressed entry starts at a multiple of 16 bytes).
+ * PLR_ERR_UNSUPPORTED: where plrf_set_shadow_caster_cutouts returns it. A refused call changes nothing. */
+int plrf_set_shadow_caster_cutouts_formatted(void* pipeline, const plrf_scene_texture_data* textures, uint32_t texture_count,
+                                             const float* const* mesh_uvs, uint32_t mesh_count,
+                                             const plrf_shadow_cutout* cutouts, uint32_t draw_count);
+/* A diagnostic, for tests and tools; a renderer has no use for it. The shape of the "sunShadowRaster.comp" record the last frame with casters made per cascade: *push_bytes is 8 (opaque casters, or all cutoffs 0), 12 (cutouts whose
+ * store is all RGBA8, from either call) or 16 (a store with a BC1 / BC3 / BC5 entry: the word textureFormats and binding 14), *storage_buffers the buffers it
+ * bound (6, 10 or 11). Zeros before the first frame with casters. Does not wait for the GPU. */
+int plrf_get_shadow_raster_record(void* pipeline, uint32_t* push_bytes, uint32_t* storage_buffers);
 /* ---- SDF instances of the GI trace from the scene: SDFGI::updateSDFScene (Techniques/SDFGI.cpp:260-313, called from renderScene every frame) as the compute pass
  * "sdfInstanceUpdate.comp", and computeMeanAlbedo (ModelImport.cpp:78-112) as "sceneMeanAlbedo.comp" (DESIGN.md "SDF instances from the scene": the instance
  * contract - padded boxes as plr_sdf_padded_bounds, the world box of the eight transformed corners, worldToLocal = inverse(model translate(bbOffset)) as adjugate

@@ -23,6 +23,17 @@ constexpr int kUvBinding = prepass::kUvBinding, kCasterMaterialBinding = prepass
               kTexelBinding = prepass::kTexelBinding; // storage buffers of a tested execution (textureCount > 0)
 struct CasterMaterial { uint32_t albedoTexture, cutoff; }; // per draw; kNoTexture: alpha 255 everywhere; the kernel uses min(cutoff, 256), 0 = opaque
 static_assert(sizeof(CasterMaterial) == 8, "caster material layout");
+// block-compressed cutout textures (DESIGN.md "Block-compressed cutout textures in the sun shadow raster"): the optional fourth push word; 0, or absent, is the
+// pass whose textures are all RGBA8 and binding 14 is ignored. 1: the texture store is the prepass's format-aware one - `texels` holds uint32 words, a compressed
+// entry's texelOffset counts words - and binding 14 (the prepass's number) holds one format code per texture
+struct FormatPushConstants { uint32_t drawCount, triangleCount, textureCount, textureFormats; };
+constexpr int kTextureFormatBinding = prepass::kTextureFormatBinding;
+using prepass::kTextureFormatBc1;
+using prepass::kTextureFormatBc3;
+using prepass::kTextureFormatBc5;
+using prepass::kTextureFormatRgba8;
+// which instantiation of the two kernels an execution runs: picked by the launcher from textureCount and textureFormats
+constexpr int kAlphaUntested = 0, kAlphaRgba8 = 1, kAlphaFormats = 2;
 using prepass::fullMipCount;
 using prepass::kAlphaCutoffDiscardAll;
 using prepass::kAlphaCutoffOpaque;
@@ -58,9 +69,11 @@ constexpr size_t scratchBytes(uint32_t triangleCount) { return recordOffset(tria
 struct alignas(16) CutoutRecord {
     SetupRecord s;
     uint32_t test;             // bits 0 - 8: kAlphaCutoffOpaque: the record takes the opaque path (c = 0, or no usable texture and c <= 255); kAlphaCutoffDiscardAll:
-                               // it is dropped whole; else c of a sampled record. Bits 16 - 23: fw. Bit 24: L1 != L0
+                               // it is dropped whole; else c of a sampled record. Bits 16 - 23: fw. Bit 24: L1 != L0. Bit 25 (a format-aware execution): the
+                               // texture is BC3 - a sampled record is RGBA8 or BC3, a BC1 or BC5 one has alpha 255 everywhere and takes the opaque path
     uint32_t size0, size1;     // W | H << 16 of levels L0 and L1
-    uint32_t base0Low, base0High; // the first texel of level L0 in `texels`, 64 bits; L1's is base0 + W_L0 H_L0 where L1 != L0
+    uint32_t base0Low, base0High; // the first texel of level L0 in `texels`, 64 bits; L1's is base0 + W_L0 H_L0 where L1 != L0. A BC3 record: the first word of
+                               // L0's blocks, and L1's is base0 + 4 ceil(W_L0 / 4) ceil(H_L0 / 4)
     float u0, v0, u1, v1, u2, v2; // the vertices' UVs
     uint32_t pad;
 };

@@ -119,6 +119,21 @@ int plrf_set_shadow_caster_cutouts(void* p, const plrf_scene_texture* textures, 
         ((FramePipeline*)p)->setShadowCasterCutouts(t.empty() ? nullptr : t.data(), textureCount, meshUvs, meshCount, m.empty() ? nullptr : m.data(), drawCount);
     })
 }
+int plrf_set_shadow_caster_cutouts_formatted(void* p, const plrf_scene_texture_data* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount,
+                                             const plrf_shadow_cutout* cutouts, uint32_t drawCount) {
+    if (!p) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({
+        std::vector<SceneTextureData> t(textures ? textureCount : 0u);
+        for (size_t i = 0; i < t.size(); i++) t[i] = {textures[i].data, textures[i].bytes, textures[i].width, textures[i].height, textures[i].mip_count, textures[i].format};
+        std::vector<ShadowCutout> m(cutouts ? drawCount : 0u);
+        for (size_t i = 0; i < m.size(); i++) m[i] = {cutouts[i].albedo_texture, cutouts[i].alpha_cutoff};
+        ((FramePipeline*)p)->setShadowCasterCutoutsFormatted(t.empty() ? nullptr : t.data(), textureCount, meshUvs, meshCount, m.empty() ? nullptr : m.data(), drawCount);
+    })
+}
+int plrf_get_shadow_raster_record(void* p, uint32_t* pushBytes, uint32_t* storageBuffers) {
+    if (!p || !pushBytes || !storageBuffers) return PLR_ERR_INVALID_ARGUMENT;
+    PLRF_TRY_REFUSAL({ ((FramePipeline*)p)->shadowRasterRecord(pushBytes, storageBuffers); })
+}
 int plrf_get_shadow_raster_stats(void* p, uint32_t cascade, plrf_shadow_raster_stats* out) {
     if (!p || !out) return PLR_ERR_INVALID_ARGUMENT;
     PLRF_TRY_REFUSAL({

@@ -1347,8 +1347,11 @@ void FramePipeline::renderSunShadowCascades() {
                                                     StorageBufferResource(m_casterScratch[c].handle, false, plr::sunraster::kScratchBinding)};
         // without cutouts, or while every cutoff is 0: the 8-byte record
         const bool tested = m_casterAlphaTested && m_casterTextureCount;
-        const plr::sunraster::CutoutPushConstants pc{m_casterDrawCount, m_casterTriangleCount, tested ? m_casterTextureCount : 0u};
-        exe.pushConstants = dataToCharArray(&pc, tested ? sizeof(pc) : sizeof(plr::sunraster::PushConstants));
+        // a store with a compressed entry: the 16-byte record and binding 14; every other tested one is the 12-byte record it was
+        const bool formatted = tested && m_casterCompressed;
+        const plr::sunraster::FormatPushConstants pc{m_casterDrawCount, m_casterTriangleCount, tested ? m_casterTextureCount : 0u, formatted ? 1u : 0u};
+        exe.pushConstants = dataToCharArray(&pc, formatted ? sizeof(pc) : tested ? sizeof(plr::sunraster::CutoutPushConstants) : sizeof(plr::sunraster::PushConstants));
+        if (formatted) exe.genericInfo.resources.storageBuffers.push_back(StorageBufferResource(m_casterTextureFormats.handle, true, plr::sunraster::kTextureFormatBinding));
         if (tested) {
             auto& buffers = exe.genericInfo.resources.storageBuffers;
             buffers.push_back(StorageBufferResource(m_casterUvs.handle, true, plr::sunraster::kUvBinding));
@@ -1356,6 +1359,8 @@ void FramePipeline::renderSunShadowCascades() {
             buffers.push_back(StorageBufferResource(m_casterTextures.handle, true, plr::sunraster::kTextureBinding));
             buffers.push_back(StorageBufferResource(m_casterTexels.handle, true, plr::sunraster::kTexelBinding));
         }
+        m_casterPushBytes = (uint32_t)exe.pushConstants.size();
+        m_casterBufferCount = (uint32_t)exe.genericInfo.resources.storageBuffers.size();
         m_be.setComputePassExecution(exe);
     }
 }
@@ -1421,6 +1426,26 @@ void FramePipeline::setShadowCasterCutouts(const SceneTexture* textures, uint32_
         fillBuffer(m_casterScratch[c], nullptr, plr::sunraster::cutoutScratchBytes(m_casterTriangleCount));
     m_casterTextureCount = textureCount;
     m_casterAlphaTested = packed.tested;
+    m_casterCompressed = false; // (the store of a formatted call is replaced)
+}
+
+void FramePipeline::setShadowCasterCutoutsFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts,
+                                                    uint32_t drawCount) {
+    if (partitionedWithoutRaster(m_requestedSettings))
+        throw FramePipelineRefusal(PLR_ERR_UNSUPPORTED, "setShadowCasterCutoutsFormatted: a band / tile pipeline cannot rasterise shadow casters");
+    if (textureCount == 0) { dropCasterCutouts(); return; }
+    const PackedFormattedShadowCutouts packed = packShadowCasterCutoutsFormatted(textures, textureCount, meshUvs, meshCount, cutouts, drawCount, m_casterMeshVertexCounts.data(),
+                                                                                 (uint32_t)m_casterMeshVertexCounts.size(), m_casterDrawCount); // validates everything before anything is changed
+    fillBuffer(m_casterUvs, packed.uvs);
+    fillBuffer(m_casterMaterials, packed.materials);
+    fillBuffer(m_casterTextures, packed.textures);
+    fillBuffer(m_casterTexels, packed.texels);
+    if (packed.compressed) fillBuffer(m_casterTextureFormats, packed.formats); // (an all-RGBA8 store is setShadowCasterCutouts': no binding 14)
+    for (int c = 0; c < settings.shading.sunShadowCascadeCount; c++) // a tested execution's records are larger; a format-aware one's have the same size
+        fillBuffer(m_casterScratch[c], nullptr, plr::sunraster::cutoutScratchBytes(m_casterTriangleCount));
+    m_casterTextureCount = textureCount;
+    m_casterAlphaTested = packed.tested;
+    m_casterCompressed = packed.compressed;
 }
 
 void FramePipeline::setShadowCasterTransforms(const float* matrices16, uint32_t drawCount) {

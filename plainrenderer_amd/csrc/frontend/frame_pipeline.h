@@ -452,6 +452,16 @@ struct PackedShadowCutouts {
 // casterMeshVertexCounts / casterDrawCount: of the casters the pipeline holds (casterDrawCount 0: none). Throws FramePipelineRefusal.
 PackedShadowCutouts packShadowCasterCutouts(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts,
                                             uint32_t drawCount, const uint32_t* casterMeshVertexCounts, uint32_t casterMeshCount, uint32_t casterDrawCount);
+// what setShadowCasterCutoutsFormatted validates and packs, without a backend: PackedShadowCutouts - `textures` with word offsets, `texels` with the blocks of a
+// compressed texture at a multiple of 4 words, the store packSceneTexturesFormatted gives the same textures - and binding 14 of a format-aware "sunShadowRaster.comp"
+struct PackedFormattedShadowCutouts : PackedShadowCutouts {
+    std::vector<uint32_t> formats;
+    bool compressed = false; // an entry that is not RGBA8: only then the frames record the fourth push-constant word
+};
+// Throws FramePipelineRefusal: what packShadowCasterCutouts refuses, an unknown format, mipCount 0 on a compressed entry, a bytes mismatch, more than 2^28 words
+PackedFormattedShadowCutouts packShadowCasterCutoutsFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount,
+                                                              const ShadowCutout* cutouts, uint32_t drawCount, const uint32_t* casterMeshVertexCounts, uint32_t casterMeshCount,
+                                                              uint32_t casterDrawCount);
 // the scene's SDF (plr_frame.h plrf_set_scene_sdf): per mesh an index from addSdfVolume*, kSceneSdfBake, or kNoSceneTexture (no SDF: its draws make no instance)
 constexpr uint32_t kSceneSdfBake = 0xfffffffeu;
 // of the scene the pipeline holds: the packed positions and per mesh its vertex count, per draw its mesh and its current model matrix
@@ -503,8 +513,18 @@ public:
     // 16384, too many mips, null texels, a texture index out of range, a cutoff above 255, more than 2^28 texels, a non-finite UV are PLR_ERR_INVALID_ARGUMENT; a
     // band / tile pipeline is PLR_ERR_UNSUPPORTED. A refused call changes nothing.
     void setShadowCasterCutouts(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts, uint32_t drawCount);
+    // setShadowCasterCutouts for textures that carry a format (DESIGN.md "Block-compressed cutout textures in the sun shadow raster"): entries as for
+    // setSceneTexturesFormatted. While an entry is BC1, BC3 or BC5 and a cutoff is not 0 the cascades are recorded with the fourth push-constant word and binding
+    // 14, and the kernel decodes a BC3 tap's alpha block (BC1 and BC5 have alpha 255 everywhere); a call whose entries are all RGBA8 records exactly the pass
+    // setShadowCasterCutouts records. The two calls replace one another's store; lifetime and removal are setShadowCasterCutouts'. Refusals: what that call
+    // refuses, an unknown format, mipCount 0 on a compressed entry, a bytes mismatch, more than 2^28 words in total. A refused call changes nothing.
+    void setShadowCasterCutoutsFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts,
+                                         uint32_t drawCount);
     // counters of the last frame's execution for `cascade`; waits for the GPU. Zero before the first frame with casters.
     ShadowRasterStats shadowRasterStats(uint32_t cascade);
+    // the shape of the record the last frame with casters made per cascade: the bytes of its push constants (8: opaque, 12: tested, 16: format-aware) and the storage
+    // buffers it bound (6, 10, 11). Zeros before the first frame with casters. Does not wait
+    void shadowRasterRecord(uint32_t* pushBytes, uint32_t* storageBuffers) const { *pushBytes = m_casterPushBytes; *storageBuffers = m_casterBufferCount; }
     // RenderFrontend::renderDepthPrepass (RenderFrontend.cpp:351, 792-802) as "depthPrepassRaster.comp" (kernels/depth_prepass_raster.hip): while a scene is set every
     // frame records one execution in front of the depth pyramid (also under the SDF debug view) that writes the current render target's depth and motion and the
     // normal, albedo and specular images from the pipeline's own camera matrices and jitter; without a scene the uploaded G-buffer is used. Everything is
@@ -731,9 +751,11 @@ private:
     // cutouts: created by the first setShadowCasterCutouts; 0 textures, or no cutoff other than 0 = the 8-byte pass record
     uint32_t m_casterTextureCount = 0;
     bool m_casterAlphaTested = false;
+    bool m_casterCompressed = false; // setShadowCasterCutoutsFormatted with an entry that is not RGBA8: the 16-byte pass record and binding 14
+    uint32_t m_casterPushBytes = 0, m_casterBufferCount = 0; // of the cascades' record as the last frame made it (shadowRasterRecord)
     std::vector<uint32_t> m_casterMeshVertexCounts;
-    GrowableBuffer m_casterUvs, m_casterMaterials, m_casterTextures, m_casterTexels;
-    void dropCasterCutouts() { m_casterTextureCount = 0; m_casterAlphaTested = false; } // every setShadowCasters: they belonged to the casters that are gone
+    GrowableBuffer m_casterUvs, m_casterMaterials, m_casterTextures, m_casterTexels, m_casterTextureFormats;
+    void dropCasterCutouts() { m_casterTextureCount = 0; m_casterAlphaTested = m_casterCompressed = false; } // every setShadowCasters: they belonged to the casters that are gone
     // scene meshes: created by the first setSceneMeshes (a pipeline without a scene allocates and records nothing for them)
     uint32_t m_sceneDrawCount = 0, m_sceneTriangleCount = 0;
     bool m_scenePassCreated = false, m_scenePreviousValid = false, m_sceneRecorded = false; // recorded: a frame has run the pass for the scene now set

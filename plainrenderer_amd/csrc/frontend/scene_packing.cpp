@@ -1,9 +1,10 @@
 // Validation and packing of scene meshes, their material textures, their alpha cutoffs and their normal maps for "depthPrepassRaster.comp"
 // (FramePipeline::setSceneMeshes, setSceneTextures, setSceneTexturesFormatted, setSceneAlphaCutoffs, setSceneNormalMaps) and of the shadow casters and their
-// cutouts for "sunShadowRaster.comp" (setShadowCasters, setShadowCasterCutouts), the host's decoder and encoder of BC1 / BC3 / BC5 blocks, and the layout and job
+// cutouts for "sunShadowRaster.comp" (setShadowCasters, setShadowCasterCutouts, setShadowCasterCutoutsFormatted), the host's decoder and encoder of BC1 / BC3 / BC5 blocks, and the layout and job
 // tables of the texture store the GPU builds (buildSceneTextures: "textureMipChain.comp", "textureBlockEncode.comp"): host code without a backend
 // call, so that a stand-alone program can run it under a sanitizer (tools/scene_packing_check.cpp for both mesh sets, tools/scene_texture_check.cpp,
-// tools/scene_alpha_check.cpp, tools/scene_normal_check.cpp, tools/shadow_cutout_check.cpp, tools/scene_bc_check.cpp, tools/draw_bounds_check.cpp).
+// tools/scene_alpha_check.cpp, tools/scene_normal_check.cpp, tools/shadow_cutout_check.cpp, tools/shadow_cutout_bc_check.cpp, tools/scene_bc_check.cpp,
+// tools/draw_bounds_check.cpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -268,19 +269,12 @@ static int textureFormatCode(uint32_t format) {
     }
 }
 
-// everything is validated before anything is built. An RGBA8 entry is packed as packSceneTextures packs it; a compressed one starts at a multiple of 4 words (16
-// bytes), zeros in front of it where needed. Without a compressed entry the result is packSceneTextures' own, and `compressed` stays false
-PackedFormattedTextures packSceneTexturesFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials,
-                                                   uint32_t drawCount, const uint32_t* sceneMeshVertexCounts, uint32_t sceneMeshCount, uint32_t sceneDrawCount) {
+// ---- the format-aware store, shared by the scene's textures (setSceneTexturesFormatted) and the shadow casters' cutouts (setShadowCasterCutoutsFormatted): the
+// checks per texture and the layout first, the store once the call's other checks have passed. `refuse` throws with the call's name in front
+struct FormattedLayout { std::vector<uint32_t> codes, offsets; uint64_t total = 0; }; // per texture the contract's format code and the word offset; the words in all
+template <class Refuse> static FormattedLayout validateFormattedTextures(const SceneTextureData* textures, uint32_t textureCount, Refuse&& refuse) {
     namespace pp = plr::prepass;
-    const std::string call = "setSceneTexturesFormatted";
-    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
-    if (sceneDrawCount == 0) refuse("no scene set (plrf_set_scene_meshes comes first)");
-    if (meshCount != sceneMeshCount) refuse("mesh count " + std::to_string(meshCount) + " differs from the mesh count " + std::to_string(sceneMeshCount) + " of the scene");
-    if (drawCount != sceneDrawCount) refuse("draw count " + std::to_string(drawCount) + " differs from the draw count " + std::to_string(sceneDrawCount) + " of the scene");
-    if (!textures || !materials) refuse("textures or materials are null");
-    uint64_t total = 0;
-    std::vector<uint32_t> codes(textureCount), offsets(textureCount);
+    FormattedLayout at{std::vector<uint32_t>(textureCount), std::vector<uint32_t>(textureCount), 0};
     for (uint32_t t = 0; t < textureCount; t++) {
         const SceneTextureData& tex = textures[t];
         const int code = textureFormatCode(tex.format);
@@ -294,34 +288,56 @@ PackedFormattedTextures packSceneTexturesFormatted(const SceneTextureData* textu
         if (tex.bytes != given)
             refuse("bytes mismatch: texture " + std::to_string(t) + " (" + std::to_string(tex.width) + " x " + std::to_string(tex.height) + ", " + std::to_string(std::max(1u, tex.mipCount)) +
                    " level(s)) has " + std::to_string(tex.bytes) + " bytes, its levels hold " + std::to_string(given));
-        if (blocks) total = (total + 3u) & ~(uint64_t)3u;
-        offsets[t] = (uint32_t)std::min<uint64_t>(total, 0xffffffffu); // (a total that does not fit is refused below)
-        total += pp::textureWords((uint32_t)code, tex.width, tex.height, tex.mipCount ? tex.mipCount : full);
-        codes[t] = (uint32_t)code;
+        if (blocks) at.total = (at.total + 3u) & ~(uint64_t)3u;
+        at.offsets[t] = (uint32_t)std::min<uint64_t>(at.total, 0xffffffffu); // (a total that does not fit is refused by the caller)
+        at.total += pp::textureWords((uint32_t)code, tex.width, tex.height, tex.mipCount ? tex.mipCount : full);
+        at.codes[t] = (uint32_t)code;
     }
+    return at;
+}
+// An RGBA8 entry is packed as packTextureStore packs it; a compressed one starts at a multiple of 4 words (16 bytes), zeros in front of it where needed. Returns
+// whether an entry is compressed: without one the table and the words are packTextureStore's own
+static bool packFormattedStore(const SceneTextureData* textures, uint32_t textureCount, const FormattedLayout& at, std::vector<uint32_t>& table, std::vector<uint32_t>& words) {
+    namespace pp = plr::prepass;
+    bool compressed = false;
+    table.resize((size_t)textureCount * 4u);
+    words.reserve((size_t)at.total);
+    for (uint32_t t = 0; t < textureCount; t++) {
+        const SceneTextureData& tex = textures[t];
+        words.resize(at.offsets[t], 0u); // (the padding in front of a compressed texture)
+        const pp::Texture entry{at.offsets[t], tex.width, tex.height, tex.mipCount ? tex.mipCount : pp::fullMipCount(tex.width, tex.height)};
+        std::memcpy(table.data() + (size_t)t * 4u, &entry, sizeof(entry));
+        const size_t given = (size_t)(tex.bytes / 4u);
+        words.resize(words.size() + given);
+        std::memcpy(words.data() + at.offsets[t], tex.data, given * 4u); // (the caller's data may sit at any alignment)
+        if (tex.mipCount == 0) appendMipChain(words, tex.width, tex.height);
+        compressed = compressed || at.codes[t] != pp::kTextureFormatRgba8;
+    }
+    return compressed;
+}
+
+// everything is validated before anything is built. Without a compressed entry the result is packSceneTextures' own, and `compressed` stays false
+PackedFormattedTextures packSceneTexturesFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const SceneMaterial* materials,
+                                                   uint32_t drawCount, const uint32_t* sceneMeshVertexCounts, uint32_t sceneMeshCount, uint32_t sceneDrawCount) {
+    namespace pp = plr::prepass;
+    const std::string call = "setSceneTexturesFormatted";
+    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
+    if (sceneDrawCount == 0) refuse("no scene set (plrf_set_scene_meshes comes first)");
+    if (meshCount != sceneMeshCount) refuse("mesh count " + std::to_string(meshCount) + " differs from the mesh count " + std::to_string(sceneMeshCount) + " of the scene");
+    if (drawCount != sceneDrawCount) refuse("draw count " + std::to_string(drawCount) + " differs from the draw count " + std::to_string(sceneDrawCount) + " of the scene");
+    if (!textures || !materials) refuse("textures or materials are null");
+    const FormattedLayout at = validateFormattedTextures(textures, textureCount, refuse);
     for (uint32_t d = 0; d < drawCount; d++)
         for (uint32_t index : {materials[d].albedoTexture, materials[d].specularTexture})
             if (index != kNoSceneTexture && index >= textureCount)
                 refuse("material texture index out of range: draw " + std::to_string(d) + " names texture " + std::to_string(index) + " of " + std::to_string(textureCount));
-    if (total > pp::kMaxTexels) refuse("too many texels: " + std::to_string(total) + " words in all levels of all textures, at most 2^28");
+    if (at.total > pp::kMaxTexels) refuse("too many texels: " + std::to_string(at.total) + " words in all levels of all textures, at most 2^28");
     PackedFormattedTextures out;
     out.uvs = packUvs(meshUvs, meshCount, sceneMeshVertexCounts, refuse);
     out.materials.resize((size_t)drawCount * 2u);
     for (uint32_t d = 0; d < drawCount; d++) { out.materials[2u * d] = materials[d].albedoTexture; out.materials[2u * d + 1u] = materials[d].specularTexture; }
-    out.textures.resize((size_t)textureCount * 4u);
-    out.texels.reserve((size_t)total);
-    for (uint32_t t = 0; t < textureCount; t++) {
-        const SceneTextureData& tex = textures[t];
-        out.texels.resize(offsets[t], 0u); // (the padding in front of a compressed texture)
-        const pp::Texture entry{offsets[t], tex.width, tex.height, tex.mipCount ? tex.mipCount : pp::fullMipCount(tex.width, tex.height)};
-        std::memcpy(out.textures.data() + (size_t)t * 4u, &entry, sizeof(entry));
-        const size_t words = (size_t)(tex.bytes / 4u);
-        out.texels.resize(out.texels.size() + words);
-        std::memcpy(out.texels.data() + offsets[t], tex.data, words * 4u); // (the caller's data may sit at any alignment)
-        if (tex.mipCount == 0) appendMipChain(out.texels, tex.width, tex.height);
-        out.compressed = out.compressed || codes[t] != pp::kTextureFormatRgba8;
-    }
-    out.formats = codes;
+    out.compressed = packFormattedStore(textures, textureCount, at, out.textures, out.texels);
+    out.formats = at.codes;
     return out;
 }
 
@@ -534,6 +550,19 @@ PackedTextureBuild packSceneTextureBuild(const SceneTextureSource* textures, uin
     return out;
 }
 
+// the cutouts of the caster draws, whichever store they index: returns whether a cutoff is not 0
+template <class Refuse> static bool validateCutouts(const ShadowCutout* cutouts, uint32_t drawCount, uint32_t textureCount, Refuse&& refuse) {
+    bool tested = false;
+    for (uint32_t d = 0; d < drawCount; d++) {
+        if (cutouts[d].albedoTexture != kNoSceneTexture && cutouts[d].albedoTexture >= textureCount)
+            refuse("texture index out of range: draw " + std::to_string(d) + " names texture " + std::to_string(cutouts[d].albedoTexture) + " of " + std::to_string(textureCount));
+        if (cutouts[d].alphaCutoff > 255u)
+            refuse("cutoff out of range: draw " + std::to_string(d) + " has " + std::to_string(cutouts[d].alphaCutoff) + ", a cutoff code is 0 (opaque) .. 255");
+        tested = tested || cutouts[d].alphaCutoff != plr::prepass::kAlphaCutoffOpaque;
+    }
+    return tested;
+}
+
 // everything is validated before anything is built
 PackedShadowCutouts packShadowCasterCutouts(const SceneTexture* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount, const ShadowCutout* cutouts,
                                             uint32_t drawCount, const uint32_t* casterMeshVertexCounts, uint32_t casterMeshCount, uint32_t casterDrawCount) {
@@ -546,18 +575,36 @@ PackedShadowCutouts packShadowCasterCutouts(const SceneTexture* textures, uint32
     if (!textures || !cutouts) refuse("textures or cutouts are null");
     const uint64_t total = validateTextures(textures, textureCount, refuse);
     PackedShadowCutouts out;
-    for (uint32_t d = 0; d < drawCount; d++) {
-        if (cutouts[d].albedoTexture != kNoSceneTexture && cutouts[d].albedoTexture >= textureCount)
-            refuse("texture index out of range: draw " + std::to_string(d) + " names texture " + std::to_string(cutouts[d].albedoTexture) + " of " + std::to_string(textureCount));
-        if (cutouts[d].alphaCutoff > 255u)
-            refuse("cutoff out of range: draw " + std::to_string(d) + " has " + std::to_string(cutouts[d].alphaCutoff) + ", a cutoff code is 0 (opaque) .. 255");
-        out.tested = out.tested || cutouts[d].alphaCutoff != pp::kAlphaCutoffOpaque;
-    }
+    out.tested = validateCutouts(cutouts, drawCount, textureCount, refuse);
     if (total > pp::kMaxTexels) refuse("too many texels: " + std::to_string(total) + " in all levels of all textures, at most 2^28");
     out.uvs = packUvs(meshUvs, meshCount, casterMeshVertexCounts, refuse);
     out.materials.resize((size_t)drawCount * 2u);
     for (uint32_t d = 0; d < drawCount; d++) { out.materials[2u * d] = cutouts[d].albedoTexture; out.materials[2u * d + 1u] = cutouts[d].alphaCutoff; }
     packTextureStore(textures, textureCount, total, out.textures, out.texels);
+    return out;
+}
+
+// everything is validated before anything is built: packShadowCasterCutouts' checks in its order, with the format-aware store's checks per texture
+// (validateFormattedTextures) where that one has validateTextures', and the store packed by packFormattedStore
+PackedFormattedShadowCutouts packShadowCasterCutoutsFormatted(const SceneTextureData* textures, uint32_t textureCount, const float* const* meshUvs, uint32_t meshCount,
+                                                              const ShadowCutout* cutouts, uint32_t drawCount, const uint32_t* casterMeshVertexCounts, uint32_t casterMeshCount,
+                                                              uint32_t casterDrawCount) {
+    namespace pp = plr::prepass;
+    const std::string call = "setShadowCasterCutoutsFormatted";
+    auto refuse = [&](const std::string& why) { throw FramePipelineRefusal(PLR_ERR_INVALID_ARGUMENT, call + ": " + why); };
+    if (casterDrawCount == 0) refuse("no casters set (plrf_set_shadow_casters comes first)");
+    if (meshCount != casterMeshCount) refuse("mesh count " + std::to_string(meshCount) + " differs from the mesh count " + std::to_string(casterMeshCount) + " of the casters");
+    if (drawCount != casterDrawCount) refuse("draw count " + std::to_string(drawCount) + " differs from the draw count " + std::to_string(casterDrawCount) + " of the casters");
+    if (!textures || !cutouts) refuse("textures or cutouts are null");
+    const FormattedLayout at = validateFormattedTextures(textures, textureCount, refuse);
+    PackedFormattedShadowCutouts out;
+    out.tested = validateCutouts(cutouts, drawCount, textureCount, refuse);
+    if (at.total > pp::kMaxTexels) refuse("too many texels: " + std::to_string(at.total) + " words in all levels of all textures, at most 2^28");
+    out.uvs = packUvs(meshUvs, meshCount, casterMeshVertexCounts, refuse);
+    out.materials.resize((size_t)drawCount * 2u);
+    for (uint32_t d = 0; d < drawCount; d++) { out.materials[2u * d] = cutouts[d].albedoTexture; out.materials[2u * d + 1u] = cutouts[d].alphaCutoff; }
+    out.compressed = packFormattedStore(textures, textureCount, at, out.textures, out.texels);
+    out.formats = at.codes;
     return out;
 }
 

@@ -54,18 +54,36 @@
 //     current value need not be sampled
 //   deviations from the reference: isotropic trilinear filtering for g_sampler_anisotropicRepeat; l is the depth's fp32 weight, not an exact plane
 //
+// THE FORMAT CLAUSE (DESIGN.md "Block-compressed cutout textures in the sun shadow raster"; tests/shadow_bc_reference.py implements it independently, bit for bit),
+// of an execution with textureCount > 0 and textureFormats = 1. The cutout contract stands word for word except its texture store clause, which becomes the
+// prepass's format-aware store (DESIGN.md "Block-compressed textures in the depth prepass"):
+//   texture store: buffer `textureFormats` holds one code per texture, kTextureFormatRgba8 / Bc1 / Bc3 / Bc5 = 0 .. 3; `texels` holds uint32 words and an entry's
+//     texelOffset counts words. A compressed entry's level l is ceil(W_l / 4) x ceil(H_l / 4) blocks (BC1: 2 words, BC3 and BC5: 4), row-major, levels back to
+//     back, and its offset must be a multiple of its block's words. An entry is usable by the cutout contract's rule and: a code above BC5, or a misaligned
+//     offset, makes it unusable (alpha 255 everywhere, as for a draw without a texture). A block that does not lie wholly inside `texels` reads 0; an RGBA8
+//     entry's texel outside `texels` reads 0, as before
+//   alpha of a texel: bits 24 - 31 of what the block decode contract (device/bc_decode.h) yields for it - BC3: its block's alpha block, {a0, a1, 16 indices of 3
+//     bits}: index 0 -> a0, 1 -> a1, a0 > a1: ((8 - k) a0 + (k - 1) a1 + 3) / 7, else 6 -> 0, 7 -> 255, ((6 - k) a0 + (k - 1) a1 + 2) / 5; BC1 and BC5: 255
+//   everything downstream is unchanged: the level per triangle from the texture's texel dimensions, bias 0, 8 sub-texel bits, repeat wrap,
+//     S = (256 - fw) S_L0 + fw S_L1, round half even, alpha >= c, the order-independent maximum, the counters
+//   the property: an execution with compressed entries equals, texel for texel and counter for counter, the same execution whose store holds
+//     plr_decode_bc_to_rgba8 of the same levels
+//
 // Two kernels. SET-UP: a lane per triangle finds its draw, transforms, snaps, culls and boxes; survivors are appended through a cursor (one atomic per block) to a dense
 // array of 4-byte tile rectangles and an array of set-up records (order free: the result is a maximum). TILES: a 256-thread block per 64 x 64 tile keeps the tile as
 // 4096 words of LDS; each wave scans the rectangles and walks those that touch its tile; LDS atomic max; the block then stores its tile as Depth16 rows. Every tile
 // scans every rectangle: no bins in this version. The draw lookup and the record are device/raster_setup.h's, the scan, the walk and a fragment's coverage and
 // depth device/raster_tile_walk.h's, both shared with "depthPrepassRaster.comp"; this file holds the transform, the block's append, what becomes of a fragment
-// (clamp, encode, alpha test, maximum), the tile's store and the launcher. Both kernels are templates over kAlphaTest, picked by textureCount; the `false`
-// instantiations hold none of the cutout code. The tested set-up stores everything that depends on the triangle alone (cutoff, level sizes, first texel,
+// (clamp, encode, alpha test, maximum), the tile's store and the launcher. Both kernels are templates over a three-way mode - kAlphaUntested, kAlphaRgba8,
+// kAlphaFormats - picked by textureCount and textureFormats; the untested instantiations hold none of the cutout code and the RGBA8-tested ones none of the
+// format code. The format-aware set-up decides per record: a BC1 or BC5 texture has alpha 255 everywhere and its record is stored like one without a usable
+// texture; an RGBA8 or BC3 record reaches the fragment hook, bit 25 of its test word telling them apart, and a BC3 tap loads its alpha block alone. The tested set-up stores everything that depends on the triangle alone (cutoff, level sizes, first texel,
 // fw, the three UVs) behind the set-up record (128 bytes per record instead of 80); only u, v and the taps are per fragment.
 #include <algorithm>
 #include <type_traits>
 
 #include "../backend.h"
+#include "../device/bc_decode.h"
 #include "../device/detmath.h"
 #include "../device/raster_setup.h"
 #include "../device/raster_tile_walk.h"
@@ -87,8 +105,17 @@ struct CutoutSetupParams {
     uint64_t uvVertexCount;
     uint32_t textureCount;
 };
+// a format-aware execution's set-up: the same, and one format code per texture
+struct FormatSetupParams {
+    CutoutSetupParams c;
+    const uint32_t* formats;
+};
+template <int kMode> using SetupArgs = std::conditional_t<kMode == kAlphaFormats, FormatSetupParams, std::conditional_t<kMode == kAlphaRgba8, CutoutSetupParams, SetupParams>>;
 PLR_DI const SetupParams& plainParams(const SetupParams& a) { return a; }
 PLR_DI const SetupParams& plainParams(const CutoutSetupParams& a) { return a.s; }
+PLR_DI const SetupParams& plainParams(const FormatSetupParams& a) { return a.c.s; }
+PLR_DI const CutoutSetupParams& cutoutParams(const CutoutSetupParams& a) { return a; }
+PLR_DI const CutoutSetupParams& cutoutParams(const FormatSetupParams& a) { return a.c; }
 PLR_DI SetupRecord& setupOf(SetupRecord& r) { return r; }
 PLR_DI SetupRecord& setupOf(CutoutRecord& r) { return r.s; }
 
@@ -102,8 +129,17 @@ PLR_DI bool usableTexture(const Texture* textures, uint32_t textureCount, uint32
     return true;
 }
 
+// the uint32 words of a w x h level: texels, or the 16-byte blocks of a BC3 level
+PLR_DI uint64_t levelWords(bool bc3, uint32_t w, uint32_t h) {
+    return bc3 ? (uint64_t)((w + 3u) >> 2) * (uint64_t)((h + 3u) >> 2) * 4u : (uint64_t)w * (uint64_t)h;
+}
+
 // what the alpha of a fragment of this triangle needs beyond its weights (the cutout contract: material, UVs, level): once per record. v: the three vertices
-PLR_DI void cutoutOfTriangle(const CutoutSetupParams& p, uint32_t draw, const uint64_t v[3], CutoutRecord& r) {
+// Params: CutoutSetupParams, or FormatSetupParams (the format clause: the entry's format code decides whether it is usable, constant or sampled)
+template <class Params>
+PLR_DI void cutoutOfTriangle(const Params& args, uint32_t draw, const uint64_t v[3], CutoutRecord& r) {
+    constexpr bool kFormats = std::is_same_v<Params, FormatSetupParams>;
+    const CutoutSetupParams& p = cutoutParams(args);
     r.test = kAlphaCutoffOpaque;
     r.size0 = r.size1 = r.base0Low = r.base0High = r.pad = 0u;
     r.u0 = r.v0 = r.u1 = r.v1 = r.u2 = r.v2 = 0.f;
@@ -113,6 +149,14 @@ PLR_DI void cutoutOfTriangle(const CutoutSetupParams& p, uint32_t draw, const ui
     if (c == kAlphaCutoffDiscardAll) { r.test = kAlphaCutoffDiscardAll; return; } // no alpha code reaches 256, sampled or constant
     Texture tex;
     if (!usableTexture(p.textures, p.textureCount, m.albedoTexture, &tex)) return; // alpha 255 everywhere: opaque for c <= 255
+    bool bc3 = false;
+    if constexpr (kFormats) {
+        const uint32_t format = args.formats[m.albedoTexture]; // (usable: the index is inside the table, and the launcher checked textureCount entries)
+        if (format > kTextureFormatBc5) return;                // unusable by the prepass's rule
+        if (format != kTextureFormatRgba8 && (tex.texelOffset & (format == kTextureFormatBc1 ? 1u : 3u)) != 0u) return; // a misaligned offset: unusable too
+        if (format == kTextureFormatBc1 || format == kTextureFormatBc5) return; // alpha 255 everywhere: stored like a record without a usable texture
+        bc3 = format == kTextureFormatBc3;
+    }
     float uv[6];
     for (int k = 0; k < 3; k++) { // a vertex outside `uvs` has (0, 0)
         const bool inside = v[k] < p.uvVertexCount;
@@ -138,16 +182,20 @@ PLR_DI void cutoutOfTriangle(const CutoutSetupParams& p, uint32_t draw, const ui
     const int q = (int)__builtin_floorf(lod * 256.f + 0.5f);
     const int L0 = q >> 8, L1 = min(L0 + 1, (int)tex.mipCount - 1);
     uint64_t base = tex.texelOffset;
-    for (int l = 0; l < L0; l++) base += (uint64_t)max(1u, tex.width >> l) * (uint64_t)max(1u, tex.height >> l);
-    r.test = c | ((uint32_t)(q & 255) << 16) | (L1 != L0 ? 1u << 24 : 0u);
+    for (int l = 0; l < L0; l++) {
+        if constexpr (kFormats) base += levelWords(bc3, max(1u, tex.width >> l), max(1u, tex.height >> l));
+        else base += (uint64_t)max(1u, tex.width >> l) * (uint64_t)max(1u, tex.height >> l);
+    }
+    r.test = c | ((uint32_t)(q & 255) << 16) | (L1 != L0 ? 1u << 24 : 0u) | (bc3 ? 1u << 25 : 0u);
     r.size0 = max(1u, tex.width >> L0) | (max(1u, tex.height >> L0) << 16); // (a level is at most 16384 wide and high: 15 bits)
     r.size1 = max(1u, tex.width >> L1) | (max(1u, tex.height >> L1) << 16);
     r.base0Low = (uint32_t)base; r.base0High = (uint32_t)(base >> 32);
     r.u0 = uv[0]; r.v0 = uv[1]; r.u1 = uv[2]; r.v1 = uv[3]; r.u2 = uv[4]; r.v2 = uv[5];
 }
 
-template <bool kAlphaTest>
-__global__ __launch_bounds__(256) void sunShadowSetupKernel(std::conditional_t<kAlphaTest, CutoutSetupParams, SetupParams> args) {
+template <int kMode>
+__global__ __launch_bounds__(256) void sunShadowSetupKernel(SetupArgs<kMode> args) {
+    constexpr bool kAlphaTest = kMode != kAlphaUntested;
     const SetupParams& p = plainParams(args);
     const uint32_t t = blockIdx.x * 256u + threadIdx.x, lane = threadIdx.x & 63u;
     const uint32_t wave = threadIdx.x >> 6;
@@ -218,7 +266,7 @@ __global__ __launch_bounds__(256) void sunShadowSetupKernel(std::conditional_t<k
         const uint32_t slot = base + (uint32_t)__popcll(survivorMask & ((1ull << lane) - 1ull));
         if (slot < p.capacity) { // (always: the cursor counts at most triangleCount survivors and the launcher sized the arrays for that many)
             p.rects[slot] = rect;
-            if constexpr (kAlphaTest) args.records[slot] = rec;
+            if constexpr (kAlphaTest) cutoutParams(args).records[slot] = rec;
             else p.records[slot] = rec;
         }
     }
@@ -263,12 +311,17 @@ PLR_DI int wrapRepeat(int64_t t, int n) {
 }
 
 // the alpha channel's weighted sum over the four taps of one level (w x h texels, the first at `base`); every address in 64 bits and checked before its load
-PLR_DI uint32_t alphaTaps(const uint32_t* texels, uint64_t texelCount, uint64_t base, int w, int h, double u, double v) {
+// kFormats, bc3: the level is BC3 blocks and a tap decodes its alpha block alone (device/bc_decode.h, kFirst == 3: the block's word address is checked there)
+template <bool kFormats = false>
+PLR_DI uint32_t alphaTaps(const uint32_t* texels, uint64_t texelCount, uint64_t base, int w, int h, double u, double v, bool bc3 = false) {
     const int64_t Tu = (int64_t)__builtin_floor((u * (double)w - 0.5) * 256.0 + 0.5), Tv = (int64_t)__builtin_floor((v * (double)h - 0.5) * 256.0 + 0.5);
     const uint32_t fx = (uint32_t)(Tu & 255), fy = (uint32_t)(Tv & 255);
     const int x0 = wrapRepeat(Tu >> 8, w), y0 = wrapRepeat(Tv >> 8, h);
     const int x1 = x0 + 1 == w ? 0 : x0 + 1, y1 = y0 + 1 == h ? 0 : y0 + 1;
     auto fetch = [&](int x, int y) {
+        if constexpr (kFormats) {
+            if (bc3) return prepass::blockTexel<3>(texels, texelCount, base, kTextureFormatBc3, w, x, y) >> 24;
+        }
         const uint64_t at = base + (uint64_t)y * (uint64_t)w + (uint64_t)x;
         return (at < texelCount ? texels[at] : 0u) >> 24;
     };
@@ -276,6 +329,7 @@ PLR_DI uint32_t alphaTaps(const uint32_t* texels, uint64_t texelCount, uint64_t 
 }
 
 // the alpha code of the fragment of record r with the depth's weights l1, l2 (the cutout contract)
+template <bool kFormats = false>
 PLR_DI uint32_t fragmentAlpha(const CutoutRecord& r, const uint32_t* texels, uint64_t texelCount, float l1, float l2) {
     const double u0 = (double)r.u0, v0 = (double)r.v0;
     double u = (u0 + (double)l1 * ((double)r.u1 - u0)) + (double)l2 * ((double)r.u2 - u0);
@@ -284,15 +338,18 @@ PLR_DI uint32_t fragmentAlpha(const CutoutRecord& r, const uint32_t* texels, uin
     const uint32_t fw = (r.test >> 16) & 255u;
     const uint64_t base = (uint64_t)r.base0Low | ((uint64_t)r.base0High << 32);
     const int w = (int)(r.size0 & 0xffffu), h = (int)(r.size0 >> 16);
-    const uint32_t s0 = alphaTaps(texels, texelCount, base, w, h, u, v);
+    const bool bc3 = kFormats && ((r.test >> 25) & 1u) != 0u; // (a constant false in the RGBA8-tested instantiation: levelWords is then W H, the taps the texel taps)
+    const uint32_t s0 = alphaTaps<kFormats>(texels, texelCount, base, w, h, u, v, bc3);
     uint32_t s1 = 0u;
     if (fw != 0u) // (with fw == 0 the upper level has no weight; with L1 == L0 it is the same level again)
-        s1 = alphaTaps(texels, texelCount, (r.test >> 24) & 1u ? base + (uint64_t)w * (uint64_t)h : base, (int)(r.size1 & 0xffffu), (int)(r.size1 >> 16), u, v);
+        s1 = alphaTaps<kFormats>(texels, texelCount, (r.test >> 24) & 1u ? base + levelWords(bc3, (uint32_t)w, (uint32_t)h) : base, (int)(r.size1 & 0xffffu), (int)(r.size1 >> 16), u, v, bc3);
     const uint32_t S = (256u - fw) * s0 + fw * s1;
     return (S + 0x7fffffu + ((S >> 24) & 1u)) >> 24;
 }
 
-// a tested execution's fragment: the same, and a record with a cutoff samples its alpha before the maximum
+// a tested execution's fragment: the same, and a record with a cutoff samples its alpha before the maximum. kFormats: `texels` are the words of a format-aware
+// store, texelCount their number, and a record is RGBA8 or BC3 (bit 25 of its test word)
+template <bool kFormats>
 struct CutoutWalk : rastercov::PlainWalk {
     uint32_t* tile;
     int ox, oy;
@@ -312,14 +369,15 @@ struct CutoutWalk : rastercov::PlainWalk {
         const uint32_t c = r.test & 0x1ffu;
         if (c != kAlphaCutoffOpaque) { // the one branch: every other record's fragment goes the opaque way
             if (code <= *cell) return; // a filter only: the atomic below decides
-            if (fragmentAlpha(r, texels, texelCount, weights[0], weights[1]) < c) return;
+            if (fragmentAlpha<kFormats>(r, texels, texelCount, weights[0], weights[1]) < c) return;
         }
         atomicMax(cell, code);
     }
 };
 
-template <bool kAlphaTest>
-__global__ __launch_bounds__(256) void sunShadowTileKernel(std::conditional_t<kAlphaTest, CutoutTileParams, TileParams> args) {
+template <int kMode>
+__global__ __launch_bounds__(256) void sunShadowTileKernel(std::conditional_t<kMode != kAlphaUntested, CutoutTileParams, TileParams> args) {
+    constexpr bool kAlphaTest = kMode != kAlphaUntested;
     const TileParams& p = plainParams(args);
     __shared__ uint32_t tile[kTileSize * kTileSize];
     __shared__ uint32_t hitQueue[4][256]; // per wave: the entries of the current step that touch the tile
@@ -333,7 +391,7 @@ __global__ __launch_bounds__(256) void sunShadowTileKernel(std::conditional_t<kA
     // the kernel's time in a busy tile is the hits' arithmetic
     const rastercov::TileWindow window{tx, ty, ox, oy, min(ox + kTileSize - 1, p.res - 1), min(oy + kTileSize - 1, p.res - 1)};
     if constexpr (kAlphaTest) {
-        CutoutWalk walk{{}, tile, ox, oy, args.texels, args.texelCount, kAlphaCutoffOpaque};
+        CutoutWalk<kMode == kAlphaFormats> walk{{}, tile, ox, oy, args.texels, args.texelCount, kAlphaCutoffOpaque};
         rastercov::rasteriseTile(p.rects, args.records, n, window, hitQueue[wave], walk);
     } else {
         ShadowWalk walk{{}, tile, ox, oy};
@@ -362,9 +420,14 @@ static int launchSunShadowRaster(const PassCtx& c) {
     const uint32_t cascade = c.specUint(kCascadeIndexConstant, 0u);
     if (cascade >= 4u) return c.fail(-1, "sunShadowRaster: cascadeIndex (specialisation constant 0) is " + std::to_string(cascade) + ", a sunShadowInfo block holds 4 light matrices");
     if (c.push.size() < sizeof(PushConstants)) return c.fail(-1, "sunShadowRaster: push constants {drawCount, triangleCount} missing");
-    CutoutPushConstants pc{};
-    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0
-    const bool tested = pc.textureCount != 0u;
+    FormatPushConstants pc{};
+    std::memcpy(&pc, c.push.data(), std::min(c.push.size(), sizeof(pc)) / 4u * 4u); // 8 bytes: {drawCount, triangleCount}, textureCount 0; 12: textureFormats 0
+    const bool tested = pc.textureCount != 0u, formatted = pc.textureFormats != 0u;
+    if (formatted) {
+        if (pc.textureFormats != 1u)
+            return c.fail(-1, "sunShadowRaster: textureFormats is " + std::to_string(pc.textureFormats) + ", it must be 0 (every texture is RGBA8) or 1 (binding 14 holds a format code per texture)");
+        if (!tested) return c.fail(-1, "sunShadowRaster: textureFormats is set and textureCount is 0 (a format belongs to a texture of the texture store)");
+    }
     if (c.dispatch[0] != 1u || c.dispatch[1] != 1u || c.dispatch[2] != 1u || c.base[0] != 0u || c.base[1] != 0u)
         return c.fail(-1, "sunShadowRaster: the dispatch is {1, 1, 1} (the launcher derives its grids from the push constants and the map)");
     if (int rc = c.needSbuf(kSunShadowInfoBinding, sizeof(ShadowCascadeInfo), "sunShadowRaster sunShadowInfo")) return rc;
@@ -381,7 +444,11 @@ static int launchSunShadowRaster(const PassCtx& c) {
         if (int rc = c.needSbuf(kUvBinding, 0, "sunShadowRaster uvs (binding 6: 2 floats per vertex)")) return rc;
         if (int rc = c.needSbuf(kCasterMaterialBinding, (size_t)pc.drawCount * sizeof(CasterMaterial), "sunShadowRaster casterMaterials (binding 7: {albedoTexture, cutoff} per draw)")) return rc;
         if (int rc = c.needSbuf(kTextureBinding, (size_t)pc.textureCount * sizeof(Texture), "sunShadowRaster textures (binding 8: {texelOffset, width, height, mipCount})")) return rc;
-        if (int rc = c.needSbuf(kTexelBinding, 0, "sunShadowRaster texels (binding 9: RGBA8, every texture's levels back to back)")) return rc;
+        if (int rc = c.needSbuf(kTexelBinding, 0, formatted ? "sunShadowRaster texels (binding 9: the words of a format-aware store - RGBA8 texels, BC1 / BC3 / BC5 blocks -, every texture's levels back to back)"
+                                                            : "sunShadowRaster texels (binding 9: RGBA8, every texture's levels back to back)"))
+            return rc;
+        if (formatted)
+            if (int rc = c.needSbuf(kTextureFormatBinding, (size_t)pc.textureCount * 4u, "sunShadowRaster textureFormats (binding 14: one uint32 format code per texture)")) return rc;
     }
     if (c.sbuf[kScratchBinding].readOnly) return c.fail(-4, "sunShadowRaster: the scratch buffer (binding 5) is bound read-only");
     if (int rc = c.needStorage(kMapBinding, F_D16, "sunShadowRaster shadow map")) return rc;
@@ -395,11 +462,14 @@ static int launchSunShadowRaster(const PassCtx& c) {
         for (int b : {kUvBinding, kCasterMaterialBinding, kTextureBinding, kTexelBinding})
             if (c.sbuf[b].ptr == c.sbuf[kScratchBinding].ptr)
                 return c.fail(-4, "sunShadowRaster: the scratch buffer is also bound as an input (binding " + std::to_string(b) + ")");
+    if (formatted && c.sbuf[kTextureFormatBinding].ptr == c.sbuf[kScratchBinding].ptr)
+        return c.fail(-4, "sunShadowRaster: the scratch buffer is also bound as an input (binding 14, textureFormats)");
 
     uint8_t* scratch = (uint8_t*)c.sbuf[kScratchBinding].ptr;
     if (hipMemsetAsync(scratch, 0, sizeof(ScratchHeader), c.stream) != hipSuccess) return c.fail(-2, "sunShadowRaster: clearing the scratch header failed");
     if (pc.triangleCount) {
-        CutoutSetupParams cs{};
+        FormatSetupParams fs{};
+        CutoutSetupParams& cs = fs.c;
         SetupParams& s = cs.s;
         s.info = (const ShadowCascadeInfo*)c.sbuf[kSunShadowInfoBinding].ptr; s.transforms = (const float*)c.sbuf[kTransformBinding].ptr;
         s.positions = (const float*)c.sbuf[kPositionBinding].ptr; s.indices = (const uint32_t*)c.sbuf[kIndexBinding].ptr; s.draws = (const Draw*)c.sbuf[kDrawBinding].ptr;
@@ -413,10 +483,14 @@ static int launchSunShadowRaster(const PassCtx& c) {
             cs.uvs = (const float*)c.sbuf[kUvBinding].ptr; cs.materials = (const CasterMaterial*)c.sbuf[kCasterMaterialBinding].ptr;
             cs.textures = (const Texture*)c.sbuf[kTextureBinding].ptr; cs.records = (CutoutRecord*)(scratch + recordOffset(pc.triangleCount));
             cs.uvVertexCount = c.sbuf[kUvBinding].size / 8u; cs.textureCount = pc.textureCount;
-            sunShadowSetupKernel<true><<<divUp(pc.triangleCount, 256u), 256, 0, c.stream>>>(cs);
+            if (formatted) {
+                fs.formats = (const uint32_t*)c.sbuf[kTextureFormatBinding].ptr;
+                sunShadowSetupKernel<kAlphaFormats><<<divUp(pc.triangleCount, 256u), 256, 0, c.stream>>>(fs);
+            } else
+                sunShadowSetupKernel<kAlphaRgba8><<<divUp(pc.triangleCount, 256u), 256, 0, c.stream>>>(cs);
         } else {
             s.records = (SetupRecord*)(scratch + recordOffset(pc.triangleCount));
-            sunShadowSetupKernel<false><<<divUp(pc.triangleCount, 256u), 256, 0, c.stream>>>(s);
+            sunShadowSetupKernel<kAlphaUntested><<<divUp(pc.triangleCount, 256u), 256, 0, c.stream>>>(s);
         }
         PLR_CHECK_LAUNCH(c);
         c.splitTiming("set-up");
@@ -429,10 +503,11 @@ static int launchSunShadowRaster(const PassCtx& c) {
     if (tested) {
         ct.records = (const CutoutRecord*)(scratch + recordOffset(pc.triangleCount)); ct.texels = (const uint32_t*)c.sbuf[kTexelBinding].ptr;
         ct.texelCount = c.sbuf[kTexelBinding].size / 4u;
-        sunShadowTileKernel<true><<<dim3(tiles, tiles), 256, 0, c.stream>>>(ct);
+        if (formatted) sunShadowTileKernel<kAlphaFormats><<<dim3(tiles, tiles), 256, 0, c.stream>>>(ct); // (texelCount: the words of the format-aware store)
+        else sunShadowTileKernel<kAlphaRgba8><<<dim3(tiles, tiles), 256, 0, c.stream>>>(ct);
     } else {
         t.records = (const SetupRecord*)(scratch + recordOffset(pc.triangleCount));
-        sunShadowTileKernel<false><<<dim3(tiles, tiles), 256, 0, c.stream>>>(t);
+        sunShadowTileKernel<kAlphaUntested><<<dim3(tiles, tiles), 256, 0, c.stream>>>(t);
     }
     PLR_CHECK_LAUNCH(c);
     return 0;

@@ -356,6 +356,13 @@ class FramePipeline:
             m[k] = PlrfShadowCutout(int(albedo), int(cutoff))
         self._check(self.lib.plrf_set_shadow_caster_cutouts(self.handle, t, C.c_uint32(len(textures)), u, C.c_uint32(len(mesh_uvs)), m, C.c_uint32(len(cutouts))))
 
+    def shadow_raster_record(self):
+        """(push constant bytes, storage buffers bound) of the cascades' pass record as the last frame with casters made it: (8, 6) opaque, (12, 10) cutouts
+        whose store is all RGBA8, (16, 11) a store with a compressed entry; (0, 0) before such a frame"""
+        push, buffers = C.c_uint32(0), C.c_uint32(0)
+        self._check(self.lib.plrf_get_shadow_raster_record(self.handle, C.byref(push), C.byref(buffers)))
+        return int(push.value), int(buffers.value)
+
     def shadow_raster_stats(self, cascade):
         """(triangles submitted, triangles drawn, guard-band rejects) of the last frame's execution for the cascade; waits for the GPU"""
         s = PlrfShadowRasterStats()
@@ -415,11 +422,10 @@ class FramePipeline:
             m[k] = PlrfSceneMaterial(int(albedo), int(specular))
         self._check(self.lib.plrf_set_scene_textures(self.handle, t, C.c_uint32(len(textures)), u, C.c_uint32(len(mesh_uvs)), m, C.c_uint32(len(materials))))
 
-    def set_scene_textures_formatted(self, textures, mesh_uvs, materials):
-        """set_scene_textures for textures that carry a format: textures: [(data, width, height, mip_count, format)] with format an ImageFormat - RGBA8: data are
-        uint32 texels as for set_scene_textures (mip_count 0: the host builds the chain); BC1, BC3, BC5: data are the bytes (any array, or bytes) of the blocks of
-        mip_count >= 1 levels back to back, as image_io.load_dds_file returns them for a DXT1 / DXT5 / ATI2 file. The byte count handed over is the array's: the
-        call refuses one that is not the exact size of the levels. mesh_uvs, materials, lifetime and removal as for set_scene_textures"""
+    @staticmethod
+    def _formatted_texture_arguments(textures, mesh_uvs):
+        """the plrf_scene_texture_data array and the UV pointer array of set_scene_textures_formatted / set_shadow_caster_cutouts_formatted, and the arrays they
+        point into"""
         def as_bytes(data, fmt):  # RGBA8 texels are uint32 words whatever integer type they come in; blocks are taken as the bytes they are
             if isinstance(data, (bytes, bytearray)):
                 return np.frombuffer(data, np.uint8)
@@ -432,6 +438,26 @@ class FramePipeline:
         u = (C.POINTER(C.c_float) * max(len(uvs), 1))()
         for k, a in enumerate(uvs):
             u[k] = None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+        return t, u, (data, uvs)
+
+    def set_shadow_caster_cutouts_formatted(self, textures, mesh_uvs, cutouts):
+        """set_shadow_caster_cutouts for textures that carry a format (include/plr_frame.h plrf_set_shadow_caster_cutouts_formatted): textures as
+        set_scene_textures_formatted takes them, [(data, width, height, mip_count, format)]; mesh_uvs and cutouts as for set_shadow_caster_cutouts. The alpha of a
+        BC3 texel is its alpha block's code, of a BC1 or BC5 texel 255. The two calls replace one another's store; no textures: the cutouts are removed"""
+        t, u, keep = self._formatted_texture_arguments(textures, mesh_uvs)
+        m = (PlrfShadowCutout * max(len(cutouts), 1))()
+        for k, (albedo, cutoff) in enumerate(cutouts):
+            m[k] = PlrfShadowCutout(int(albedo), int(cutoff))
+        self.lib.plrf_set_shadow_caster_cutouts_formatted.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
+        self._check(self.lib.plrf_set_shadow_caster_cutouts_formatted(self.handle, C.cast(t, C.c_void_p), C.c_uint32(len(textures)), C.cast(u, C.c_void_p), C.c_uint32(len(mesh_uvs)),
+                                                                      C.cast(m, C.c_void_p), C.c_uint32(len(cutouts))))
+
+    def set_scene_textures_formatted(self, textures, mesh_uvs, materials):
+        """set_scene_textures for textures that carry a format: textures: [(data, width, height, mip_count, format)] with format an ImageFormat - RGBA8: data are
+        uint32 texels as for set_scene_textures (mip_count 0: the host builds the chain); BC1, BC3, BC5: data are the bytes (any array, or bytes) of the blocks of
+        mip_count >= 1 levels back to back, as image_io.load_dds_file returns them for a DXT1 / DXT5 / ATI2 file. The byte count handed over is the array's: the
+        call refuses one that is not the exact size of the levels. mesh_uvs, materials, lifetime and removal as for set_scene_textures"""
+        t, u, keep = self._formatted_texture_arguments(textures, mesh_uvs)
         m = (PlrfSceneMaterial * max(len(materials), 1))()
         for k, (albedo, specular) in enumerate(materials):
             m[k] = PlrfSceneMaterial(int(albedo), int(specular))

@@ -1,6 +1,6 @@
 """What the sun shadow cascades cost as a compute pass ("sunShadowRaster.comp", plrf_set_shadow_casters) in bench.py's 4K frame.
 
-    python tools/shadow_raster_cost.py [--out FILE] [--frames N] [--rounds R] [--instances K] [--alpha]
+    python tools/shadow_raster_cost.py [--out FILE] [--frames N] [--rounds R] [--instances K] [--alpha | --alpha-bc3]
 
 One process, one build. The casters are the three meshes of tests/shadow_raster_cases.py (box, uv_sphere, torus: 1496 triangles) instanced K times (default 202:
 about 100 k triangles) over the view frustum in front of bench.py's camera, rasterised into the frame's three 2048 x 2048 cascades with the uploaded light matrices.
@@ -13,6 +13,8 @@ about 100 k triangles) over the view frustum in front of bench.py's camera, rast
     maps are restored in front of every block without casters, so both kinds of block shade the same maps each time).
 --alpha: every draw is an alpha-tested cutout (plrf_set_shadow_caster_cutouts): the meshes' own UVs, one 256 x 256 texture whose alpha is a 0 / 255 checker in
 cells of 32 texels with its full chain, cutoff 128 - the pass' tested instantiation, against the same scene without the switch.
+--alpha-bc3: the --alpha scene with its texture stored as BC3 (plrf_set_shadow_caster_cutouts_formatted): the same chain, every level encoded on the host by
+plr_encode_rgba8_to_bc - the pass' format-aware instantiation. The report states the bytes of the texel store either way.
 --rounds 0 leaves out the frame with and without casters.
 The report goes to stdout and to --out.
 """
@@ -52,6 +54,34 @@ def checker_cutouts(draw_count):
     alpha = np.where(((x // 32) + (y // 32)) % 2 == 0, 255, 0).astype(np.uint32)
     texels = ((alpha << np.uint32(24)) | np.uint32(0x00808080)).reshape(-1)
     return [(texels, 256, 256, 0)], uvs, [(0, 128)] * draw_count  # mip_count 0: the host builds the full chain
+
+
+def checker_cutouts_bc3(draw_count):
+    """the arguments of set_shadow_caster_cutouts_formatted under --alpha-bc3: checker_cutouts' texture with its chain (the host's rule, as
+    tests/prepass_texture_reference.py writes it) as BC3 blocks. -> ((textures, mesh_uvs, cutouts), bytes of the store)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import prepass_texture_reference as tref
+    from plainrenderer_amd import image_io
+    (texels, w, h, _), = checker_cutouts(draw_count)[0]
+    mips = tref.full_mip_count(w, h)
+    chain, blocks, at = tref.build_chain(texels, w, h), [], 0
+    for l in range(mips):
+        lw, lh = tref.level_size(w, h, l)
+        blocks.append(image_io.encode_rgba8_to_bc(image_io.ImageFormat.BC3, lw, lh, chain[at:at + lw * lh]))
+        at += lw * lh
+    data = np.concatenate(blocks)
+    _, uvs, cutouts = checker_cutouts(draw_count)
+    return ([(data, w, h, mips, int(image_io.ImageFormat.BC3))], uvs, cutouts), int(data.size)
+
+
+def set_cutouts(fp, a, draw_count):
+    """-> the bytes of the casters' texel store"""
+    if a.alpha_bc3:
+        arguments, stored = checker_cutouts_bc3(draw_count)
+        fp.set_shadow_caster_cutouts_formatted(*arguments)
+        return stored
+    fp.set_shadow_caster_cutouts(*checker_cutouts(draw_count))
+    return 4 * sum(max(1, 256 >> l) ** 2 for l in range(9))
 
 
 def tile_hits(light, meshes, draws, res):
@@ -106,8 +136,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--instances", type=int, default=202)
     ap.add_argument("--alpha", action="store_true")
+    ap.add_argument("--alpha-bc3", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
+    if a.alpha and a.alpha_bc3:
+        ap.error("--alpha and --alpha-bc3 exclude one another")
     sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle")]
     import torch  # noqa: F401  (first: it brings its own HIP runtime)
     import bench
@@ -119,7 +152,7 @@ def main():
     _, cams, inputs = bench.build_scene(args, "cuda:0", W, H, None)
     inputs.upload(fp)
     lines = ["# python tools/shadow_raster_cost.py%s: bench.py's scene at %d x %d, cascades %d x %d, fast kernel set, %d frames per block"
-             % (" --alpha" if a.alpha else "", W, H, RES, RES, a.frames)]
+             % (" --alpha" if a.alpha else " --alpha-bc3" if a.alpha_bc3 else "", W, H, RES, RES, a.frames)]
     cursor = 1
     for i in range(args.warmup):
         fp.frame(cams[cursor + i], 1.0 / 60.0, 0.5)
@@ -131,11 +164,12 @@ def main():
     for label, shrink in (("meshes at scale", 1.0), ("meshes shrunk to 1 / 20", 0.05)):
         meshes, draws = instances(cams[1], a.instances, shrink)
         fp.set_shadow_casters(meshes, draws)
-        if a.alpha:
-            fp.set_shadow_caster_cutouts(*checker_cutouts(len(draws)))
+        if a.alpha or a.alpha_bc3:
+            stored = set_cutouts(fp, a, len(draws))
         times = pass_times(be, fp, cams, cursor, a.frames)
         cursor += a.frames + 1
-        lines.append("%s: %d draws" % (label, len(draws)))
+        lines.append("%s: %d draws" % (label, len(draws)) + ("; the casters' texel store holds %d bytes (%s), push constants and storage buffers of a cascade's record: %r"
+                                                            % (stored, "BC3" if a.alpha_bc3 else "RGBA8", fp.shadow_raster_record()) if a.alpha or a.alpha_bc3 else ""))
         for c in range(3):
             submitted, drawn, rejects = fp.shadow_raster_stats(c)
             setup = times.get("Sun shadow cascade %d (set-up)" % c, float("nan"))
@@ -157,8 +191,8 @@ def main():
         without_ms.append(timed_block(be, fp, cams, cursor + 1, a.frames))
         cursor += a.frames + 1
         fp.set_shadow_casters(meshes, draws)
-        if a.alpha:
-            fp.set_shadow_caster_cutouts(*checker_cutouts(len(draws)))
+        if a.alpha or a.alpha_bc3:
+            set_cutouts(fp, a, len(draws))
         fp.frame(cams[cursor], 1.0 / 60.0, 0.5)
         with_ms.append(timed_block(be, fp, cams, cursor + 1, a.frames))
         cursor += a.frames + 1
